@@ -18,12 +18,17 @@ syndromes are independent).  Two hosts for the same exchange:
                             launcher started any, only take part in the barriers.
 N = 1 is the degenerate case of either (no exchange, decode straight into the result arrays).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
+Prints ONE JSON line on rank 0 (contract in the task statement) with the extra object
   roofline     : algorithmic bytes (32*nnz per syndrome*iteration) / sweep-kernel time
+and, with --full only (a plain run sets up, warms up, times the steps and prints):
   cpu_baseline : the CPU oracle on edge lists over all host cores + its reference-faithful
                  dense mode on one, bounded samples, every sample checked against the GPU
   also         : (default workload, N = 1) the waterfall and the realistic error rate of the
                  same code, 3 steps each, under the same oracle gate.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(dump_outputs below); the synthetic inputs depend on the arguments alone, so two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -384,6 +389,31 @@ def also_small_configs(ldpc, torch, device, local_rank):
     return res
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, torch, arrays, seed=0):
+    """Writes the result arrays of the last timed step as out_dir/<name>.npy.  `arrays` maps a name to a device tensor
+    with one row per syndrome of the batch the caller handed in.  Per-syndrome scalars (flags, iteration counts) are
+    written whole as float32; per-bit arrays (hard decisions as float32, LLRs as float64) only for a fixed, seeded
+    sample of syndromes, as many as fit DUMP_BYTES, whose indices are in rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = next(iter(arrays.values())).shape[0]
+    narrow = {k: v for k, v in arrays.items() if v.dim() == 1}
+    wide = {k: v for k, v in arrays.items() if v.dim() == 2}
+    out_dtype = {k: (np.float64 if v.dtype == torch.float64 else np.float32) for k, v in arrays.items()}
+    header = 128 * (len(arrays) + 1)
+    room = DUMP_BYTES - header - sum(v.shape[0] * np.dtype(out_dtype[k]).itemsize for k, v in narrow.items())
+    row_bytes = 8 + sum(v.shape[1] * np.dtype(out_dtype[k]).itemsize for k, v in wide.items())
+    k = min(total, room // row_bytes)
+    rows = np.arange(total) if k == total else np.sort(np.random.default_rng(seed).choice(total, k, replace=False))
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    idx = torch.from_numpy(rows).to(next(iter(arrays.values())).device)
+    for name, v in arrays.items():
+        h = (v.index_select(0, idx) if v.dim() == 2 else v).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), h.astype(out_dtype[name]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -398,14 +428,19 @@ def main():
                          "N = 1 is the degenerate case of the same code.  cabi: the same exchange from ONE process through the "
                          "C ABI (ldpc_bp_create_multi: one handle and stream per GPU, RCCL send/recv from GPU 0).  replicas: every "
                          "rank decodes a shard of its own, no exchange (round 1's mode)")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra workloads of the `also` object")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure the CPU baselines and the extra workloads of the `also` object, "
+                         "every one checked against the oracle (a plain run does neither)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (at most 64 MB: a seeded sample of rows)")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra workloads of the `also` object")
     ap.add_argument("--verify", action="store_true",
                     help="scatter mode: after the timed steps the root decodes every shard once more by itself and compares")
     ap.add_argument("--waves-per-tile", type=int, default=0)
     ap.add_argument("--resident-tiles", type=int, default=0)
     ap.add_argument("--kernel-variant", type=int, default=0, help="0 auto, 1 HBM-streaming, 2 LDS-resident, 3 node-parallel, 4 team")
     ap.add_argument("--defer-threshold", type=int, default=0, help="0 auto (16), -1 off (streaming kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` object")
     ap.add_argument("--llr", action="store_true",
                     help="the timed step asks for the LLRs of every syndrome as well (scratch.log_probabs, belief_propagation.jl:163; "
                          "one GPU, decode straight into the result arrays)")
@@ -416,6 +451,8 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="all ranks share cuda:0; the exchange runs over gloo with the shards staged through the host instead of RCCL")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -601,6 +638,19 @@ def main():
         if cabi:
             vdec.close()
 
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the whole root-held batch in scatter / cabi
+        # mode, this rank's batch otherwise (the BP+OSD path returns no iteration counts)
+        if mode in ("scatter", "cabi"):
+            res = dict(zip(("errors", "converged", "iterations"), result[0]))
+        else:
+            res = {"errors": err, "converged": conv}
+            if not bposd_workload:
+                res["iterations"] = iters
+            if llr_out is not None:
+                res["llr"] = llr_out
+        dump_outputs(args.dump_outputs, torch, res)
+
     if rank == 0:
         if mode in ("scatter", "cabi"):
             err, conv, iters = (t[:batch] for t in result[0])   # the root's own shard (seed 1234)
@@ -656,7 +706,7 @@ def main():
                                "scatter_bytes_per_peer": batch * s_checks if shards > 1 else 0,
                                "gather_bytes_per_peer": batch * (n + 1 + 4) if shards > 1 else 0,
                                "sharded_matches_local": verified}
-        if not args.no_cpu_baseline and shards == 1 and not bposd_workload:
+        if args.full and not args.no_cpu_baseline and shards == 1 and not bposd_workload:
             cores = max(1, min(len(os.sched_getaffinity(0)), 16))   # a one-GPU box grants 16 cores
             k_edge = min(batch, 4096)       # (the gate of a reported C3 number is >= 4,096 syndromes)
             h_syn, h_err, h_conv, h_it = (t[:k_edge].cpu().numpy() for t in (syn0, err, conv, iters))
@@ -677,8 +727,8 @@ def main():
                               f"1 thread like the reference",
                 },
             }
-        if args.workload == "c3_full50" and shards == 1 and mode != "replicas" and not args.no_also and not args.batch and not args.per \
-                and not args.kernel_variant and not args.waves_per_tile and not args.resident_tiles:
+        if args.full and args.workload == "c3_full50" and shards == 1 and mode != "replicas" and not args.no_also and not args.batch \
+                and not args.per and not args.kernel_variant and not args.waves_per_tile and not args.resident_tiles:
             out["also"] = also_workloads(ldpc, torch, H, Hcsr, n, nnz, device, local_rank)
             out["also"].update(also_small_configs(ldpc, torch, device, local_rank))
         print(json.dumps(out), flush=True)

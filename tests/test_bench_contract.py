@@ -28,7 +28,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 
 @pytest.mark.gpu
 def test_bench_json_contract(gpu):
-    out = _run(["--workload", "c2_n1008", "--steps", "2", "--warmup", "1"], 900)
+    out = _run(["--workload", "c2_n1008", "--steps", "2", "--warmup", "1", "--full"], 900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
     assert len(lines) == 1
@@ -48,3 +48,71 @@ def test_bench_json_contract(gpu):
     assert c["gpu_matches_oracle_on_sample"] is True and c["reference_faithful_1_thread"]["cores"] == 1
     # N = 1 runs the multi-GPU path's own code (sharding.batchdecode_sharded) in its degenerate form
     assert d["config"]["mode"] == "scatter" and d["exchange"]["scatter_bytes_per_peer"] == 0
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_stays_within_budget_and_samples_rows_by_seed(tmp_path):
+    """dump_outputs writes per-syndrome scalars whole and a seeded sample of the per-bit rows, float32 / float64 only,
+    at most DUMP_BYTES in all; the same arrays give the same files."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    batch, n = 4096, 16384            # 256 MiB of float32 hard decisions: must be sampled
+    g = torch.Generator().manual_seed(3)
+    arrays = {"errors": (torch.rand((batch, n), generator=g) < 0.1).to(torch.uint8),
+              "converged": (torch.rand(batch, generator=g) < 0.5).to(torch.uint8),
+              "iterations": torch.randint(0, 51, (batch,), generator=g, dtype=torch.int32),
+              "llr": torch.randn((batch, n), generator=g, dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch, arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["converged.npy", "errors.npy", "iterations.npy", "llr.npy", "rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and got["llr"].dtype == np.float64
+    rows = got["rows"].astype(np.int64)
+    assert 0 < len(rows) < batch and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["errors"], arrays["errors"].numpy()[rows].astype(np.float32))
+    assert np.array_equal(got["llr"], arrays["llr"].numpy()[rows])
+    assert np.array_equal(got["converged"], arrays["converged"].numpy().astype(np.float32))
+    assert np.array_equal(got["iterations"], arrays["iterations"].numpy().astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    # a batch that fits is written whole
+    small = {k: v[:64] for k, v in arrays.items()}
+    bench.dump_outputs(str(tmp_path / "c"), torch, small)
+    assert np.array_equal(np.load(tmp_path / "c" / "rows.npy"), np.arange(64, dtype=np.float64))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_reproducible_outputs(gpu, tmp_path):
+    """Without --full the result line holds the headline figure and its roofline, not the CPU baselines or the `also`
+    workloads; --steps sets the number of timed steps; --dump-outputs writes the last step's results, and two runs with
+    the same arguments write the same arrays."""
+    import numpy as np
+
+    for d in ("a", "b"):
+        out = _run(["--workload", "c2_n1008", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)], 900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0 and "roofline" in r
+        assert "cpu_baseline" not in r and "also" not in r
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["converged.npy", "errors.npy", "iterations.npy", "rows.npy"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["errors"].shape == (4096, 1008) and got["converged"].shape == (4096,)
+    assert abs(float(got["converged"].astype(np.float64).mean()) - r["config"]["converged_frac"]) < 1e-6
+    assert abs(float(got["iterations"].astype(np.float64).mean()) - r["config"]["mean_iters"]) < 1e-6
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -4,8 +4,8 @@
 B="python bench.py --no-also --no-cpu-baseline --steps 3 --warmup 1"
 tools/gpu_session.sh r04a \
   700 'python -m pytest tests -m gpu -x -q' \
-  240 'python bench.py --steps 5 --warmup 2 --no-also' \
-  240 "python bench.py --no-also --steps 3 --warmup 1 --llr" \
+  240 'python bench.py --full --steps 5 --warmup 2 --no-also' \
+  240 "python bench.py --full --no-also --steps 3 --warmup 1 --llr" \
   200 "LDPC_TEAM_LLR_RAW=0 LDPC_TEAM_LLR_FOOTPRINT=0 $B --llr" \
   200 "LDPC_TEAM_LLR_RAW=1 LDPC_TEAM_LLR_FOOTPRINT=0 $B --llr" \
   200 "LDPC_TEAM_LLR_RAW=2 LDPC_TEAM_LLR_FOOTPRINT=0 $B --llr" \

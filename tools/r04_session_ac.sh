@@ -3,7 +3,7 @@
 tools/gpu_session.sh r04ac \
   900 'python -m pytest tests -m gpu -x -q' \
   300 'tools/profile_workload.sh r04d c3_full50' \
-  300 'python bench.py' \
+  300 'python bench.py --full' \
   120 'python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-also --workload wide_16000_10_5' \
   120 'python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-also --workload reg410_16380'
 tail -3 gpurun_out/r04ac_1.log

@@ -3,5 +3,5 @@
 tools/gpu_session.sh r04al \
   900 'python -m pytest tests -m gpu -x -q' \
   560 'python tools/fuzz_parity.py 420 141421' \
-  300 'python bench.py'
+  300 'python bench.py --full'
 tail -3 gpurun_out/r04al_1.log; tail -3 gpurun_out/r04al_2.log; grep -h '"metric"' gpurun_out/r04al_3.log | cut -c1-400

@@ -6,11 +6,11 @@ FD=$PWD/ldpcdecoders.jl_amd/csrc/libldpc_fastdiv.so
 tools/gpu_session.sh r04b \
   600 'python -m pytest tests/test_gpu_parity.py tests/test_gpu_multi.py -q -x -k "short_division or eight_way"' \
   900 'python -m pytest tests/test_gpu_full_size.py -q -x -k "other_regular"' \
-  200 "LDPC_TEAM_LLR_RAW=3 python bench.py --no-also --steps 3 --warmup 1 --llr" \
+  200 "LDPC_TEAM_LLR_RAW=3 python bench.py --full --no-also --steps 3 --warmup 1 --llr" \
   200 "LDPC_TEAM_LLR_RAW=3 $B --workload c3_realistic --llr" \
   200 "LDPC_TEAM_LLR_RAW=3 LDPC_TEAM_LLR_FOOTPRINT=0 $B --llr" \
   600 "LDPC_MI355X_LIB=$FD LDPC_MI355X_EXP_LIB=$FD python -m pytest tests/test_gpu_parity.py tests/test_golden.py -q -x" \
-  200 "LDPC_MI355X_LIB=$FD LDPC_MI355X_EXP_LIB=$FD python bench.py --no-also --steps 4 --warmup 1" \
+  200 "LDPC_MI355X_LIB=$FD LDPC_MI355X_EXP_LIB=$FD python bench.py --full --no-also --steps 4 --warmup 1" \
   200 "$B --steps 4" \
   200 "LDPC_MI355X_LIB=$FD LDPC_MI355X_EXP_LIB=$FD $B --steps 4" \
   200 "$B --steps 4" \

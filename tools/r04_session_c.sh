@@ -5,7 +5,7 @@ B="python bench.py --no-also --no-cpu-baseline --steps 3 --warmup 1"
 TF=$PWD/ldpcdecoders.jl_amd/csrc/libldpc_tform.so
 tools/gpu_session.sh r04c \
   900 'python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_size.py tests/test_gpu_bposd.py tests/test_golden.py tests/test_gpu_multi.py -q -x -k "llr or LLR or bposd or golden or bit_identical or eight_way or with_llrs"' \
-  200 "python bench.py --no-also --steps 3 --warmup 1 --llr" \
+  200 "python bench.py --full --no-also --steps 3 --warmup 1 --llr" \
   200 "$B --llr --llr-exact" \
   200 "$B --workload c3_realistic --llr" \
   200 "$B --workload c3_realistic --llr --llr-exact" \

@@ -4,7 +4,7 @@
 B="python bench.py --no-also --no-cpu-baseline --steps 3 --warmup 1"
 tools/gpu_session.sh r04d \
   900 'python -m pytest tests -m gpu -x -q' \
-  300 'python bench.py --steps 5 --warmup 2' \
+  300 'python bench.py --full --steps 5 --warmup 2' \
   200 "$B --steps 4" \
   200 "$B --llr" \
   200 "$B --llr --llr-exact" \

@@ -13,7 +13,7 @@ tools/gpu_session.sh r04i \
   200 "LDPC_TEAM_LLR_SCRATCH=1 $B --llr" \
   200 "LDPC_TEAM_LLR_SCRATCH=0 $B --llr" \
   200 "LDPC_TEAM_LLR_SCRATCH=0 $B --llr --llr-exact" \
-  200 "LDPC_TEAM_LLR_SCRATCH=0 python bench.py --no-also --steps 2 --warmup 1 --llr --workload c3_realistic"
+  200 "LDPC_TEAM_LLR_SCRATCH=0 python bench.py --full --no-also --steps 2 --warmup 1 --llr --workload c3_realistic"
 for k in 1 2 3 4 5 6 7 8 9 10 11 12; do echo "== step $k"; grep -h '^{' gpurun_out/r04i_$k.log | python -c "
 import sys, json
 for l in sys.stdin:

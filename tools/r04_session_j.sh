@@ -4,7 +4,7 @@
 TAG=r04b
 tools/gpu_session.sh r04j \
   900 'python -m pytest tests -m gpu -x -q' \
-  300 'python bench.py --steps 20 --warmup 5' \
+  300 'python bench.py --full --steps 20 --warmup 5' \
   420 'python tools/fuzz_parity.py 300 31415'
 for WL in c3_full50 c3_realistic c3_waterfall; do
   BENCH_ARGS="--llr" SUFFIX=_llr tools/profile_workload.sh $TAG $WL > gpurun_out/profile_${TAG}_${WL}_llr.log 2>&1
