@@ -32,6 +32,10 @@ ldpc_status stalled_error(int device);                    // ... the status ever
 ldpc_status wait_event(hipEvent_t e, int device, const char *what);
 ldpc_status wait_stream(hipStream_t s, int device, const char *what);
 ldpc_status wait_device(int device, const char *what);    // hipSetDevice(device) + hipDeviceSynchronize, bounded
+// A wait the caller polls by itself (the latency paths' flag spin) has passed the limit: what an expired wait above does, at
+// once -- LDPC_ERR_HIP naming `what`, the device marked stalled.  (Not another wait_stream(): that polls for a SECOND full
+// limit, and a kernel that ends inside it would make the call return LDPC_OK without its copy-out.)
+ldpc_status wait_expired(int device, const char *what);
 // cleanup paths (destructors): true = the device has drained and what it used may be freed
 inline bool device_idle_for_release(int device, const char *what) { return wait_device(device, what) == LDPC_OK; }
 

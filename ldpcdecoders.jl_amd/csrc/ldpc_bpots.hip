@@ -320,7 +320,7 @@ ldpc_status ldpc_bpots_decode_batch(ldpc_bpots_decoder *d, int64_t batch, const 
             if ((spins & 0xffff) == 0) {   // every ~65k polls: is the kernel still alive?  (and the bound of host_wait.hpp)
                 const int64_t lim = ldpc_detail::wait_limit_ms();
                 if (lim > 0 && std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - lat_t0).count() > lim)
-                    return ldpc_detail::wait_stream(nullptr, d->device, "BP-OTS latency path (flag of the last workgroup)");   // (expires at once: names the wait, marks the device)
+                    return ldpc_detail::wait_expired(d->device, "BP-OTS latency path (flag of the last workgroup)");   // (names the wait, marks the device; never LDPC_OK before the copy-out)
                 const hipError_t q = hipStreamQuery(nullptr);
                 if (q == hipSuccess) {
                     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == lc.ticket) break;

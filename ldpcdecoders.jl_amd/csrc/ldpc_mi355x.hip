@@ -124,6 +124,11 @@ ldpc_status wait_stream(hipStream_t s, int device, const char *what)
     }
     return poll_until([&] { return hipStreamQuery(s); }, device, what);
 }
+ldpc_status wait_expired(int device, const char *what)
+{
+    if (device_stalled(device)) return stalled_error(device);
+    return expired(device, what, wait_limit_ms());
+}
 // hipDeviceSynchronize has no query form: it runs in a helper thread that the caller waits for with the deadline; a
 // thread that never comes back is left behind (detached) with the state it shares with nobody else.
 ldpc_status wait_device(int device, const char *what)
@@ -2665,7 +2670,7 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
                 if ((spins & 0xffff) == 0) {   // every ~65k polls: is the kernel still alive?  (and the bound of host_wait.hpp)
                     const int64_t lim = ldpc_detail::wait_limit_ms();
                     if (lim > 0 && std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - lat_t0).count() > lim)
-                        return ldpc_detail::wait_stream(stream, d->device, "latency path (flag of the last workgroup)");   // (expires at once: names the wait, marks the device)
+                        return ldpc_detail::wait_expired(d->device, "latency path (flag of the last workgroup)");   // (names the wait, marks the device; never LDPC_OK before the copy-out)
                     const hipError_t q = hipStreamQuery(stream);
                     if (q == hipSuccess) {
                         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == lc.ticket) break;

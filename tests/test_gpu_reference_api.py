@@ -396,3 +396,107 @@ def test_a_host_side_wait_that_expires_names_itself(gpu):
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
                          cwd=__import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
     assert out.returncode == 0 and "BOUNDED" in out.stdout and "NOT BOUNDED" not in out.stdout, (out.returncode, out.stdout[-500:], out.stderr[-1500:])
+
+
+_LATENCY_EXPIRY_CHILD = """
+import sys, time
+import numpy as np
+import ldpcdecoders_jl_amd as ldpc
+from oracle import BPOracle, BPOTSOracle
+kind = sys.argv[1]
+SENT = 0x77
+if kind == "bp":      # n = 4096 (8,4): a single decode goes to the node-parallel kernel (messages in LDS), 46 KiB of I/O: the latency path
+    H = ldpc.codes.parity_check_csc(4096, 8, 4)
+    make = lambda it: ldpc.BeliefPropagationDecoder(H, 0.10, it)
+    oracle = lambda it: BPOracle(csc=(H.indptr, H.indices), shape=H.shape, per=0.10, max_iters=it)
+    what = "latency path (flag of the last workgroup)"
+else:                 # BP-OTS on a graph inside the LDS: its latency path
+    H = ldpc.codes.parity_check_csc(504, 6, 3)
+    make = lambda it: ldpc.BPOTSDecoder(H, 0.10, it, T=3, C=2.0)
+    oracle = lambda it: BPOTSOracle((H.indptr, H.indices), H.shape, 0.10, it, 3, 2.0)
+    what = "BP-OTS latency path (flag of the last workgroup)"
+s, n = H.shape
+syn = np.ascontiguousarray(ldpc.codes.syndromes_of(H, ldpc.codes.random_errors(n, 1, 0.10, seed=3)))
+
+def call(dec):
+    L = dec._L
+    err = np.full((1, n), SENT, dtype=np.uint8); conv = np.full(1, SENT, dtype=np.uint8)
+    its = np.full(1, -7, dtype=np.int32); llr = np.full((1, n), -7.0)
+    t0 = time.perf_counter()
+    if kind == "bp":
+        st = L.ldpc_bp_decode_batch(dec._h, 1, syn.ctypes.data, err.ctypes.data, conv.ctypes.data, llr.ctypes.data, its.ctypes.data)
+    else:
+        st = L.ldpc_bpots_decode_batch(dec._h, 1, syn.ctypes.data, err.ctypes.data, conv.ctypes.data, its.ctypes.data)
+    ms = (time.perf_counter() - t0) * 1e3
+    msg = L.ldpc_last_error().decode() if st != 0 else ""
+    return st, ms, msg, (err, conv, llr, its)
+
+def measure(it):      # (first call: code objects, pinned memory -- then the one that is timed, both under the default limit)
+    dec = make(it)
+    assert call(dec)[0] == 0
+    st, ms, _, out = call(dec)
+    assert st == 0 and not out[1][0] and out[3][0] >= it, (st, out[1], out[3])      # per 0.10: every iteration runs
+    if kind == "bp":
+        assert dec.info().last_kernel == 3
+        print("device total_ms", dec.last_timing()[1])
+    return dec, ms
+
+iters = 2000
+dec, ms = measure(iters)
+print("measured", iters, "iterations:", ms, "ms")
+iters2 = int(min(max(iters * 40.0 / ms, iters), 4_000_000))      # tens of milliseconds, from the measurement
+dec.close()
+dec, ms = measure(iters2)
+print("measured", iters2, "iterations:", ms, "ms")
+if ms < 5.0:          # too short to place the limit: raised ONCE, from the measurement
+    iters2 = int(min(iters2 * 40.0 / ms, 40_000_000))
+    dec.close()
+    dec, ms = measure(iters2)
+    print("measured", iters2, "iterations:", ms, "ms")
+limit = max(1, int(ms * 2 / 3))
+assert dec._L.ldpc_set_wait_limit_ms(limit) == 0
+st, took, msg, out = call(dec)
+print("limit", limit, "ms: status", st, "after", took, "ms:", msg[:100])
+if st == 0:           # the kernel beat the limit this time: then the outputs must be there, all of them
+    oc = oracle(iters2)
+    syn2 = syn
+    if kind == "bp":
+        oerr, oconv, ollr, oits = oc.batchdecode(syn2, want_llr=True)
+        fin = np.isfinite(ollr)
+        assert np.array_equal(out[2][~fin], ollr[~fin], equal_nan=True) and (not fin.any() or np.max(np.abs(out[2][fin] - ollr[fin])) <= 1e-5), "LDPC_OK without the LLRs"
+    else:
+        oerr, oconv, oits = oc.batchdecode(syn2)
+    assert np.array_equal(out[0], oerr) and np.array_equal(out[1], oconv) and np.array_equal(out[3], oits), "LDPC_OK without the copy-out"
+    print("IN TIME")
+else:
+    assert st == 3 and what in msg and "did not get there within" in msg, (st, msg)
+    assert took <= 2 * limit + 50.0, (took, limit)       # at once, not after a second full limit (50 ms: the process's own overhead)
+    print("EXPIRED")
+time.sleep(0.3)       # (the kernel that was left behind ends by itself: its iterations are bounded)
+t0 = time.time()
+dec.close()
+assert time.time() - t0 < 5.0
+print("DONE")
+"""
+
+
+@pytest.mark.parametrize("kind", ["bp", "ots"])
+def test_a_latency_path_wait_that_expires_never_returns_ok_without_its_outputs(gpu, kind):
+    """The latency path of the synchronous host entries (ldpc_bp_decode_batch: a single decode! on the node-parallel or LDS
+    kernel; ldpc_bpots_decode_batch on a graph inside the LDS) spins on a flag in pinned memory.  When the spin passes the
+    wait limit the call must expire AT ONCE and name itself (host_wait.hpp wait_expired()); it used to go on into
+    wait_stream(), which polls for a second full limit -- a kernel that ended inside that window made the call return
+    LDPC_OK with none of err / conv / iters / llr copied out.  A single decode, per 0.10 so that every iteration runs,
+    max_iters chosen from a measurement so that the call takes tens of milliseconds, the limit at two thirds of that --
+    inside the window -- and the outputs pre-filled with a sentinel.  Exactly two outcomes pass: LDPC_ERR_HIP naming the
+    latency-path wait within 2 x the limit, or LDPC_OK with the oracle's outputs.  One attempt; in a process of its own
+    (the stalled mark is for the life of the process), which must exit by itself."""
+    import os
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, "-c", _LATENCY_EXPIRY_CHILD, kind], capture_output=True, text=True, timeout=300,
+                         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    print(out.stdout[-1500:])
+    assert out.returncode == 0 and "DONE" in out.stdout and ("EXPIRED" in out.stdout or "IN TIME" in out.stdout), \
+        (out.returncode, out.stdout[-1500:], out.stderr[-1500:])

@@ -98,6 +98,12 @@ while time.time() - t0 < budget and cases < MAXCASES:
     if big:
         B = int(rng.choice([64, 130, 400]))
         iters = int(rng.choice([3, 7]))
+    if mid:            # (drawn BEHIND the draws above: the ends of the channel -- odds 0 / Inf, the NaN reset -- and a decode that stops after
+        #                the first iteration, which on the rows-on-chip kernels is the table path alone, on the mid-size graphs too)
+        if rng.random() < 0.15:
+            per = float(rng.choice([0.0, 1.0]))
+        if rng.random() < 0.15:
+            iters = 1
     if rng.random() < 0.5:
         E = (rng.random((B, n)) < min(per * rng.uniform(0.5, 3), 0.5)).astype(np.uint8)
         syn = ldpc.codes.syndromes_of(H, E)
@@ -227,8 +233,9 @@ while time.time() - t0 < budget and cases < MAXCASES:
         decoded += B
     if kind == 1 and H.nnz > 0:      # (any degree: nodes beyond 32 / 16 edges take the unlimited kernel)
         T, C = int(rng.choice([2, 3, 9])), float(rng.choice([1.0, 2.0, 3.0]))
-        # (the CPU oracle of BP-OTS re-runs with biases and takes minutes for 5,000 syndromes x 50 iterations -- what looked
-        #  like a stalled run in round 3 was this: the leg decodes the first 600 syndromes of the batch at most)
+        # (the CPU oracle of BP-OTS re-runs with biases and takes minutes for 5,000 syndromes x 50 iterations: the leg decodes the
+        #  first 600 syndromes of the batch at most.  It is NOT what stalled the run of seed 5151 in round 3, as this comment
+        #  used to say: that run's oracle legs were timed afterwards and cannot account for it -- DESIGN.md section 8)
         syn_ots = syn[:OTS_CAP] if OTS_CAP > 0 else syn
         pp = max(per, 1e-3) if per < 0.9 else 0.3
         os.environ.pop("LDPC_BPOTS_FORCE_NODE", None)
