@@ -185,6 +185,48 @@ ldpc_status ldpc_bp_decode_batch_device(ldpc_bp_decoder *dec, int64_t batch,
                                         void *stream);
 
 /*
+ * The same `batchdecode!(decoder, syndromes, errors, success)` (src/decoders/belief_propagation.jl:220-231) on
+ * BIT-PACKED matrices in the memory layout of a Julia `BitMatrix` -- what the reference's own test and doctest hand in
+ * as `errors` (test/test_bp_decoder.jl:26, belief_propagation.jl:217).  A BitMatrix of r x B keeps element (row, col),
+ * zero-based, as bit k = col * r + row of one flat bit string: word k >> 6 of `chunks::Vector{UInt64}`, bit k & 63,
+ * least significant bit first, columns NOT padded.  HOST buffers.
+ *
+ *   syndrome_words  uint64, 8-byte aligned, little-endian   in : the syndrome bit of (check r, column i) is bit
+ *                                                                syndrome_bit0 + i * s + r
+ *   error_words     uint64, 8-byte aligned, little-endian   out: the error bit of (bit j, column i) is bit
+ *                                                                error_bit0 + i * n + j
+ *   syndrome_bit0, error_bit0 >= 0: 0 for a whole BitMatrix; c0 * r addresses column c0 onward of a larger one
+ *   converged [batch] uint8, llr [batch][n] double (may be NULL), iters [batch] int32 (may be NULL): exactly as in
+ *   ldpc_bp_decode_batch (a Julia Vector{Bool} is a byte per element already)
+ *
+ * The call writes EXACTLY the bits [error_bit0, error_bit0 + batch * n): every other bit of the first and the last
+ * word it touches keeps its value (a BitMatrix keeps its trailing bits zero; a view does not damage its neighbours),
+ * words wholly inside the range are overwritten.  Only the words that cover a range are read or written.
+ * Hard decisions, flags, iteration counts and LLRs are those of ldpc_bp_decode_batch on the same syndromes, bit for
+ * bit: the same kernels under the same plan run on a byte image that the handle owns (counted in workspace_bytes); two
+ * streaming kernels convert at the boundary.  batch = 0: LDPC_OK, nothing touched.  max_iters = 0: the range becomes
+ * zeros.  s = 0 / n = 0 as in the byte entry.  A NULL handle, a negative batch or bit offset, a word pointer that is
+ * not 8-byte aligned, a NULL pointer where the byte entry rejects one: LDPC_ERR_INVALID_ARGUMENT before any device work.
+ *
+ * These three entries were added WITHOUT a change of LDPC_MI355X_ABI_VERSION (they only add symbols): a caller detects
+ * them by symbol lookup (dlsym / Libdl.dlsym).
+ */
+ldpc_status ldpc_bp_decode_batch_bits(ldpc_bp_decoder *dec, int64_t batch, const uint64_t *syndrome_words,
+                                      int64_t syndrome_bit0, uint64_t *error_words, int64_t error_bit0,
+                                      uint8_t *converged, double *llr, int32_t *iters);
+
+/*
+ * The bits entry with DEVICE pointers: asynchronous on `stream` and ordered on the handle exactly like
+ * ldpc_bp_decode_batch_device (bits -> bytes, that entry's kernels, bytes -> bits, all on `stream`).
+ * ldpc_bp_last_status / ldpc_bp_last_timing cover it; total_ms includes the two conversions.  The partial first / last
+ * word of the error range is read, merged and written back by the call: nothing else may write those two words
+ * until the call has finished.
+ */
+ldpc_status ldpc_bp_decode_batch_bits_device(ldpc_bp_decoder *dec, int64_t batch, const uint64_t *d_syndrome_words,
+                                             int64_t syndrome_bit0, uint64_t *d_error_words, int64_t error_bit0,
+                                             uint8_t *d_converged, double *d_llr, int32_t *d_iters, void *stream);
+
+/*
  * Was everything enqueued on this handle so far good?  Waits for the most recent
  * ldpc_bp_decode_batch_device call (and with it every earlier one: calls on a handle run in call
  * order, whatever streams they were given) and returns LDPC_OK, or LDPC_ERR_HIP if a team of
@@ -271,6 +313,14 @@ ldpc_bp_decoder *ldpc_bp_multi_handle(ldpc_bp_multi *dec, int32_t g);
  * per device; nothing hops through GPU 0.  Synchronous.  With ndev = 1 this is ldpc_bp_decode_batch. */
 ldpc_status ldpc_bp_decode_batch_multi(ldpc_bp_multi *dec, int64_t batch, const uint8_t *syndromes, uint8_t *errors,
                                        uint8_t *converged, double *llr, int32_t *iters);
+
+/* ldpc_bp_decode_batch_bits (the BitMatrix layout, belief_propagation.jl:220-231) over the devices, HOST buffers: device g
+ * takes the columns [g*B/G, (g+1)*B/G) through the single-device bits entry with syndrome_bit0 + lo * s and
+ * error_bit0 + lo * n.  Shard borders do not fall on words: two shards may share an error word, and each merges its bits
+ * into it with atomic operations on the word.  Synchronous.  There is no root-device form in bits. */
+ldpc_status ldpc_bp_decode_batch_multi_bits(ldpc_bp_multi *dec, int64_t batch, const uint64_t *syndrome_words,
+                                            int64_t syndrome_bit0, uint64_t *error_words, int64_t error_bit0,
+                                            uint8_t *converged, double *llr, int32_t *iters);
 
 /* The same with the whole batch resident in the HBM of devices[0] (pointers as for ldpc_bp_decode_batch_device):
  * scatter the syndrome shards, decode, gather hard decisions / flags (/ iteration counts / LLRs) into the caller's

@@ -11,6 +11,7 @@ Exports follow src/LDPCDecoders.jl:12-18 for the hot path (``!`` -> ``_``).
 """
 from . import _capi, codes  # noqa: F401
 from ._capi import LdpcError, build  # noqa: F401
+from .bitmatrix import BitMatrix  # noqa: F401
 from .codes import load_pcm, parity_check_matrix, save_pcm  # noqa: F401
 from .decoder import (  # noqa: F401
     AbstractDecoder,
@@ -29,5 +30,5 @@ __all__ = [
     "BeliefPropagationOSDDecoder", "OSDPostProcessor", "BPOTSDecoder",
     "decode_", "batchdecode_", "reset_", "AbstractDecoder", "BeliefPropagationDecoder",
     "BeliefPropagationScratchSpace", "parity_check_matrix", "save_pcm", "load_pcm",
-    "LdpcError", "build", "codes", "syndrome_bytes",
+    "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
 ]

@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = (
     "ldpc_bp_get_info",
     "ldpc_bp_decode_batch",
     "ldpc_bp_decode_batch_device",
+    "ldpc_bp_decode_batch_bits",
+    "ldpc_bp_decode_batch_bits_device",
     "ldpc_bp_last_status",
     "ldpc_bp_last_timing",
     "ldpc_bp_call_timing",
@@ -49,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "ldpc_bp_destroy_multi",
     "ldpc_bp_multi_handle",
     "ldpc_bp_decode_batch_multi",
+    "ldpc_bp_decode_batch_multi_bits",
     "ldpc_bp_decode_batch_multi_device",
     "ldpc_bp_multi_last_status",
     "ldpc_bp_multi_get_info",
@@ -109,7 +112,7 @@ class BPOptions(ctypes.Structure):
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "osd_host.cpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "osd_host.cpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -193,6 +196,12 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_bp_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     L.ldpc_bp_decode_batch_device.restype = i32
     L.ldpc_bp_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_bp_decode_batch_bits.restype = i32
+    L.ldpc_bp_decode_batch_bits.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp]
+    L.ldpc_bp_decode_batch_bits_device.restype = i32
+    L.ldpc_bp_decode_batch_bits_device.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
+    L.ldpc_bp_decode_batch_multi_bits.restype = i32
+    L.ldpc_bp_decode_batch_multi_bits.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp]
     L.ldpc_bp_last_status.restype = i32
     L.ldpc_bp_last_status.argtypes = [vp]
     L.ldpc_bp_last_timing.restype = i32

@@ -16,6 +16,7 @@
 #include "bp_lds_kernels.hpp"
 #include "bp_node_kernels.hpp"
 #include "bp_team_kernels.hpp"
+#include "bit_io_kernels.hpp"
 #include "pickers.hpp"
 #include "host_env.hpp"
 #include "host_wait.hpp"
@@ -575,7 +576,15 @@ struct ldpc_bp_decoder {
     // Calls on one handle share its workspace, so they execute in call order whatever streams they are
     // given: a call that arrives on another stream than its predecessor first waits for that one's last event.
     hipStream_t last_stream = nullptr;
-    hipEvent_t last_ev = nullptr;  // one of ev[][] (not owned): completion of the most recent enqueued call
+    hipEvent_t last_ev = nullptr;  // one of ev[][] / bits_ev[][] (not owned): completion of the most recent enqueued call
+    // bit-packed entries (ldpc_bp_decode_batch_bits[_device]; bit_io_kernels.hpp): byte staging of the caller's bit
+    // strings, the events that bracket conversion + decode + conversion of a call (total_ms of that call), and the
+    // pinned word images of the host pipeline (the device images are pipe_dev / st_all, the streams pipe_stream)
+    DevBuf bits_syn, bits_err;
+    hipEvent_t bits_ev[kRing][2] = {};
+    bool bits_timed[kRing] = {};
+    void *bits_pin[kPipe] = {};
+    size_t bits_pin_cap[kPipe] = {};
     int inject_fault = 0;          // tests (experiments build, LDPC_TEAM_INJECT_FAULT at create): 1 = team kernels raise the fault word at once, 2 = a member misses the roll call
     unsigned rollcall_ticks = 2000000u;   // 20 ms of the 100 MHz clock: how long the members of a team wait for each other at launch (team_rollcall)
 
@@ -587,7 +596,7 @@ struct ldpc_bp_decoder {
         DevBuf *all[] = {&row_ptr, &edge_bit, &col_ptr, &csc2csr, &msg, &ctrl, &synmask, &nevermask,
                          &errmask, &finmask, &llr_t, &st_all, &node_msg, &done_ctr, &team_ws, &team_ws_lvl[0], &team_ws_lvl[1], &cold,
                          &rows_ctab, &rows_vtab, &rows_lds_edge, &rows_reg_edge, &rows_posmap,
-                         &irr_ctab, &irr_ptab, &irr_ploc, &irr_lds_edge, &irr_posmap};
+                         &irr_ctab, &irr_ptab, &irr_ploc, &irr_lds_edge, &irr_posmap, &bits_syn, &bits_err};
         for (DevBuf *b : all) b->release(idle);
         for (int l = 0; l < 2; ++l)
             for (DevBuf *b : {&lvl_state[l], &lvl_list[l], &lvl_it[l], &lvl_syn[l], &lvl_never[l], &lvl_err[l], &lvl_fin[l], &lvl_llr[l]}) b->release(idle);
@@ -598,6 +607,11 @@ struct ldpc_bp_decoder {
         if (team_fault) (void)hipHostFree(team_fault);
         for (void *&q : pipe_pin)
             if (q) (void)hipHostFree(q);
+        for (void *&q : bits_pin)
+            if (q) (void)hipHostFree(q);
+        for (auto &pair : bits_ev)
+            for (hipEvent_t &e : pair)
+                if (e) (void)hipEventDestroy(e);
         for (hipStream_t &q : pipe_stream)
             if (q) (void)hipStreamDestroy(q);
         for (auto &row : pipe_ev)
@@ -1084,7 +1098,7 @@ ldpc_status ldpc_bp_get_info(const ldpc_bp_decoder *d, ldpc_bp_info *info)
                            &d->lvl_syn[0], &d->lvl_syn[1], &d->lvl_never[0], &d->lvl_never[1], &d->lvl_err[0], &d->lvl_err[1], &d->lvl_fin[0], &d->lvl_fin[1],
                            &d->lvl_llr[0], &d->lvl_llr[1], &d->team_ws, &d->team_ws_lvl[0], &d->team_ws_lvl[1],
                            &d->rows_ctab, &d->rows_vtab, &d->rows_lds_edge, &d->rows_reg_edge, &d->rows_posmap,
-                           &d->irr_ctab, &d->irr_ptab, &d->irr_ploc, &d->irr_lds_edge, &d->irr_posmap};
+                           &d->irr_ctab, &d->irr_ptab, &d->irr_ploc, &d->irr_lds_edge, &d->irr_posmap, &d->bits_syn, &d->bits_err};
     for (const DevBuf *b : all) info->workspace_bytes += (int64_t)b->cap;
     info->last_kernel = d->last_kernel;
     info->last_team_size = d->last_team;
@@ -2013,6 +2027,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     char *ctrl = (char *)d->ctrl.p + 64 * slot;
     d->timed[slot] = false;
     d->two_events[slot] = false;
+    d->bits_timed[slot] = false;
     // single-kernel paths: the kernel zeroes the control slot of the NEXT call, so a call that finds its
     // slot clean enqueues no memset, and only two events bracket the one kernel (measured on C2, batch
     // 4096: fill kernel 3.5 us + ~10 us of dependency gap on either side of a 94 us decode kernel)
@@ -2796,6 +2811,235 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
     }
 }
 
+}  // extern "C"
+
+// ---- bit-packed entries (include/ldpc_mi355x.h: ldpc_bp_decode_batch_bits[_device]) -- conversion at the boundary:
+// bits -> the handle's byte staging, the byte entry's kernels unchanged on it, bytes -> bits (bit_io_kernels.hpp).
+
+// everything that can be refused without a device; *done = nothing to do (batch 0)
+static ldpc_status bits_check_args(const ldpc_bp_decoder *d, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
+                                   const uint64_t *err_w, int64_t err_bit0, const uint8_t *conv, bool *done)
+{
+    *done = false;
+    if (!d) return fail(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
+    if (batch < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (syn_bit0 < 0 || err_bit0 < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "negative bit offset");
+    if ((((uintptr_t)syn_w) | ((uintptr_t)err_w)) & 7) return fail(LDPC_ERR_INVALID_ARGUMENT, "word pointers must be 8-byte aligned");
+    if (batch == 0) { *done = true; return LDPC_OK; }
+    if ((d->s > 0 && !syn_w) || (d->n > 0 && !err_w) || !conv)
+        return fail(LDPC_ERR_INVALID_ARGUMENT, "syndrome_words/error_words/converged pointer is NULL");
+    return LDPC_OK;
+}
+
+extern "C" ldpc_status ldpc_bp_decode_batch_bits_device(ldpc_bp_decoder *d, int64_t batch, const uint64_t *d_syn_w,
+                                                        int64_t syn_bit0, uint64_t *d_err_w, int64_t err_bit0,
+                                                        uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)
+{
+    bool done;
+    ldpc_status st = bits_check_args(d, batch, d_syn_w, syn_bit0, d_err_w, err_bit0, d_conv, &done);
+    if (st != LDPC_OK || done) return st;
+    HIP_TRY(hipSetDevice(d->device));
+    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
+    hipStream_t stream = (hipStream_t)stream_v;
+    const long long ns = (long long)batch * d->s, nn = (long long)batch * d->n;
+    if ((st = d->bits_syn.ensure((size_t)std::max<long long>(ns, 16))) != LDPC_OK) return st;
+    if ((st = d->bits_err.ensure((size_t)std::max<long long>(nn, 16))) != LDPC_OK) return st;
+    const int slot = (int)(d->ncalls % ldpc_bp_decoder::kRing);   // the slot the byte entry below takes
+    for (hipEvent_t &e : d->bits_ev[slot])
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // the staging is the handle's: like the workspace it is used in call order, whatever streams the calls are given
+    if (d->last_ev && d->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, d->last_ev, 0));
+    d->last_stream = stream;
+    HIP_TRY(hipEventRecord(d->bits_ev[slot][0], stream));
+    if (ns > 0) {
+        const int grid = ldpc_bitio::grid_for((ns + 1023) >> 10, d->num_cus);
+        hipLaunchKernelGGL(ldpc_bitio::bits_to_bytes_kernel, dim3((unsigned)grid), dim3(ldpc_bitio::kThreads), 0, stream,
+                           (const ldpc_bitio::bu64 *)d_syn_w + (syn_bit0 >> 6), (int)(syn_bit0 & 63), (uint8_t *)d->bits_syn.p, ns);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint64_t calls_before = d->ncalls;
+    st = ldpc_bp_decode_batch_device(d, batch, (const uint8_t *)d->bits_syn.p, (uint8_t *)d->bits_err.p, d_conv, d_llr, d_iters, stream_v);
+    if (st != LDPC_OK) return st;
+    if (nn > 0) {
+        const int off = (int)(err_bit0 & 63);
+        const int grid = ldpc_bitio::grid_for((ldpc_bitio::words_covering(off, nn) + 14) / 15, d->num_cus);
+        hipLaunchKernelGGL(ldpc_bitio::bytes_to_bits_kernel, dim3((unsigned)grid), dim3(ldpc_bitio::kThreads), 0, stream,
+                           (const uint8_t *)d->bits_err.p, nn, (ldpc_bitio::bu64 *)d_err_w + (err_bit0 >> 6), off);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(d->bits_ev[slot][1], stream));
+    d->last_ev = d->bits_ev[slot][1];
+    d->bits_timed[slot] = d->ncalls == calls_before + 1;
+    return LDPC_OK;
+}
+
+namespace {
+// Bits [off, off + nbits) of src -> the same bits of dst (word 0 of both holds bit 0 of the numbering).  Interior words
+// are copied; a partial first / last word is merged under its mask with atomic and / or on the word, because the shards
+// of the multi-device entry merge from threads of their own and two neighbouring shards can share a word.
+void merge_bit_range(uint64_t *dst, const uint64_t *src, int off, size_t nbits)
+{
+    if (!nbits) return;
+    const size_t nw = ((size_t)off + nbits + 63) >> 6;
+    const int end = (int)(((size_t)off + nbits) & 63);
+    auto masked = [&](size_t q, uint64_t mask) {
+        (void)__atomic_fetch_and(&dst[q], ~mask, __ATOMIC_RELAXED);
+        (void)__atomic_fetch_or(&dst[q], src[q] & mask, __ATOMIC_RELAXED);
+    };
+    const uint64_t mfirst = ~(uint64_t)0 << off, mlast = end ? ((uint64_t)1 << end) - 1 : ~(uint64_t)0;
+    if (nw == 1) { masked(0, mfirst & mlast); return; }
+    size_t lo = 0, hi = nw;
+    if (off) { masked(0, mfirst); lo = 1; }
+    if (end) { masked(nw - 1, mlast); hi = nw - 1; }
+    if (hi > lo) parallel_memcpy(dst + lo, src + lo, (hi - lo) * sizeof(uint64_t));
+}
+}  // namespace
+
+static ldpc_status decode_batch_bits_host_impl(ldpc_bp_decoder *d, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
+                                               uint64_t *err_w, int64_t err_bit0, uint8_t *conv, double *llr, int32_t *iters)
+{
+    HIP_TRY(hipSetDevice(d->device));
+    const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
+    ldpc_status st;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    auto wbytes = [](size_t nbits) { return (((nbits + 63) >> 6) + 1) * sizeof(uint64_t); };   // words covering nbits at any offset
+    // one chunk of columns [b0, b0 + nb) in a host image hp: where its words lie in the caller's arrays
+    struct Span { size_t w0; int off; size_t nwords; };
+    auto span_of = [](int64_t bit0, size_t b0, size_t nb, size_t r) {
+        const size_t lo = (size_t)bit0 + b0 * r;
+        Span sp;
+        sp.w0 = lo >> 6; sp.off = (int)(lo & 63);
+        sp.nwords = nb * r ? (size_t)ldpc_bitio::words_covering(sp.off, (long long)(nb * r)) : 0;
+        return sp;
+    };
+    {
+        // Small batches (a plain decode! is batch = 1): one pinned image, one copy in, one copy out -- as the byte entry
+        const size_t o_err = up(wbytes(B * s)), o_conv = o_err + up(wbytes(B * n)), o_it = o_conv + up(B),
+                     o_llr = o_it + up(B * sizeof(int32_t)), total = o_llr + (llr ? up(B * n * sizeof(double)) : 0);
+        if (total <= ((size_t)4 << 20)) {
+            hipStream_t stream = nullptr;
+            if ((st = d->st_all.ensure(total)) != LDPC_OK) return st;
+            if (d->pin_cap < total) {
+                if (d->pin) (void)hipHostFree(d->pin);
+                d->pin = nullptr; d->pin_cap = 0;
+                HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
+                d->pin_cap = total;
+            }
+            char *hp = (char *)d->pin, *dp = (char *)d->st_all.p;
+            const Span ss = span_of(syn_bit0, 0, B, s), se = span_of(err_bit0, 0, B, n);
+            if (ss.nwords) {
+                std::memcpy(hp, syn_w + ss.w0, ss.nwords * sizeof(uint64_t));
+                HIP_TRY(hipMemcpyAsync(dp, hp, ss.nwords * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            }
+            st = ldpc_bp_decode_batch_bits_device(d, batch, (const uint64_t *)dp, ss.off, (uint64_t *)(dp + o_err), se.off,
+                                                  (uint8_t *)(dp + o_conv), llr ? (double *)(dp + o_llr) : nullptr,
+                                                  (int32_t *)(dp + o_it), stream);
+            if (st != LDPC_OK) return st;
+            HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
+            if ((st = ldpc_detail::wait_stream(stream, d->device, "ldpc_bp_decode_batch_bits (small batch: stream synchronise)")) != LDPC_OK) return st;
+            merge_bit_range(err_w + se.w0, (const uint64_t *)(hp + o_err), se.off, B * n);
+            std::memcpy(conv, hp + o_conv, B);
+            if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));
+            if (llr) std::memcpy(llr, hp + o_llr, B * n * sizeof(double));
+            return LDPC_OK;
+        }
+    }
+    // Large batches: the byte entry's 3-slot pipeline (pinned copy, H2D, decode, D2H, copy out) on word images.  A chunk
+    // of columns starts at any bit: its image holds the words that cover it, the device entry gets the offset into the
+    // first one, and the copy out merges the first / last word under a mask.
+    {
+        const size_t bps = (s + n + 7) / 8 + 1 + sizeof(int32_t) + (llr ? n * sizeof(double) : 0);   // bytes per syndrome, bit layout
+        const bool lds_path = d->variant != 1 && d->lds_logS[llr ? 1 : 0] >= 0;
+        size_t cb = ((size_t)24 << 20) / std::max<size_t>(bps, 1);
+        cb = std::max<size_t>(cb, lds_path ? 32768 : 65536);      // enough syndromes to fill the chip
+        cb = (cb + 4095) & ~(size_t)4095;
+        if (B < cb + cb / 2) cb = B;                               // no tiny trailing chunk
+        if (const char *e = exp_env("LDPC_BITS_CHUNK_SYNDROMES")) cb = (size_t)std::max<long>(1, std::atol(e));   // (tests: chunk borders inside words)
+        const size_t nchunks = (B + cb - 1) / cb;
+        const size_t o_err = up(wbytes(cb * s)), o_conv = o_err + up(wbytes(cb * n)), o_it = o_conv + up(cb),
+                     o_llr = o_it + up(cb * sizeof(int32_t)), total = o_llr + (llr ? up(cb * n * sizeof(double)) : 0);
+        for (int q = 0; q < 3; ++q)
+            if (!d->pipe_stream[q]) HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
+        for (auto &row : d->pipe_ev)
+            for (hipEvent_t &e : row)
+                if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        const int R = (int)std::min<size_t>(ldpc_bp_decoder::kPipe, nchunks);
+        for (int q = 0; q < R; ++q) {
+            if (d->bits_pin_cap[q] < total) {
+                if (d->bits_pin[q]) (void)hipHostFree(d->bits_pin[q]);
+                d->bits_pin[q] = nullptr; d->bits_pin_cap[q] = 0;
+                HIP_TRY(hipHostMalloc(&d->bits_pin[q], total, hipHostMallocDefault));
+                d->bits_pin_cap[q] = total;
+            }
+            if ((st = d->pipe_dev[q].ensure(total)) != LDPC_OK) return st;
+        }
+        hipStream_t s_in = d->pipe_stream[0], s_comp = d->pipe_stream[1], s_out = d->pipe_stream[2];
+        auto drain = [&](size_t j) -> ldpc_status {
+            const int slot = (int)(j % (size_t)R);
+            const size_t b0 = j * cb, nb = std::min(cb, B - b0);
+            {
+                const ldpc_status wst = ldpc_detail::wait_event(d->pipe_ev[slot][2], d->device, "ldpc_bp_decode_batch_bits (host pipeline: results of a chunk)");
+                if (wst != LDPC_OK) return wst;
+            }
+            const char *hp = (const char *)d->bits_pin[slot];
+            const Span se = span_of(err_bit0, b0, nb, n);
+            merge_bit_range(err_w + se.w0, (const uint64_t *)(hp + o_err), se.off, nb * n);
+            std::memcpy(conv + b0, hp + o_conv, nb);
+            if (iters) std::memcpy(iters + b0, hp + o_it, nb * sizeof(int32_t));
+            if (llr) parallel_memcpy(llr + b0 * n, hp + o_llr, nb * n * sizeof(double));
+            return LDPC_OK;
+        };
+        ldpc_status pst = LDPC_OK;
+        for (size_t k = 0; k < nchunks && pst == LDPC_OK; ++k) {
+            const int slot = (int)(k % (size_t)R);
+            const size_t b0 = k * cb, nb = std::min(cb, B - b0);
+            if (k >= (size_t)R && (pst = drain(k - R)) != LDPC_OK) break;
+            char *hp = (char *)d->bits_pin[slot], *dp = (char *)d->pipe_dev[slot].p;
+            const Span ss = span_of(syn_bit0, b0, nb, s), se = span_of(err_bit0, b0, nb, n);
+            hipError_t e = hipSuccess;
+            if (ss.nwords) {
+                parallel_memcpy(hp, syn_w + ss.w0, ss.nwords * sizeof(uint64_t));
+                e = hipMemcpyAsync(dp, hp, ss.nwords * sizeof(uint64_t), hipMemcpyHostToDevice, s_in);
+            }
+            if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][0], s_in);
+            if (e == hipSuccess) e = hipStreamWaitEvent(s_comp, d->pipe_ev[slot][0], 0);
+            if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, std::string("host pipeline of the bits entry (H2D): ") + hipGetErrorString(e)); break; }
+            pst = ldpc_bp_decode_batch_bits_device(d, (int64_t)nb, (const uint64_t *)dp, ss.off, (uint64_t *)(dp + o_err), se.off,
+                                                   (uint8_t *)(dp + o_conv), llr ? (double *)(dp + o_llr) : nullptr,
+                                                   (int32_t *)(dp + o_it), s_comp);
+            if (pst != LDPC_OK) break;
+            e = hipEventRecord(d->pipe_ev[slot][1], s_comp);
+            if (e == hipSuccess) e = hipStreamWaitEvent(s_out, d->pipe_ev[slot][1], 0);
+            if (e == hipSuccess) e = hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, s_out);
+            if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][2], s_out);
+            if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, std::string("host pipeline of the bits entry (D2H): ") + hipGetErrorString(e)); break; }
+        }
+        if (pst == LDPC_OK)
+            for (size_t j = nchunks > (size_t)R ? nchunks - R : 0; j < nchunks && pst == LDPC_OK; ++j) pst = drain(j);
+        if (pst != LDPC_OK) {
+            const std::string keep = g_err;
+            (void)ldpc_detail::wait_device(d->device, "ldpc_bp_decode_batch_bits (host pipeline: drain after an error)");   // nothing of this call may still be in flight when we return
+            g_err = keep;
+        }
+        return pst;
+    }
+}
+
+extern "C" ldpc_status ldpc_bp_decode_batch_bits(ldpc_bp_decoder *d, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
+                                                 uint64_t *err_w, int64_t err_bit0, uint8_t *conv, double *llr, int32_t *iters)
+{
+    bool done;
+    ldpc_status st = bits_check_args(d, batch, syn_w, syn_bit0, err_w, err_bit0, conv, &done);
+    if (st != LDPC_OK || done) return st;
+    st = decode_batch_bits_host_impl(d, batch, syn_w, syn_bit0, err_w, err_bit0, conv, llr, iters);
+    // synchronous, like ldpc_bp_decode_batch: a team that lost a workgroup is known by now -- decode once more without teams
+    if (st == LDPC_OK && report_team_fault(d) != LDPC_OK)
+        st = decode_batch_bits_host_impl(d, batch, syn_w, syn_bit0, err_w, err_bit0, conv, llr, iters);
+    return st;
+}
+
+extern "C" {
+
 ldpc_status ldpc_bp_last_status(ldpc_bp_decoder *d)
 {
     if (!d) return fail(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
@@ -2820,13 +3064,15 @@ ldpc_status ldpc_bp_call_timing(ldpc_bp_decoder *d, int32_t calls_back, double *
     if (!d->timed[slot]) return LDPC_OK;
     HIP_TRY(hipSetDevice(d->device));
     const int e0 = d->two_events[slot] ? 1 : 0, e3 = d->two_events[slot] ? 2 : 3;
+    const bool bits = d->bits_timed[slot];   // a bits entry: total_ms spans its two conversions as well
     {
-        const ldpc_status wst = ldpc_detail::wait_event(d->ev[slot][e3], d->device, "ldpc_bp_call_timing (wait for that call)");
+        const ldpc_status wst = ldpc_detail::wait_event(bits ? d->bits_ev[slot][1] : d->ev[slot][e3], d->device, "ldpc_bp_call_timing (wait for that call)");
         if (wst != LDPC_OK) return wst;
     }
     float a = 0.f, b = 0.f;
     HIP_TRY(hipEventElapsedTime(&a, d->ev[slot][1], d->ev[slot][2]));
-    HIP_TRY(hipEventElapsedTime(&b, d->ev[slot][e0], d->ev[slot][e3]));
+    if (bits) HIP_TRY(hipEventElapsedTime(&b, d->bits_ev[slot][0], d->bits_ev[slot][1]));
+    else HIP_TRY(hipEventElapsedTime(&b, d->ev[slot][e0], d->ev[slot][e3]));
     if (sweep_ms) *sweep_ms = a;
     if (total_ms) *total_ms = b;
     if (sum_iters) {

@@ -343,6 +343,43 @@ ldpc_status ldpc_bp_decode_batch_multi(ldpc_bp_multi *m, int64_t batch, const ui
     return LDPC_OK;
 }
 
+// ---- HOST form on bit-packed matrices (BitMatrix layout): the same sharding, the offsets move instead of the pointers
+ldpc_status ldpc_bp_decode_batch_multi_bits(ldpc_bp_multi *m, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
+                                            uint64_t *err_w, int64_t err_bit0, uint8_t *conv, double *llr, int32_t *iters)
+{
+    if (!m) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
+    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (syn_bit0 < 0 || err_bit0 < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative bit offset");
+    if ((((uintptr_t)syn_w) | ((uintptr_t)err_w)) & 7) return set_error(LDPC_ERR_INVALID_ARGUMENT, "word pointers must be 8-byte aligned");
+    if (batch == 0) return LDPC_OK;
+    if ((m->s > 0 && !syn_w) || (m->n > 0 && !err_w) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "syndrome_words/error_words/converged pointer is NULL");
+    m->timed = false;
+    const int G = m->ndev;
+    std::vector<ldpc_status> st((size_t)G, LDPC_OK);
+    std::vector<std::string> msg((size_t)G);
+    auto work = [&](int g) {
+        int64_t lo, hi;
+        shard_bounds(batch, G, g, &lo, &hi);
+        if (hi <= lo) return;
+        (void)hipSetDevice(m->dev[(size_t)g]);   // (the current device is a per-thread setting)
+        // a word that two shards share is merged atomically by each of them (ldpc_mi355x.hip, merge_bit_range)
+        st[(size_t)g] = ldpc_bp_decode_batch_bits(m->h[(size_t)g], hi - lo, syn_w, syn_bit0 + lo * m->s, err_w, err_bit0 + lo * m->n,
+                                                  conv + lo, llr ? llr + (size_t)lo * (size_t)m->n : nullptr, iters ? iters + lo : nullptr);
+        if (st[(size_t)g] != LDPC_OK) msg[(size_t)g] = ldpc_last_error();
+    };
+    if (G == 1) {
+        DeviceGuard guard;
+        work(0);
+    } else {
+        std::vector<std::thread> th;
+        for (int g = 0; g < G; ++g) th.emplace_back(work, g);
+        for (auto &t : th) t.join();
+    }
+    for (int g = 0; g < G; ++g)
+        if (st[(size_t)g] != LDPC_OK) return set_error(st[(size_t)g], "device " + std::to_string(m->dev[(size_t)g]) + " (shard " + std::to_string(g) + "): " + msg[(size_t)g]);
+    return LDPC_OK;
+}
+
 // ---- ROOT-DEVICE form
 ldpc_status ldpc_bp_decode_batch_multi_device(ldpc_bp_multi *m, int64_t batch, const uint8_t *d_syn, uint8_t *d_err,
                                               uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)

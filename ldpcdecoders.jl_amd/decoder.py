@@ -23,6 +23,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _capi
+from .bitmatrix import BitMatrix
 
 
 class AbstractDecoder:
@@ -243,6 +244,72 @@ class BeliefPropagationDecoder(AbstractDecoder):
                           llr.data_ptr() if llr is not None else None,
                           iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)))
 
+    # -- bit-packed (BitMatrix layout) entries --------------------------------
+    def decode_batch_bits_words(self, batch: int, syn_words: np.ndarray, syn_bit0: int, err_words: np.ndarray,
+                                err_bit0: int, want_llr: bool = False, want_iters: bool = False):
+        """ldpc_bp_decode_batch_bits (ldpc_bp_decode_batch_multi_bits with devices=) on host word vectors: the syndrome
+        bit of (check r, column i) is bit syn_bit0 + i*s + r of `syn_words`, the error bit of (bit j, column i) becomes
+        bit err_bit0 + i*n + j of `err_words` (uint64, written in place; no other bit changes).
+        Returns (converged [B] u8, llr [B][n] | None, iters [B] | None)."""
+        B = int(batch)
+        for w, bit0, r in ((syn_words, syn_bit0, self.s), (err_words, err_bit0, self.n)):
+            if not (isinstance(w, np.ndarray) and w.dtype == np.uint64 and w.ndim == 1 and w.flags.c_contiguous):
+                raise TypeError("word vectors must be contiguous one-dimensional uint64 arrays")
+            if B >= 0 and bit0 >= 0 and int(bit0) + B * r > 64 * w.size:
+                raise IndexError("the bit range ends behind the word vector")   # BoundsError
+        conv = np.empty(max(B, 0), dtype=np.uint8)
+        llr = np.empty((B, self.n), dtype=np.float64) if want_llr else None
+        its = np.empty(B, dtype=np.int32) if want_iters else None
+        entry, handle = ((self._L.ldpc_bp_decode_batch_multi_bits, self._m) if self._m
+                         else (self._L.ldpc_bp_decode_batch_bits, self._h))
+        self._check(entry(handle, B, syn_words.ctypes.data, int(syn_bit0), err_words.ctypes.data, int(err_bit0),
+                          conv.ctypes.data, llr.ctypes.data if want_llr else None, its.ctypes.data if want_iters else None))
+        return conv, llr, its
+
+    def decode_batch_bits_host(self, syn: BitMatrix, out: Optional[BitMatrix] = None, want_llr: bool = False,
+                               want_iters: bool = False):
+        """syn: BitMatrix s x B.  Returns (errors BitMatrix n x B, converged [B] u8, llr [B][n] | None, iters | None);
+        `out` = a BitMatrix n x B to write into (every element is overwritten, its trailing bits stay as they are)."""
+        if not isinstance(syn, BitMatrix):
+            raise TypeError("syn must be a BitMatrix")
+        if syn.rows != self.s:
+            raise AssertionError("syndrome length does not match the number of checks")
+        B = syn.cols
+        if out is None:
+            out = BitMatrix.zeros(self.n, B)
+        elif not isinstance(out, BitMatrix) or out.shape != (self.n, B):
+            raise AssertionError("out must be a BitMatrix of n x B")
+        conv, llr, its = self.decode_batch_bits_words(B, syn.chunks, 0, out.chunks, 0, want_llr, want_iters)
+        return out, conv, llr, its
+
+    def decode_batch_bits_device(self, batch: int, syn_words, syn_bit0: int, err_words, err_bit0: int, conv,
+                                 llr=None, iters=None, stream: Optional[int] = None) -> None:
+        """HBM-resident bit strings: `syn_words` / `err_words` are contiguous one-dimensional torch tensors of 64-bit
+        words (int64, or uint64 viewed as such) on the decoder's GPU, bit numbering as in decode_batch_bits_words;
+        conv [B] u8, llr [B][n] f64 | None, iters [B] i32 | None.  Asynchronous on `stream` (ldpc_bp_decode_batch_bits_device)."""
+        import torch
+
+        if self._m:
+            raise _capi.LdpcError(5, "decode_batch_bits_device: there is no root-device form of the bits entry "
+                                     "(shard borders fall inside words; use decode_batch_bits_host with devices=, "
+                                     "or a single-device decoder)")
+        B = int(batch)
+        for w in (syn_words, err_words):
+            assert w.is_cuda and w.dim() == 1 and w.is_contiguous() and w.element_size() == 8 and not w.dtype.is_floating_point
+        assert syn_bit0 >= 0 and int(syn_bit0) + B * self.s <= 64 * syn_words.numel()
+        assert err_bit0 >= 0 and int(err_bit0) + B * self.n <= 64 * err_words.numel()
+        assert conv.is_cuda and conv.dtype == torch.uint8 and conv.is_contiguous() and conv.numel() == B
+        if llr is not None:
+            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
+        if iters is not None:
+            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
+        if stream is None:
+            stream = torch.cuda.current_stream(conv.device).cuda_stream
+        self._check(self._L.ldpc_bp_decode_batch_bits_device(
+            self._h, B, syn_words.data_ptr(), int(syn_bit0), err_words.data_ptr(), int(err_bit0), conv.data_ptr(),
+            llr.data_ptr() if llr is not None else None, iters.data_ptr() if iters is not None else None,
+            ctypes.c_void_p(stream)))
+
     # -- reference interface (methods; free functions below) ----------------
     def decode_(self, syndrome):
         return decode_(self, syndrome)
@@ -283,6 +350,8 @@ def batchdecode_(decoder: AbstractDecoder, syndromes, errors, success=None):
     ``errors`` is ``n x B`` and is overwritten; ``success`` (length B, bool) is
     allocated when omitted (abstract_decoder.jl:44-48).  Returns
     ``(errors, success)``."""
+    if isinstance(syndromes, BitMatrix) or isinstance(errors, BitMatrix):
+        return _batchdecode_bits(decoder, syndromes, errors, success)
     syndromes = np.asarray(syndromes) if not isinstance(syndromes, np.ndarray) else syndromes
     if syndromes.ndim != 2 or errors.ndim != 2:
         raise TypeError("syndromes and errors must be matrices")
@@ -310,5 +379,51 @@ def batchdecode_(decoder: AbstractDecoder, syndromes, errors, success=None):
         # the whole batch are not shipped back for that, the last column is re-decoded alone
         _, _, llr, _ = decoder.decode_batch_host(syn_bs[-1:], want_llr=True)
         decoder.scratch.err[:] = err[-1]
+        decoder.scratch.log_probabs[:] = llr[0]
+    return errors, success
+
+
+def _batchdecode_bits(decoder, syndromes, errors, success):
+    """batchdecode_ when `syndromes` and / or `errors` is a BitMatrix: that argument goes to the bits entry as it is
+    (no dense copy of it is made).  A dense `syndromes` next to a BitMatrix `errors` -- the shape of the reference's
+    doctest -- is packed once."""
+    if not isinstance(syndromes, BitMatrix):
+        syndromes = np.asarray(syndromes)
+    if syndromes.ndim != 2 or errors.ndim != 2:
+        raise TypeError("syndromes and errors must be matrices")
+    B = syndromes.shape[1]
+    if success is None:
+        success = np.empty(B, dtype=np.bool_)
+    assert syndromes.shape[1] == errors.shape[1]                  # :221
+    assert syndromes.shape[1] == len(success)                     # :222
+    if not isinstance(decoder, BeliefPropagationDecoder):
+        # the generic per-column loop (abstract_decoder.jl:31-42) works on dense columns
+        dense_syn = syndromes.to_dense() if isinstance(syndromes, BitMatrix) else syndromes
+        dense_err = np.zeros(errors.shape, dtype=np.uint8) if isinstance(errors, BitMatrix) else errors
+        _, success = batchdecode_(decoder, dense_syn, dense_err, success)
+        if isinstance(errors, BitMatrix):
+            errors.chunks[:] = BitMatrix.from_dense(dense_err).chunks
+        return errors, success
+    if syndromes.shape[0] != decoder.s or errors.shape[0] != decoder.n:
+        raise IndexError("syndromes/errors row count does not match the decoder")
+    if not isinstance(syndromes, BitMatrix):
+        syn_u8 = syndrome_bytes(syndromes)
+        if syn_u8.size and syn_u8.max() > 1:
+            # entries other than 0/1 (never matched, :181) have no bit form: the byte entry decodes, the result is packed
+            dense_err = np.zeros(errors.shape, dtype=np.uint8)
+            _, success = batchdecode_(decoder, syndromes, dense_err, success)
+            errors.chunks[:] = BitMatrix.from_dense(dense_err).chunks
+            return errors, success
+        syndromes = BitMatrix.from_dense(syn_u8)                  # np.packbits, once
+    out = errors if isinstance(errors, BitMatrix) else BitMatrix.zeros(decoder.n, B)
+    _, conv, _, _ = decoder.decode_batch_bits_host(syndromes, out=out)
+    if out is not errors:
+        errors[:, :] = out.to_dense()                             # 0/1 -> eltype(errors)  (:227)
+    success[:] = conv.astype(np.bool_)                            # :226
+    if B > 0:
+        # the scratch holds the last column's result, as after the reference's loop: that column is decoded alone
+        last = BitMatrix.zeros(decoder.n, 1)
+        _, llr, _ = decoder.decode_batch_bits_words(1, syndromes.chunks, (B - 1) * decoder.s, last.chunks, 0, want_llr=True)
+        decoder.scratch.err[:] = last.column(0)
         decoder.scratch.log_probabs[:] = llr[0]
     return errors, success

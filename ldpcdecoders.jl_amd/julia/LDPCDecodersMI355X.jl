@@ -17,6 +17,7 @@
 module LDPCDecodersMI355X
 
 using SparseArrays
+import Libdl
 import LDPCDecoders
 import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 
@@ -60,6 +61,8 @@ mutable struct MI355XBeliefPropagationDecoder <: AbstractDecoder
     syn_u8::Vector{UInt8}
     err_u8::Vector{UInt8}
     conv_u8::Vector{UInt8}
+    syn_bits::BitVector      # reusable packed images for the bits entry (bit_io.jl)
+    err_bits::BitVector
 end
 
 """
@@ -99,7 +102,7 @@ function MI355XBeliefPropagationDecoder(H, per::Float64, max_iters::Int; device:
         h[] = ccall((:ldpc_bp_multi_handle, libldpc), Ptr{Cvoid}, (Ptr{Cvoid}, Int32), m, 0)
     end
     d = MI355XBeliefPropagationDecoder(per, max_iters, s, n, sparse_H, sparse_HT,
-            MI355XScratch(zeros(n), fill(per, n), zeros(n)), h[], m, UInt8[], UInt8[], UInt8[])
+            MI355XScratch(zeros(n), fill(per, n), zeros(n)), h[], m, UInt8[], UInt8[], UInt8[], BitVector(), BitVector())
     finalizer(d) do x
         if x.multi != C_NULL
             ccall((:ldpc_bp_destroy_multi, libldpc), Cint, (Ptr{Cvoid},), x.multi)   # (owns every per-GPU handle)
@@ -158,6 +161,24 @@ function decode!(d::MI355XBeliefPropagationDecoder, syndrome::AbstractVector)   
     return d.scratch.err, d.conv_u8[1] != 0                   # alias of the scratch, like :187
 end
 
+# the two host entries on explicit pointers (bit_io.jl chooses between them by the argument types)
+bytes_call(d::MI355XBeliefPropagationDecoder, B, syn, err, conv, llr) = d.multi != C_NULL ?
+    ccall((:ldpc_bp_decode_batch_multi, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          d.multi, B, syn, err, conv, llr, C_NULL) :
+    ccall((:ldpc_bp_decode_batch, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          d.handle, B, syn, err, conv, llr, C_NULL)
+bits_call(d::MI355XBeliefPropagationDecoder, B, synw, sbit0, errw, ebit0, conv, llr) = d.multi != C_NULL ?
+    ccall((:ldpc_bp_decode_batch_multi_bits, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt64}, Int64, Ptr{UInt64}, Int64, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          d.multi, B, synw, sbit0, errw, ebit0, conv, llr, C_NULL) :
+    ccall((:ldpc_bp_decode_batch_bits, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt64}, Int64, Ptr{UInt64}, Int64, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          d.handle, B, synw, sbit0, errw, ebit0, conv, llr, C_NULL)
+
+include(joinpath(@__DIR__, "bit_io.jl"))
+
 function batchdecode!(d::MI355XBeliefPropagationDecoder, syndromes::AbstractMatrix,
                       errors::AbstractMatrix, success::AbstractVector{Bool})   # :220-231
     @assert size(syndromes, 2) == size(errors, 2)             # :221
@@ -166,35 +187,12 @@ function batchdecode!(d::MI355XBeliefPropagationDecoder, syndromes::AbstractMatr
     size(syndromes, 1) == d.s || throw(DimensionMismatch("syndromes has $(size(syndromes,1)) rows, decoder has $(d.s) checks"))
     size(errors, 1) == d.n || throw(DimensionMismatch("errors has $(size(errors,1)) rows, decoder has $(d.n) bits"))
     B == 0 && return errors, success
-    resize!(d.syn_u8, d.s * B); resize!(d.err_u8, d.n * B); resize!(d.conv_u8, B)
-    # BitMatrix / Matrix{Int} / views are normalised to the ABI's byte image; column i of the
-    # s x B matrix is the i-th contiguous run of s bytes
-    @inbounds for i in 1:B, r in 1:d.s
-        d.syn_u8[(i - 1) * d.s + r] = syndrome_byte(syndromes[r, i])
-    end
-    check(host_decode(d, B, Ptr{Float64}(C_NULL)))            # one call, one matrix -- on one GPU or partitioned over `devices`
-    @inbounds for i in 1:B
-        success[i] = d.conv_u8[i] != 0                        # :226
-        for j in 1:d.n
-            errors[j, i] = d.err_u8[(i - 1) * d.n + j]        # :227 (0/1 -> eltype(errors))
-        end
-    end
-    # the reference's per-column loop (:224-228) leaves the scratch with the LAST column's decision and LLRs: the
-    # decision is in hand, the LLRs come from a second call on that one column (deterministic per syndrome)
-    @inbounds for j in 1:d.n
-        d.scratch.err[j] = d.err_u8[(B - 1) * d.n + j]
-    end
-    GC.@preserve d begin
-        last_err = Vector{UInt8}(undef, d.n); last_conv = Vector{UInt8}(undef, 1)
-        syn_last = pointer(d.syn_u8, (B - 1) * d.s + 1)
-        check(d.multi != C_NULL ?
-              ccall((:ldpc_bp_decode_batch_multi, libldpc), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-                    d.multi, 1, syn_last, last_err, last_conv, d.scratch.log_probabs, C_NULL) :
-              ccall((:ldpc_bp_decode_batch, libldpc), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-                    d.handle, 1, syn_last, last_err, last_conv, d.scratch.log_probabs, C_NULL))
-    end
+    # one call, one matrix -- on one GPU or partitioned over `devices`.  BitMatrix arguments go to the bits entry in
+    # place, Matrix{UInt8} / Matrix{Bool} to the byte entry in place, anything else is packed once (bit_io.jl)
+    marshal_batchdecode!(d, d.s, d.n, syndromes, errors, success)
+    # the reference's per-column loop (:224-228) leaves the scratch with the LAST column's decision and LLRs: that
+    # column is decoded once more alone (deterministic per syndrome)
+    last_column!(d, d.s, d.n, syndromes, d.scratch.err, d.scratch.log_probabs)
     return errors, success                                    # :230
 end
 

@@ -30,6 +30,7 @@
 module LDPCDecodersMI355XDropIn
 
 using SparseArrays
+import Libdl
 import LDPCDecoders
 import LDPCDecoders: BeliefPropagationDecoder
 
@@ -48,6 +49,8 @@ mutable struct Handle
     syn_u8::Vector{UInt8}
     err_u8::Vector{UInt8}
     conv_u8::Vector{UInt8}
+    syn_bits::BitVector      # reusable packed images for the bits entry (bit_io.jl)
+    err_bits::BitVector
 end
 
 # GPUs that decoders created from now on partition their batches over (empty: the current device)
@@ -80,7 +83,7 @@ function handle_of(d::BeliefPropagationDecoder)
                             (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Float64, Int64, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
                             d.s, d.n, length(rowval), colptr, rowval, d.per, d.max_iters, opts, h))
             end
-            hd = Handle(h[], multi, UInt8[], UInt8[], UInt8[])
+            hd = Handle(h[], multi, UInt8[], UInt8[], UInt8[], BitVector(), BitVector())
             finalizer(hd) do x
                 if x.ptr != C_NULL
                     x.multi ? ccall((:ldpc_bp_destroy_multi, libldpc), Cint, (Ptr{Cvoid},), x.ptr) :
@@ -123,6 +126,24 @@ function LDPCDecoders.decode!(d::BeliefPropagationDecoder, syndrome::AbstractVec
     return d.scratch.err, h.conv_u8[1] != 0                                                # the alias of :187
 end
 
+# the two host entries on explicit pointers (bit_io.jl chooses between them by the argument types)
+bytes_call(h::Handle, B, syn, err, conv, llr) = h.multi ?
+    ccall((:ldpc_bp_decode_batch_multi, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          h.ptr, B, syn, err, conv, llr, C_NULL) :
+    ccall((:ldpc_bp_decode_batch, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          h.ptr, B, syn, err, conv, llr, C_NULL)
+bits_call(h::Handle, B, synw, sbit0, errw, ebit0, conv, llr) = h.multi ?
+    ccall((:ldpc_bp_decode_batch_multi_bits, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt64}, Int64, Ptr{UInt64}, Int64, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          h.ptr, B, synw, sbit0, errw, ebit0, conv, llr, C_NULL) :
+    ccall((:ldpc_bp_decode_batch_bits, libldpc), Cint,
+          (Ptr{Cvoid}, Int64, Ptr{UInt64}, Int64, Ptr{UInt64}, Int64, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+          h.ptr, B, synw, sbit0, errw, ebit0, conv, llr, C_NULL)
+
+include(joinpath(@__DIR__, "bit_io.jl"))
+
 function LDPCDecoders.batchdecode!(d::BeliefPropagationDecoder, syndromes::AbstractMatrix,
                                    errors::AbstractMatrix, success::AbstractVector{Bool})   # overwrites :220-231
     @assert size(syndromes, 2) == size(errors, 2)                                          # :221
@@ -130,36 +151,13 @@ function LDPCDecoders.batchdecode!(d::BeliefPropagationDecoder, syndromes::Abstr
     B = size(syndromes, 2)
     B == 0 && return errors, success
     h = handle_of(d)
-    resize!(h.syn_u8, d.s * B); resize!(h.err_u8, d.n * B); resize!(h.conv_u8, B)
-    @inbounds for i in 1:B, r in 1:d.s
-        h.syn_u8[(i - 1) * d.s + r] = syndrome_byte(syndromes[r, i])
-    end
-    check(decode_batch(h, B, Ptr{Float64}(C_NULL)))
-    @inbounds for i in 1:B
-        success[i] = h.conv_u8[i] != 0                                                     # :226
-        for j in 1:d.n
-            errors[j, i] = h.err_u8[(i - 1) * d.n + j]                                     # :227
-        end
-    end
+    # BitMatrix arguments (the reference's doctest and test pass `errors` as one) go to the bits entry in place,
+    # Matrix{UInt8} / Matrix{Bool} to the byte entry in place, anything else is packed once: bit_io.jl
+    marshal_batchdecode!(h, d.s, d.n, syndromes, errors, success)
     # The reference leaves the scratch holding the LAST column's state (:224-228 runs decode! per column, and decode!
-    # fills scratch.err and scratch.log_probabs, :163-168): `scratch.err` gets that column's decision, and
-    # `scratch.log_probabs` its LLRs -- asked for from the library for that one column alone (a second call with
-    # batch = 1 on the bytes already marshalled: the decoder is deterministic per syndrome, so these are the LLRs of the
-    # decode above; shipping 8 n bytes back for EVERY column would double the batch call's I/O for nothing)
-    @inbounds for j in 1:d.n
-        d.scratch.err[j] = h.err_u8[(B - 1) * d.n + j]
-    end
-    GC.@preserve h begin
-        last_err = Vector{UInt8}(undef, d.n); last_conv = Vector{UInt8}(undef, 1)
-        syn_last = pointer(h.syn_u8, (B - 1) * d.s + 1)
-        check(h.multi ?
-              ccall((:ldpc_bp_decode_batch_multi, libldpc), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-                    h.ptr, 1, syn_last, last_err, last_conv, d.scratch.log_probabs, C_NULL) :
-              ccall((:ldpc_bp_decode_batch, libldpc), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
-                    h.ptr, 1, syn_last, last_err, last_conv, d.scratch.log_probabs, C_NULL))
-    end
+    # fills scratch.err and scratch.log_probabs, :163-168): that one column is decoded once more alone, with LLRs (the
+    # decoder is deterministic per syndrome; shipping 8 n bytes back for EVERY column would double the call's I/O)
+    last_column!(h, d.s, d.n, syndromes, d.scratch.err, d.scratch.log_probabs)
     return errors, success                                                                 # :230
 end
 
