@@ -392,6 +392,76 @@ ldpc_status ldpc_bpots_decode_batch_device(ldpc_bpots_decoder *dec, int64_t batc
                                            uint8_t *d_errors, uint8_t *d_converged, int32_t *d_iters,
                                            void *stream);
 
+/* ------------------------------------------------------------------------
+ * Bit-flip decoder: `BitFlipDecoder(H, per, max_iters)` (src/decoders/iterative_bitflip.jl:61-68), the reference's
+ * fourth exported decoder.  Per syndrome, with err = 0 and votes = 0 once (reset!, :84-88), for iter = 1 .. max_iters:
+ *   1. H * err mod 2 == syndrome: converged, stop (:122-127).  An entry other than 0/1 can never be equal.
+ *   2. every check adds +1 (mismatched) or -1 (matched) to the vote of each of its bits (:131-143); the votes are NOT
+ *      cleared between iterations.
+ *   3. if the largest vote is >= 0, ONE bit among those that hold it is toggled (:145-149); otherwise the loop stops
+ *      and reports converged = true although the syndrome is not matched (:150-152: what the code does).
+ * Everything but the choice in step 3 -- `rand(max_idxs)` in the reference -- is integer arithmetic with one legal
+ * outcome, so the output is the reference's for SOME realisation of its rand calls, and this header says which:
+ *
+ * The tie rule.  The candidates (bits whose vote equals the maximum) are ordered by ascending bit index, k of them.
+ * LDPC_BF_TIE_FIRST takes candidate 0, LDPC_BF_TIE_LAST candidate k - 1.  LDPC_BF_TIE_RANDOM (default) takes candidate
+ *     ((r >> 32) * k) >> 32,   r = mix(mix(seed + 0x9E3779B97F4A7C15 * (column0 + i + 1)) + iter)
+ * in uint64 arithmetic, where mix is the SplitMix64 finaliser
+ *     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ * i is the column's index in the call and iter the 1-based iteration.  No state is carried from call to call: column i
+ * of a call with column0 = c is decoded exactly like column 0 of a call with column0 = c + i, whatever kernel, chunking
+ * or stream is used.
+ *
+ * These entries were added WITHOUT a change of LDPC_MI355X_ABI_VERSION (they only add symbols): a caller detects them
+ * by symbol lookup, like the bits entries.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_bitflip_decoder ldpc_bitflip_decoder;
+
+enum { LDPC_BF_TIE_RANDOM = 0, LDPC_BF_TIE_FIRST = 1, LDPC_BF_TIE_LAST = 2 };
+
+/* Optional; pass NULL to ldpc_bitflip_create for defaults (current device, LDPC_BF_TIE_RANDOM, seed 0, auto). */
+typedef struct ldpc_bitflip_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    int32_t tie_break;       /* LDPC_BF_TIE_* */
+    uint64_t seed;           /* of the RANDOM rule */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2, 3 force that tier of ldpc_bitflip_kernel (1, 2: LDPC_ERR_UNSUPPORTED when
+                                the state of a syndrome does not fit it) */
+    int32_t reserved[11];
+} ldpc_bitflip_options;
+
+/* H as the zero-based CSC pattern with the checks of ldpc_bp_create (ascending rows, in range).  EVERY stored entry is
+ * an edge: the reference reads the stored values (`sparse_H[i, j]`, `sparse_H * err`), so a caller that holds stored
+ * `false` entries drops them first (`dropzeros`; both Julia shims do).  `per` is stored, nothing computes with it (as
+ * in the reference).  The vote accumulators are exact: 32-bit when max_iters * (largest bit degree) < 2^31, 64-bit
+ * otherwise.  tie_break outside 0..2 / kernel_variant outside 0..3: LDPC_ERR_INVALID_ARGUMENT. */
+ldpc_status ldpc_bitflip_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
+                                double per, int64_t max_iters, const ldpc_bitflip_options *options,
+                                ldpc_bitflip_decoder **out);
+ldpc_status ldpc_bitflip_destroy(ldpc_bitflip_decoder *dec);
+/* Which tier this decoder's graph takes: 1 = on-chip (state in LDS), one wave per syndrome (n <= 2048, <= 40 KiB of
+ * state); 2 = on-chip, one 16-wave workgroup per syndrome (<= 159 KiB of state: 9 n + s + n / 16 bytes); 3 = unlimited
+ * (state in a global workspace; any H with nnz < 2^28); 4 = unlimited with 64-bit votes; 0 for NULL. */
+int32_t ldpc_bitflip_kernel(const ldpc_bitflip_decoder *dec);
+
+/* Replaces `batchdecode!(decoder::BitFlipDecoder, syndromes, errors, converged)` (:189-201) and, with batch = 1,
+ * `decode!` (:116-157).  HOST buffers, laid out as for ldpc_bp_decode_batch.
+ *   syndromes   [batch][s] uint8  in
+ *   errors      [batch][n] uint8  out: err (:156)
+ *   converged   [batch]    uint8  out: the reference's flag (1 for stop reasons 1 AND 2)
+ *   iters       [batch]    int32  out, may be NULL: loop iterations entered (the one that stops counts; 0 for max_iters = 0)
+ *   stop_reason [batch]    uint8  out, may be NULL: 0 = ran out of iterations, 1 = syndrome matched, 2 = no bit with a
+ *                                 non-negative vote (with n = 0 there is no bit at all: reason 2 as well)
+ *   column0 >= 0: the number the first column of this call carries in the tie rule above.
+ * max_iters = 0: zeros, converged = 0.  batch = 0: LDPC_OK, nothing touched.  A NULL handle, a negative batch or
+ * column0, a NULL pointer where ldpc_bp_decode_batch rejects one: LDPC_ERR_INVALID_ARGUMENT before any device work. */
+ldpc_status ldpc_bitflip_decode_batch(ldpc_bitflip_decoder *dec, int64_t batch, int64_t column0, const uint8_t *syndromes,
+                                      uint8_t *errors, uint8_t *converged, int32_t *iters, uint8_t *stop_reason);
+/* Same with DEVICE pointers, asynchronous on `stream`; calls on one handle execute in call order: a call given another
+ * stream than its predecessor waits (on the device) for that predecessor first. */
+ldpc_status ldpc_bitflip_decode_batch_device(ldpc_bitflip_decoder *dec, int64_t batch, int64_t column0,
+                                             const uint8_t *d_syndromes, uint8_t *d_errors, uint8_t *d_converged,
+                                             int32_t *d_iters, uint8_t *d_stop_reason, void *stream);
+
 /* Diagnostics: 100 MHz ticks spent in {check sweep, variable sweep, convergence test}
  * of that call, summed over workgroups (one sampling wave each). */
 ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *dec, int32_t calls_back, uint64_t ticks[3]);

@@ -63,6 +63,11 @@ EXPORTED_SYMBOLS = (
     "ldpc_bpots_kernel",
     "ldpc_bpots_decode_batch",
     "ldpc_bpots_decode_batch_device",
+    "ldpc_bitflip_create",
+    "ldpc_bitflip_destroy",
+    "ldpc_bitflip_kernel",
+    "ldpc_bitflip_decode_batch",
+    "ldpc_bitflip_decode_batch_device",
 )
 # ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
 DEBUG_SYMBOLS = ("ldpc_debug_team_rows", "ldpc_debug_team_plan", "ldpc_debug_div_check", "ldpc_debug_process_state",
@@ -109,10 +114,20 @@ class BPOptions(ctypes.Structure):
     ]
 
 
+BF_TIE_RANDOM, BF_TIE_FIRST, BF_TIE_LAST = 0, 1, 2
+
+
+class BitFlipOptions(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32), ("tie_break", ctypes.c_int32), ("seed", ctypes.c_uint64),
+        ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 11),
+    ]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "osd_host.cpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "osd_host.cpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -226,6 +241,16 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_bpots_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp]
     L.ldpc_bpots_decode_batch_device.restype = i32
     L.ldpc_bpots_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    L.ldpc_bitflip_create.restype = i32
+    L.ldpc_bitflip_create.argtypes = [i64, i64, i64, vp, vp, f64, i64, ctypes.POINTER(BitFlipOptions), ctypes.POINTER(vp)]
+    L.ldpc_bitflip_destroy.restype = i32
+    L.ldpc_bitflip_destroy.argtypes = [vp]
+    L.ldpc_bitflip_kernel.restype = i32
+    L.ldpc_bitflip_kernel.argtypes = [vp]
+    L.ldpc_bitflip_decode_batch.restype = i32
+    L.ldpc_bitflip_decode_batch.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp]
+    L.ldpc_bitflip_decode_batch_device.restype = i32
+    L.ldpc_bitflip_decode_batch_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
     L.ldpc_debug_process_state.restype = vp
     L.ldpc_debug_adopt_process_state.restype = i32
     L.ldpc_debug_adopt_process_state.argtypes = [vp]

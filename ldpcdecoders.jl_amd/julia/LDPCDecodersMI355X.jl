@@ -21,7 +21,7 @@ import Libdl
 import LDPCDecoders
 import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 
-export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder
+export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder, MI355XBitFlipDecoder
 
 const libldpc = get(ENV, "LDPC_MI355X_LIB", "libldpc_mi355x.so")
 
@@ -305,5 +305,92 @@ function decode!(d::MI355XBPOTSDecoder, syndrome::AbstractVector)               
 end
 # batchdecode! on it is the reference's generic per-column method (abstract_decoder.jl:31-48);
 # a batched override would call ldpc_bpots_decode_batch with B columns exactly like the BP type above.
+
+# ---------------------------------------------------------------------------------------------
+# Bit flip (src/decoders/iterative_bitflip.jl:61-68, 116-201) over ldpc_bitflip_*.  The reference breaks ties among the
+# bits with the largest vote with `rand`; the library's tie rule (include/ldpc_mi355x.h) is a function of (seed, column
+# number, iteration): the decoder numbers the columns it decodes (`columns_decoded`), so repeated decode! calls on one
+# syndrome draw fresh tie-breaks and a fixed seed replays a session.
+# ---------------------------------------------------------------------------------------------
+mutable struct MI355XBitFlipDecoder <: AbstractDecoder
+    per::Float64; max_iters::Int; s::Int; n::Int
+    sparse_H::SparseMatrixCSC{Bool,Int}
+    err::Vector{Int}
+    columns_decoded::Int64
+    handle::Ptr{Cvoid}
+end
+
+"ldpc_bitflip_options: int32 device, int32 tie_break, uint64 seed, int32 kernel_variant, int32 reserved[11] (64 bytes)"
+function bitflip_options(device::Integer, tie_break::Integer, seed::Integer, kernel_variant::Integer)
+    opts = zeros(Int32, 16)
+    opts[1] = Int32(device); opts[2] = Int32(tie_break); opts[5] = Int32(kernel_variant)
+    sd = UInt64(seed)
+    opts[3] = reinterpret(Int32, UInt32(sd & 0xffffffff)); opts[4] = reinterpret(Int32, UInt32(sd >> 32))   # little-endian
+    return opts
+end
+
+"""
+    MI355XBitFlipDecoder(H, per, max_iters; tie_break=0, seed=0, device=-1, kernel_variant=0)
+
+`tie_break`: 0 random (seeded), 1 first, 2 last candidate in ascending bit order.
+"""
+function MI355XBitFlipDecoder(H, per::Float64, max_iters::Int; tie_break::Integer=0, seed::Integer=0,
+                              device::Integer=-1, kernel_variant::Integer=0)
+    s, n = size(H)
+    sp = dropzeros(SparseMatrixCSC{Bool,Int}(sparse(H)))      # only `true` entries count (`sparse_H[i, j]`, :135)
+    colptr = Int64.(sp.colptr .- 1); rowval = Int64.(rowvals(sp) .- 1)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:ldpc_bitflip_create, libldpc), Cint,
+                (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Float64, Int64, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                s, n, length(rowval), colptr, rowval, per, max_iters, bitflip_options(device, tie_break, seed, kernel_variant), h))
+    d = MI355XBitFlipDecoder(per, max_iters, s, n, sp, zeros(Int, n), 0, h[])
+    finalizer(d) do x
+        x.handle != C_NULL && ccall((:ldpc_bitflip_destroy, libldpc), Cint, (Ptr{Cvoid},), x.handle)
+        x.handle = C_NULL
+    end
+    return d
+end
+
+reset!(d::MI355XBitFlipDecoder) = d     # :84-88: the device state is reset inside every decode call
+
+bitflip_call(handle, B, column0, syn, err, conv) =
+    check(ccall((:ldpc_bitflip_decode_batch, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int32}, Ptr{UInt8}),
+                handle, B, column0, syn, err, conv, C_NULL, C_NULL))
+
+function decode!(d::MI355XBitFlipDecoder, syndrome::AbstractVector)                    # :116-157
+    length(syndrome) == d.s || throw(BoundsError(syndrome, d.s))
+    syn = UInt8[syndrome_byte(x) for x in syndrome]
+    err = Vector{UInt8}(undef, d.n); conv = Vector{UInt8}(undef, 1)
+    bitflip_call(d.handle, 1, d.columns_decoded, syn, err, conv)
+    d.columns_decoded += 1
+    d.err .= err
+    return d.err, conv[1] != 0            # (setup.err, converged)
+end
+
+# 0/1 bytes already: Matrix{UInt8} and Matrix{Bool} are the ABI's [B][s] image and go through without a conversion loop
+bitflip_image(syndromes::Matrix{UInt8}) = all(x -> x <= 0x01, syndromes) ? syndromes : map(syndrome_byte, syndromes)
+bitflip_image(syndromes::Matrix{Bool}) = reinterpret(UInt8, syndromes)
+bitflip_image(syndromes::AbstractMatrix) = UInt8[syndrome_byte(x) for x in syndromes]
+
+function batchdecode!(d::MI355XBitFlipDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix,
+                      converged::AbstractVector{Bool})                                 # :189-201, one device call
+    @assert size(syndromes, 2) == size(errors, 2)
+    @assert size(syndromes, 2) == length(converged)
+    size(syndromes, 1) == d.s && size(errors, 1) == d.n || throw(DimensionMismatch("syndromes / errors rows"))
+    B = size(syndromes, 2)
+    B == 0 && return errors, converged
+    direct = errors isa Matrix{UInt8} || errors isa Matrix{Bool}
+    err = direct ? reinterpret(UInt8, errors) : Matrix{UInt8}(undef, d.n, B)
+    conv = Vector{UInt8}(undef, B)
+    bitflip_call(d.handle, B, d.columns_decoded, bitflip_image(syndromes), err, conv)
+    d.columns_decoded += B
+    direct || (errors .= err)
+    converged .= conv .!= 0
+    d.err .= view(err, :, B)
+    return errors, converged
+end
+batchdecode!(d::MI355XBitFlipDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix) =
+    batchdecode!(d, syndromes, errors, Vector{Bool}(undef, size(syndromes, 2)))
 
 end # module

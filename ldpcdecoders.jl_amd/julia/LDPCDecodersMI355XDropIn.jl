@@ -32,7 +32,7 @@ module LDPCDecodersMI355XDropIn
 using SparseArrays
 import Libdl
 import LDPCDecoders
-import LDPCDecoders: BeliefPropagationDecoder
+import LDPCDecoders: BeliefPropagationDecoder, BitFlipDecoder
 
 const libldpc = get(ENV, "LDPC_MI355X_LIB", "libldpc_mi355x.so")
 
@@ -159,6 +159,81 @@ function LDPCDecoders.batchdecode!(d::BeliefPropagationDecoder, syndromes::Abstr
     # decoder is deterministic per syndrome; shipping 8 n bytes back for EVERY column would double the call's I/O)
     last_column!(h, d.s, d.n, syndromes, d.scratch.err, d.scratch.log_probabs)
     return errors, success                                                                 # :230
+end
+
+# ---------------------------------------------------------------------------------------------
+# The reference's own BitFlipDecoder (src/decoders/iterative_bitflip.jl:35-59) over ldpc_bitflip_*.  Its struct is
+# immutable too; the handle table is keyed like the BP one, on a vector every decoder owns exactly one of
+# (`scratch.votes`).  The `rand(max_idxs)` of :148 becomes the library's tie rule (include/ldpc_mi355x.h): random with
+# BITFLIP_SEED[], columns numbered per handle, so repeated calls draw fresh tie-breaks.
+# ---------------------------------------------------------------------------------------------
+mutable struct BitFlipHandle
+    ptr::Ptr{Cvoid}          # ldpc_bitflip_decoder*
+    columns_decoded::Int64
+end
+
+const BITFLIP_SEED = Ref{UInt64}(0)      # seed of decoders whose handle is created from now on
+const BITFLIP_HANDLES = WeakKeyDict{Vector{Int64},BitFlipHandle}()
+
+function handle_of(d::BitFlipDecoder)
+    lock(HANDLES_LOCK) do
+        get!(BITFLIP_HANDLES, d.scratch.votes) do
+            sp = dropzeros(d.sparse_H)                         # only `true` entries count (`sparse_H[i, j]`, :135)
+            colptr = Int64.(sp.colptr .- 1); rowval = Int64.(rowvals(sp) .- 1)
+            # ldpc_bitflip_options: int32 device, int32 tie_break (0 = random), uint64 seed, int32 kernel_variant, reserved
+            opts = zeros(Int32, 16); opts[1] = Int32(-1)
+            opts[3] = reinterpret(Int32, UInt32(BITFLIP_SEED[] & 0xffffffff)); opts[4] = reinterpret(Int32, UInt32(BITFLIP_SEED[] >> 32))
+            h = Ref{Ptr{Cvoid}}(C_NULL)
+            check(ccall((:ldpc_bitflip_create, libldpc), Cint,
+                        (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Float64, Int64, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                        d.s, d.n, length(rowval), colptr, rowval, d.per, d.max_iters, opts, h))
+            hd = BitFlipHandle(h[], 0)
+            finalizer(hd) do x
+                x.ptr != C_NULL && ccall((:ldpc_bitflip_destroy, libldpc), Cint, (Ptr{Cvoid},), x.ptr)
+                x.ptr = C_NULL
+            end
+            hd
+        end
+    end
+end
+
+function bitflip_call(h::BitFlipHandle, B, syn, err, conv)
+    check(ccall((:ldpc_bitflip_decode_batch, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int32}, Ptr{UInt8}),
+                h.ptr, B, h.columns_decoded, syn, err, conv, C_NULL, C_NULL))
+    h.columns_decoded += B
+end
+
+function LDPCDecoders.decode!(d::BitFlipDecoder, syndrome::AbstractVector)                  # overwrites :116-157
+    length(syndrome) == d.s || throw(BoundsError(syndrome, d.s))
+    h = handle_of(d)
+    syn = UInt8[syndrome_byte(x) for x in syndrome]
+    err = Vector{UInt8}(undef, d.n); conv = Vector{UInt8}(undef, 1)
+    bitflip_call(h, 1, syn, err, conv)
+    d.scratch.err .= err
+    return d.scratch.err, conv[1] != 0
+end
+
+bitflip_image(syndromes::Matrix{UInt8}) = all(x -> x <= 0x01, syndromes) ? syndromes : map(syndrome_byte, syndromes)
+bitflip_image(syndromes::Matrix{Bool}) = reinterpret(UInt8, syndromes)     # passed as it is
+bitflip_image(syndromes::AbstractMatrix) = UInt8[syndrome_byte(x) for x in syndromes]
+
+function LDPCDecoders.batchdecode!(d::BitFlipDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix,
+                                   converged::AbstractVector{Bool})                         # overwrites :189-201
+    @assert size(syndromes, 2) == size(errors, 2)
+    @assert size(syndromes, 2) == length(converged)
+    size(syndromes, 1) == d.s && size(errors, 1) == d.n || throw(DimensionMismatch("syndromes / errors rows"))
+    B = size(syndromes, 2)
+    B == 0 && return errors, converged
+    h = handle_of(d)
+    direct = errors isa Matrix{UInt8} || errors isa Matrix{Bool}
+    err = direct ? reinterpret(UInt8, errors) : Matrix{UInt8}(undef, d.n, B)
+    conv = Vector{UInt8}(undef, B)
+    bitflip_call(h, B, bitflip_image(syndromes), err, conv)
+    direct || (errors .= err)
+    converged .= conv .!= 0
+    d.scratch.err .= view(err, :, B)
+    return errors, converged
 end
 
 end # module
