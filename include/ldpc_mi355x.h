@@ -358,6 +358,34 @@ ldpc_status ldpc_osd_postprocess_batch(const ldpc_osd *osd, int64_t batch, const
                                        const uint8_t *bp_errors, const double *llr, uint8_t *errors,
                                        int32_t nthreads);
 
+/* The same step ON THE DEVICE, opt-in (the host form above stays the default): new HIP kernels for gfx950
+ * (csrc/osd_kernels.hpp), for BP outputs that are already device-resident.
+ *
+ * The rule, stated because two libms do not return the same ulp of exp: p = pm_exp(llr) (csrc/portable_math.h,
+ * bit-identical on host and device), key = p > 1-p ? p : 1-p, columns ordered by (key descending, column index
+ * ascending).  A NaN LLR (BP produces none for 0 < per < 1) orders last among all columns, by ascending index.  On the
+ * rare syndrome where libm's exp and pm_exp (<= 1 ulp apart) order two nearly tied columns differently, the device form
+ * may return another, equally valid estimate than the host form.  A syndrome entry that is not 0 counts as 1 (an
+ * asynchronous entry cannot return a per-entry status; the host entry's rejection stays).  bp_errors entries are 0 / 1.
+ * The estimate for a syndrome outside the column space of H (no error has it) is not specified.
+ *
+ * ldpc_osd_device_prepare: once per handle.  device = -1: the current device.  Uploads the packed rows, picks the tier
+ * (kernel_variant 0) or takes the forced one (1..3; LDPC_ERR_UNSUPPORTED when a syndrome's state does not fit tier 1 /
+ * 2), allocates the tier-3 workspace.  osd_order > 16 (2^16 candidates per syndrome): LDPC_ERR_UNSUPPORTED, use the
+ * host entry.  Arguments are checked before any device work.
+ * ldpc_osd_device_kernel: 1 = on-chip, one wave per syndrome (s <= 128, n <= 512); 2 = on-chip, one 16-wave workgroup
+ * per syndrome, working rows in dynamic LDS (state <= 159 KiB: s * 8 * (n/64 + 1 made odd) + 12 n + 4 s + the candidate
+ * bitsets; `parity_check_matrix(1000, 10, 9)` takes 138 KiB); 3 = unlimited (state in a slot of a global workspace,
+ * grid capped so that the slots stay below 1 GiB); 0 = not prepared / NULL.
+ * ldpc_osd_postprocess_batch_device: DEVICE pointers, asynchronous on `stream`, shapes as ldpc_osd_postprocess_batch.
+ * d_errors may alias d_bp_errors (in place).  batch = 0: LDPC_OK, nothing touched.  Calls on one handle run in call
+ * order whatever streams they are given.  ldpc_osd_destroy frees the device side. */
+ldpc_status ldpc_osd_device_prepare(ldpc_osd *osd, int32_t device, int32_t kernel_variant);
+int32_t ldpc_osd_device_kernel(const ldpc_osd *osd);
+ldpc_status ldpc_osd_postprocess_batch_device(ldpc_osd *osd, int64_t batch, const uint8_t *d_syndromes,
+                                              const uint8_t *d_bp_errors, const double *d_llr, uint8_t *d_errors,
+                                              void *stream);
+
 /* ------------------------------------------------------------------------
  * BP-OTS decoder: LLR-domain tanh/atanh BP with oscillation-driven prior biasing.
  * Graphs whose messages fit one CU's LDS (every code of the reference's BP-OTS tests) take an LDS-resident

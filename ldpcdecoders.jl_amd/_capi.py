@@ -58,6 +58,9 @@ EXPORTED_SYMBOLS = (
     "ldpc_osd_create",
     "ldpc_osd_destroy",
     "ldpc_osd_postprocess_batch",
+    "ldpc_osd_device_prepare",
+    "ldpc_osd_device_kernel",
+    "ldpc_osd_postprocess_batch_device",
     "ldpc_bpots_create",
     "ldpc_bpots_destroy",
     "ldpc_bpots_kernel",
@@ -127,7 +130,7 @@ class BitFlipOptions(ctypes.Structure):
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "osd_host.cpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "osd_host.cpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -231,6 +234,12 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_osd_destroy.argtypes = [vp]
     L.ldpc_osd_postprocess_batch.restype = i32
     L.ldpc_osd_postprocess_batch.argtypes = [vp, i64, vp, vp, vp, vp, i32]
+    L.ldpc_osd_device_prepare.restype = i32
+    L.ldpc_osd_device_prepare.argtypes = [vp, i32, i32]
+    L.ldpc_osd_device_kernel.restype = i32
+    L.ldpc_osd_device_kernel.argtypes = [vp]
+    L.ldpc_osd_postprocess_batch_device.restype = i32
+    L.ldpc_osd_postprocess_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     L.ldpc_bpots_create.restype = i32
     L.ldpc_bpots_create.argtypes = [i64, i64, i64, vp, vp, f64, i64, i64, f64, i32, ctypes.POINTER(vp)]
     L.ldpc_bpots_destroy.restype = i32

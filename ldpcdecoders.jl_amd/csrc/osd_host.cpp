@@ -12,6 +12,7 @@
 // (row operations do not care about column order), the residual syndrome and the
 // candidate weights are popcounts, and syndromes of a batch are spread over host threads.
 #include "../../include/ldpc_mi355x.h"
+#include "osd_handle.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,13 +29,6 @@ ldpc_status set_error(ldpc_status st, const std::string &msg);  // defined in ld
 using ldpc_detail::set_error;
 
 typedef uint64_t u64;
-
-struct ldpc_osd {
-    int64_t m = 0, n = 0;
-    int64_t order = 0;
-    int64_t nw = 0;            // words per row
-    std::vector<u64> rows;     // m * nw, bit c of row i = H[i, c]
-};
 
 namespace {
 
@@ -233,6 +227,7 @@ ldpc_status ldpc_osd_create(int64_t s, int64_t n, int64_t nnz, const int64_t *co
 
 ldpc_status ldpc_osd_destroy(ldpc_osd *d)
 {
+    if (d && d->dev_free) d->dev_free(d->dev);   // the device side of ldpc_osd_device_prepare (ldpc_osd_device.hip)
     delete d;
     return LDPC_OK;
 }

@@ -266,6 +266,24 @@ function batchdecode!(d::MI355XBeliefPropagationOSDDecoder, syndromes::AbstractM
     return errors, success
 end
 
+# The opt-in DEVICE form of the ordered-statistics step (include/ldpc_mi355x.h: its stated reliability key, the tiers).
+# For callers that keep their batches on the GPU (AMDGPU.jl arrays, or pointers obtained elsewhere): prepare once, then
+# hand device pointers and a hipStream_t; `d_errors` may be `d_bp_errors` itself.
+osd_device_prepare!(d::MI355XBeliefPropagationOSDDecoder; device::Integer=-1, kernel_variant::Integer=0) =
+    check(ccall((:ldpc_osd_device_prepare, libldpc), Cint, (Ptr{Cvoid}, Int32, Int32), d.osd_handle, device, kernel_variant))
+
+osd_device_kernel(d::MI355XBeliefPropagationOSDDecoder) =
+    Int(ccall((:ldpc_osd_device_kernel, libldpc), Int32, (Ptr{Cvoid},), d.osd_handle))
+
+function osd_postprocess_device!(d::MI355XBeliefPropagationOSDDecoder, batch::Integer, d_syndromes::Ptr{UInt8},
+                                 d_bp_errors::Ptr{UInt8}, d_llr::Ptr{Float64}, d_errors::Ptr{UInt8},
+                                 stream::Ptr{Cvoid}=C_NULL)
+    check(ccall((:ldpc_osd_postprocess_batch_device, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{UInt8}, Ptr{Cvoid}),
+                d.osd_handle, batch, d_syndromes, d_bp_errors, d_llr, d_errors, stream))
+    return nothing
+end
+
 # ---------------------------------------------------------------------------------------------
 # BP-OTS (src/decoders/bpots_decoder.jl:39-115, 225-340) over ldpc_bpots_* (LDS-resident kernel for small graphs,
 # node-parallel kernel with the messages in global memory up to n ~ 30,000; beyond that LDPCMI355XError(5, ...)).

@@ -4,6 +4,11 @@
 BP runs on the MI355X (the hot path); the ordered-statistics step is host code inside
 libldpc_mi355x.so (`ldpc_osd_postprocess_batch`, bit-packed GF(2) elimination threaded over
 the batch) -- BASELINE config 5 asks for exactly that split ("BP+OSD post-processing on host").
+
+Opt-in (`osd="device"`): the same step as HIP kernels (`ldpc_osd_postprocess_batch_device`), for batches
+that should not leave the GPU.  Its reliability key is the stated one (include/ldpc_mi355x.h: pm_exp, ties by
+column index); on the rare syndrome where libm's exp orders two nearly tied columns the other way round, it
+returns another, equally valid estimate than the host form.
 """
 from __future__ import annotations
 
@@ -52,17 +57,71 @@ class OSDPostProcessor:
                                                            L.ctypes.data, out.ctypes.data, int(nthreads)))
         return out
 
+    # -- the opt-in device form ------------------------------------------------
+    def prepare_device(self, device=None, kernel_variant: int = 0) -> int:
+        """Upload the packed rows to `device` (None: the current one) and pick the kernel tier (0: by size; 1..3
+        force it).  Once per post-processor.  Returns the tier (`.kernel`)."""
+        _capi.check(_capi.lib().ldpc_osd_device_prepare(self._h, -1 if device is None else int(device), int(kernel_variant)))
+        return self.kernel
+
+    @property
+    def kernel(self) -> int:
+        """Tier of the device form (ldpc_osd_device_kernel): 1 one wave per syndrome, 2 one workgroup per syndrome
+        (state in LDS), 3 unlimited (state in a global workspace); 0 = not prepared."""
+        return int(_capi.lib().ldpc_osd_device_kernel(self._h)) if self._h else 0
+
+    def postprocess_device(self, syn, bp_err, llr, out=None, stream=None):
+        """torch tensors on the prepared device: syn [B][s] u8, bp_err [B][n] u8, llr [B][n] f64, all contiguous
+        -> errors [B][n] u8 (`out`; may be `bp_err` itself: in place).  Asynchronous on `stream` (a hipStream_t as
+        int; default = torch's current stream)."""
+        import torch
+
+        B = int(syn.shape[0])
+        if out is None:
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=bp_err.device)
+        for x in (syn, bp_err, out):
+            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous()
+        assert tuple(syn.shape) == (B, self.s) and tuple(bp_err.shape) == (B, self.n)
+        assert tuple(llr.shape) == (B, self.n) and tuple(out.shape) == (B, self.n)
+        if stream is None:
+            stream = torch.cuda.current_stream(bp_err.device).cuda_stream
+        _capi.check(_capi.lib().ldpc_osd_postprocess_batch_device(self._h, B, syn.data_ptr(), bp_err.data_ptr(),
+                                                                  llr.data_ptr(), out.data_ptr(), ctypes.c_void_p(stream)))
+        return out
+
 
 class BeliefPropagationOSDDecoder(AbstractDecoder):
-    """`BeliefPropagationOSDDecoder(H, per, max_iters; osd_order=0)` (belief_propagation_osd.jl:26-29)."""
+    """`BeliefPropagationOSDDecoder(H, per, max_iters; osd_order=0)` (belief_propagation_osd.jl:26-29).
+    osd="host" (default): the ordered-statistics step in host threads; osd="device": in HIP kernels on the BP
+    decoder's GPU (`OSDPostProcessor.postprocess_device`), so that `batchdecode_device` never leaves the device."""
 
-    def __init__(self, H, per: float, max_iters: int, *, osd_order: int = 0, **bp_kwargs):
+    def __init__(self, H, per: float, max_iters: int, *, osd_order: int = 0, osd: str = "host", **bp_kwargs):
+        if osd not in ("host", "device"):
+            raise ValueError('osd must be "host" or "device"')
         # (exact LLRs: OSD orders the bits by reliability, :53-55 -- two that differ beyond the 21st bit must not tie)
         bp_kwargs.setdefault("llr_exact", True)
         self.bp_decoder = BeliefPropagationDecoder(H, per, max_iters, **bp_kwargs)   # :27
         self.H = H                                                                    # :21
         self.osd_order = int(osd_order)                                               # :23
         self._osd = OSDPostProcessor(H, osd_order)
+        self.osd = osd
+        if osd == "device":
+            self._osd.prepare_device(self.bp_decoder.info().device)
+
+    def _postprocess_host_arrays(self, syn_bs, err, llr, nthreads):
+        """The OSD step on host arrays: host threads, or (osd="device") the kernel through device copies."""
+        if self.osd != "device":
+            return self._osd.postprocess(syn_bs, err, llr, nthreads=nthreads)
+        import torch
+
+        dev = torch.device("cuda", self.bp_decoder.info().device)
+        d_syn = torch.from_numpy(np.ascontiguousarray(syn_bs, dtype=np.uint8)).to(dev)
+        d_err = torch.from_numpy(np.ascontiguousarray(err, dtype=np.uint8)).to(dev)
+        d_llr = torch.from_numpy(np.ascontiguousarray(llr, dtype=np.float64)).to(dev)
+        with torch.cuda.device(dev):
+            self._osd.postprocess_device(d_syn, d_err, d_llr, out=d_err)
+        return d_err.cpu().numpy()
 
     def decode_(self, syndrome) -> Tuple[np.ndarray, bool]:
         """`decode!(decoder::BeliefPropagationOSDDecoder, syndrome)` (:49-61): returns
@@ -74,7 +133,7 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
         err, conv, llr, _ = bp.decode_batch_host(syn.reshape(1, -1), want_llr=True)        # :51-52
         bp.scratch.err[:] = err[0]
         bp.scratch.log_probabs[:] = llr[0]
-        out = self._osd.postprocess(syn.reshape(1, -1), err, llr, nthreads=1)              # :53-60
+        out = self._postprocess_host_arrays(syn.reshape(1, -1), err, llr, 1)               # :53-60
         return out[0].astype(np.bool_), bool(conv[0])
 
     def batchdecode_(self, syndromes, errors, success=None, nthreads: int = 0):
@@ -90,7 +149,7 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
         bp = self.bp_decoder
         syn_bs = np.ascontiguousarray(syndrome_bytes(syndromes).T)
         err, conv, llr, _ = bp.decode_batch_host(syn_bs, want_llr=True)
-        out = self._osd.postprocess(syn_bs, err, llr, nthreads=nthreads)
+        out = self._postprocess_host_arrays(syn_bs, err, llr, nthreads)
         errors[:, :] = out.T
         success[:] = conv.astype(np.bool_)
         if B > 0:
@@ -104,12 +163,17 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
         with osd_order = 0 a converged syndrome is returned unchanged by the reference's shortcut
         (belief_propagation_osd.jl:66-74: zero residual), so its OSD call is skipped; with
         osd_order > 0 every syndrome is post-processed, like the reference.
-        Returns (errors [B][n] uint8 tensor, converged [B] uint8 tensor, number sent to OSD)."""
+        Returns (errors [B][n] uint8 tensor, converged [B] uint8 tensor, number sent to OSD).
+        With osd="device" nothing of the payload leaves the GPU: the same two passes for osd_order = 0, the OSD
+        kernel on the compacted unconverged rows and an index scatter; for osd_order > 0 one BP pass with LLRs and
+        the OSD kernel in place on the whole batch."""
         import torch
 
         bp = self.bp_decoder
         B = int(syn.shape[0])
         dev = syn.device
+        if self.osd == "device":
+            return self._batchdecode_device_resident(syn)
         err = torch.empty((B, bp.n), dtype=torch.uint8, device=dev)
         conv = torch.empty(B, dtype=torch.uint8, device=dev)
         if self.osd_order == 0 and getattr(self, "_osd_frac", 0.0) <= 0.2:
@@ -143,4 +207,43 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
             out = self._osd.postprocess(syn[idx].cpu().numpy(), err[idx].cpu().numpy(), llr[idx].cpu().numpy(),
                                         nthreads=nthreads)
             err[idx] = torch.from_numpy(out).to(dev)
+        return err, conv, k
+
+    def _batchdecode_device_resident(self, syn):
+        import torch
+
+        bp = self.bp_decoder
+        B = int(syn.shape[0])
+        dev = syn.device
+        err = torch.empty((B, bp.n), dtype=torch.uint8, device=dev)
+        conv = torch.empty(B, dtype=torch.uint8, device=dev)
+        if self.osd_order > 0:
+            llr = torch.empty((B, bp.n), dtype=torch.float64, device=dev)
+            bp.decode_batch_device(syn, err, conv, llr, None)
+            if B:
+                self._osd.postprocess_device(syn, err, llr, out=err)
+            return err, conv, B
+        if getattr(self, "_osd_frac", 0.0) <= 0.2:
+            # two passes, as on the host path: no 8n-byte LLR row for the syndromes BP converges on
+            bp.decode_batch_device(syn, err, conv, None, None)
+            idx = torch.nonzero(conv == 0, as_tuple=False).flatten()   # (its size is the one scalar the host reads)
+            k = int(idx.numel())
+            self._osd_frac = k / max(B, 1)
+            if k:
+                sub = syn[idx].contiguous()
+                e2 = torch.empty((k, bp.n), dtype=torch.uint8, device=dev)
+                c2 = torch.empty(k, dtype=torch.uint8, device=dev)
+                l2 = torch.empty((k, bp.n), dtype=torch.float64, device=dev)
+                bp.decode_batch_device(sub, e2, c2, l2, None)
+                self._osd.postprocess_device(sub, e2, l2, out=e2)
+                err[idx] = e2
+            return err, conv, k
+        # many unconverged: one pass with LLRs; the kernel returns the BP estimate of a converged syndrome unchanged
+        # (zero residual, :72-74), so it runs in place on the whole batch
+        llr = torch.empty((B, bp.n), dtype=torch.float64, device=dev)
+        bp.decode_batch_device(syn, err, conv, llr, None)
+        k = int((conv == 0).sum())
+        self._osd_frac = k / max(B, 1)
+        if k:
+            self._osd.postprocess_device(syn, err, llr, out=err)
         return err, conv, k
