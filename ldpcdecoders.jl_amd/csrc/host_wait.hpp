@@ -12,17 +12,14 @@
 // the stall; memory the device may still be using is leaked rather than freed), and the helper thread, if any, is left
 // behind detached.  The limit is per process: ldpc_set_wait_limit_ms() (include/ldpc_mi355x.h), default 600 s, 0 = wait
 // for ever as before.
+// Everything declared here is implemented in host_common.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/ldpc_mi355x.h"
 
 namespace ldpc_detail {
-
-ldpc_status set_error(ldpc_status st, const std::string &msg);   // ldpc_mi355x.hip: what ldpc_last_error() returns
 
 int64_t wait_limit_ms();                                  // 0 = no bound
 bool device_stalled(int device);                          // a wait on this device has expired in this process

@@ -17,18 +17,8 @@
 
 using namespace ldpc;
 
-#include "host_wait.hpp"   // set_error, and the bounded forms of every host-side wait
+#include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
 using ldpc_detail::set_error;
-
-#define BF_TRY(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (void)hipGetLastError();                                                         \
-            return set_error(e_ == hipErrorOutOfMemory ? LDPC_ERR_OUT_OF_MEMORY : LDPC_ERR_HIP, \
-                             std::string(#expr) + ": " + hipGetErrorString(e_));             \
-        }                                                                                    \
-    } while (0)
 
 static constexpr size_t kBfWaveLds = (size_t)40 * 1024, kBfGroupLds = (size_t)159 * 1024;
 static constexpr int kBfGroupWaves = 16;
@@ -46,17 +36,14 @@ struct ldpc_bitflip_decoder {
     size_t ws_cap = 0;
     bool kernel_ready = false;
     int per_cu = 1;
-    // calls on a handle run in call order whatever streams they are given (they share the workspace)
-    hipEvent_t last_done = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool have_last = false;
+    ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (they share the workspace)
     ~ldpc_bitflip_decoder()
     {
         if (ldpc_detail::device_stalled(device)) return;   // (host_wait.hpp: nothing a stalled device may still use is freed)
         void *all[] = {row_ptr, csr_col, col_ptr, csc_row, stage, ws};
         for (void *q : all)
             if (q) (void)hipFree(q);
-        if (last_done) (void)hipEventDestroy(last_done);
+        calls.destroy();
     }
 };
 
@@ -80,33 +67,15 @@ ldpc_status ldpc_bitflip_create(int64_t s, int64_t n, int64_t nnz, const int64_t
 {
     if (!out) return set_error(LDPC_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    if (s < 0 || n < 0 || nnz < 0 || !colptr || (nnz > 0 && !rowval) || max_iters < 0 || max_iters > INT32_MAX)
-        return set_error(LDPC_ERR_INVALID_ARGUMENT, "bad dimensions / NULL pattern / max_iters");
-    if (colptr[0] != 0 || colptr[n] != nnz) return set_error(LDPC_ERR_INVALID_ARGUMENT, "colptr is not a zero-based CSC pointer array");
-    for (int64_t j = 0; j < n; ++j) {
-        if (colptr[j + 1] < colptr[j]) return set_error(LDPC_ERR_INVALID_ARGUMENT, "colptr is not non-decreasing");
-        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-            if (rowval[k] < 0 || rowval[k] >= s) return set_error(LDPC_ERR_INVALID_ARGUMENT, "rowval entry outside [0, s)");
-            if (k > colptr[j] && rowval[k] <= rowval[k - 1])
-                return set_error(LDPC_ERR_INVALID_ARGUMENT, "row indices must be strictly ascending inside each column");
-        }
-    }
+    ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, max_iters);
+    if (st != LDPC_OK || (st = ldpc_detail::check_csc_pattern(s, n, nnz, colptr, rowval)) != LDPC_OK) return st;
     const int tie = options ? options->tie_break : LDPC_BF_TIE_RANDOM, variant = options ? options->kernel_variant : 0;
     int device = options ? options->device : -1;
     if (tie < 0 || tie > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "tie_break must be LDPC_BF_TIE_RANDOM, _FIRST or _LAST");
     if (variant < 0 || variant > 3) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1, 2 or 3");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return set_error(LDPC_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    }
-    if (device < 0) BF_TRY(hipGetDevice(&device));
-    if (device >= ndev) return set_error(LDPC_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    BF_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    BF_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return set_error(LDPC_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if ((st = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (this library has no CPU fallback)")) != LDPC_OK)
+        return st;
     if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
         return set_error(LDPC_ERR_UNSUPPORTED, "bit-flip kernels: graph too large for 32-bit edge indexing");
 
@@ -116,25 +85,8 @@ ldpc_status ldpc_bitflip_create(int64_t s, int64_t n, int64_t nnz, const int64_t
     d->device = device; d->num_cus = prop.multiProcessorCount;
     d->tie_break = tie; d->seed = options ? options->seed : 0;
     // CSR (checks -> bits, ascending) next to the caller's CSC
-    std::vector<int> row_ptr((size_t)s + 1, 0), col_ptr((size_t)n + 1), csr_col((size_t)std::max<int64_t>(nnz, 1)),
-        csc_row((size_t)std::max<int64_t>(nnz, 1));
-    for (int64_t k = 0; k < nnz; ++k) row_ptr[(size_t)rowval[k] + 1]++;
-    for (int64_t i = 0; i < s; ++i) {
-        d->max_cdeg = std::max(d->max_cdeg, row_ptr[(size_t)i + 1]);
-        row_ptr[(size_t)i + 1] += row_ptr[(size_t)i];
-    }
-    {
-        std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
-        for (int64_t j = 0; j < n; ++j) {
-            col_ptr[(size_t)j] = (int)colptr[j];
-            d->max_bdeg = std::max(d->max_bdeg, (int)(colptr[j + 1] - colptr[j]));
-            for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-                csr_col[(size_t)fill[(size_t)rowval[k]]++] = (int)j;
-                csc_row[(size_t)k] = (int)rowval[k];
-            }
-        }
-        col_ptr[(size_t)n] = (int)nnz;
-    }
+    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
+    d->max_cdeg = g.max_cdeg; d->max_bdeg = g.max_bdeg;
     while ((1 << d->rw_shift) < d->max_cdeg) d->rw_shift++;
     // |votes[j]| <= max_iters * deg[j]: 32-bit accumulators are exact below 2^31, beyond that the 64-bit kernel decodes
     const bool wide_votes = max_iters * (int64_t)d->max_bdeg >= ((int64_t)1 << 31);
@@ -145,12 +97,9 @@ ldpc_status ldpc_bitflip_create(int64_t s, int64_t n, int64_t nnz, const int64_t
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant: the state of a syndrome does not fit that on-chip tier");
     }
     d->tier = wide_votes ? 4 : variant ? variant : fits1 ? 1 : fits2 ? 2 : 3;
-    auto up = [&](int *&dst, const std::vector<int> &v) -> bool {
-        if (hipMalloc((void **)&dst, std::max<size_t>(v.size(), 1) * sizeof(int)) != hipSuccess) return false;
-        return hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(d->row_ptr, row_ptr) || !up(d->csr_col, csr_col) || !up(d->col_ptr, col_ptr) || !up(d->csc_row, csc_row) ||
-        hipEventCreateWithFlags(&d->last_done, hipEventDisableTiming) != hipSuccess) {
+    using ldpc_detail::upload_ints;
+    if (!upload_ints(&d->row_ptr, g.row_ptr) || !upload_ints(&d->csr_col, g.csr_col) || !upload_ints(&d->col_ptr, g.col_ptr) ||
+        !upload_ints(&d->csc_row, g.csc_row) || d->calls.create() != hipSuccess) {
         (void)hipGetLastError();
         delete d;
         return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the Tanner graph failed");
@@ -181,14 +130,15 @@ ldpc_status ldpc_bitflip_decode_batch_device(ldpc_bitflip_decoder *d, int64_t ba
     if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
     if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
     hipStream_t stream = (hipStream_t)stream_v;
-    BF_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
-    if (d->have_last && d->last_stream != stream) BF_TRY(hipStreamWaitEvent(stream, d->last_done, 0));
+    ldpc_status st = d->calls.enter(stream);
+    if (st != LDPC_OK) return st;
     if (d->max_iters == 0) {   // the loop at :121 never runs: err = 0, converged = false
-        if (d->n > 0) BF_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
-        BF_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_iters) BF_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
-        if (d_stop) BF_TRY(hipMemsetAsync(d_stop, 0, (size_t)batch, stream));
+        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
+        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
+        if (d_stop) LDPC_HIP_TRY(hipMemsetAsync(d_stop, 0, (size_t)batch, stream));
     } else {
         const bool global = d->tier >= 3;
         const int threads = d->tier == 1 ? 64 : kBfGroupWaves * 64;
@@ -196,28 +146,16 @@ ldpc_status ldpc_bitflip_decode_batch_device(ldpc_bitflip_decoder *d, int64_t ba
         const size_t lds = global ? 0 : state;
         bf_kernel_t k = bf_kernel_of(d->tier);
         if (!d->kernel_ready) {
-            if (lds) BF_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, threads, lds) != hipSuccess || per_cu <= 0) {
-                (void)hipGetLastError();
-                per_cu = 1;
-            }
-            d->per_cu = per_cu;
+            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, threads, lds);
             d->kernel_ready = true;
         }
         int64_t grid = std::min<int64_t>(batch, (int64_t)d->per_cu * d->num_cus);
         if (global) {
             grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kBfWorkspaceCap / state)));
-            if (d->ws_cap < (size_t)grid * state) {
-                if (d->ws) {
-                    const ldpc_status ws = ldpc_detail::wait_device(d->device, "bit-flip workspace regrow (device synchronise before the free)");
-                    if (ws != LDPC_OK) return ws;
-                    (void)hipFree(d->ws);
-                }
-                d->ws = nullptr; d->ws_cap = 0;
-                BF_TRY(hipMalloc((void **)&d->ws, (size_t)grid * state));
-                d->ws_cap = (size_t)grid * state;
-            }
+            st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
+                                                 "bit-flip workspace regrow (device synchronise before the free)");
+            if (st != LDPC_OK) return st;
         }
         BfParams p{};
         p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.tie_break = d->tie_break; p.rw_shift = d->rw_shift;
@@ -226,11 +164,9 @@ ldpc_status ldpc_bitflip_decode_batch_device(ldpc_bitflip_decoder *d, int64_t ba
         p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.col_ptr = d->col_ptr; p.csc_row = d->csc_row;
         p.ws = d->ws; p.slot_bytes = (long long)state;
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
-        BF_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
     }
-    BF_TRY(hipEventRecord(d->last_done, stream));
-    d->last_stream = stream; d->have_last = true;
-    return LDPC_OK;
+    return d->calls.leave(stream);
 }
 
 ldpc_status ldpc_bitflip_decode_batch(ldpc_bitflip_decoder *d, int64_t batch, int64_t column0, const uint8_t *syn,
@@ -241,30 +177,22 @@ ldpc_status ldpc_bitflip_decode_batch(ldpc_bitflip_decoder *d, int64_t batch, in
     if (column0 < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative column0");
     if (batch == 0) return LDPC_OK;
     if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
-    BF_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_err = up(B * s), o_conv = o_err + up(B * n), o_it = o_conv + up(B), o_stop = o_it + up(B * 4),
-                 total = o_stop + up(B);
-    if (d->stage_cap < total) {
-        if (d->stage) {
-            const ldpc_status ws = ldpc_detail::wait_device(d->device, "bit-flip staging regrow (device synchronise before the free)");
-            if (ws != LDPC_OK) return ws;
-            (void)hipFree(d->stage);
-        }
-        d->stage = nullptr; d->stage_cap = 0;
-        BF_TRY(hipMalloc(&d->stage, total));
-        d->stage_cap = total;
-    }
+    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][stopped]
+    image.take(B * s);
+    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4), o_stop = image.take(B), total = image.at;
+    ldpc_status st = ldpc_detail::grow_device_buffer(&d->stage, &d->stage_cap, total, d->device, "bit-flip staging regrow (device synchronise before the free)");
+    if (st != LDPC_OK) return st;
     char *dp = (char *)d->stage;
-    if (s > 0) BF_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
-    ldpc_status st = ldpc_bitflip_decode_batch_device(d, batch, column0, (const uint8_t *)dp, (uint8_t *)(dp + o_err),
+    if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
+    st = ldpc_bitflip_decode_batch_device(d, batch, column0, (const uint8_t *)dp, (uint8_t *)(dp + o_err),
                                                       (uint8_t *)(dp + o_conv), (int32_t *)(dp + o_it), (uint8_t *)(dp + o_stop), nullptr);
     if (st != LDPC_OK) return st;
-    if (n > 0) BF_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
-    BF_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
-    if (iters) BF_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
-    if (stop) BF_TRY(hipMemcpyAsync(stop, dp + o_stop, B, hipMemcpyDeviceToHost, nullptr));
+    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
+    LDPC_HIP_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
+    if (iters) LDPC_HIP_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
+    if (stop) LDPC_HIP_TRY(hipMemcpyAsync(stop, dp + o_stop, B, hipMemcpyDeviceToHost, nullptr));
     return ldpc_detail::wait_stream(nullptr, d->device, "ldpc_bitflip_decode_batch (stream synchronise)");
 }
 

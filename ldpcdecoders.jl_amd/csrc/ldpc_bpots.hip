@@ -12,7 +12,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
 #include <new>
 #include <string>
@@ -20,18 +19,8 @@
 
 using namespace ldpc;
 
-#include "host_wait.hpp"   // set_error, and the bounded forms of every host-side wait
+#include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
 using ldpc_detail::set_error;
-
-#define OTS_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (void)hipGetLastError();                                                         \
-            return set_error(e_ == hipErrorOutOfMemory ? LDPC_ERR_OUT_OF_MEMORY : LDPC_ERR_HIP, \
-                             std::string(#expr) + ": " + hipGetErrorString(e_));             \
-        }                                                                                    \
-    } while (0)
 
 struct ldpc_bpots_decoder {
     int64_t s = 0, n = 0, nnz = 0, max_iters = 0, T = 9;
@@ -87,54 +76,20 @@ ldpc_status ldpc_bpots_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
 {
     if (!out) return set_error(LDPC_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    if (s < 0 || n < 0 || nnz < 0 || !colptr || (nnz > 0 && !rowval) || max_iters < 0 || max_iters > INT32_MAX)
-        return set_error(LDPC_ERR_INVALID_ARGUMENT, "bad dimensions / NULL pattern / max_iters");
+    ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, max_iters);
+    if (st != LDPC_OK) return st;
     if (T < 1) return set_error(LDPC_ERR_INVALID_ARGUMENT, "T must be >= 1 (iter % T, bpots_decoder.jl:295)");
-    if (colptr[0] != 0 || colptr[n] != nnz) return set_error(LDPC_ERR_INVALID_ARGUMENT, "colptr is not a zero-based CSC pointer array");
-    for (int64_t j = 0; j < n; ++j) {
-        if (colptr[j + 1] < colptr[j]) return set_error(LDPC_ERR_INVALID_ARGUMENT, "colptr is not non-decreasing");
-        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-            if (rowval[k] < 0 || rowval[k] >= s) return set_error(LDPC_ERR_INVALID_ARGUMENT, "rowval entry outside [0, s)");
-            if (k > colptr[j] && rowval[k] <= rowval[k - 1])
-                return set_error(LDPC_ERR_INVALID_ARGUMENT, "row indices must be strictly ascending inside each column");
-        }
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return set_error(LDPC_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    }
-    if (device < 0) OTS_TRY(hipGetDevice(&device));
-    if (device >= ndev) return set_error(LDPC_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    OTS_TRY(hipSetDevice(device));
+    if ((st = ldpc_detail::check_csc_pattern(s, n, nnz, colptr, rowval)) != LDPC_OK) return st;
     hipDeviceProp_t prop;
-    OTS_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return set_error(LDPC_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if ((st = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (this library has no CPU fallback)")) != LDPC_OK)
+        return st;
 
     ldpc_bpots_decoder *d = new (std::nothrow) ldpc_bpots_decoder();
     if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     d->s = s; d->n = n; d->nnz = nnz; d->max_iters = max_iters; d->T = T; d->per = per; d->C = C;
     d->device = device; d->num_cus = prop.multiProcessorCount;
-    std::vector<int> row_ptr((size_t)s + 1, 0), col_ptr((size_t)n + 1), csc2csr((size_t)std::max<int64_t>(nnz, 1)),
-        csc_row((size_t)std::max<int64_t>(nnz, 1));
-    for (int64_t k = 0; k < nnz; ++k) row_ptr[(size_t)rowval[k] + 1]++;
-    for (int64_t i = 0; i < s; ++i) {
-        d->max_cdeg = std::max(d->max_cdeg, row_ptr[(size_t)i + 1]);
-        row_ptr[(size_t)i + 1] += row_ptr[(size_t)i];
-    }
-    {
-        std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
-        for (int64_t j = 0; j < n; ++j) {
-            col_ptr[(size_t)j] = (int)colptr[j];
-            d->max_bdeg = std::max(d->max_bdeg, (int)(colptr[j + 1] - colptr[j]));
-            for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-                csc2csr[(size_t)k] = fill[(size_t)rowval[k]]++;
-                csc_row[(size_t)k] = (int)rowval[k];
-            }
-        }
-        col_ptr[(size_t)n] = (int)nnz;
-    }
+    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
+    d->max_cdeg = g.max_cdeg; d->max_bdeg = g.max_bdeg;
     if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "BP-OTS kernels: graph too large for 32-bit edge indexing");
@@ -156,11 +111,9 @@ ldpc_status ldpc_bpots_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
         // buckets: everything in the global slot, any degree (the reference's BPOTSDecoder has no limit either)
         d->big_mode = wide || force_node >= 2 || ots_node_lds_bytes((int)s, (int)n) + 1024 > (size_t)156 * 1024;
     }
-    auto up = [&](int *&dst, const std::vector<int> &v) -> bool {
-        if (hipMalloc((void **)&dst, std::max<size_t>(v.size(), 1) * sizeof(int)) != hipSuccess) return false;
-        return hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(d->row_ptr, row_ptr) || !up(d->csc_row, csc_row) || !up(d->col_ptr, col_ptr) || !up(d->csc2csr, csc2csr) ||
+    using ldpc_detail::upload_ints;
+    if (!upload_ints(&d->row_ptr, g.row_ptr) || !upload_ints(&d->csc_row, g.csc_row) || !upload_ints(&d->col_ptr, g.col_ptr) ||
+        !upload_ints(&d->csc2csr, g.csc2csr) ||
         hipMalloc((void **)&d->queue, 64) != hipSuccess || hipMalloc((void **)&d->done_ctr, 64) != hipSuccess ||
         hipMemset(d->done_ctr, 0, 64) != hipSuccess) {
         (void)hipGetLastError();
@@ -197,12 +150,12 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
     if (batch == 0) return LDPC_OK;
     if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
     hipStream_t stream = (hipStream_t)stream_v;
-    OTS_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
     if (d->max_iters == 0) {   // the loop at :239 never runs: best_decisions = 0, converged = false
-        if (d->n > 0) OTS_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
-        OTS_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_iters) OTS_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
+        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
+        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
         return LDPC_OK;
     }
     if (d->node_mode) {
@@ -210,21 +163,14 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
         ots_node_kernel_t nk = d->big_mode ? (ots_node_kernel_t)bpots_big_kernel : pick_ots_node(d->max_cdeg, d->max_bdeg);
         const size_t nlds = d->big_mode ? 0 : ots_node_lds_bytes((int)d->s, (int)d->n);
         if (!d->kernel_ready) {
-            if (nlds) OTS_TRY(hipFuncSetAttribute((const void *)nk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nlds));
+            if (nlds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)nk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nlds));
             d->kernel_ready = true;
         }
         const int grid = (int)std::min<int64_t>(batch, d->num_cus);
         const size_t slot = d->big_mode ? ots_big_slot_doubles((int)d->s, (int)d->n, (int)d->nnz) : ots_node_slot_doubles((int)d->n, (int)d->nnz);
-        if (d->node_ws_cap < (size_t)grid * slot * sizeof(double)) {
-            if (d->node_ws) {
-                const ldpc_status ws = ldpc_detail::wait_device(d->device, "BP-OTS workspace regrow (device synchronise before the free)");
-                if (ws != LDPC_OK) return ws;
-                (void)hipFree(d->node_ws);
-            }
-            d->node_ws = nullptr; d->node_ws_cap = 0;
-            OTS_TRY(hipMalloc((void **)&d->node_ws, (size_t)grid * slot * sizeof(double)));
-            d->node_ws_cap = (size_t)grid * slot * sizeof(double);
-        }
+        const ldpc_status ws = ldpc_detail::grow_device_buffer((void **)&d->node_ws, &d->node_ws_cap, (size_t)grid * slot * sizeof(double), d->device,
+                                                               "BP-OTS workspace regrow (device synchronise before the free)");
+        if (ws != LDPC_OK) return ws;
         OtsNodeParams np{};
         np.s = (int)d->s; np.n = (int)d->n; np.nnz = (int)d->nnz; np.max_iters = (int)d->max_iters; np.T = (int)d->T;
         np.batch = batch;
@@ -232,10 +178,10 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
         np.C = d->C;
         np.syn = d_syn; np.err = d_err; np.conv = d_conv; np.iters = d_iters; np.queue = d->queue;
         np.ws = d->node_ws; np.slot_doubles = (long long)slot;
-        OTS_TRY(hipMemsetAsync(d->queue, 0, 64, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d->queue, 0, 64, stream));
         hipLaunchKernelGGL(nk, dim3((unsigned)grid), dim3(kOtsNodeThreads), nlds, stream, np, (const int *)d->row_ptr,
                            (const int *)d->csc_row, (const int *)d->col_ptr, (const int *)d->csc2csr);
-        OTS_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
         return LDPC_OK;
     }
     const int64_t ngroups = (batch + (1ll << d->logS) - 1) >> d->logS;
@@ -249,13 +195,8 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
     const size_t lds = ots_lds_bytes((int)d->s, (int)d->n, (int)d->nnz, 1 << d->logS);
     ots_kernel_t k = pick_ots(d->max_cdeg, d->max_bdeg);
     if (!d->kernel_ready) {
-        OTS_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, kOtsThreads, lds) != hipSuccess || per_cu <= 0) {
-            (void)hipGetLastError();
-            per_cu = 1;
-        }
-        d->per_cu = per_cu;
+        LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, kOtsThreads, lds);
         d->kernel_ready = true;
     }
     p.done_count = d->done_ctr; p.done_flag = nullptr; p.done_ticket = 0;
@@ -264,15 +205,15 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
         p.done_flag = lat->flag; p.done_ticket = lat->ticket;
         hipLaunchKernelGGL(k, dim3((unsigned)ngroups), dim3(kOtsThreads), lds, stream, p, (const int *)d->row_ptr,
                            (const int *)d->csc_row, (const int *)d->col_ptr, (const int *)d->csc2csr);
-        OTS_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
         return LDPC_OK;
     }
     const int grid = (int)std::min<int64_t>(ngroups, (int64_t)d->per_cu * d->num_cus);
     p.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, ngroups / ((int64_t)grid * 16)));
-    OTS_TRY(hipMemsetAsync(d->queue, 0, 64, stream));
+    LDPC_HIP_TRY(hipMemsetAsync(d->queue, 0, 64, stream));
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kOtsThreads), lds, stream, p, (const int *)d->row_ptr,
                        (const int *)d->csc_row, (const int *)d->col_ptr, (const int *)d->csc2csr);
-    OTS_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -291,19 +232,20 @@ ldpc_status ldpc_bpots_decode_batch(ldpc_bpots_decoder *d, int64_t batch, const 
     if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
     if (batch == 0) return LDPC_OK;
     if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
-    OTS_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_err = up(B * s), o_conv = o_err + up(B * n), o_it = o_conv + up(B), total = o_it + up(B * 4);
+    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations]
+    image.take(B * s);
+    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4), total = image.at;
     static const bool lat_off = exp_env("LDPC_NO_LATENCY_PATH") != nullptr;
     const int64_t lat_groups = d->node_mode ? batch : (batch + (1ll << d->logS) - 1) >> d->logS;
     if (!d->node_mode && !lat_off && total <= ((size_t)256 << 10) && d->max_iters > 0 && lat_groups <= 2 * (int64_t)d->num_cus) {
         const size_t hdr = 256;
         if (!d->lat_pin) {
             const size_t cap = hdr + ((size_t)256 << 10);
-            OTS_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
+            LDPC_HIP_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
             std::memset(d->lat_pin, 0, hdr);
-            OTS_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));
+            LDPC_HIP_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));
             d->lat_pin_cap = cap;
         }
         char *hp = (char *)d->lat_pin + hdr, *dp = (char *)d->lat_pin_dev + hdr;
@@ -314,48 +256,22 @@ ldpc_status ldpc_bpots_decode_batch(ldpc_bpots_decoder *d, int64_t batch, const 
         ldpc_status lst = bpots_decode_impl(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
                                             (int32_t *)(dp + o_it), nullptr, &lc);
         if (lst != LDPC_OK) return lst;
-        const auto lat_t0 = std::chrono::steady_clock::now();
-        for (uint64_t spins = 1;; ++spins) {
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == lc.ticket) break;
-            if ((spins & 0xffff) == 0) {   // every ~65k polls: is the kernel still alive?  (and the bound of host_wait.hpp)
-                const int64_t lim = ldpc_detail::wait_limit_ms();
-                if (lim > 0 && std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - lat_t0).count() > lim)
-                    return ldpc_detail::wait_expired(d->device, "BP-OTS latency path (flag of the last workgroup)");   // (names the wait, marks the device; never LDPC_OK before the copy-out)
-                const hipError_t q = hipStreamQuery(nullptr);
-                if (q == hipSuccess) {
-                    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == lc.ticket) break;
-                    return set_error(LDPC_ERR_HIP, "latency path: the kernel finished without raising its flag");
-                }
-                if (q != hipErrorNotReady) {
-                    (void)hipGetLastError();
-                    return set_error(LDPC_ERR_HIP, std::string("latency path: ") + hipGetErrorString(q));
-                }
-            }
-            __builtin_ia32_pause();
-        }
+        if ((lst = ldpc_detail::wait_flag(flag, lc.ticket, nullptr, d->device, "BP-OTS latency path (flag of the last workgroup)")) != LDPC_OK) return lst;
         std::memcpy(err, hp + o_err, B * n);
         std::memcpy(conv, hp + o_conv, B);
         if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));
         return LDPC_OK;
     }
-    if (d->stage_cap < total) {
-        if (d->stage) {
-            const ldpc_status ws = ldpc_detail::wait_device(d->device, "BP-OTS staging regrow (device synchronise before the free)");
-            if (ws != LDPC_OK) return ws;
-            (void)hipFree(d->stage);
-        }
-        d->stage = nullptr; d->stage_cap = 0;
-        OTS_TRY(hipMalloc(&d->stage, total));
-        d->stage_cap = total;
-    }
+    const ldpc_status gs = ldpc_detail::grow_device_buffer(&d->stage, &d->stage_cap, total, d->device, "BP-OTS staging regrow (device synchronise before the free)");
+    if (gs != LDPC_OK) return gs;
     char *dp = (char *)d->stage;
-    if (s > 0) OTS_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
+    if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
     ldpc_status st = ldpc_bpots_decode_batch_device(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err),
                                                     (uint8_t *)(dp + o_conv), (int32_t *)(dp + o_it), nullptr);
     if (st != LDPC_OK) return st;
-    if (n > 0) OTS_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
-    OTS_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
-    if (iters) OTS_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
+    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
+    LDPC_HIP_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
+    if (iters) LDPC_HIP_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
     return ldpc_detail::wait_stream(nullptr, d->device, "ldpc_bpots_decode_batch (stream synchronise)");
 }
 

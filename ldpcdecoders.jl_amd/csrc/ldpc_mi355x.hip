@@ -19,12 +19,10 @@
 #include "bit_io_kernels.hpp"
 #include "pickers.hpp"
 #include "host_env.hpp"
-#include "host_wait.hpp"
+#include "host_common.hpp"
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,153 +36,11 @@
 
 using namespace ldpc;
 
-namespace {
-
-thread_local std::string g_err;
-
-ldpc_status fail(ldpc_status st, const std::string &msg)
-{
-    g_err = msg;
-    return st;
-}
-
-}  // namespace
-
-namespace ldpc_detail {
-// shared with osd_host.cpp: records the message ldpc_last_error() returns
-ldpc_status set_error(ldpc_status st, const std::string &msg) { return fail(st, msg); }
-
-// ---- bounded host-side waits (host_wait.hpp)
-namespace {
-std::atomic<int64_t> g_wait_limit_ms{600000};
-constexpr int kMaxDev = 64;
-std::atomic<bool> g_stalled[kMaxDev];
-std::mutex g_stall_mu;
-std::string g_stall_msg[kMaxDev];
-
-ldpc_status expired(int device, const char *what, int64_t limit_ms)
-{
-    const std::string msg = std::string(what) + ": the device did not get there within " + std::to_string(limit_ms) +
-                            " ms (ldpc_set_wait_limit_ms); device " + std::to_string(device) +
-                            " is taken to be stalled: every later call on it fails with this message, and what it may still be "
-                            "using is not freed";
-    if (device >= 0 && device < kMaxDev) {
-        std::lock_guard<std::mutex> lk(g_stall_mu);
-        if (!g_stalled[device].load()) { g_stall_msg[device] = msg; g_stalled[device].store(true); }
-    }
-    return fail(LDPC_ERR_HIP, msg);
-}
-
-template <class Query>
-ldpc_status poll_until(Query &&query, int device, const char *what)
-{
-    if (device_stalled(device)) return stalled_error(device);
-    const int64_t limit = g_wait_limit_ms.load(std::memory_order_relaxed);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        const hipError_t q = query();
-        if (q == hipSuccess) return LDPC_OK;
-        if (q != hipErrorNotReady) {
-            (void)hipGetLastError();
-            return fail(LDPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(q));
-        }
-        if (spins < 64) { __builtin_ia32_pause(); continue; }   // (a query is ~1 us: the first polls back to back)
-        const int64_t us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (limit > 0 && us > limit * 1000) return expired(device, what, limit);
-        if (us < 300) __builtin_ia32_pause();                    // latency-bound calls (a small batch is ~100 us): keep polling
-        else if (us < 5000) std::this_thread::yield();
-        else std::this_thread::sleep_for(std::chrono::microseconds(us < 100000 ? 50 : 200));
-    }
-}
-}  // namespace
-
-int64_t wait_limit_ms() { return g_wait_limit_ms.load(std::memory_order_relaxed); }
-bool device_stalled(int device) { return device >= 0 && device < kMaxDev && g_stalled[device].load(std::memory_order_acquire); }
-ldpc_status stalled_error(int device)
-{
-    std::lock_guard<std::mutex> lk(g_stall_mu);
-    return fail(LDPC_ERR_HIP, (device >= 0 && device < kMaxDev) ? g_stall_msg[device] : std::string("device stalled"));
-}
-ldpc_status wait_event(hipEvent_t e, int device, const char *what)
-{
-    if (wait_limit_ms() == 0 && !device_stalled(device)) {       // unbounded, as before round 4
-        const hipError_t q = hipEventSynchronize(e);
-        if (q == hipSuccess) return LDPC_OK;
-        (void)hipGetLastError();
-        return fail(LDPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(q));
-    }
-    return poll_until([&] { return hipEventQuery(e); }, device, what);
-}
-ldpc_status wait_stream(hipStream_t s, int device, const char *what)
-{
-    if (wait_limit_ms() == 0 && !device_stalled(device)) {
-        const hipError_t q = hipStreamSynchronize(s);
-        if (q == hipSuccess) return LDPC_OK;
-        (void)hipGetLastError();
-        return fail(LDPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(q));
-    }
-    return poll_until([&] { return hipStreamQuery(s); }, device, what);
-}
-ldpc_status wait_expired(int device, const char *what)
-{
-    if (device_stalled(device)) return stalled_error(device);
-    return expired(device, what, wait_limit_ms());
-}
-// hipDeviceSynchronize has no query form: it runs in a helper thread that the caller waits for with the deadline; a
-// thread that never comes back is left behind (detached) with the state it shares with nobody else.
-ldpc_status wait_device(int device, const char *what)
-{
-    if (device_stalled(device)) return stalled_error(device);
-    const int64_t limit = wait_limit_ms();
-    if (limit == 0) {
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        hipError_t q = hipSetDevice(device);
-        if (q == hipSuccess) q = hipDeviceSynchronize();
-        if (prev >= 0) (void)hipSetDevice(prev);
-        if (q == hipSuccess) return LDPC_OK;
-        (void)hipGetLastError();
-        return fail(LDPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(q));
-    }
-    struct Shared { std::mutex m; std::condition_variable cv; bool done = false; hipError_t e = hipSuccess; };
-    auto sh = std::make_shared<Shared>();
-    std::thread([sh, device] {
-        hipError_t q = hipSetDevice(device);
-        if (q == hipSuccess) q = hipDeviceSynchronize();
-        if (q != hipSuccess) (void)hipGetLastError();
-        std::lock_guard<std::mutex> lk(sh->m);
-        sh->e = q; sh->done = true;
-        sh->cv.notify_all();
-    }).detach();
-    std::unique_lock<std::mutex> lk(sh->m);
-    if (!sh->cv.wait_for(lk, std::chrono::milliseconds(limit), [&] { return sh->done; })) {
-        lk.unlock();
-        return expired(device, what, limit);
-    }
-    if (sh->e == hipSuccess) return LDPC_OK;
-    return fail(LDPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(sh->e));
-}
-}  // namespace ldpc_detail
+using ldpc_detail::DeviceGuard;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? LDPC_ERR_OUT_OF_MEMORY : LDPC_ERR_HIP,     \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                    \
-        }                                                                                      \
-    } while (0)
-
-// Current device of the calling thread, put back when the scope ends (pool eviction and the multi-device entries
-// switch devices; the caller's choice must survive them).
-struct DeviceGuard {
-    int prev = -1;
-    DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; } }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+constexpr auto &fail = ldpc_detail::set_error;   // (host_common.hip)
 
 // A chunk group: physical chunks (hipMemCreate) mapped side by side -- each by ONE hipMemMap, access granted mapping by
 // mapping -- at an aligned base inside a virtual reservation of its own.  This is how every message array of >= 1 GiB is
@@ -627,12 +483,8 @@ ldpc_status ldpc_bp_decoder::prepare_kernel(const void *fn, int threads, size_t 
 {
     for (auto &ki : kernel_info)
         if (ki.first == fn) { *per_cu = ki.second; return LDPC_OK; }
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, lds) != hipSuccess || nb <= 0) {
-        (void)hipGetLastError();
-        nb = 1;
-    }
+    LDPC_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int nb = ldpc_detail::blocks_per_cu(fn, threads, lds);
     kernel_info.emplace_back(fn, nb);
     *per_cu = nb;
     return LDPC_OK;
@@ -805,21 +657,12 @@ extern "C" {
 
 int32_t ldpc_abi_version(void) { return LDPC_MI355X_ABI_VERSION; }
 
-ldpc_status ldpc_set_wait_limit_ms(int64_t ms)
-{
-    if (ms < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "negative wait limit");
-    ldpc_detail::g_wait_limit_ms.store(ms);
-    return LDPC_OK;
-}
-int64_t ldpc_get_wait_limit_ms(void) { return ldpc_detail::wait_limit_ms(); }
-
 ldpc_status ldpc_trim_memory(void)
 {
     pool_drop_all();
     return LDPC_OK;
 }
 const char *ldpc_build_target(void) { return "gfx950"; }
-const char *ldpc_last_error(void) { return g_err.c_str(); }
 
 int32_t ldpc_device_count(void)
 {
@@ -832,7 +675,7 @@ int32_t ldpc_device_count(void)
     for (int d = 0; d < cnt; ++d) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, d) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) ++usable;
+        if (ldpc_detail::is_gfx950(prop)) ++usable;
     }
     return usable;
 }
@@ -867,38 +710,16 @@ ldpc_status ldpc_bp_create(int64_t s, int64_t n, int64_t nnz, const int64_t *col
 {
     if (!out) return fail(LDPC_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    if (s < 0 || n < 0 || nnz < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "negative dimension");
-    if (!colptr || (nnz > 0 && !rowval)) return fail(LDPC_ERR_INVALID_ARGUMENT, "colptr/rowval is NULL");
-    if (max_iters < 0 || max_iters > INT32_MAX) return fail(LDPC_ERR_INVALID_ARGUMENT, "max_iters out of range");
+    ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, max_iters);
+    if (st != LDPC_OK) return st;
     if (s >= INT32_MAX || n >= INT32_MAX || nnz >= (int64_t)INT32_MAX / 64 * 8)
         return fail(LDPC_ERR_UNSUPPORTED, "graph too large for 32-bit edge indexing");
-    if (colptr[0] != 0 || colptr[n] != nnz)
-        return fail(LDPC_ERR_INVALID_ARGUMENT, "colptr[0] must be 0 and colptr[n] must equal nnz (zero-based CSC)");
-    for (int64_t j = 0; j < n; ++j) {
-        if (colptr[j + 1] < colptr[j]) return fail(LDPC_ERR_INVALID_ARGUMENT, "colptr is not non-decreasing");
-        for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-            if (rowval[k] < 0 || rowval[k] >= s)
-                return fail(LDPC_ERR_INVALID_ARGUMENT, "rowval entry outside [0, s)");
-            if (k > colptr[j] && rowval[k] <= rowval[k - 1])
-                return fail(LDPC_ERR_INVALID_ARGUMENT,
-                            "row indices must be strictly ascending inside each column (SparseMatrixCSC invariant)");
-        }
-    }
+    if ((st = ldpc_detail::check_csc_pattern(s, n, nnz, colptr, rowval)) != LDPC_OK) return st;
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(LDPC_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    }
-    int device = options ? options->device : -1;
-    if (device < 0) HIP_TRY(hipGetDevice(&device));
-    if (device >= ndev) return fail(LDPC_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    int device = 0;
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(LDPC_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-    if (ldpc_detail::device_stalled(device)) return ldpc_detail::stalled_error(device);
+    if ((st = ldpc_detail::select_device(options ? options->device : -1, &device, &prop,
+                                         "no HIP device available (this library has no CPU fallback)")) != LDPC_OK) return st;
 
     ldpc_bp_decoder *d = new (std::nothrow) ldpc_bp_decoder();
     if (!d) return fail(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -906,30 +727,11 @@ ldpc_status ldpc_bp_create(int64_t s, int64_t n, int64_t nnz, const int64_t *col
     d->device = device;
     d->num_cus = prop.multiProcessorCount;
 
-    // sparse(H') (belief_propagation.jl:64): CSR of H, bits ascending inside each check,
-    // plus for every CSC edge its position in that check-major order.
-    std::vector<int> row_ptr((size_t)s + 1, 0), edge_bit((size_t)std::max<int64_t>(nnz, 1)),
-        col_ptr((size_t)n + 1), csc2csr((size_t)std::max<int64_t>(nnz, 1));
-    for (int64_t k = 0; k < nnz; ++k) row_ptr[(size_t)rowval[k] + 1]++;
-    for (int64_t i = 0; i < s; ++i) {
-        d->max_cdeg = std::max(d->max_cdeg, row_ptr[(size_t)i + 1]);
-        row_ptr[(size_t)i + 1] += row_ptr[(size_t)i];
-    }
-    {
-        std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
-        for (int64_t j = 0; j < n; ++j) {
-            col_ptr[(size_t)j] = (int)colptr[j];
-            d->max_bdeg = std::max(d->max_bdeg, (int)(colptr[j + 1] - colptr[j]));
-            for (int64_t k = colptr[j]; k < colptr[j + 1]; ++k) {
-                int q = fill[(size_t)rowval[k]]++;
-                edge_bit[(size_t)q] = (int)j;
-                csc2csr[(size_t)k] = q;
-            }
-        }
-        col_ptr[(size_t)n] = (int)nnz;
-    }
+    // sparse(H') (belief_propagation.jl:64): CSR of H next to the caller's CSC (the kernels call the CSR's bits edge_bit)
+    const ldpc_detail::TannerGraph graph = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
+    const std::vector<int> &row_ptr = graph.row_ptr, &edge_bit = graph.csr_col, &col_ptr = graph.col_ptr, &csc2csr = graph.csc2csr;
+    d->max_cdeg = graph.max_cdeg; d->max_bdeg = graph.max_bdeg;
 
-    ldpc_status st = LDPC_OK;
     auto upload = [&](DevBuf &b, const std::vector<int> &v) -> ldpc_status {
         ldpc_status r = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(int));
         if (r != LDPC_OK) return r;
@@ -1673,7 +1475,7 @@ extern "C" ldpc_status ldpc_debug_div_check(int64_t count, const double *num, co
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(LDPC_ERR_NO_DEVICE, "no HIP device available"); }
     const size_t bytes = (size_t)count * sizeof(double);
     double *dv = nullptr;
-    HIP_TRY(hipMalloc((void **)&dv, 4 * bytes));
+    LDPC_HIP_TRY(hipMalloc((void **)&dv, 4 * bytes));
     hipError_t e = hipMemcpy(dv, num, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dv + count, den, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -1695,7 +1497,7 @@ extern "C" ldpc_status ldpc_debug_llr_check(int64_t count, const double *odds, d
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(LDPC_ERR_NO_DEVICE, "no HIP device available"); }
     const size_t bytes = (size_t)count * sizeof(double);
     double *dv = nullptr;
-    HIP_TRY(hipMalloc((void **)&dv, 3 * bytes));
+    LDPC_HIP_TRY(hipMalloc((void **)&dv, 3 * bytes));
     hipError_t e = hipMemcpy(dv, odds, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(llr_check_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, dv, dv + count, dv + 2 * count, (long long)count);
@@ -2012,7 +1814,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     if (batch == 0) return LDPC_OK;
     if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv)
         return fail(LDPC_ERR_INVALID_ARGUMENT, "syndromes/errors/converged pointer is NULL");
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
     const int64_t s = d->s, n = d->n;
     {
@@ -2036,15 +1838,15 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     // Calls on one handle execute in call order whatever streams they are given (they share its workspace and
     // its control slots -- a kernel of call N zeroes the slot of call N+1): a call that arrives on another
     // stream than its predecessor waits for that one's last event first.
-    if (d->last_ev && d->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, d->last_ev, 0));
+    if (d->last_ev && d->last_stream != stream) LDPC_HIP_TRY(hipStreamWaitEvent(stream, d->last_ev, 0));
     d->last_stream = stream;
 
     if (d->max_iters == 0) {
         // the loop at belief_propagation.jl:134 never runs: err = 0, log_probabs = 0, converged = false
-        if (n > 0) HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * n, stream));
-        HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_llr && n > 0) HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * n * sizeof(double), stream));
-        if (d_iters) HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
+        if (n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * n, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
+        if (d_llr && n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * n * sizeof(double), stream));
+        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
         return LDPC_OK;
     }
 
@@ -2085,18 +1887,18 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             hipLaunchKernelGGL(lk, dim3((unsigned)ngroups64), dim3((unsigned)lthreads), lds, stream, lp,
                                (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
                                (const int *)d->csc2csr.p);
-            HIP_TRY(hipGetLastError());
+            LDPC_HIP_TRY(hipGetLastError());
             return LDPC_OK;
         }
-        if (!d->ctrl_clean[slot]) HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
+        if (!d->ctrl_clean[slot]) LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
         d->ctrl_clean[slot] = false;
         lp.next_ctrl = (u64 *)next_ctrl;
-        HIP_TRY(hipEventRecord(ev[1], stream));
+        LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
         hipLaunchKernelGGL(lk, dim3((unsigned)lgrid), dim3((unsigned)lthreads), lds, stream, lp,
                            (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
                            (const int *)d->csc2csr.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[2], stream));
+        LDPC_HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
         d->ctrl_clean[nslot] = true;
         d->timed[nslot] = false;
         d->timed[slot] = true;
@@ -2141,18 +1943,18 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             hipLaunchKernelGGL(nk, dim3((unsigned)ngrid), dim3((unsigned)nthreads), nlds, stream, np,
                                (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
                                (const int *)d->csc2csr.p);
-            HIP_TRY(hipGetLastError());
+            LDPC_HIP_TRY(hipGetLastError());
             return LDPC_OK;
         }
-        if (!d->ctrl_clean[slot]) HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
+        if (!d->ctrl_clean[slot]) LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
         d->ctrl_clean[slot] = false;
         np.next_ctrl = (u64 *)next_ctrl;
-        HIP_TRY(hipEventRecord(ev[1], stream));
+        LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
         hipLaunchKernelGGL(nk, dim3((unsigned)ngrid), dim3((unsigned)nthreads), nlds, stream, np,
                            (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
                            (const int *)d->csc2csr.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[2], stream));
+        LDPC_HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
         d->ctrl_clean[nslot] = true;
         d->timed[nslot] = false;
         d->two_events[slot] = true;
@@ -2273,7 +2075,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         if ((st = d->lvl_err[l - 1].ensure(std::max<size_t>(ct * n, 1) * sizeof(u64))) != LDPC_OK) return st;
         if ((st = d->lvl_fin[l - 1].ensure(std::max<size_t>(ct * n, 1) * sizeof(u64))) != LDPC_OK) return st;
         if (want_llr && (st = d->lvl_llr[l - 1].ensure(std::max<size_t>(ct * n, 1) * kTile * sizeof(double))) != LDPC_OK) return st;
-        HIP_TRY(hipMemsetAsync(d->lvl_never[l - 1].p, 0, ct * sizeof(u64), stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d->lvl_never[l - 1].p, 0, ct * sizeof(u64), stream));
         // Few stragglers (the usual case): the node-parallel kernel finishes them, one workgroup per syndrome
         // straight from / into the caller's arrays, instead of a handful of tiles that each sweep the whole
         // graph with a few lanes alive.  Decided on the device: the launches of the paths not taken find the
@@ -2296,10 +2098,10 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         }
     }
 
-    HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
+    LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
     d->ctrl_clean[slot] = false;
-    HIP_TRY(hipMemsetAsync(d->nevermask.p, 0, (size_t)ntiles * sizeof(u64), stream));
-    HIP_TRY(hipEventRecord(ev[0], stream));
+    LDPC_HIP_TRY(hipMemsetAsync(d->nevermask.p, 0, (size_t)ntiles * sizeof(u64), stream));
+    LDPC_HIP_TRY(hipEventRecord(ev[0], stream));
     // four checks (bits) per lane in the pack / unpack kernels where the caller's arrays allow 4-byte accesses
     const bool syn_v4 = s % 4 == 0 && ((uintptr_t)d_syn & 3u) == 0, err_v4 = n % 4 == 0 && ((uintptr_t)d_err & 3u) == 0;
     if (s > 0) {
@@ -2307,7 +2109,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         hipLaunchKernelGGL(syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, stream, d_syn, (long long)batch, (int)s,
                            (u64 *)d->synmask.p, (u64 *)d->nevermask.p, (const int *)nullptr,
                            (const unsigned int *)nullptr, 0u);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
     }
     const int *a_row = (const int *)d->row_ptr.p, *a_eb = (const int *)d->edge_bit.p, *a_col = (const int *)d->col_ptr.p,
               *a_c2r = (const int *)d->csc2csr.p;
@@ -2357,7 +2159,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         hand_off_into(unused, cold[l], l + 1);
     }
     hipLaunchKernelGGL(store_cold_kernel, dim3(1), dim3(64), 0, stream, cold[0], cold[1], cold[2], d_cold);
-    HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     bp_kernel_t kfn = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, threads);
     const int always_release = d->team_always_release ? 1 : 0;
     auto team_params = [&](DevBuf &wsbuf, int nteams, int tiles, TeamParams &tp) -> ldpc_status {
@@ -2366,7 +2168,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         const size_t ws_bytes = ctl_bytes + (size_t)tiles * mism_stride * sizeof(u64);
         ldpc_status r = wsbuf.ensure(ws_bytes);
         if (r != LDPC_OK) return r;
-        HIP_TRY(hipMemsetAsync(wsbuf.p, 0, ws_bytes, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(wsbuf.p, 0, ws_bytes, stream));
         tp.ctl = (unsigned int *)wsbuf.p;
         tp.mism = (u64 *)((char *)wsbuf.p + ctl_bytes);
         tp.mism_stride = (int)mism_stride;
@@ -2390,7 +2192,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     bool team_ran = team > 1;
     int llr_raw_out = 0;   // the fresh pass left posterior odds, not logarithms, in llr_t (TeamParams::llr_raw)
     const int *llr_posmap = nullptr;   // ... in the dealt bit order of the rows-on-chip tables: position of every bit
-    HIP_TRY(hipEventRecord(ev[1], stream));
+    LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
     if (team > 1) {
         TeamParams tp{};
         if ((st = team_params(d->team_ws, plan.nteams, ntiles, tp)) != LDPC_OK) return st;
@@ -2500,7 +2302,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     if (!team_ran) {
         hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)threads), 0, stream, p, a_row, a_eb, a_col, a_c2r,
                            (const u64 *)d->synmask.p, (const u64 *)d->nevermask.p);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
     }
     // ---- passes over the packed levels (tile kernel in place / teams on packed tiles; the node kernel comes last)
     bp_kernel_t kfn2 = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, threads, true);
@@ -2514,7 +2316,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             hipLaunchKernelGGL(syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, stream, d_syn, (long long)0, (int)s,
                                (u64 *)d->lvl_syn[l - 1].p, (u64 *)d->lvl_never[l - 1].p, (const int *)d->lvl_list[l - 1].p,
                                (const unsigned int *)L.count, L.node_take);
-            HIP_TRY(hipGetLastError());
+            LDPC_HIP_TRY(hipGetLastError());
         }
         BPParams q = p;
         q.msg = (double *)d->lvl_state[l - 1].p;
@@ -2530,7 +2332,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         hand_off_into(q, cold[l], l + 1);   // (sets q.defer_thresh too)
         const int g2 = std::max(1, std::min(occ2 * d->num_cus, L.cap_tiles));
         hipLaunchKernelGGL(kfn2, dim3((unsigned)g2), dim3((unsigned)threads), 0, stream, q, a_row, a_eb, a_col, a_c2r, l_syn, l_nev);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
         if (L.team_cap) {
             BPParams q3 = q;
             q3.count_skip = L.node_take;
@@ -2541,22 +2343,22 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             tp.count_max = L.team_cap;
             team_kernel_t tk = pick_team_kernel(d->max_cdeg, d->max_bdeg, want_llr, true);
             void *args[] = {&q3, &tp, &a_row, &a_eb, &a_col, &a_c2r, &l_syn, &l_nev};
-            HIP_TRY(launch_team_grid(d, tk, L.t_grid, args, stream, team_lds_bytes()));
+            LDPC_HIP_TRY(launch_team_grid(d, tk, L.t_grid, args, stream, team_lds_bytes()));
         }
     }
-    HIP_TRY(hipEventRecord(ev[2], stream));
+    LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
     // ---- results out: level 0 first, then every level over the rows its lower levels gave up
     if (n > 0) {
         dim3 g((unsigned)((n + 63) / 64), (unsigned)ntiles);
         const dim3 ge((unsigned)((n + (err_v4 ? 255 : 63)) / (err_v4 ? 256 : 64)), (unsigned)ntiles);
         hipLaunchKernelGGL(err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, ge, dim3(64), 0, stream, (const u64 *)d->finmask.p,
                            (long long)batch, (int)n, d_err, (const int *)nullptr, (const unsigned int *)nullptr, 0u);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
         if (want_llr) {
             const dim3 gl(g.x, (g.y + 7u) & ~7u);     // (unpack_llr_kernel deals the tiles over the XCDs in eights)
             hipLaunchKernelGGL(unpack_llr_kernel, gl, dim3(256), 0, stream, (const double *)d->llr_t.p,
                                (long long)batch, (int)n, d_llr, (const int *)nullptr, (const unsigned int *)nullptr, 0u, llr_raw_out, d->llr_exact ? 1 : 0, llr_posmap);
-            HIP_TRY(hipGetLastError());
+            LDPC_HIP_TRY(hipGetLastError());
         }
         for (int l = 1; l <= nlevels; ++l) {
             dim3 g2((unsigned)((n + 63) / 64), (unsigned)lv[l].cap_tiles);
@@ -2564,13 +2366,13 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             hipLaunchKernelGGL(err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, ge2, dim3(64), 0, stream, (const u64 *)d->lvl_fin[l - 1].p,
                                (long long)0, (int)n, d_err, (const int *)d->lvl_list[l - 1].p,
                                (const unsigned int *)lv[l].count, lv[l].node_take);
-            HIP_TRY(hipGetLastError());
+            LDPC_HIP_TRY(hipGetLastError());
             if (want_llr) {
                 const dim3 gl2(g2.x, (g2.y + 7u) & ~7u);
                 hipLaunchKernelGGL(unpack_llr_kernel, gl2, dim3(256), 0, stream, (const double *)d->lvl_llr[l - 1].p,
                                    (long long)0, (int)n, d_llr, (const int *)d->lvl_list[l - 1].p,
                                    (const unsigned int *)lv[l].count, lv[l].node_take, 0, 0, (const int *)nullptr);
-                HIP_TRY(hipGetLastError());
+                LDPC_HIP_TRY(hipGetLastError());
             }
         }
     }
@@ -2603,9 +2405,9 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         np.done_count = nullptr; np.done_flag = nullptr; np.done_ticket = 0; np.next_ctrl = nullptr;
         np.split_check = d->node_split_check; np.split_edge = d->node_split_edge;
         hipLaunchKernelGGL(nk, dim3((unsigned)ngrid), dim3((unsigned)nthreads), nlds, stream, np, a_row, a_eb, a_col, a_c2r);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(ev[3], stream));
+    LDPC_HIP_TRY(hipEventRecord(ev[3], stream));
     d->timed[slot] = true;
     d->last_ev = ev[3];
     return LDPC_OK;
@@ -2643,16 +2445,17 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
     if (batch == 0) return ldpc_bp_decode_batch_device(d, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv)
         return fail(LDPC_ERR_INVALID_ARGUMENT, "syndromes/errors/converged pointer is NULL");
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
     ldpc_status st;
     hipStream_t stream = nullptr;
     // Small batches (decode! is batch = 1): one pinned staging image, ONE copy in and ONE copy out
     // instead of five pageable transfers -- the call is latency-bound, not bandwidth-bound.
     {
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t o_err = up(B * s), o_conv = o_err + up(B * n), o_it = o_conv + up(B),
-                     o_llr = o_it + up(B * sizeof(int32_t)), total = o_llr + (llr ? up(B * n * sizeof(double)) : 0);
+        ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][LLRs]
+        image.take(B * s);
+        const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * sizeof(int32_t)),
+                     o_llr = image.take(llr ? B * n * sizeof(double) : 0), total = image.at;
         // Tiny batches on the two kernels that read their input once (a plain decode! above all): the
         // kernel works on a host-mapped image directly and raises a flag in it when the last workgroup
         // is through -- ONE runtime call (the launch) instead of nine, no copies, no stream synchronisation.
@@ -2666,9 +2469,9 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
                 if (d->lat_pin) (void)hipHostFree(d->lat_pin);
                 d->lat_pin = nullptr; d->lat_pin_cap = 0;
                 const size_t cap = hdr + ((size_t)256 << 10);
-                HIP_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
+                LDPC_HIP_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
                 std::memset(d->lat_pin, 0, hdr);
-                HIP_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));
+                LDPC_HIP_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));
                 d->lat_pin_cap = cap;
             }
             char *hp = (char *)d->lat_pin + hdr, *dp = (char *)d->lat_pin_dev + hdr;
@@ -2679,25 +2482,7 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
             st = decode_device_impl(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
                                     llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it), stream, &lc);
             if (st != LDPC_OK) return st;
-            const auto lat_t0 = std::chrono::steady_clock::now();
-            for (uint64_t spins = 1;; ++spins) {
-                if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == lc.ticket) break;
-                if ((spins & 0xffff) == 0) {   // every ~65k polls: is the kernel still alive?  (and the bound of host_wait.hpp)
-                    const int64_t lim = ldpc_detail::wait_limit_ms();
-                    if (lim > 0 && std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - lat_t0).count() > lim)
-                        return ldpc_detail::wait_expired(d->device, "latency path (flag of the last workgroup)");   // (names the wait, marks the device; never LDPC_OK before the copy-out)
-                    const hipError_t q = hipStreamQuery(stream);
-                    if (q == hipSuccess) {
-                        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == lc.ticket) break;
-                        return fail(LDPC_ERR_HIP, "latency path: the kernel finished without raising its flag");
-                    }
-                    if (q != hipErrorNotReady) {
-                        (void)hipGetLastError();
-                        return fail(LDPC_ERR_HIP, std::string("latency path: ") + hipGetErrorString(q));
-                    }
-                }
-                __builtin_ia32_pause();
-            }
+            if ((st = ldpc_detail::wait_flag(flag, lc.ticket, stream, d->device, "latency path (flag of the last workgroup)")) != LDPC_OK) return st;
             std::memcpy(err, hp + o_err, B * n);
             std::memcpy(conv, hp + o_conv, B);
             if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));
@@ -2709,16 +2494,16 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
             if (d->pin_cap < total) {
                 if (d->pin) (void)hipHostFree(d->pin);
                 d->pin = nullptr; d->pin_cap = 0;
-                HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
+                LDPC_HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
                 d->pin_cap = total;
             }
             char *hp = (char *)d->pin, *dp = (char *)d->st_all.p;
             std::memcpy(hp, syn, B * s);
-            if (s > 0) HIP_TRY(hipMemcpyAsync(dp, hp, B * s, hipMemcpyHostToDevice, stream));
+            if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, hp, B * s, hipMemcpyHostToDevice, stream));
             st = ldpc_bp_decode_batch_device(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
                                              llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it), stream);
             if (st != LDPC_OK) return st;
-            HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
+            LDPC_HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
             if ((st = ldpc_detail::wait_stream(stream, d->device, "ldpc_bp_decode_batch (small batch: stream synchronise)")) != LDPC_OK) return st;
             std::memcpy(err, hp + o_err, B * n);
             std::memcpy(conv, hp + o_conv, B);
@@ -2733,7 +2518,6 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
     // (A single pageable hipMemcpy each way measured 11 GB/s and made the call 5-7x slower than the
     // HBM-resident entry for small codes.)
     {
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
         const size_t bps = s + n + 1 + sizeof(int32_t) + (llr ? n * sizeof(double) : 0);   // bytes per syndrome
         const bool lds_path = d->variant != 1 && d->lds_logS[llr ? 1 : 0] >= 0;
         size_t chunk_mb = 24;
@@ -2743,13 +2527,15 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
         cb = (cb + 4095) & ~(size_t)4095;
         if (B < cb + cb / 2) cb = B;                               // no tiny trailing chunk
         const size_t nchunks = (B + cb - 1) / cb;
-        const size_t o_err = up(cb * s), o_conv = o_err + up(cb * n), o_it = o_conv + up(cb),
-                     o_llr = o_it + up(cb * sizeof(int32_t)), total = o_llr + (llr ? up(cb * n * sizeof(double)) : 0);
+        ldpc_detail::Carve image;
+        image.take(cb * s);
+        const size_t o_err = image.take(cb * n), o_conv = image.take(cb), o_it = image.take(cb * sizeof(int32_t)),
+                     o_llr = image.take(llr ? cb * n * sizeof(double) : 0), total = image.at;
         for (int q = 0; q < 3; ++q)
-            if (!d->pipe_stream[q]) HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
+            if (!d->pipe_stream[q]) LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
         for (auto &row : d->pipe_ev)
             for (hipEvent_t &e : row)
-                if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                if (!e) LDPC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         const int R = (int)std::min<size_t>(ldpc_bp_decoder::kPipe, nchunks);
         if (d->pipe_pin_cap < total) {
             for (void *&q : d->pipe_pin) {
@@ -2759,7 +2545,7 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
             d->pipe_pin_cap = 0;
         }
         for (int q = 0; q < R; ++q) {
-            if (!d->pipe_pin[q]) HIP_TRY(hipHostMalloc(&d->pipe_pin[q], total, hipHostMallocDefault));
+            if (!d->pipe_pin[q]) LDPC_HIP_TRY(hipHostMalloc(&d->pipe_pin[q], total, hipHostMallocDefault));
             if ((st = d->pipe_dev[q].ensure(total)) != LDPC_OK) return st;
         }
         d->pipe_pin_cap = std::max(d->pipe_pin_cap, total);
@@ -2803,9 +2589,9 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
         if (pst == LDPC_OK)
             for (size_t j = nchunks > (size_t)R ? nchunks - R : 0; j < nchunks && pst == LDPC_OK; ++j) pst = drain(j);
         if (pst != LDPC_OK) {
-            const std::string keep = g_err;
+            const std::string keep = ldpc_detail::last_error();
             (void)ldpc_detail::wait_device(d->device, "ldpc_bp_decode_batch (host pipeline: drain after an error)");   // nothing of this call may still be in flight when we return
-            g_err = keep;
+            (void)fail(pst, keep);
         }
         return pst;
     }
@@ -2838,7 +2624,7 @@ extern "C" ldpc_status ldpc_bp_decode_batch_bits_device(ldpc_bp_decoder *d, int6
     bool done;
     ldpc_status st = bits_check_args(d, batch, d_syn_w, syn_bit0, d_err_w, err_bit0, d_conv, &done);
     if (st != LDPC_OK || done) return st;
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
     hipStream_t stream = (hipStream_t)stream_v;
     const long long ns = (long long)batch * d->s, nn = (long long)batch * d->n;
@@ -2846,16 +2632,16 @@ extern "C" ldpc_status ldpc_bp_decode_batch_bits_device(ldpc_bp_decoder *d, int6
     if ((st = d->bits_err.ensure((size_t)std::max<long long>(nn, 16))) != LDPC_OK) return st;
     const int slot = (int)(d->ncalls % ldpc_bp_decoder::kRing);   // the slot the byte entry below takes
     for (hipEvent_t &e : d->bits_ev[slot])
-        if (!e) HIP_TRY(hipEventCreate(&e));
+        if (!e) LDPC_HIP_TRY(hipEventCreate(&e));
     // the staging is the handle's: like the workspace it is used in call order, whatever streams the calls are given
-    if (d->last_ev && d->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, d->last_ev, 0));
+    if (d->last_ev && d->last_stream != stream) LDPC_HIP_TRY(hipStreamWaitEvent(stream, d->last_ev, 0));
     d->last_stream = stream;
-    HIP_TRY(hipEventRecord(d->bits_ev[slot][0], stream));
+    LDPC_HIP_TRY(hipEventRecord(d->bits_ev[slot][0], stream));
     if (ns > 0) {
         const int grid = ldpc_bitio::grid_for((ns + 1023) >> 10, d->num_cus);
         hipLaunchKernelGGL(ldpc_bitio::bits_to_bytes_kernel, dim3((unsigned)grid), dim3(ldpc_bitio::kThreads), 0, stream,
                            (const ldpc_bitio::bu64 *)d_syn_w + (syn_bit0 >> 6), (int)(syn_bit0 & 63), (uint8_t *)d->bits_syn.p, ns);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
     }
     const uint64_t calls_before = d->ncalls;
     st = ldpc_bp_decode_batch_device(d, batch, (const uint8_t *)d->bits_syn.p, (uint8_t *)d->bits_err.p, d_conv, d_llr, d_iters, stream_v);
@@ -2865,9 +2651,9 @@ extern "C" ldpc_status ldpc_bp_decode_batch_bits_device(ldpc_bp_decoder *d, int6
         const int grid = ldpc_bitio::grid_for((ldpc_bitio::words_covering(off, nn) + 14) / 15, d->num_cus);
         hipLaunchKernelGGL(ldpc_bitio::bytes_to_bits_kernel, dim3((unsigned)grid), dim3(ldpc_bitio::kThreads), 0, stream,
                            (const uint8_t *)d->bits_err.p, nn, (ldpc_bitio::bu64 *)d_err_w + (err_bit0 >> 6), off);
-        HIP_TRY(hipGetLastError());
+        LDPC_HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(d->bits_ev[slot][1], stream));
+    LDPC_HIP_TRY(hipEventRecord(d->bits_ev[slot][1], stream));
     d->last_ev = d->bits_ev[slot][1];
     d->bits_timed[slot] = d->ncalls == calls_before + 1;
     return LDPC_OK;
@@ -2898,10 +2684,9 @@ void merge_bit_range(uint64_t *dst, const uint64_t *src, int off, size_t nbits)
 static ldpc_status decode_batch_bits_host_impl(ldpc_bp_decoder *d, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
                                                uint64_t *err_w, int64_t err_bit0, uint8_t *conv, double *llr, int32_t *iters)
 {
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
     ldpc_status st;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     auto wbytes = [](size_t nbits) { return (((nbits + 63) >> 6) + 1) * sizeof(uint64_t); };   // words covering nbits at any offset
     // one chunk of columns [b0, b0 + nb) in a host image hp: where its words lie in the caller's arrays
     struct Span { size_t w0; int off; size_t nwords; };
@@ -2914,28 +2699,30 @@ static ldpc_status decode_batch_bits_host_impl(ldpc_bp_decoder *d, int64_t batch
     };
     {
         // Small batches (a plain decode! is batch = 1): one pinned image, one copy in, one copy out -- as the byte entry
-        const size_t o_err = up(wbytes(B * s)), o_conv = o_err + up(wbytes(B * n)), o_it = o_conv + up(B),
-                     o_llr = o_it + up(B * sizeof(int32_t)), total = o_llr + (llr ? up(B * n * sizeof(double)) : 0);
+        ldpc_detail::Carve image;
+        image.take(wbytes(B * s));
+        const size_t o_err = image.take(wbytes(B * n)), o_conv = image.take(B), o_it = image.take(B * sizeof(int32_t)),
+                     o_llr = image.take(llr ? B * n * sizeof(double) : 0), total = image.at;
         if (total <= ((size_t)4 << 20)) {
             hipStream_t stream = nullptr;
             if ((st = d->st_all.ensure(total)) != LDPC_OK) return st;
             if (d->pin_cap < total) {
                 if (d->pin) (void)hipHostFree(d->pin);
                 d->pin = nullptr; d->pin_cap = 0;
-                HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
+                LDPC_HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
                 d->pin_cap = total;
             }
             char *hp = (char *)d->pin, *dp = (char *)d->st_all.p;
             const Span ss = span_of(syn_bit0, 0, B, s), se = span_of(err_bit0, 0, B, n);
             if (ss.nwords) {
                 std::memcpy(hp, syn_w + ss.w0, ss.nwords * sizeof(uint64_t));
-                HIP_TRY(hipMemcpyAsync(dp, hp, ss.nwords * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+                LDPC_HIP_TRY(hipMemcpyAsync(dp, hp, ss.nwords * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             }
             st = ldpc_bp_decode_batch_bits_device(d, batch, (const uint64_t *)dp, ss.off, (uint64_t *)(dp + o_err), se.off,
                                                   (uint8_t *)(dp + o_conv), llr ? (double *)(dp + o_llr) : nullptr,
                                                   (int32_t *)(dp + o_it), stream);
             if (st != LDPC_OK) return st;
-            HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
+            LDPC_HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
             if ((st = ldpc_detail::wait_stream(stream, d->device, "ldpc_bp_decode_batch_bits (small batch: stream synchronise)")) != LDPC_OK) return st;
             merge_bit_range(err_w + se.w0, (const uint64_t *)(hp + o_err), se.off, B * n);
             std::memcpy(conv, hp + o_conv, B);
@@ -2956,19 +2743,21 @@ static ldpc_status decode_batch_bits_host_impl(ldpc_bp_decoder *d, int64_t batch
         if (B < cb + cb / 2) cb = B;                               // no tiny trailing chunk
         if (const char *e = exp_env("LDPC_BITS_CHUNK_SYNDROMES")) cb = (size_t)std::max<long>(1, std::atol(e));   // (tests: chunk borders inside words)
         const size_t nchunks = (B + cb - 1) / cb;
-        const size_t o_err = up(wbytes(cb * s)), o_conv = o_err + up(wbytes(cb * n)), o_it = o_conv + up(cb),
-                     o_llr = o_it + up(cb * sizeof(int32_t)), total = o_llr + (llr ? up(cb * n * sizeof(double)) : 0);
+        ldpc_detail::Carve image;
+        image.take(wbytes(cb * s));
+        const size_t o_err = image.take(wbytes(cb * n)), o_conv = image.take(cb), o_it = image.take(cb * sizeof(int32_t)),
+                     o_llr = image.take(llr ? cb * n * sizeof(double) : 0), total = image.at;
         for (int q = 0; q < 3; ++q)
-            if (!d->pipe_stream[q]) HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
+            if (!d->pipe_stream[q]) LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
         for (auto &row : d->pipe_ev)
             for (hipEvent_t &e : row)
-                if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                if (!e) LDPC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         const int R = (int)std::min<size_t>(ldpc_bp_decoder::kPipe, nchunks);
         for (int q = 0; q < R; ++q) {
             if (d->bits_pin_cap[q] < total) {
                 if (d->bits_pin[q]) (void)hipHostFree(d->bits_pin[q]);
                 d->bits_pin[q] = nullptr; d->bits_pin_cap[q] = 0;
-                HIP_TRY(hipHostMalloc(&d->bits_pin[q], total, hipHostMallocDefault));
+                LDPC_HIP_TRY(hipHostMalloc(&d->bits_pin[q], total, hipHostMallocDefault));
                 d->bits_pin_cap[q] = total;
             }
             if ((st = d->pipe_dev[q].ensure(total)) != LDPC_OK) return st;
@@ -3017,9 +2806,9 @@ static ldpc_status decode_batch_bits_host_impl(ldpc_bp_decoder *d, int64_t batch
         if (pst == LDPC_OK)
             for (size_t j = nchunks > (size_t)R ? nchunks - R : 0; j < nchunks && pst == LDPC_OK; ++j) pst = drain(j);
         if (pst != LDPC_OK) {
-            const std::string keep = g_err;
+            const std::string keep = ldpc_detail::last_error();
             (void)ldpc_detail::wait_device(d->device, "ldpc_bp_decode_batch_bits (host pipeline: drain after an error)");   // nothing of this call may still be in flight when we return
-            g_err = keep;
+            (void)fail(pst, keep);
         }
         return pst;
     }
@@ -3043,7 +2832,7 @@ extern "C" {
 ldpc_status ldpc_bp_last_status(ldpc_bp_decoder *d)
 {
     if (!d) return fail(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     if (d->last_ev) {
         const ldpc_status wst = ldpc_detail::wait_event(d->last_ev, d->device, "ldpc_bp_last_status (wait for the handle's last call)");
         if (wst != LDPC_OK) return wst;
@@ -3062,7 +2851,7 @@ ldpc_status ldpc_bp_call_timing(ldpc_bp_decoder *d, int32_t calls_back, double *
         return fail(LDPC_ERR_INVALID_ARGUMENT, "calls_back outside the timing ring");
     const int slot = (int)((d->ncalls - 1 - (uint64_t)calls_back) % ldpc_bp_decoder::kRing);
     if (!d->timed[slot]) return LDPC_OK;
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     const int e0 = d->two_events[slot] ? 1 : 0, e3 = d->two_events[slot] ? 2 : 3;
     const bool bits = d->bits_timed[slot];   // a bits entry: total_ms spans its two conversions as well
     {
@@ -3070,14 +2859,14 @@ ldpc_status ldpc_bp_call_timing(ldpc_bp_decoder *d, int32_t calls_back, double *
         if (wst != LDPC_OK) return wst;
     }
     float a = 0.f, b = 0.f;
-    HIP_TRY(hipEventElapsedTime(&a, d->ev[slot][1], d->ev[slot][2]));
-    if (bits) HIP_TRY(hipEventElapsedTime(&b, d->bits_ev[slot][0], d->bits_ev[slot][1]));
-    else HIP_TRY(hipEventElapsedTime(&b, d->ev[slot][e0], d->ev[slot][e3]));
+    LDPC_HIP_TRY(hipEventElapsedTime(&a, d->ev[slot][1], d->ev[slot][2]));
+    if (bits) LDPC_HIP_TRY(hipEventElapsedTime(&b, d->bits_ev[slot][0], d->bits_ev[slot][1]));
+    else LDPC_HIP_TRY(hipEventElapsedTime(&b, d->ev[slot][e0], d->ev[slot][e3]));
     if (sweep_ms) *sweep_ms = a;
     if (total_ms) *total_ms = b;
     if (sum_iters) {
         u64 v = 0;
-        HIP_TRY(hipMemcpy(&v, (char *)d->ctrl.p + 64 * slot + 8, sizeof v, hipMemcpyDeviceToHost));
+        LDPC_HIP_TRY(hipMemcpy(&v, (char *)d->ctrl.p + 64 * slot + 8, sizeof v, hipMemcpyDeviceToHost));
         *sum_iters = (int64_t)v;
     }
     return LDPC_OK;
@@ -3091,12 +2880,12 @@ ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *d, int32_t calls_back, uin
         return fail(LDPC_ERR_INVALID_ARGUMENT, "calls_back outside the timing ring");
     const int slot = (int)((d->ncalls - 1 - (uint64_t)calls_back) % ldpc_bp_decoder::kRing);
     if (!d->timed[slot]) return LDPC_OK;
-    HIP_TRY(hipSetDevice(d->device));
+    LDPC_HIP_TRY(hipSetDevice(d->device));
     {
         const ldpc_status wst = ldpc_detail::wait_event(d->ev[slot][d->two_events[slot] ? 2 : 3], d->device, "ldpc_bp_call_phase_ticks (wait for that call)");
         if (wst != LDPC_OK) return wst;
     }
-    HIP_TRY(hipMemcpy(ticks, (char *)d->ctrl.p + 64 * slot + 16, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    LDPC_HIP_TRY(hipMemcpy(ticks, (char *)d->ctrl.p + 64 * slot + 16, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return LDPC_OK;
 }
 

@@ -22,7 +22,7 @@
 // There is no CPU path here either: everything decodes through ldpc_bp_decode_batch[_device].
 #include "../../include/ldpc_mi355x.h"
 #include "host_env.hpp"
-#include "host_wait.hpp"
+#include "host_common.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -37,19 +37,10 @@
 #include <thread>
 #include <vector>
 
-using ldpc_detail::set_error;   // (ldpc_mi355x.hip, declared in host_wait.hpp)
+using ldpc_detail::DeviceGuard;
+using ldpc_detail::set_error;
 
 namespace {
-
-#define MHIP_TRY(expr)                                                                              \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            (void)hipGetLastError();                                                                \
-            return set_error(e_ == hipErrorOutOfMemory ? LDPC_ERR_OUT_OF_MEMORY : LDPC_ERR_HIP,     \
-                             std::string(#expr) + ": " + hipGetErrorString(e_));                    \
-        }                                                                                           \
-    } while (0)
 
 // ---- RCCL, bound at run time
 struct Rccl {
@@ -111,12 +102,6 @@ struct GroupGuard {
     ncclResult_t start() { const ncclResult_t r = R->GroupStart(); open = r == ncclSuccess; return r; }
     ncclResult_t end() { open = false; return R->GroupEnd(); }
     ~GroupGuard() { if (open) (void)R->GroupEnd(); }
-};
-
-struct DeviceGuard {
-    int prev = -1;
-    DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; } }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
 struct Buf {
@@ -408,16 +393,16 @@ ldpc_status ldpc_bp_decode_batch_multi_device(ldpc_bp_multi *m, int64_t batch, c
         shard_bounds(batch, G, g, &lo, &hi);
         const size_t c = (size_t)(hi - lo);
         if (!c) continue;
-        MHIP_TRY(hipSetDevice(m->dev[(size_t)g]));
+        LDPC_HIP_TRY(hipSetDevice(m->dev[(size_t)g]));
         ldpc_bp_multi::Shard &sh = m->shard[(size_t)g];
-        MHIP_TRY(sh.syn.ensure(std::max<size_t>(c * s, 1)));
-        MHIP_TRY(sh.err.ensure(std::max<size_t>(c * n, 1)));
-        MHIP_TRY(sh.conv.ensure(c));
-        if (d_iters) MHIP_TRY(sh.iters.ensure(c * sizeof(int32_t)));
-        if (d_llr) MHIP_TRY(sh.llr.ensure(std::max<size_t>(c * n, 1) * sizeof(double)));
+        LDPC_HIP_TRY(sh.syn.ensure(std::max<size_t>(c * s, 1)));
+        LDPC_HIP_TRY(sh.err.ensure(std::max<size_t>(c * n, 1)));
+        LDPC_HIP_TRY(sh.conv.ensure(c));
+        if (d_iters) LDPC_HIP_TRY(sh.iters.ensure(c * sizeof(int32_t)));
+        if (d_llr) LDPC_HIP_TRY(sh.llr.ensure(std::max<size_t>(c * n, 1) * sizeof(double)));
     }
-    MHIP_TRY(hipSetDevice(m->dev[0]));
-    MHIP_TRY(hipEventRecord(m->ev_t[0], R));
+    LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
+    LDPC_HIP_TRY(hipEventRecord(m->ev_t[0], R));
 
     // ---- scatter: syndromes of shard g -> device g
     if (use_rccl) {
@@ -452,20 +437,20 @@ ldpc_status ldpc_bp_decode_batch_multi_device(ldpc_bp_multi *m, int64_t batch, c
             return LDPC_ERR_HIP;
         }
     } else if (G > 1) {
-        MHIP_TRY(hipSetDevice(m->dev[0]));
-        MHIP_TRY(hipEventRecord(m->ev_in, R));
+        LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
+        LDPC_HIP_TRY(hipEventRecord(m->ev_in, R));
         for (int g = 1; g < G; ++g) {
             int64_t lo, hi;
             shard_bounds(batch, G, g, &lo, &hi);
             const size_t c = (size_t)(hi - lo);
             if (!c) continue;
-            MHIP_TRY(hipSetDevice(m->dev[(size_t)g]));
-            MHIP_TRY(hipStreamWaitEvent(m->st[(size_t)g], m->ev_in, 0));
-            if (s) MHIP_TRY(hipMemcpyPeerAsync(m->shard[(size_t)g].syn.p, m->dev[(size_t)g], d_syn + (size_t)lo * s, m->dev[0], c * s, m->st[(size_t)g]));
+            LDPC_HIP_TRY(hipSetDevice(m->dev[(size_t)g]));
+            LDPC_HIP_TRY(hipStreamWaitEvent(m->st[(size_t)g], m->ev_in, 0));
+            if (s) LDPC_HIP_TRY(hipMemcpyPeerAsync(m->shard[(size_t)g].syn.p, m->dev[(size_t)g], d_syn + (size_t)lo * s, m->dev[0], c * s, m->st[(size_t)g]));
         }
     }
-    MHIP_TRY(hipSetDevice(m->dev[0]));
-    MHIP_TRY(hipEventRecord(m->ev_t[1], R));
+    LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
+    LDPC_HIP_TRY(hipEventRecord(m->ev_t[1], R));
 
     // ---- decode: every device its shard, on its own stream; the root straight into the caller's arrays
     for (int g = 0; g < G; ++g) {
@@ -490,8 +475,8 @@ ldpc_status ldpc_bp_decode_batch_multi_device(ldpc_bp_multi *m, int64_t batch, c
             return ds;
         }
     }
-    MHIP_TRY(hipSetDevice(m->dev[0]));
-    MHIP_TRY(hipEventRecord(m->ev_t[2], R));
+    LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
+    LDPC_HIP_TRY(hipEventRecord(m->ev_t[2], R));
 
     // ---- gather: hard decisions, flags (, iteration counts, LLRs) of shard g -> the caller's arrays on the root
     if (use_rccl) {
@@ -541,18 +526,18 @@ ldpc_status ldpc_bp_decode_batch_multi_device(ldpc_bp_multi *m, int64_t batch, c
             const size_t c = (size_t)(hi - lo);
             if (!c) continue;
             ldpc_bp_multi::Shard &sh = m->shard[(size_t)g];
-            MHIP_TRY(hipSetDevice(m->dev[(size_t)g]));
-            MHIP_TRY(hipEventRecord(m->ev_done[(size_t)g], m->st[(size_t)g]));
-            MHIP_TRY(hipSetDevice(m->dev[0]));
-            MHIP_TRY(hipStreamWaitEvent(R, m->ev_done[(size_t)g], 0));
-            if (n) MHIP_TRY(hipMemcpyPeerAsync(d_err + (size_t)lo * n, m->dev[0], sh.err.p, m->dev[(size_t)g], c * n, R));
-            MHIP_TRY(hipMemcpyPeerAsync(d_conv + lo, m->dev[0], sh.conv.p, m->dev[(size_t)g], c, R));
-            if (d_iters) MHIP_TRY(hipMemcpyPeerAsync(d_iters + lo, m->dev[0], sh.iters.p, m->dev[(size_t)g], c * sizeof(int32_t), R));
-            if (d_llr && n) MHIP_TRY(hipMemcpyPeerAsync(d_llr + (size_t)lo * n, m->dev[0], sh.llr.p, m->dev[(size_t)g], c * n * sizeof(double), R));
+            LDPC_HIP_TRY(hipSetDevice(m->dev[(size_t)g]));
+            LDPC_HIP_TRY(hipEventRecord(m->ev_done[(size_t)g], m->st[(size_t)g]));
+            LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
+            LDPC_HIP_TRY(hipStreamWaitEvent(R, m->ev_done[(size_t)g], 0));
+            if (n) LDPC_HIP_TRY(hipMemcpyPeerAsync(d_err + (size_t)lo * n, m->dev[0], sh.err.p, m->dev[(size_t)g], c * n, R));
+            LDPC_HIP_TRY(hipMemcpyPeerAsync(d_conv + lo, m->dev[0], sh.conv.p, m->dev[(size_t)g], c, R));
+            if (d_iters) LDPC_HIP_TRY(hipMemcpyPeerAsync(d_iters + lo, m->dev[0], sh.iters.p, m->dev[(size_t)g], c * sizeof(int32_t), R));
+            if (d_llr && n) LDPC_HIP_TRY(hipMemcpyPeerAsync(d_llr + (size_t)lo * n, m->dev[0], sh.llr.p, m->dev[(size_t)g], c * n * sizeof(double), R));
         }
     }
-    MHIP_TRY(hipSetDevice(m->dev[0]));
-    MHIP_TRY(hipEventRecord(m->ev_t[3], R));
+    LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
+    LDPC_HIP_TRY(hipEventRecord(m->ev_t[3], R));
     m->timed = true;
     return LDPC_OK;
 }
@@ -584,15 +569,15 @@ ldpc_status ldpc_bp_multi_get_info(ldpc_bp_multi *m, ldpc_bp_multi_info *info)
     for (int g = 0; g < m->ndev; ++g) info->devices[g] = m->dev[(size_t)g];
     if (!m->timed) return LDPC_OK;
     DeviceGuard guard;
-    MHIP_TRY(hipSetDevice(m->dev[0]));
+    LDPC_HIP_TRY(hipSetDevice(m->dev[0]));
     {
         const ldpc_status ws = ldpc_detail::wait_event(m->ev_t[3], m->dev[0], "ldpc_bp_multi_get_info (wait for the most recent root-device call)");
         if (ws != LDPC_OK) return ws;
     }
     float a = 0.f, b = 0.f, c = 0.f;
-    MHIP_TRY(hipEventElapsedTime(&a, m->ev_t[0], m->ev_t[1]));
-    MHIP_TRY(hipEventElapsedTime(&b, m->ev_t[1], m->ev_t[2]));
-    MHIP_TRY(hipEventElapsedTime(&c, m->ev_t[2], m->ev_t[3]));
+    LDPC_HIP_TRY(hipEventElapsedTime(&a, m->ev_t[0], m->ev_t[1]));
+    LDPC_HIP_TRY(hipEventElapsedTime(&b, m->ev_t[1], m->ev_t[2]));
+    LDPC_HIP_TRY(hipEventElapsedTime(&c, m->ev_t[2], m->ev_t[3]));
     info->scatter_ms = a; info->root_decode_ms = b; info->gather_ms = c;
     for (int g = 0; g < m->ndev; ++g) {
         int64_t lo, hi;

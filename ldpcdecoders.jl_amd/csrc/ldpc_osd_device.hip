@@ -18,18 +18,8 @@
 
 using namespace ldpc;
 
-#include "host_wait.hpp"   // set_error, and the bounded forms of every host-side wait
+#include "host_common.hpp"   // set_error, LDPC_HIP_TRY, select_device, CallOrder and (host_wait.hpp) the bounded waits
 using ldpc_detail::set_error;
-
-#define OSD_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (void)hipGetLastError();                                                         \
-            return set_error(e_ == hipErrorOutOfMemory ? LDPC_ERR_OUT_OF_MEMORY : LDPC_ERR_HIP, \
-                             std::string(#expr) + ": " + hipGetErrorString(e_));             \
-        }                                                                                    \
-    } while (0)
 
 static constexpr int64_t kOsdWaveRows = 128, kOsdWaveCols = 512;
 static constexpr size_t kOsdGroupLds = (size_t)159 * 1024;
@@ -44,10 +34,7 @@ struct OsdDevice {
     osd_u64 *rows = nullptr;
     unsigned char *ws = nullptr;   // tier 3: [grid][state]
     int64_t ws_grid = 0;
-    // calls on a handle run in call order whatever streams they are given (tier 3: they share the workspace)
-    hipEvent_t last_done = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool have_last = false;
+    ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (tier 3: they share the workspace)
 };
 
 typedef void (*osd_kernel_t)(OsdParams);
@@ -70,7 +57,7 @@ void osd_device_free(void *v)
         ldpc_detail::device_idle_for_release(dv->device, "ldpc_osd_destroy (device synchronise)")) {
         if (dv->rows) (void)hipFree(dv->rows);
         if (dv->ws) (void)hipFree(dv->ws);
-        if (dv->last_done) (void)hipEventDestroy(dv->last_done);
+        dv->calls.destroy();
     }
     delete dv;
 }
@@ -95,19 +82,9 @@ ldpc_status ldpc_osd_device_prepare(ldpc_osd *d, int32_t device, int32_t kernel_
     if ((kernel_variant == 1 && !fits1) || (kernel_variant == 2 && !fits2))
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant: the state of a syndrome does not fit that on-chip tier");
     if (state > kOsdWorkspaceCap) return set_error(LDPC_ERR_UNSUPPORTED, "device OSD: the state of one syndrome exceeds the workspace cap");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return set_error(LDPC_ERR_NO_DEVICE, "no HIP device available (the device OSD entries have no CPU fallback)");
-    }
-    if (device < 0) OSD_TRY(hipGetDevice(&device));
-    if (device >= ndev) return set_error(LDPC_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    OSD_TRY(hipSetDevice(device));
-    if (ldpc_detail::device_stalled(device)) return ldpc_detail::stalled_error(device);
     hipDeviceProp_t prop;
-    OSD_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return set_error(LDPC_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    const ldpc_status sel = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (the device OSD entries have no CPU fallback)");
+    if (sel != LDPC_OK) return sel;
 
     OsdDevice *dv = new (std::nothrow) OsdDevice();
     if (!dv) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -124,16 +101,11 @@ ldpc_status ldpc_osd_device_prepare(ldpc_osd *d, int32_t device, int32_t kernel_
     if (hipMalloc((void **)&dv->rows, row_bytes) != hipSuccess) return fail(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the packed rows failed");
     if (!d->rows.empty() && hipMemcpy(dv->rows, d->rows.data(), d->rows.size() * sizeof(osd_u64), hipMemcpyHostToDevice) != hipSuccess)
         return fail(LDPC_ERR_HIP, "upload of the packed rows failed");
-    if (hipEventCreateWithFlags(&dv->last_done, hipEventDisableTiming) != hipSuccess) return fail(LDPC_ERR_HIP, "hipEventCreate failed");
+    if (dv->calls.create() != hipSuccess) return fail(LDPC_ERR_HIP, "hipEventCreate failed");
     osd_kernel_t k = osd_kernel_of(dv->tier);
     if (dv->lds && hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv->lds) != hipSuccess)
         return fail(LDPC_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, dv->threads, dv->lds) != hipSuccess || per_cu <= 0) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    dv->per_cu = per_cu;
+    const int per_cu = dv->per_cu = ldpc_detail::blocks_per_cu((const void *)k, dv->threads, dv->lds);
     if (dv->tier == 3) {
         dv->ws_grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)per_cu * dv->num_cus, (int64_t)(kOsdWorkspaceCap / state)));
         if (hipMalloc((void **)&dv->ws, (size_t)dv->ws_grid * state) != hipSuccess)
@@ -158,9 +130,10 @@ ldpc_status ldpc_osd_postprocess_batch_device(ldpc_osd *d, int64_t batch, const 
     if (d->n == 0) return LDPC_OK;   // nothing to write
     OsdDevice *dv = (OsdDevice *)d->dev;
     hipStream_t stream = (hipStream_t)stream_v;
-    OSD_TRY(hipSetDevice(dv->device));
+    LDPC_HIP_TRY(hipSetDevice(dv->device));
     if (ldpc_detail::device_stalled(dv->device)) return ldpc_detail::stalled_error(dv->device);
-    if (dv->have_last && dv->last_stream != stream) OSD_TRY(hipStreamWaitEvent(stream, dv->last_done, 0));
+    const ldpc_status ent = dv->calls.enter(stream);
+    if (ent != LDPC_OK) return ent;
     int64_t grid = std::min<int64_t>(batch, (int64_t)dv->per_cu * dv->num_cus);
     if (dv->tier == 3) grid = std::min<int64_t>(grid, dv->ws_grid);
     OsdParams p{};
@@ -169,10 +142,8 @@ ldpc_status ldpc_osd_postprocess_batch_device(ldpc_osd *d, int64_t batch, const 
     p.syn = d_syndromes; p.bp = d_bp_errors; p.llr = d_llr; p.out = d_errors;
     p.rows = dv->rows; p.ws = dv->ws; p.slot_bytes = (long long)dv->state;
     hipLaunchKernelGGL(osd_kernel_of(dv->tier), dim3((unsigned)grid), dim3((unsigned)dv->threads), dv->lds, stream, p);
-    OSD_TRY(hipGetLastError());
-    OSD_TRY(hipEventRecord(dv->last_done, stream));
-    dv->last_stream = stream; dv->have_last = true;
-    return LDPC_OK;
+    LDPC_HIP_TRY(hipGetLastError());
+    return dv->calls.leave(stream);
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 #include <vector>
 
 namespace ldpc_detail {
-ldpc_status set_error(ldpc_status st, const std::string &msg);  // defined in ldpc_mi355x.hip
+ldpc_status set_error(ldpc_status st, const std::string &msg);  // defined in host_common.hip
 }
 using ldpc_detail::set_error;
 
