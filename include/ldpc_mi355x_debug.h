@@ -1,8 +1,8 @@
 /*
  * ldpc_mi355x_debug.h -- test hooks of libldpc_mi355x.so.  NOT part of the drop-in boundary (include/ldpc_mi355x.h):
  * nothing here replaces a reference interface; the CPU test-suite uses these entries to check, without a GPU, the
- * host-side planning the team kernel relies on (ldpcdecoders.jl_amd/csrc/ldpc_mi355x.hip: team_plan_pure(),
- * team_rows_tables()).  Pure host code; no device is needed or touched.
+ * host-side planning the team kernel relies on (ldpcdecoders.jl_amd/csrc/team_plan.cpp: team_plan_pure(),
+ * team_rows_tables(), team_irr_tables()).  Pure host code; no device is needed or touched.
  */
 #ifndef LDPC_MI355X_DEBUG_H
 #define LDPC_MI355X_DEBUG_H
@@ -41,7 +41,7 @@ ldpc_status ldpc_debug_team_rows(int64_t s, int64_t n, const int64_t *colptr, co
                                  int32_t *vtab, int32_t *ctab, int32_t *lds_edge, int32_t *reg_edge);
 
 /* The tables with which the team kernel keeps WHOLE CHECKS of an IRREGULAR graph (any CSC pattern) in the LDS of their
-   owners (csrc/ldpc_mi355x.hip team_irr_tables(); bp_team_kernels.hpp, IRR), for teams of `members` workgroups and nodes
+   owners (csrc/team_plan.cpp team_irr_tables(); bp_team_kernels.hpp, IRR), for teams of `members` workgroups and nodes
    inside the register buckets dc_bucket / dv_bucket.  Out: shape = {R = LDS rows per member (at most 312), rows in LDS in
    all}; ctab2 [s + 1][2] = per check {its first CSR row, its first LDS row or -1}; ptab [n + 1][2] = per position of the
    dealt bit order {first entry of its edge list in ploc, the bit | 1 << 31 when one of its edges is in LDS}; ploc [nnz] =

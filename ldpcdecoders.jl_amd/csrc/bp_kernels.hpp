@@ -30,11 +30,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "team_layout.hpp"   // kTile, and what the team kernel shares with the host's planner
+
 namespace ldpc {
 
 typedef unsigned long long u64;
-
-constexpr int kTile = 64;  // syndromes per tile == wavefront width on gfx950
 
 // Build-time tuning knobs (defaults = the shipped configuration; DESIGN.md lists what was measured)
 #ifndef LDPC_MIN_WAVES   // 2nd __launch_bounds__ argument = waves per SIMD the register budget must allow.

@@ -39,9 +39,7 @@
 #pragma once
 #include "bp_kernels.hpp"
 
-#ifndef LDPC_TEAM_THREADS   // threads per member (experiments: 1024 = one 16-wave member per CU)
-#define LDPC_TEAM_THREADS 512
-#endif
+// (LDPC_TEAM_THREADS, threads per member: team_layout.hpp)
 #ifndef LDPC_TEAM_ROWS_WIDE   // 1 = the rows-in-LDS instantiation may use 256 VGPRs (it runs one workgroup per CU)
 #define LDPC_TEAM_ROWS_WIDE 1
 #endif
@@ -71,9 +69,7 @@ namespace ldpc {
 //                             them (they follow each other)
 //   csc2csr  -> vtab [n][VT]  per position p of the dealt bit order: CSR rows of its DV edges, their LDS rows or -1, the
 //                             bit (| 1 << 31 when one of its edges is in LDS), padding to VT = 8 or 16 words
-__host__ __device__ constexpr int team_vtab_words(int dv) { return 2 * dv + 1 <= 8 ? 8 : 16; }
-// the degree pairs that have a rows-in-LDS instantiation (pick_team.hip)
-__host__ __device__ constexpr bool team_rows_degrees_ok(int dc, int dv) { return dc >= 6 && dc <= 10 && dv >= 3 && dv <= 5; }
+// (team_vtab_words(), team_rows_degrees_ok(), kTeamRowsMax: team_layout.hpp)
 
 // One position record of vtab, read with as few scalar loads as its width allows (words 0 ... 7 in one, the rest in one more).
 template <int DV>
@@ -117,7 +113,7 @@ __device__ __forceinline__ TeamVRec<DV> team_vrec_load(const int *__restrict__ v
 // both the row's check and its bit in every iteration.  So a part of every member's share of a sweep belongs to its
 // waves BY RIGHT (the first static_c check chunks / static_v position chunks: chunk l of the share to wave l % W; the
 // rest is dealt from the counter in LDS as before), and the host puts a bit whose owning check is such a wave's into
-// a position that is the same wave's (team_rows_tables()).  A wave keeps up to kTeamRegRows rows in the TOP of its
+// a position that is the same wave's (team_plan.cpp team_rows_tables()).  A wave keeps up to kTeamRegRows rows in the TOP of its
 // register file: row x in v[192 + 2x], v[193 + 2x], addressed with the wave-uniform row number through the VGPR index
 // mode (s_set_gpr_idx_on + v_mov_b32).  The rows-on-chip instantiations run one 8-wave workgroup per CU (156 KB of
 // LDS), i.e. two waves per SIMD: 256 registers a lane are theirs anyway, and the compiler needs about 130 of them and
@@ -136,8 +132,7 @@ __device__ __forceinline__ TeamVRec<DV> team_vrec_load(const int *__restrict__ v
 // the owner of its first check) -- a quarter of the checks is updated without touching memory (check_update_regs, or
 // check_update_exact on the LDS rows) and every bit has exactly its first edge on chip (bit_update_pair_first /
 // bit_update_multi_first).  The general updates below (a pointer per edge; check_update_onchip, bit_update_onchip)
-// remain for graphs and knob settings that spread the on-chip rows.
-constexpr int kTeamRegRows = 32;
+// remain for graphs and knob settings that spread the on-chip rows.  (kTeamRegRows: team_layout.hpp)
 #define LDPC_TEAM_TOP_VGPRS                                                                                                      \
     "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207",     \
         "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223", \
@@ -256,10 +251,9 @@ constexpr unsigned int kTeamRollcallFailed = 0x80000000u;
 // one_xcd: every member of the team runs on the same XCD, so their stores meet in ONE L2 and the
 // release (a write-back of that L2) is not needed; the acquire (this CU's L1) always is.
 // Returns false when the team is broken (somebody timed out): the caller leaves the kernel.
-constexpr int kTeamMaxMembers = 256;
+// (kTeamMaxMembers, kTeamCheckChunk: team_layout.hpp)
 constexpr int kTeamCtlMember = 64;                                  // first member line
 constexpr int kTeamCtlWords = 64 + 32 * kTeamMaxMembers;            // per team
-constexpr int kTeamCheckChunk = 2;                                  // checks per chunk of the check sweep
 
 #ifndef LDPC_TEAM_BARRIER_COUNTER
 #define LDPC_TEAM_BARRIER_COUNTER 0

@@ -18,6 +18,7 @@
 #include "bp_team_kernels.hpp"
 #include "bit_io_kernels.hpp"
 #include "pickers.hpp"
+#include "team_plan.hpp"
 #include "host_env.hpp"
 #include "host_common.hpp"
 
@@ -680,30 +681,6 @@ int32_t ldpc_device_count(void)
     return usable;
 }
 
-// The check-degree bucket of the IRR instantiation (bp_team_kernels.hpp) an irregular graph is decoded with: 8 or 16 --
-// the 32-wide straight-line code on generic pointers does not fit the registers.  A graph with a FEW wider checks (the
-// tail of a random construction; one wide check of a test) still takes the 16-wide instantiation: those checks stay in
-// the slot (the packing never puts them in LDS); up to 32 edges they are updated in two halves (check_update_halves:
-// the first half's rows are read twice), beyond that on the O(deg^2) path of every kernel (check_update_any: deg^2 / 2
-// divisions instead of 2 deg).  Admitted while the checks of 17 ... 32 edges hold at most an eighth of the edges and the
-// O(deg^2) ones cost at most 1 / 32 more divisions than the graph has anyway (2 nnz); otherwise 0: every row in the
-// slot, the plain 32-wide team kernel.
-static int team_irr_dc_bucket(const std::vector<int> &row_ptr, int s, int64_t nnz)
-{
-    int max_deg = 0;
-    int64_t halves = 0;   // edges of the checks of 17 ... 32 edges
-    int64_t wide = 0;     // sum of deg^2 over the checks beyond 32 edges
-    for (int i = 0; i < s; ++i) {
-        const int deg = row_ptr[(size_t)i + 1] - row_ptr[(size_t)i];
-        max_deg = std::max(max_deg, deg);
-        if (deg > 32) wide += (int64_t)deg * deg;
-        else if (deg > 16) halves += deg;
-    }
-    if (max_deg <= 8) return 8;
-    if (max_deg <= 16) return 16;
-    return (halves * 8 <= nnz && wide * 8 <= nnz) ? 16 : 0;      // (deg^2 / 2 against 2 nnz / 32)
-}
-
 ldpc_status ldpc_bp_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr,
                            const int64_t *rowval, double per, int64_t max_iters,
                            const ldpc_bp_options *options, ldpc_bp_decoder **out)
@@ -1014,290 +991,110 @@ static bool team_geometry(ldpc_bp_decoder *d, bool want_llr, int *per_xcd, int *
     return *per_xcd >= 1;
 }
 
-// LDS rows a member of a persistent team can hold: 312 x 512 B = 156 KiB of the 160 KiB (the kernel's own few words beside)
-constexpr int kTeamRowsMax = 312;
-
 static bool team_rows_possible(const ldpc_bp_decoder *d) { return d->team_rows_on && !d->h_csc2csr.empty() && !d->wpt_fixed; }
 static bool team_irr_possible(const ldpc_bp_decoder *d) { return d->team_rows_on && !d->h_row_ptr.empty() && !d->wpt_fixed && d->irr_dcb > 0; }
 
-// What the team plan depends on (pure data: ldpc_debug_team_plan() plans without a device for a CPU test)
-struct TeamPlanIn {
-    int64_t nnz = 0, max_iters = 0;
-    size_t cache = 0;          // budget of message slots in flight (ldpc_bp_decoder::team_cache)
-    int xcds_forced = 0;       // LDPC_TEAM_XCDS
-    bool team_max_set = false; // LDPC_TEAM_MAX given: no teams over all XCDs for <= 3 tiles
-    bool rows_possible = false;
-    int rows_dv = 4;           // bit degree of the regular graph (one edge per bit is a candidate for a row in LDS)
-    int reg_rows = 0;          // rows a member's waves keep in registers on top of the LDS (W x regs per wave)
-    int num_cus = 256;
-    int per_xcd = 0, gcap = 0; // team_geometry(): team workgroups one XCD hosts, members per team at most
-    int gcap_one = 0;          // ... members at most of a persistent team that has an XCD to itself (>= gcap)
-    // <= 3 tiles, members over all XCDs: members at most, message rows a member at least.  (Round 3, one tile of the C3 code,
-    // a single decode! / 50 iterations: 64 members 0.294 / 3.44 ms, 96: 0.246 / 2.96, 128: 0.221 / 2.62, 192: 0.230 / 2.70,
-    // 256: 0.244 / 3.00; n = 32768, 50 iterations: 64: 5.64, 128: 3.83, 192: 3.57, 256: 3.72 ms -- profiles/r03_scatter_tune.txt)
-    int scatter_max = 192, scatter_rows = 512;
-    // ... and up to how many tiles a batch is dealt that way (LDPC_TEAM_SCATTER_TILES).  (50 iterations, C3 code / n = 32768,
-    // all-XCD teams against one team per XCD: 1 tile 2.4 / 3.4 against 5.1 / 10.2 ms, 2 tiles 3.3 / 5.2, 3 tiles 4.3 / 7.1,
-    // 4 tiles 5.09 / 10.7 against 5.00 / 10.2, 5 tiles 6.1 / 13.9 against 5.1 / 12.1 -- profiles/r03_scatter_tiles.txt)
-    int scatter_tiles = 3;
-    // bytes a team keeps rewriting besides its message slot: with LLRs wanted the posterior odds of every bit of the tile in
-    // hand, n x 512 B per iteration (they live in the cache with the slot, and count against the same budget)
-    size_t extra = 0;
-    // an irregular graph whose tables (team_irr_tables()) were built for teams of irr_G members keep irr_on_chip of the
-    // tile's rows in LDS: counted off the slots of such teams
-    bool irr_possible = false;
-    int irr_G = 0, irr_on_chip = 0;
-    // WIDE teams (round 4): T < 8 persistent teams of (all workgroups) / T members each, dealt over ALL XCDs, rows on
-    // chip -- for graphs of which eight slots do not fit the Infinity Cache but a few do (n = 65536: 128 MiB a slot, 96 MiB
-    // with a quarter of the rows on chip: two; n = 32768: four).  Every barrier then writes the XCDs' L2s back (the
-    // members share no L2), and still -- 16,384 syndromes x 50 iterations, profiles/r04_wide_teams.txt -- n = 65536: 910 ms
-    // against the tile kernel's 1238 and eight one-XCD teams' 1228 (T = 1: 1112, T = 4: 1133: four slots are 384 MiB);
-    // n = 32768: T = 4 442 ms against eight one-XCD teams' 496 (T = 2: 533).  Without rows on chip: no (n = 65536, T = 2:
-    // 1300 ms).  0 = automatic (team_wide_auto()), -1 = never, T > 0 = forced (LDPC_TEAM_WIDE, experiments).
-    int wide = 0;
-};
-
-// What a member is expected to keep on chip (a bit dealt to a member that owns one of its dv checks: 1 / dv of the edges
-// are candidates; the LDS holds kTeamRowsMax of them, the waves' registers reg_rows more).
-static int team_rows_expected(const TeamPlanIn &in, int G)
+// one table of the team kernel on the device
+static ldpc_status team_upload(DevBuf &b, const std::vector<int> &v)
 {
-    if (!in.rows_possible && in.irr_possible) return G == in.irr_G ? in.irr_on_chip / std::max(G, 1) : 0;
-    return in.rows_possible ? (int)std::min<int64_t>(kTeamRowsMax + in.reg_rows, in.nnz / std::max(in.rows_dv, 1) / std::max(G, 1)) : 0;
+    ldpc_status r = b.ensure(std::max<size_t>(v.size() * 4, 4));
+    if (r != LDPC_OK) return r;
+    if (hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return fail(LDPC_ERR_HIP, "hipMemcpy of the team tables failed"); }
+    return LDPC_OK;
 }
 
-// The tables of TeamRows for teams of G members (kept until another G is asked for), for a regular graph whose checks
-// have dc edges each and whose bits dv.  Checks are dealt as the kernel deals them -- chunk c of 2 checks to member
-// c % G -- and so are the POSITIONS of the bit order, in chunks of 4; the bits are put into positions by the graph: a
-// bit goes to the member, among the owners of its dv checks, that has most room left (any member once those are
-// full).  Every edge whose check and bit then share the owner is a candidate for a row ON CHIP:
-//   * in the REGISTERS of one wave (TeamRegPlan; regs_per_wave > 0).  Inside a member the first `static_c` check
-//     chunks and the first `static_v` position chunks of every sweep belong to its waves by right (chunk l of the
-//     member's share to wave l % W; the rest is dealt from a counter as the waves finish).  A bit whose owning check
-//     sits in a static chunk of wave w is put into a static position of that same wave, as long as the wave has
-//     register rows and static positions left: that edge is then read and written by ONE wave in both sweeps of every
-//     iteration and lives in its registers, numbered per wave in check order;
-//   * else in the member's LDS: up to kTeamRowsMax per member, numbered in check order.
-// Tables: ctab [s][4] = per check {mask of its edges in LDS, LDS row of the first of them, mask of its edges in
-// registers, register row of the first of them} (a check's rows of either kind follow each other); vtab [n][vt]
-// (vt = team_vtab_words(dv)) = per position the CSR rows of the bit's dv edges, where each lives (>= 0: that LDS row,
-// -1: the slot, <= -2: register row -2 - x of the wave), the bit (| 1 << 31 when one of its edges is not in the
-// slot), padding; lds_edge [G][R], reg_edge [G][W][regs_per_wave] = the CSR rows held (-1: none), for the write-back
-// before a hand-off.
-// (pure host code: ldpc_debug_team_rows() hands the tables to a CPU test)
-struct TeamRegPlan {
-    int regs_per_wave = 0;        // 0 = no rows in registers
-    int static_c = 0, static_v = 0;   // chunks of a member's share of the check / variable sweep that belong to waves by right (multiples of W)
-    int W = LDPC_TEAM_THREADS / 64;
-    bool concentrate = true;       // bits go to the owner of their first check where there is room (team_rows_tables())
-    bool whole_checks = false;     // ... and only checks with ALL their rows on chip keep them there
-    bool strays_last = true;       // bits with a later edge on chip take a member's last positions (team_rows_tables(); LDPC_TEAM_STRAYS_LAST=0: by number)
-};
-struct TeamRowTables {
-    int R = 0;                    // LDS rows per member (the largest count; kTeamRowsMax at most)
-    int vt = 0;                   // words per position record of vtab
-    size_t in_lds = 0, in_regs = 0;   // edges with a row in LDS / in registers
-    std::vector<int> vtab, ctab, lds_edge, reg_edge;
-};
-// the static part of a member's share under a plan: `frac_num / 4` of the smallest member's chunks, whole rounds of W
-static TeamRegPlan team_reg_plan(int n, int s, int G, int regs_per_wave, int quarters, int dv, int dc)
+static ldpc_status team_irr_build(ldpc_bp_decoder *d, int G)
 {
-    TeamRegPlan rp;
-    // Rows of checks that are only PARTLY on chip (a member's room beyond the whole checks of its block: 2-3 % of the
-    // rows) put those checks and their bits on the general per-edge updates.  Round 4, 65,536 syndromes x 50 iterations,
-    // alternating on one box, with them / whole checks only: bit degree 3 -- (3,6) n = 16380 505.2 / 491.2 ms, (3,9)
-    // 503.0 / 498.5 ms: whole checks only; bit degree 4 and 5 -- C3 703.6 / 706.5 ms, (4,10) 354.5 / 358.2 ms, (5,10)
-    // 488.9 / 493.4 ms: with them.  (profiles/r04_tform_ab.txt)
-    rp.whole_checks = dv == 3;
-    // ... and where they stay, their bits take a member's last positions (team_rows_tables()): C3 full-50 702.5 -> 700.9 ms, per
-    // 0.02 49.1 -> 48.7 ms, with LLRs 739.8 -> 735.2 ms; check degree 10 lost by it ((4,10) 353.2 -> 354.5 ms, (5,10) 488.5 ->
-    // 491.4 ms) and keeps them dealt by number.
-    rp.strays_last = dc <= 9;
-    const int W = rp.W;
-    const int nch_c = (s + kTeamCheckChunk - 1) / kTeamCheckChunk, nch_v = (n + 3) / 4;
-    const int min_c = nch_c / G, min_v = nch_v / G;           // the smallest member's share
-    rp.static_c = std::max(W, min_c * quarters / 4 / W * W);
-    rp.static_v = std::max(W, min_v * quarters / 4 / W * W);
-    if (min_c < 2 * W || min_v < 2 * W || quarters <= 0) { rp.static_c = W; rp.static_v = W; }   // (round 2's dealing: a wave's first chunk is its by right)
-    else rp.regs_per_wave = regs_per_wave;
-    return rp;
+    if (d->irr_G == G) return LDPC_OK;
+    const TeamIrrTables t = team_irr_tables((int)d->n, (int)d->s, (int)d->nnz, d->h_row_ptr, d->h_edge_bit, d->h_col_ptr, d->h_irr_c2r, G,
+                                            d->irr_dcb, team_bucket_dv(d->max_bdeg));
+    if (t.why) return fail(LDPC_ERR_HIP, t.why);
+    ldpc_status st;
+    if ((st = ldpc_detail::wait_device(d->device, "team tables of an irregular graph (device synchronise before the tables are replaced)")) != LDPC_OK) return st;
+    if ((st = team_upload(d->irr_ctab, t.ctab2)) != LDPC_OK || (st = team_upload(d->irr_ptab, t.ptab)) != LDPC_OK || (st = team_upload(d->irr_ploc, t.ploc)) != LDPC_OK ||
+        (st = team_upload(d->irr_lds_edge, t.lds_edge)) != LDPC_OK || (st = team_upload(d->irr_posmap, t.posmap)) != LDPC_OK)
+        return st;
+    d->irr_G = G; d->irr_R = t.R; d->irr_on_chip = (int)t.in_lds;
+    if (exp_env("LDPC_TEAM_DEBUG"))
+        std::fprintf(stderr, "[ldpc] team tables (irregular graph): %d members, %d LDS rows each at most, %zu of %d edges in LDS\n", G, t.R, t.in_lds, (int)d->nnz);
+    return LDPC_OK;
 }
-static TeamRowTables team_rows_tables(int n, int s, int nnz, int dc, int dv, const std::vector<int> &c2r, int G, const TeamRegPlan &rp)
+
+static ldpc_status team_rows_build(ldpc_bp_decoder *d, int G)
 {
-    TeamRowTables out;
-    const int vt = team_vtab_words(dv), W = rp.W, RC = rp.regs_per_wave;
-    auto check_owner = [&](int i) { return (i / kTeamCheckChunk) % G; };
-    // the wave that owns check i by right inside its member, or -1 (dealt dynamically)
-    auto check_wave = [&](int i) { const int l = (i / kTeamCheckChunk) / G; return (RC > 0 && l < rp.static_c) ? l % W : -1; };
-    auto pos_wave = [&](int p) { const int l = (p / 4) / G; return (RC > 0 && l < rp.static_v) ? l % W : -1; };
-    std::vector<int> cap((size_t)G, 0), member_of_bit((size_t)n, -1);
-    for (int p = 0; p < n; ++p) cap[(size_t)((p / 4) % G)]++;
-    std::vector<int> room = cap;
-    // A bit goes to the owner of its FIRST check while that member has room, else to the owner of another of its checks
-    // (the one with most room).  First check first: in a Gallager code the first block's check i holds bits
-    // wr * i ... wr * i + wr - 1, so all of them land with that check's owner and the rows that end up on chip are
-    // whole checks' worth -- a quarter of the checks need no memory at all and the others none of the detours of a
-    // mixed update (two clean checks of a chunk load their rows together) -- instead of one or two rows in nearly
-    // every check (LDPC_TEAM_CONCENTRATE=0, experiments build: most room only, as in round 2).
-    for (int j = 0; j < n; ++j) {
-        int best = -1;
-        for (int k = 0; k < dv; ++k) {
-            const int m = check_owner(c2r[(size_t)dv * j + k] / dc);
-            if (room[(size_t)m] <= 0) continue;
-            if (k == 0 && rp.concentrate) { best = m; break; }
-            if (best < 0 || room[(size_t)m] > room[(size_t)best]) best = m;
-        }
-        if (best >= 0) { member_of_bit[(size_t)j] = best; room[(size_t)best]--; }
-    }
-    for (int j = 0, m = 0; j < n; ++j) {
-        if (member_of_bit[(size_t)j] >= 0) continue;
-        while (m < G && room[(size_t)m] == 0) ++m;
-        if (m >= G) std::abort();   // (cannot happen: the members' rooms add up to n positions and every bit takes one)
-        member_of_bit[(size_t)j] = m; room[(size_t)m]--;
-    }
-    // positions of every member in ascending order, and which of them belong to a wave by right
-    std::vector<std::vector<int>> pos_of((size_t)G), bits_of((size_t)G);
-    for (int p = 0; p < n; ++p) pos_of[(size_t)((p / 4) % G)].push_back(p);
-    for (int j = 0; j < n; ++j) bits_of[(size_t)member_of_bit[(size_t)j]].push_back(j);
-    std::vector<int> bit((size_t)n, -1), reg_of((size_t)nnz, -1);
-    std::vector<std::vector<char>> placed_of((size_t)G);        // per member: which of bits_of[m] already have a position (register rows)
-    std::vector<std::vector<int>> reg_rows((size_t)G * W);       // per (member, wave): the CSR rows held in registers
-    // (whole checks: a wave's registers take a multiple of dc rows, so that no check is split between registers and LDS --
-    //  a split check is all on chip and still pays the general update: 30 of 32 rows a wave for dc = 6 and 10)
-    const int RCw = rp.concentrate ? RC / dc * dc : RC;
-    std::vector<std::vector<int>> reg_bits((size_t)G * W);      // ... and the bits those rows belong to (they get that wave's static positions)
-    auto static_positions = [&](int m) {                         // of each wave of member m, ascending
-        std::vector<std::vector<int>> spos((size_t)W);
-        for (int p : pos_of[(size_t)m]) { const int w = pos_wave(p); if (w >= 0) spos[(size_t)w].push_back(p); }
-        return spos;
-    };
-    for (int m = 0; m < G; ++m) {
-        const std::vector<std::vector<int>> spos = static_positions(m);
-        std::vector<char> placed(bits_of[(size_t)m].size(), 0);
-        if (RC > 0)
-            for (size_t b = 0; b < bits_of[(size_t)m].size(); ++b) {
-                const int j = bits_of[(size_t)m][b];
-                for (int k = 0; k < dv; ++k) {
-                    const int q = c2r[(size_t)dv * j + k], i = q / dc;
-                    if (check_owner(i) != m) continue;
-                    const int w = check_wave(i);
-                    if (w < 0 || (int)reg_rows[(size_t)m * W + w].size() >= RCw || reg_bits[(size_t)m * W + w].size() >= spos[(size_t)w].size()) continue;
-                    reg_bits[(size_t)m * W + w].push_back(j);
-                    reg_rows[(size_t)m * W + w].push_back(q);
-                    placed[b] = 1;
-                    break;
-                }
-            }
-        placed_of[(size_t)m] = std::move(placed);   // (positions are given out once the LDS rows are known: below)
-    }
-    // LDS candidates per member (check and bit share the owner, not in registers), in check order; the first kTeamRowsMax of each get rows
-    std::vector<char> is_reg((size_t)nnz, 0);
-    for (auto &v : reg_rows) for (int q : v) is_reg[(size_t)q] = 1;
-    std::vector<std::vector<int>> cand((size_t)G);
-    for (int j = 0; j < n; ++j)
-        for (int k = 0; k < dv; ++k) {
-            const int q = c2r[(size_t)dv * j + k];
-            if (!is_reg[(size_t)q] && check_owner(q / dc) == member_of_bit[(size_t)j]) cand[(size_t)member_of_bit[(size_t)j]].push_back(q);
-        }
-    for (auto &v : cand) { std::sort(v.begin(), v.end()); if ((int)v.size() > kTeamRowsMax) v.resize(kTeamRowsMax); }
-    if (rp.whole_checks) {
-        // only whole checks stay on chip: a check with SOME rows on chip takes the general update (pointers per edge),
-        // which costs more than the few rows save -- in a Gallager code these are the stray edges beyond the first block
-        std::vector<int> on_chip((size_t)s, 0);
-        for (auto &v : reg_rows) for (int q : v) on_chip[(size_t)(q / dc)]++;
-        for (auto &v : cand) for (int q : v) on_chip[(size_t)(q / dc)]++;
-        auto partial = [&](int q) { return on_chip[(size_t)(q / dc)] < dc; };
-        for (auto &v : reg_rows) v.erase(std::remove_if(v.begin(), v.end(), partial), v.end());
-        for (auto &v : cand) v.erase(std::remove_if(v.begin(), v.end(), partial), v.end());
-    }
-    // The other bits fill the positions that are left, in ascending order -- first the bits with at most their FIRST edge on
-    // chip, then the "strays" (a later edge in LDS: the room a member has beyond the whole checks of its block).  A position
-    // chunk with one stray in it leaves the four-at-once update for the general one, and dealt by number the strays sat
-    // in a third of all chunks (30 ... 52 of a member's 128 at the C3 size, and the members with most were the slowest of
-    // every variable sweep); together they fill a tenth, at the upper end of the member's positions, which its waves deal
-    // among themselves.
-    {
-        std::vector<char> in_cand((size_t)nnz, 0);
-        for (auto &v : cand) for (int q : v) in_cand[(size_t)q] = 1;
-        auto is_stray = [&](int j) {
-            bool stray = false;
-            if (!rp.strays_last) return false;
-            for (int k = 1; k < dv; ++k) stray = stray || in_cand[(size_t)c2r[(size_t)dv * j + k]];
-            return stray;
-        };
+    if (d->rows_G == G) return LDPC_OK;
+    // (three quarters of a member's share dealt statically measured 1 % faster than dealing all but the first chunk from
+    // the counter -- 873 against 883 ms on the full C3 batch --; rows in registers need it)
+    TeamRegPlan rp = team_reg_plan((int)d->n, (int)d->s, G, d->team_regs, d->team_static_quarters, d->rows_dv, d->rows_dc);
+    if (const char *e = exp_env("LDPC_TEAM_CONCENTRATE")) { rp.concentrate = std::atoi(e) != 0; rp.whole_checks = std::atoi(e) == 2; }
+    if (const char *e = exp_env("LDPC_TEAM_STRAYS_LAST")) rp.strays_last = std::atoi(e) != 0;
+    const TeamRowTables t = team_rows_tables((int)d->n, (int)d->s, (int)d->nnz, d->rows_dc, d->rows_dv, d->h_csc2csr, G, rp);
+    if (t.why) return fail(LDPC_ERR_HIP, t.why);
+    ldpc_status st;
+    if ((st = ldpc_detail::wait_device(d->device, "team row tables (device synchronise before the tables are replaced)")) != LDPC_OK) return st;   // (a launch that still reads the tables of another G)
+    std::vector<int> posmap((size_t)d->n, 0);
+    for (int p = 0; p < (int)d->n; ++p) posmap[(size_t)(t.vtab[(size_t)p * t.vt + 2 * d->rows_dv] & 0x7fffffff)] = p;
+    if ((st = team_upload(d->rows_posmap, posmap)) != LDPC_OK) return st;
+    if ((st = team_upload(d->rows_ctab, t.ctab)) != LDPC_OK || (st = team_upload(d->rows_vtab, t.vtab)) != LDPC_OK ||
+        (st = team_upload(d->rows_lds_edge, t.lds_edge)) != LDPC_OK || (st = team_upload(d->rows_reg_edge, t.reg_edge)) != LDPC_OK)
+        return st;
+    d->rows_G = G; d->rows_R = t.R; d->rows_on_chip = (int)(t.in_lds + t.in_regs);
+    d->rows_regs = rp.regs_per_wave; d->rows_static_c = rp.static_c; d->rows_static_v = rp.static_v;
+    {   // the leading chunks of EVERY member's share of the check sweep whose two checks have all their rows on chip (TeamRows::first_c)
+        const int full = (1 << d->rows_dc) - 1, W = LDPC_TEAM_THREADS / 64;
+        int first = rp.static_c;
         for (int m = 0; m < G; ++m) {
-            // the bits with a row in a wave's registers: that wave's static positions, strays last as well
-            const std::vector<std::vector<int>> spos = static_positions(m);
-            for (int w = 0; w < W; ++w) {
-                size_t at = 0;
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int j : reg_bits[(size_t)m * W + w])
-                        if ((int)is_stray(j) == pass) bit[(size_t)spos[(size_t)w][at++]] = j;
+            int l = 0;
+            for (; l < first; ++l) {
+                const int64_t i = (int64_t)kTeamCheckChunk * ((int64_t)l * G + m);
+                bool whole = i + kTeamCheckChunk <= d->s;
+                for (int q = 0; whole && q < kTeamCheckChunk; ++q)
+                    whole = t.ctab[(size_t)4 * (i + q)] == full || t.ctab[(size_t)4 * (i + q) + 2] == full;
+                if (!whole) break;
             }
-            const std::vector<int> &bm = bits_of[(size_t)m];
-            const std::vector<char> &placed = placed_of[(size_t)m];
-            std::vector<int> order;
-            for (int pass = 0; pass < 2; ++pass)
-                for (size_t b = 0; b < bm.size(); ++b) {
-                    if (placed[b]) continue;
-                    if ((int)is_stray(bm[b]) == pass) order.push_back(bm[b]);
-                }
-            size_t b = 0;
-            for (int p : pos_of[(size_t)m]) {
-                if (bit[(size_t)p] >= 0) continue;
-                if (b >= order.size()) std::abort();   // (cannot happen: a member has as many bits as positions)
-                bit[(size_t)p] = order[b++];
-            }
+            first = std::min(first, l);
         }
+        d->rows_first_c = first / W * W;
     }
-    for (int mw = 0; mw < G * W; ++mw) {
-        std::sort(reg_rows[(size_t)mw].begin(), reg_rows[(size_t)mw].end());
-        for (int x = 0; x < (int)reg_rows[(size_t)mw].size(); ++x) reg_of[(size_t)reg_rows[(size_t)mw][(size_t)x]] = x;
-        out.in_regs += reg_rows[(size_t)mw].size();
-    }
-    int R = 0;
-    for (auto &v : cand) R = std::max(R, (int)v.size());
-    R = std::max(R, 1);
-    std::vector<int> lds_row_of((size_t)nnz, -1);
-    std::vector<int> &lds_edge = out.lds_edge, &reg_edge = out.reg_edge;
-    lds_edge.assign((size_t)G * R, -1);
-    reg_edge.assign((size_t)G * W * std::max(RC, 1), -1);
-    std::vector<int> &vtab = out.vtab, &ctab = out.ctab;
-    vtab.assign((size_t)n * vt, 0);
-    ctab.assign((size_t)s * 4, 0);
-    for (int m = 0; m < G; ++m)
-        for (int r = 0; r < (int)cand[(size_t)m].size(); ++r) {
-            const int q = cand[(size_t)m][(size_t)r], i = q / dc;
-            lds_row_of[(size_t)q] = r;
-            lds_edge[(size_t)m * R + r] = q;
-            if (ctab[(size_t)4 * i] == 0) ctab[(size_t)4 * i + 1] = r;   // (ascending q: the check's LDS edges follow each other)
-            ctab[(size_t)4 * i] |= 1 << (q - dc * i);
-        }
-    for (int mw = 0; mw < G * W; ++mw)
-        for (int x = 0; x < (int)reg_rows[(size_t)mw].size(); ++x) {
-            const int q = reg_rows[(size_t)mw][(size_t)x], i = q / dc;
-            reg_edge[(size_t)mw * RC + x] = q;
-            if (ctab[(size_t)4 * i + 2] == 0) ctab[(size_t)4 * i + 3] = x;
-            ctab[(size_t)4 * i + 2] |= 1 << (q - dc * i);
-        }
-    for (int p = 0; p < n; ++p) {
-        const int j = bit[(size_t)p];
-        bool any = false;
-        for (int k = 0; k < dv; ++k) {
-            const int q = c2r[(size_t)dv * j + k];
-            vtab[(size_t)p * vt + k] = q;
-            const int where = reg_of[(size_t)q] >= 0 ? -2 - reg_of[(size_t)q] : lds_row_of[(size_t)q];
-            vtab[(size_t)p * vt + dv + k] = where;
-            any = any || where != -1;
-        }
-        vtab[(size_t)p * vt + 2 * dv] = any ? (j | (int)0x80000000u) : j;
-    }
-    out.R = R;
-    out.vt = vt;
-    for (auto &v : cand) out.in_lds += v.size();
-    return out;
+    if (exp_env("LDPC_TEAM_DEBUG"))
+        std::fprintf(stderr, "[ldpc] team rows: %d members, %d LDS rows each at most, %zu of %d edges in LDS, %zu in registers (%d per wave at most; static chunks %d / %d)\n",
+                     G, t.R, t.in_lds, (int)d->nnz, t.in_regs, rp.regs_per_wave, rp.static_c, rp.static_v);
+    return LDPC_OK;
 }
 
-// include/ldpc_mi355x_debug.h: the tables above for a CPU test
+static TeamPlanIn team_plan_in(const ldpc_bp_decoder *d, int per_xcd, int gcap, int gcap_one = 0, bool want_llr = false)
+{
+    TeamPlanIn in;
+    in.extra = (want_llr && d->team_llr_footprint) ? (size_t)std::max<int64_t>(d->n, 0) * kTile * (d->team_llr_raw == 5 ? sizeof(double) : sizeof(unsigned int)) : 0;
+    in.nnz = d->nnz; in.max_iters = d->max_iters; in.cache = d->team_cache; in.xcds_forced = d->team_xcds;
+    in.team_max_set = d->team_max_set; in.rows_possible = team_rows_possible(d); in.rows_dv = std::max(d->rows_dv, 1); in.num_cus = d->num_cus;
+    in.reg_rows = in.rows_possible ? d->team_regs * (LDPC_TEAM_THREADS / 64) : 0;
+    in.per_xcd = per_xcd; in.gcap = gcap; in.gcap_one = std::max(gcap, gcap_one);
+    if (const char *e = exp_env("LDPC_TEAM_SCATTER_MAX")) in.scatter_max = std::max(3, std::min(kTeamMaxMembers, std::atoi(e)));
+    if (const char *e = exp_env("LDPC_TEAM_SCATTER_ROWS")) in.scatter_rows = std::max(1, std::atoi(e));
+    if (const char *e = exp_env("LDPC_TEAM_SCATTER_TILES")) in.scatter_tiles = std::max(0, std::min(16, std::atoi(e)));
+    if (const char *e = exp_env("LDPC_TEAM_WIDE")) in.wide = std::max(-1, std::min(8, std::atoi(e)));
+    return in;
+}
+
+static TeamPlan team_plan(ldpc_bp_decoder *d, int64_t batch, bool want_llr)
+{
+    int per_xcd = 0, gcap = 0, gcap_one = 0;
+    if (!team_geometry(d, want_llr, &per_xcd, &gcap, &gcap_one)) return TeamPlan();
+    TeamPlanIn in = team_plan_in(d, per_xcd, gcap, gcap_one, want_llr);
+    if (!in.rows_possible && team_irr_possible(d)) {
+        // an irregular graph: its tables are built once for the team size the plan is most likely to choose (all the CUs
+        // of an XCD, or the most members the 2048-row rule admits), so that the plan can count the rows in LDS off the slots
+        const int G0 = std::min(std::max(gcap, gcap_one), per_xcd);
+        if (d->irr_G == 0 && G0 >= 3) (void)team_irr_build(d, G0);
+        in.irr_possible = true; in.irr_G = d->irr_G; in.irr_on_chip = d->irr_on_chip;
+    }
+    return team_plan_pure(in, batch);
+}
+
+static int team_size(ldpc_bp_decoder *d, int64_t batch, bool want_llr) { return team_plan(d, batch, want_llr).G; }
+
+// include/ldpc_mi355x_debug.h: the tables of team_plan.hpp for a CPU test
 extern "C" ldpc_status ldpc_debug_team_rows(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t members,
                                             int32_t regs_per_wave, int32_t static_quarters, int32_t *degrees, int32_t *shape,
                                             int32_t *vtab, int32_t *ctab, int32_t *lds_edge, int32_t *reg_edge)
@@ -1321,6 +1118,7 @@ extern "C" ldpc_status ldpc_debug_team_rows(int64_t s, int64_t n, const int64_t 
     }
     const TeamRegPlan rp = team_reg_plan((int)n, (int)s, members, regs_per_wave, static_quarters, dv, dc);
     const TeamRowTables t = team_rows_tables((int)n, (int)s, (int)nnz, dc, dv, c2r, members, rp);
+    if (t.why) return fail(LDPC_ERR_HIP, t.why);
     degrees[0] = dc; degrees[1] = dv;
     shape[0] = t.vt; shape[1] = t.R; shape[2] = rp.static_c; shape[3] = rp.static_v; shape[4] = rp.regs_per_wave;
     std::memcpy(vtab, t.vtab.data(), t.vtab.size() * sizeof(int));
@@ -1330,90 +1128,7 @@ extern "C" ldpc_status ldpc_debug_team_rows(int64_t s, int64_t n, const int64_t 
     return LDPC_OK;
 }
 
-// IRREGULAR graphs (round 4): whole checks in the LDS of their owners (bp_team_kernels.hpp, IRR).  Checks are dealt as the
-// kernel deals them (chunk c of 2 checks to member c % G), positions of the bit order in chunks of 4.  A check can live
-// in its owner's LDS when EVERY one of its bits can be given to that member -- then nobody else ever touches its rows
-// in either sweep.  That is a set packing over the checks (two checks that share a bit exclude each other); it is
-// taken greedily in check order, within each member's capacity (kTeamRowsMax LDS rows, its share of the positions),
-// and only over nodes inside the kernel's register buckets (dcb / dvb).  Tables: ctab2 [s + 1][2], ptab [n + 1][2],
-// ploc [nnz], lds_edge [G][R] (the CSR rows held, -1 beyond a member's count), posmap [n] (position of every bit).
-// (pure host code: ldpc_debug_team_irr() hands the tables to a CPU test)
-struct TeamIrrTables {
-    int R = 1;
-    size_t in_lds = 0;
-    std::vector<int> ctab2, ptab, ploc, lds_edge, posmap;
-};
-static TeamIrrTables team_irr_tables(int n, int s, int nnz, const std::vector<int> &row_ptr, const std::vector<int> &edge_bit,
-                                     const std::vector<int> &col_ptr, const std::vector<int> &c2r, int G, int dcb, int dvb)
-{
-    TeamIrrTables out;
-    auto owner = [&](int i) { return (i / kTeamCheckChunk) % G; };
-    std::vector<int> room_pos((size_t)G, 0), next_lds((size_t)G, 0), member_of_bit((size_t)n, -1), lds_base((size_t)s, -1);
-    for (int p = 0; p < n; ++p) room_pos[(size_t)((p / 4) % G)]++;
-    for (int i = 0; i < s; ++i) {
-        const int e0 = row_ptr[(size_t)i], deg = row_ptr[(size_t)i + 1] - e0, m = owner(i);
-        if (deg <= 0 || deg > dcb || room_pos[(size_t)m] < deg || next_lds[(size_t)m] + deg > kTeamRowsMax) continue;
-        bool ok = true;
-        for (int k = 0; k < deg && ok; ++k) {
-            const int j = edge_bit[(size_t)e0 + k];
-            ok = member_of_bit[(size_t)j] < 0 && col_ptr[(size_t)j + 1] - col_ptr[(size_t)j] <= dvb;
-        }
-        if (!ok) continue;
-        for (int k = 0; k < deg; ++k) member_of_bit[(size_t)edge_bit[(size_t)e0 + k]] = m;
-        room_pos[(size_t)m] -= deg;
-        lds_base[(size_t)i] = next_lds[(size_t)m];
-        next_lds[(size_t)m] += deg;
-        out.in_lds += (size_t)deg;
-    }
-    for (int j = 0, m = 0; j < n; ++j) {             // the other bits: wherever there is room
-        if (member_of_bit[(size_t)j] >= 0) continue;
-        while (m < G && room_pos[(size_t)m] == 0) ++m;
-        if (m >= G) std::abort();                    // (cannot happen: the rooms add up to n positions)
-        member_of_bit[(size_t)j] = m; room_pos[(size_t)m]--;
-    }
-    // positions of every member in ascending order take its bits in ascending order
-    std::vector<std::vector<int>> bits_of((size_t)G);
-    for (int j = 0; j < n; ++j) bits_of[(size_t)member_of_bit[(size_t)j]].push_back(j);
-    std::vector<size_t> taken((size_t)G, 0);
-    std::vector<int> bit_at((size_t)n, -1);
-    out.posmap.assign((size_t)std::max(n, 1), 0);
-    for (int p = 0; p < n; ++p) {
-        const int m = (p / 4) % G;
-        const int j = bits_of[(size_t)m][taken[(size_t)m]++];
-        bit_at[(size_t)p] = j;
-        out.posmap[(size_t)j] = p;
-    }
-    for (int m = 0; m < G; ++m) out.R = std::max(out.R, next_lds[(size_t)m]);
-    std::vector<int> check_of((size_t)std::max(nnz, 1), 0);
-    for (int i = 0; i < s; ++i)
-        for (int e = row_ptr[(size_t)i]; e < row_ptr[(size_t)i + 1]; ++e) check_of[(size_t)e] = i;
-    out.ctab2.assign(((size_t)s + 1) * 2, -1);
-    for (int i = 0; i <= s; ++i) out.ctab2[(size_t)2 * i] = row_ptr[(size_t)i];
-    for (int i = 0; i < s; ++i) out.ctab2[(size_t)2 * i + 1] = lds_base[(size_t)i];
-    out.lds_edge.assign((size_t)G * out.R, -1);
-    for (int i = 0; i < s; ++i)
-        if (lds_base[(size_t)i] >= 0)
-            for (int e = row_ptr[(size_t)i]; e < row_ptr[(size_t)i + 1]; ++e)
-                out.lds_edge[(size_t)owner(i) * out.R + lds_base[(size_t)i] + (e - row_ptr[(size_t)i])] = e;
-    out.ptab.assign(((size_t)n + 1) * 2, 0);
-    out.ploc.assign((size_t)std::max(nnz, 1), 0);
-    int at = 0;
-    for (int p = 0; p < n; ++p) {
-        const int j = bit_at[(size_t)p];
-        out.ptab[(size_t)2 * p] = at;
-        bool any = false;
-        for (int k = col_ptr[(size_t)j]; k < col_ptr[(size_t)j + 1]; ++k) {
-            const int q = c2r[(size_t)k], i = check_of[(size_t)q];
-            if (lds_base[(size_t)i] >= 0) { out.ploc[(size_t)at++] = -1 - (lds_base[(size_t)i] + (q - row_ptr[(size_t)i])); any = true; }
-            else out.ploc[(size_t)at++] = q;
-        }
-        out.ptab[(size_t)2 * p + 1] = any ? (j | (int)0x80000000u) : j;
-    }
-    out.ptab[(size_t)2 * n] = at;
-    return out;
-}
-
-// include/ldpc_mi355x_debug.h: the tables above for a CPU test
+// include/ldpc_mi355x_debug.h: the tables of an irregular graph (team_plan.hpp) for a CPU test
 extern "C" ldpc_status ldpc_debug_team_irr(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t members,
                                            int32_t dc_bucket, int32_t dv_bucket, int32_t *shape, int32_t *ctab2, int32_t *ptab,
                                            int32_t *ploc, int32_t *lds_edge, int32_t *posmap)
@@ -1435,6 +1150,7 @@ extern "C" ldpc_status ldpc_debug_team_irr(int64_t s, int64_t n, const int64_t *
     }
     col_ptr[(size_t)n] = (int)nnz;
     const TeamIrrTables t = team_irr_tables((int)n, (int)s, (int)nnz, row_ptr, edge_bit, col_ptr, c2r, members, dc_bucket, dv_bucket);
+    if (t.why) return fail(LDPC_ERR_HIP, t.why);
     shape[0] = t.R; shape[1] = (int32_t)t.in_lds;
     std::memcpy(ctab2, t.ctab2.data(), t.ctab2.size() * sizeof(int));
     std::memcpy(ptab, t.ptab.data(), t.ptab.size() * sizeof(int));
@@ -1444,25 +1160,19 @@ extern "C" ldpc_status ldpc_debug_team_irr(int64_t s, int64_t n, const int64_t *
     return LDPC_OK;
 }
 
-static ldpc_status team_irr_build(ldpc_bp_decoder *d, int G)
+// include/ldpc_mi355x_debug.h: the plan for a CPU test (an MI355X's geometry: 256 CUs, one team workgroup per CU)
+extern "C" ldpc_status ldpc_debug_team_plan(int64_t nnz, int64_t max_iters, int64_t batch, int32_t cache_mib, int32_t rows_dv,
+                                            int32_t out[6])
 {
-    if (d->irr_G == G) return LDPC_OK;
-    const TeamIrrTables t = team_irr_tables((int)d->n, (int)d->s, (int)d->nnz, d->h_row_ptr, d->h_edge_bit, d->h_col_ptr, d->h_irr_c2r, G,
-                                            d->irr_dcb, team_bucket_dv(d->max_bdeg));
-    auto up = [&](DevBuf &b, const std::vector<int> &v) -> ldpc_status {
-        ldpc_status r = b.ensure(std::max<size_t>(v.size() * 4, 4));
-        if (r != LDPC_OK) return r;
-        if (hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return fail(LDPC_ERR_HIP, "hipMemcpy of the team tables failed"); }
-        return LDPC_OK;
-    };
-    ldpc_status st;
-    if ((st = ldpc_detail::wait_device(d->device, "team tables of an irregular graph (device synchronise before the tables are replaced)")) != LDPC_OK) return st;
-    if ((st = up(d->irr_ctab, t.ctab2)) != LDPC_OK || (st = up(d->irr_ptab, t.ptab)) != LDPC_OK || (st = up(d->irr_ploc, t.ploc)) != LDPC_OK ||
-        (st = up(d->irr_lds_edge, t.lds_edge)) != LDPC_OK || (st = up(d->irr_posmap, t.posmap)) != LDPC_OK)
-        return st;
-    d->irr_G = G; d->irr_R = t.R; d->irr_on_chip = (int)t.in_lds;
-    if (exp_env("LDPC_TEAM_DEBUG"))
-        std::fprintf(stderr, "[ldpc] team tables (irregular graph): %d members, %d LDS rows each at most, %zu of %d edges in LDS\n", G, t.R, t.in_lds, (int)d->nnz);
+    if (!out || nnz < 0 || batch < 0 || cache_mib < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "bad argument");
+    TeamPlanIn in;
+    in.nnz = nnz; in.max_iters = max_iters; in.cache = (size_t)cache_mib << 20; in.rows_possible = rows_dv > 0; in.rows_dv = std::max(rows_dv, 1);
+    in.reg_rows = rows_dv > 0 ? kTeamRegRows * (LDPC_TEAM_THREADS / 64) : 0;
+    in.num_cus = 256; in.per_xcd = 32;
+    in.gcap = (int)std::min<int64_t>(32, std::max<int64_t>(1, nnz / 2048));
+    in.gcap_one = nnz / kTeamMinRowsOne >= 32 ? 32 : in.gcap;
+    const TeamPlan pl = team_plan_pure(in, batch);
+    out[0] = pl.G; out[1] = pl.nteams; out[2] = pl.grid; out[3] = pl.xcds; out[4] = pl.scatter ? 1 : 0; out[5] = pl.rows ? 1 : 0;
     return LDPC_OK;
 }
 
@@ -1509,243 +1219,6 @@ extern "C" ldpc_status ldpc_debug_llr_check(int64_t count, const double *odds, d
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(LDPC_ERR_HIP, std::string("ldpc_debug_llr_check: ") + hipGetErrorString(e)); }
     return LDPC_OK;
 }
-
-static ldpc_status team_rows_build(ldpc_bp_decoder *d, int G)
-{
-    if (d->rows_G == G) return LDPC_OK;
-    // (three quarters of a member's share dealt statically measured 1 % faster than dealing all but the first chunk from
-    // the counter -- 873 against 883 ms on the full C3 batch --; rows in registers need it)
-    TeamRegPlan rp = team_reg_plan((int)d->n, (int)d->s, G, d->team_regs, d->team_static_quarters, d->rows_dv, d->rows_dc);
-    if (const char *e = exp_env("LDPC_TEAM_CONCENTRATE")) { rp.concentrate = std::atoi(e) != 0; rp.whole_checks = std::atoi(e) == 2; }
-    if (const char *e = exp_env("LDPC_TEAM_STRAYS_LAST")) rp.strays_last = std::atoi(e) != 0;
-    const TeamRowTables t = team_rows_tables((int)d->n, (int)d->s, (int)d->nnz, d->rows_dc, d->rows_dv, d->h_csc2csr, G, rp);
-    auto up = [&](DevBuf &b, const std::vector<int> &v) -> ldpc_status {
-        ldpc_status r = b.ensure(std::max<size_t>(v.size() * 4, 4));
-        if (r != LDPC_OK) return r;
-        if (hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return fail(LDPC_ERR_HIP, "hipMemcpy of the team row tables failed"); }
-        return LDPC_OK;
-    };
-    ldpc_status st;
-    if ((st = ldpc_detail::wait_device(d->device, "team row tables (device synchronise before the tables are replaced)")) != LDPC_OK) return st;   // (a launch that still reads the tables of another G)
-    std::vector<int> posmap((size_t)d->n, 0);
-    for (int p = 0; p < (int)d->n; ++p) posmap[(size_t)(t.vtab[(size_t)p * t.vt + 2 * d->rows_dv] & 0x7fffffff)] = p;
-    if ((st = up(d->rows_posmap, posmap)) != LDPC_OK) return st;
-    if ((st = up(d->rows_ctab, t.ctab)) != LDPC_OK || (st = up(d->rows_vtab, t.vtab)) != LDPC_OK ||
-        (st = up(d->rows_lds_edge, t.lds_edge)) != LDPC_OK || (st = up(d->rows_reg_edge, t.reg_edge)) != LDPC_OK)
-        return st;
-    d->rows_G = G; d->rows_R = t.R; d->rows_on_chip = (int)(t.in_lds + t.in_regs);
-    d->rows_regs = rp.regs_per_wave; d->rows_static_c = rp.static_c; d->rows_static_v = rp.static_v;
-    {   // the leading chunks of EVERY member's share of the check sweep whose two checks have all their rows on chip (TeamRows::first_c)
-        const int full = (1 << d->rows_dc) - 1, W = LDPC_TEAM_THREADS / 64;
-        int first = rp.static_c;
-        for (int m = 0; m < G; ++m) {
-            int l = 0;
-            for (; l < first; ++l) {
-                const int64_t i = (int64_t)kTeamCheckChunk * ((int64_t)l * G + m);
-                bool whole = i + kTeamCheckChunk <= d->s;
-                for (int q = 0; whole && q < kTeamCheckChunk; ++q)
-                    whole = t.ctab[(size_t)4 * (i + q)] == full || t.ctab[(size_t)4 * (i + q) + 2] == full;
-                if (!whole) break;
-            }
-            first = std::min(first, l);
-        }
-        d->rows_first_c = first / W * W;
-    }
-    if (exp_env("LDPC_TEAM_DEBUG"))
-        std::fprintf(stderr, "[ldpc] team rows: %d members, %d LDS rows each at most, %zu of %d edges in LDS, %zu in registers (%d per wave at most; static chunks %d / %d)\n",
-                     G, t.R, t.in_lds, (int)d->nnz, t.in_regs, rp.regs_per_wave, rp.static_c, rp.static_v);
-    return LDPC_OK;
-}
-
-// Persistent teams whose message slots in flight stay inside the cache budget (LDPC_TEAM_CACHE_MIB, default 240 of
-// the Infinity Cache's 256 MiB): how many XCDs host teams (8, 7 or 6), how many teams each, how many members a
-// team -- the combination that gives most workgroups a tile.  For the n = 16384 code (32 MiB a slot) with every row in
-// the slot that is SEVEN teams of 32: with an eighth the slots fill the cache to the brim and every team is a fifth
-// slower (full batch, 50 iterations, round 2: 1111 ms on 8 XCDs, 1011 ms on 7, 1158 ms on 6); with the rows a member
-// keeps on chip counted off the slot (`rows`: 312 in LDS + 8 x 32 in registers) it is EIGHT (round 3: 712 ms).
-// false: nothing fits, not even the second tier below.
-static bool team_fit(const TeamPlanIn &in, int64_t ntiles, bool rows, int *xcds, int *tpx, int *G)
-{
-    const int per_xcd = in.per_xcd, gcap = in.gcap;
-    const size_t state = std::max<size_t>((size_t)in.nnz, 1) * kTile * sizeof(double);
-    const size_t cache = in.cache;
-    if (!cache) return false;
-    // the combination that gives most workgroups a tile -- but among combinations within 15 % of that, the one that
-    // uses most XCDs (their L2s and ports; fewer, larger teams per XCD): x runs downwards, so the first one that
-    // qualifies wins.  ((3,6) n = 16380: eight teams of 23 on eight XCDs measured 7.1 TB/s, sixteen of 16 6.3)
-    int64_t best = 0;
-    // (not fewer than seven XCDs: n = 24576, 48 MiB slots -- six cached teams 382 ms for 16,384 syndromes x 50 iterations,
-    //  eight partly cached ones 350 ms; n = 20480: seven cached 283 ms, eight 282 ms -- profiles/r03_midsize_plan.txt)
-    const int x_hi = in.xcds_forced ? in.xcds_forced : 8, x_lo = in.xcds_forced ? in.xcds_forced : 7;
-    for (int pass = 0; pass < 2; ++pass)
-    for (int x = x_hi; x >= x_lo; --x)
-        for (int t = 1; t <= per_xcd / 3; ++t) {
-            if ((size_t)x * (size_t)t * (state + in.extra - (rows ? state / (size_t)std::max(in.rows_dv, 1) : 0)) > cache) break;   // (1 / dv at most can be in LDS)
-            if (t > 1 && (int64_t)x * (t - 1) >= ntiles) break;            // no more teams than tiles
-            const int g = std::min(t == 1 ? std::max(gcap, in.gcap_one) : gcap, per_xcd / t);
-            if (g < 3) break;
-            // rows that the members keep in LDS are not in the cache
-            if ((size_t)x * (size_t)t * (state + in.extra - (rows ? (size_t)g * team_rows_expected(in, g) * kTile * sizeof(double) : 0)) > cache) continue;
-            const int64_t w = std::min<int64_t>((int64_t)x * t, ntiles) * g;   // workgroups with a tile
-            if (pass == 0) { if (w > best) best = w; }
-            else if (w * 100 >= best * 85) { *xcds = x; *tpx = t; *G = g; return true; }
-        }
-    if (best > 0) return true;
-    // Slots up to 3.3 x the budget: one team per XCD still pays -- the slots are partly cached or not at all, and a team
-    // streams what is not as well as three tile-kernel workgroups per CU do, with 8 slots instead of 768 (round 3, 50
-    // iterations, teams against the tile kernel: n = 40960, 80 MiB a slot: 16,384 syndromes 693 against 874 ms, 65,536
-    // syndromes 2.76 against 2.94 s; n = 49152: 874 against 1071 ms, 3.51 against 3.70 s).  Beyond that (n = 65536,
-    // 128 MiB a slot: 4.96 against 4.85 s) the tile kernel stays.  (profiles/r03_midsize_plan.txt)
-    // (Graphs WITHOUT rows on chip of this kind -- irregular ones, degree pairs without an instantiation -- stay inside
-    //  the budget: 16,384 syndromes x 50 iterations of an irregular n = 20480 graph, 8 x 35 MiB of slots: eight teams
-    //  381-392 ms, the tile kernel 319-328 ms, seven teams with whole checks in LDS 319 ms; n = 32768, 8 x 56 MiB: 570 /
-    //  626 ms against 518 ms -- profiles/r04_irregular.txt.  Regular graphs with rows on chip get wide teams long before
-    //  this: team_wide_auto().)
-    if (!in.xcds_forced && in.rows_possible && (size_t)8 * state <= cache / 10 * 33 && std::min(gcap, per_xcd) >= 3) {
-        *xcds = 8; *tpx = 1; *G = std::min(gcap, per_xcd);
-        return true;
-    }
-    return false;
-}
-
-// How a batch of fresh tiles is dealt to teams (bp_team_kernels.hpp).  G = 1: no teams for it.
-//   * up to 3 tiles: one team per tile, its members dealt over ALL XCDs (scatter), 128-192 of them;
-//   * as many tiles as fit one round of teams with the slots at most a quarter over the cache budget: one team per
-//     tile (8 tiles of the n = 16384 code: 8 teams once rather than 7 teams twice);
-//   * otherwise PERSISTENT teams inside the budget (team_fit()): a team takes tile after tile in its own slot;
-//   * nothing fits (larger graphs; LDPC_TEAM_CACHE_MIB=0): round 1's rule -- one team per tile, at most one tile
-//     per CU -- and batches of more tiles than CUs stay with the tile kernel, which streams from HBM as well as
-//     teams would.
-struct TeamPlan {
-    int G = 1;            // members per team
-    int nteams = 0;       // teams (and message slots)
-    int grid = 0;         // workgroups to launch
-    int xcds = 8, tpx = 0;   // XCDs that host teams, teams per XCD (not in scatter mode)
-    bool scatter = false;
-    bool wide = false;       // a few persistent teams over all XCDs (TeamPlanIn::wide)
-    bool irr = false;        // an irregular graph: members keep whole checks in LDS (team_irr_tables())
-    bool rows = false;       // members keep the rows that only they touch in LDS (TeamRows)
-};
-
-// How many wide teams (TeamPlanIn::wide) a batch of ntiles gets by itself: as many as keep their slots -- less the rows
-// their members keep on chip, plus a tile's LLR rows when wanted -- inside the cache budget, when that is fewer than the
-// eight one-XCD teams the plan would otherwise build (eight or more fit: nothing to do, the C3 code) and the graph has a
-// rows-on-chip instantiation (without rows on chip wide teams lose).  0 = none.
-static int team_wide_auto(const TeamPlanIn &in, int64_t ntiles)
-{
-    if (!in.cache || in.xcds_forced || in.team_max_set || !in.rows_possible || in.reg_rows <= 0 || in.per_xcd < 8) return 0;
-    const size_t state = std::max<size_t>((size_t)in.nnz, 1) * kTile * sizeof(double);
-    for (int T = 7; T >= 1; --T) {
-        const int G = (int)std::min<int64_t>(kTeamMaxMembers, (int64_t)8 * in.per_xcd / T);
-        if (in.nnz / G < in.scatter_rows) continue;                       // (a member keeps >= 512 message rows per sweep)
-        const size_t on_chip = (size_t)G * (size_t)team_rows_expected(in, G) * kTile * sizeof(double);
-        const size_t slot = state - std::min(on_chip, state) + in.extra;
-        if ((size_t)T * slot > in.cache) continue;
-        // eight one-XCD teams' slots would fit as well, or nearly (a quarter over the budget): that plan (no write-backs at
-        // the barriers) stays
-        const int G8 = std::min(std::max(in.gcap, in.gcap_one), in.per_xcd);
-        const size_t slot8 = state - std::min((size_t)G8 * (size_t)team_rows_expected(in, G8) * kTile * sizeof(double), state) + in.extra;
-        if ((size_t)8 * slot8 <= in.cache + in.cache / 4) return 0;
-        return (int)std::min<int64_t>(T, ntiles);
-    }
-    return 0;
-}
-
-static TeamPlan team_plan_pure(const TeamPlanIn &in, int64_t batch)
-{
-    TeamPlan pl;
-    const int per_xcd = in.per_xcd, gcap = in.gcap;
-    const int64_t ntiles = (batch + kTile - 1) / kTile;
-    if (ntiles < 1 || per_xcd < 1) return pl;
-    if ((size_t)ntiles * ((size_t)in.max_iters + 32) * sizeof(u64) > ((size_t)64 << 20)) return pl;   // mismatch words per tile and iteration
-    int64_t team = 1, nteams = 0;
-    const int wide = in.wide > 0 ? in.wide : in.wide == 0 ? team_wide_auto(in, ntiles) : 0;
-    if (wide > 0 && ntiles > in.scatter_tiles) {
-        team = std::min<int64_t>(kTeamMaxMembers, (int64_t)8 * per_xcd / wide);
-        nteams = std::min<int64_t>(wide, ntiles);
-        pl.scatter = true;
-        pl.wide = true;
-    } else if (ntiles <= in.scatter_tiles && !in.team_max_set) {
-        // dealt over all 8 XCDs (scatter mode of the kernel): larger teams pay -- one tile of the C3 code, 50
-        // iterations: 32 members 5.4 ms, 48: 4.3 ms, 64: 3.4 ms, 128: 2.6 ms (a member still has >= 512 message rows per sweep)
-        const int64_t cap = std::min<int64_t>(in.scatter_max, std::max<int64_t>(gcap, in.nnz / std::max(in.scatter_rows, 1)));
-        team = std::min<int64_t>(cap, (int64_t)8 * per_xcd / ntiles);
-        nteams = ntiles;
-        pl.scatter = true;
-    } else {
-        const int64_t need = (ntiles + 7) / 8;
-        const size_t state = std::max<size_t>((size_t)in.nnz, 1) * kTile * sizeof(double);
-        int x = 8, t = (int)need, g = 0;
-        const bool one_round = in.cache && !in.xcds_forced && (size_t)8 * (size_t)need * state <= in.cache + in.cache / 4;
-        // (With the rows in LDS alone -- 15 % of a tile -- the budget is applied to whole slots: eight teams of the C3 code,
-        // 8 x 27 MiB, measured 981 ms for the full batch, seven 957.  With rows in the waves' registers as well a quarter
-        // of a tile is on chip and the rows on chip are taken off the slots: 8 x 24 MiB fit, and eight teams measured
-        // 833 ms against 877 on seven -- round 3.)
-        if (one_round || !team_fit(in, ntiles, (in.rows_possible && in.reg_rows > 0) || (in.irr_possible && in.irr_on_chip > 0), &x, &t, &g)) {
-            if (!one_round && ntiles > in.num_cus) return pl;
-            x = 8; t = (int)need;
-            g = (int)std::min<int64_t>(gcap, (int64_t)per_xcd / t);
-        }
-        team = g;
-        nteams = (int64_t)x * t;
-        pl.xcds = x; pl.tpx = t;
-    }
-    if (team < 3) return pl;   // two workgroups per tile measured no better than the tile kernel's one of 16 waves
-    pl.G = (int)std::min<int64_t>(team, kTeamMaxMembers);
-    pl.rows = (!pl.scatter || pl.wide) && in.rows_possible && team_rows_expected(in, pl.G) >= 16;
-    pl.irr = !pl.scatter && !in.rows_possible && in.irr_possible;
-    pl.nteams = (int)nteams;
-    pl.grid = pl.scatter ? pl.nteams * pl.G : 8 * pl.G * pl.tpx;
-    return pl;
-}
-
-static TeamPlanIn team_plan_in(const ldpc_bp_decoder *d, int per_xcd, int gcap, int gcap_one = 0, bool want_llr = false)
-{
-    TeamPlanIn in;
-    in.extra = (want_llr && d->team_llr_footprint) ? (size_t)std::max<int64_t>(d->n, 0) * kTile * (d->team_llr_raw == 5 ? sizeof(double) : sizeof(unsigned int)) : 0;
-    in.nnz = d->nnz; in.max_iters = d->max_iters; in.cache = d->team_cache; in.xcds_forced = d->team_xcds;
-    in.team_max_set = d->team_max_set; in.rows_possible = team_rows_possible(d); in.rows_dv = std::max(d->rows_dv, 1); in.num_cus = d->num_cus;
-    in.reg_rows = in.rows_possible ? d->team_regs * (LDPC_TEAM_THREADS / 64) : 0;
-    in.per_xcd = per_xcd; in.gcap = gcap; in.gcap_one = std::max(gcap, gcap_one);
-    if (const char *e = exp_env("LDPC_TEAM_SCATTER_MAX")) in.scatter_max = std::max(3, std::min(kTeamMaxMembers, std::atoi(e)));
-    if (const char *e = exp_env("LDPC_TEAM_SCATTER_ROWS")) in.scatter_rows = std::max(1, std::atoi(e));
-    if (const char *e = exp_env("LDPC_TEAM_SCATTER_TILES")) in.scatter_tiles = std::max(0, std::min(16, std::atoi(e)));
-    if (const char *e = exp_env("LDPC_TEAM_WIDE")) in.wide = std::max(-1, std::min(8, std::atoi(e)));
-    return in;
-}
-
-static TeamPlan team_plan(ldpc_bp_decoder *d, int64_t batch, bool want_llr)
-{
-    int per_xcd = 0, gcap = 0, gcap_one = 0;
-    if (!team_geometry(d, want_llr, &per_xcd, &gcap, &gcap_one)) return TeamPlan();
-    TeamPlanIn in = team_plan_in(d, per_xcd, gcap, gcap_one, want_llr);
-    if (!in.rows_possible && team_irr_possible(d)) {
-        // an irregular graph: its tables are built once for the team size the plan is most likely to choose (all the CUs
-        // of an XCD, or the most members the 2048-row rule admits), so that the plan can count the rows in LDS off the slots
-        const int G0 = std::min(std::max(gcap, gcap_one), per_xcd);
-        if (d->irr_G == 0 && G0 >= 3) (void)team_irr_build(d, G0);
-        in.irr_possible = true; in.irr_G = d->irr_G; in.irr_on_chip = d->irr_on_chip;
-    }
-    return team_plan_pure(in, batch);
-}
-
-// include/ldpc_mi355x_debug.h: the plan for a CPU test (an MI355X's geometry: 256 CUs, one team workgroup per CU)
-extern "C" ldpc_status ldpc_debug_team_plan(int64_t nnz, int64_t max_iters, int64_t batch, int32_t cache_mib, int32_t rows_dv,
-                                            int32_t out[6])
-{
-    if (!out || nnz < 0 || batch < 0 || cache_mib < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "bad argument");
-    TeamPlanIn in;
-    in.nnz = nnz; in.max_iters = max_iters; in.cache = (size_t)cache_mib << 20; in.rows_possible = rows_dv > 0; in.rows_dv = std::max(rows_dv, 1);
-    in.reg_rows = rows_dv > 0 ? kTeamRegRows * (LDPC_TEAM_THREADS / 64) : 0;
-    in.num_cus = 256; in.per_xcd = 32;
-    in.gcap = (int)std::min<int64_t>(32, std::max<int64_t>(1, nnz / 2048));
-    in.gcap_one = nnz / kTeamMinRowsOne >= 32 ? 32 : in.gcap;
-    const TeamPlan pl = team_plan_pure(in, batch);
-    out[0] = pl.G; out[1] = pl.nteams; out[2] = pl.grid; out[3] = pl.xcds; out[4] = pl.scatter ? 1 : 0; out[5] = pl.rows ? 1 : 0;
-    return LDPC_OK;
-}
-
-static int team_size(ldpc_bp_decoder *d, int64_t batch, bool want_llr) { return team_plan(d, batch, want_llr).G; }
 
 // Small batches on graphs beyond the LDS: one workgroup per syndrome (bp_node_kernels.hpp) or teams of
 // workgroups per 64-syndrome tile?  Estimated time of one iteration, from the measurements in DESIGN.md:

@@ -94,7 +94,7 @@ Rccl *rccl()
 // ordinals are all settled before the group opens --, and a group in which an RCCL call has failed is discarded by
 // ncclGroupEnd, not launched (NCCL 2.27 group.cc: the thread's group error makes ncclGroupEnd clean the queued tasks up
 // and return that error), so closing it cannot send the caller's stream waiting for a peer that never comes.  After
-// such a failure the communicators are aborted (exchange_failed()): the next root-device call builds new ones.
+// such a failure the communicators are torn down (ncclCommAbort, exchange_failed()): the next root-device call builds new ones.
 struct GroupGuard {
     Rccl *R;
     bool open = false;
@@ -193,7 +193,7 @@ void drain_streams(ldpc_bp_multi *m, hipStream_t root)
 }
 
 // An RCCL call failed inside a group (the group has been closed and discarded by then, see GroupGuard): the
-// communicators are in an unknown state -- abort them; the next root-device call creates new ones.
+// communicators are in an unknown state -- ncclCommAbort them; the next root-device call creates new ones.
 void exchange_failed(ldpc_bp_multi *m, hipStream_t root)
 {
     drain_streams(m, root);

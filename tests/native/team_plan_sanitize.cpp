@@ -1,0 +1,120 @@
+// team_plan_sanitize.cpp -- the team planner and the table builders (ldpcdecoders.jl_amd/csrc/team_plan.cpp) under
+// AddressSanitizer + UndefinedBehaviorSanitizer: index arithmetic over std::vector<int> with hand-computed offsets, on
+// the smallest shapes that reach every branch.  CPU build only (the GPU pool offers no sanitizers); built and run by
+// tests/test_team_rows_cpu.py::test_team_plan_under_sanitizers.  What the tables must SAY about the graph is that
+// file's business; here only what is cheap: every call succeeds, the tables have the sizes the layout promises, the
+// write-back lists name edges of the graph, the bit order is a permutation, a plan never asks for more workgroups than
+// the chip hosts.  Exit code 0 and "OK ..." = nothing found.
+#include "../../ldpcdecoders.jl_amd/csrc/team_plan.hpp"
+
+#include <algorithm>
+#include <cstdio>
+
+using namespace ldpc;
+
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); return false; } } while (0)
+
+static uint32_t lcg_state = 12345u;
+static uint32_t lcg() { lcg_state = lcg_state * 1664525u + 1013904223u; return lcg_state >> 8; }
+
+static bool edges_ok(const std::vector<int> &v, size_t size, int nnz)
+{
+    CHECK(v.size() == size);
+    for (int q : v) CHECK(q == -1 || (q >= 0 && q < nnz));
+    return true;
+}
+static bool is_permutation(std::vector<int> bits)
+{
+    std::sort(bits.begin(), bits.end());
+    for (size_t j = 0; j < bits.size(); ++j) CHECK(bits[j] == (int)j);
+    return true;
+}
+
+// A (dc, dv)-regular graph of dv blocks: block b deals the bits, in an order of its own (a shuffle by the LCG), to
+// the rows b n ... b n + n - 1 of the check-major message array -- dc in a row make a check, so where dc divides n
+// block b's check i holds the bits at places dc i ... dc i + dc - 1 of that order (a Gallager code).
+static bool regular(int n, int G, int dc, int dv, int regs, int quarters)
+{
+    const int nnz = n * dv, s = nnz / dc, W = LDPC_TEAM_THREADS / 64;
+    CHECK(nnz % dc == 0);
+    std::vector<int> c2r((size_t)nnz), order((size_t)n);
+    for (int b = 0; b < dv; ++b) {
+        for (int j = 0; j < n; ++j) order[(size_t)j] = j;
+        for (int t = n - 1; t > 0; --t) std::swap(order[(size_t)t], order[(size_t)(lcg() % (uint32_t)(t + 1))]);
+        for (int t = 0; t < n; ++t) c2r[(size_t)dv * order[(size_t)t] + b] = b * n + t;
+    }
+    const TeamRegPlan rp = team_reg_plan(n, s, G, regs, quarters, dv, dc);
+    const TeamRowTables t = team_rows_tables(n, s, nnz, dc, dv, c2r, G, rp);
+    CHECK(t.why == nullptr);
+    CHECK(t.vt == team_vtab_words(dv) && t.R >= 1 && t.R <= kTeamRowsMax && rp.regs_per_wave <= kTeamRegRows);
+    CHECK(t.vtab.size() == (size_t)n * t.vt && t.ctab.size() == (size_t)s * 4);
+    if (!edges_ok(t.lds_edge, (size_t)G * t.R, nnz) || !edges_ok(t.reg_edge, (size_t)G * W * std::max(rp.regs_per_wave, 1), nnz)) return false;
+    std::vector<int> bits((size_t)n);
+    for (int p = 0; p < n; ++p) bits[(size_t)p] = t.vtab[(size_t)p * t.vt + 2 * dv] & 0x7fffffff;
+    return is_permutation(bits);
+}
+
+// Random columns of degree 2 ... 6 (distinct checks), in both orders as ldpc_debug_team_irr derives them.
+static bool irregular(int n, int s, int G, int dcb, int dvb)
+{
+    std::vector<int> col_ptr((size_t)n + 1, 0), rowval, row_ptr((size_t)s + 1, 0);
+    for (int j = 0; j < n; ++j) {
+        const int deg = 2 + (int)(lcg() % 5u);
+        for (int k = 0; k < deg;) {
+            const int i = (int)(lcg() % (uint32_t)s);
+            if (std::find(rowval.begin() + col_ptr[(size_t)j], rowval.end(), i) != rowval.end()) continue;
+            rowval.push_back(i); row_ptr[(size_t)i + 1]++; ++k;
+        }
+        col_ptr[(size_t)j + 1] = (int)rowval.size();
+    }
+    const int nnz = (int)rowval.size();
+    for (int i = 0; i < s; ++i) row_ptr[(size_t)i + 1] += row_ptr[(size_t)i];
+    std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1), edge_bit((size_t)nnz), c2r((size_t)nnz);
+    for (int j = 0; j < n; ++j)
+        for (int k = col_ptr[(size_t)j]; k < col_ptr[(size_t)j + 1]; ++k) { const int q = fill[(size_t)rowval[(size_t)k]]++; edge_bit[(size_t)q] = j; c2r[(size_t)k] = q; }
+    const int bucket = team_irr_dc_bucket(row_ptr, s, nnz);
+    CHECK(bucket == 0 || bucket == 8 || bucket == 16);
+    const TeamIrrTables t = team_irr_tables(n, s, nnz, row_ptr, edge_bit, col_ptr, c2r, G, dcb, dvb);
+    CHECK(t.why == nullptr && t.R >= 1 && t.R <= kTeamRowsMax && t.in_lds <= (size_t)nnz);
+    CHECK(t.ctab2.size() == ((size_t)s + 1) * 2 && t.ptab.size() == ((size_t)n + 1) * 2 && t.ploc.size() == (size_t)nnz && t.posmap.size() == (size_t)n);
+    if (!edges_ok(t.lds_edge, (size_t)G * t.R, nnz)) return false;
+    std::vector<int> bits((size_t)n);
+    for (int p = 0; p < n; ++p) bits[(size_t)p] = t.ptab[(size_t)2 * p + 1] & 0x7fffffff;
+    return is_permutation(bits) && is_permutation(t.posmap);
+}
+
+// The plan for an MI355X's geometry, as ldpc_debug_team_plan sets it up (256 CUs, one team workgroup per CU).
+static bool plans(int *count)
+{
+    for (int64_t nnz : {(int64_t)0, (int64_t)1, (int64_t)4096, (int64_t)65536, (int64_t)262144})
+        for (int64_t batch : {(int64_t)0, (int64_t)1, (int64_t)64, (int64_t)193, (int64_t)65536, (int64_t)1 << 20})
+            for (size_t cache : {(size_t)0, (size_t)240 << 20})
+                for (int rows_dv : {0, 3, 4}) {
+                    TeamPlanIn in;
+                    in.nnz = nnz; in.max_iters = 50; in.cache = cache; in.rows_possible = rows_dv > 0; in.rows_dv = std::max(rows_dv, 1);
+                    in.reg_rows = rows_dv > 0 ? kTeamRegRows * (LDPC_TEAM_THREADS / 64) : 0;
+                    in.num_cus = 256; in.per_xcd = 32;
+                    in.gcap = (int)std::min<int64_t>(32, std::max<int64_t>(1, nnz / 2048));
+                    in.gcap_one = nnz / 1100 >= 32 ? 32 : in.gcap;
+                    const TeamPlan pl = team_plan_pure(in, batch);
+                    CHECK(pl.G >= 1 && pl.G <= kTeamMaxMembers && pl.grid >= 0 && pl.grid <= 8 * in.per_xcd);
+                    ++*count;
+                }
+    return true;
+}
+
+int main()
+{
+    int nplans = 0;
+    const bool ok = regular(1024, 3, 8, 4, 32, 3) && regular(1008, 5, 6, 3, 0, 3) && regular(3990, 6, 7, 3, 12, 3) &&
+                    regular(4000, 7, 10, 5, 20, 3) &&
+                    regular(4096, 8, 8, 4, 32, 0) &&    // no static quarters: a wave's first chunk only (static = W)
+                    regular(130, 32, 8, 4, 32, 3) &&    // shares smaller than 2 W, 32 members for 33 chunks (dc does not divide n: a check may straddle two blocks)
+                    irregular(1000, 500, 3, 8, 4) && irregular(1000, 500, 3, 16, 16) && irregular(1000, 500, 32, 8, 4) &&
+                    irregular(1000, 500, 32, 16, 16) &&
+                    irregular(96, 64, 32, 8, 4) && irregular(96, 64, 32, 16, 16) &&   // 24 position chunks: members without a position
+                    plans(&nplans);
+    if (!ok) return 1;
+    std::printf("OK 6 regular and 6 irregular table sets, %d plans\n", nplans);
+    return 0;
+}

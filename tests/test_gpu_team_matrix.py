@@ -8,7 +8,7 @@ uses (LDPC_TEAM_MIN_ROWS=1, LDPC_TEAM_MAX=4); what ran is read back from ldpc_bp
 not reach its instantiation FAILS.  Every comparison is against BPOracle on every syndrome and every bit: hard decisions,
 converged flags and iteration counts equal, non-finite LLRs equal exactly, finite ones within LLR_CUT_TOL.
 
-Fewer teams than tiles.  The matrix batch is 8 tiles; the plan (ldpc_mi355x.hip team_plan_pure()) gives 8 tiles 8 teams
+Fewer teams than tiles.  The matrix batch is 8 tiles; the plan (team_plan.cpp team_plan_pure()) gives 8 tiles 8 teams
 whatever LDPC_TEAM_CACHE_KIB says while register rows are off -- a budget of >= 6.4 slots is `one_round`, a smaller one
 fails team_fit()'s first tier (7 whole slots) and lands on its second (one team per XCD) or on one team per tile -- so the
 cache budget alone cannot make a team take a second tile in all four instantiations of a pair.  LDPC_TEAM_XCDS=7 can: it

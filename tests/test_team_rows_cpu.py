@@ -1,8 +1,10 @@
-"""The host side of the team kernel's rows-in-LDS mode (bp_team_kernels.hpp TeamRows, ldpc_mi355x.hip
+"""The host side of the team kernel's rows-in-LDS mode (bp_team_kernels.hpp TeamRows, team_plan.cpp
 team_rows_tables()), checked without a GPU through ldpc_debug_team_rows: whatever the kernel reads from these tables
 must describe the graph it decodes -- the dealt bit order is a permutation, every position carries its bit's four
 message rows, a row lives in LDS only if its check AND its bit belong to the same member (nobody else may ever need it),
-no two rows share an LDS slot, and the per-check and per-member views agree with the per-edge one."""
+no two rows share an LDS slot, and the per-check and per-member views agree with the per-edge one.  The planner and the
+table builders are a HIP-free unit (team_plan.hpp / team_plan.cpp over team_layout.hpp); the last test here runs them
+under AddressSanitizer + UBSan."""
 import ctypes
 
 import numpy as np
@@ -121,7 +123,7 @@ def test_row_tables_describe_the_graph(n, members, wr, wc, regs):
 @pytest.mark.parametrize("n,members,wr,wc", [(16384, 32, 8, 4), (16380, 23, 6, 3), (16000, 32, 10, 5), (16380, 32, 9, 3), (16380, 32, 10, 4), (16380, 32, 7, 5)])
 def test_on_chip_rows_are_whole_checks_of_the_first_block(n, members, wr, wc):
     """What the fast paths of the kernel live on (bp_team_kernels.hpp check_update_regs, bit_update_pair_first /
-    bit_update_multi_first; ldpc_mi355x.hip team_rows_tables(): a bit goes to the owner of its FIRST check): in a
+    bit_update_multi_first; team_plan.cpp team_rows_tables(): a bit goes to the owner of its FIRST check): in a
     Gallager code the rows a member keeps on chip are its first-block checks, complete, as far as its capacity (312 rows
     in LDS, 8 x 32 in registers) goes -- a check with all its rows in one wave's registers or all in LDS needs no pointer
     per edge, and every bit has at most its first edge on chip plus a stray one now and then."""
@@ -191,7 +193,7 @@ def plan(nnz, batch, cache_mib=240, max_iters=50, regular=1, dv=4):
 
 
 def test_team_plan_by_graph_and_batch():
-    """The host's choice of teams (ldpc_mi355x.hip team_plan_pure / team_fit), for an MI355X's geometry.  Message slot of
+    """The host's choice of teams (team_plan.cpp team_plan_pure / team_fit), for an MI355X's geometry.  Message slot of
     a graph: nnz x 512 B; budget of slots in flight: 240 MiB of the 256 MiB Infinity Cache."""
     c3 = 65536                                                   # n = 16384, (4,8)-regular: 32 MiB a slot
     # the headline batch: EIGHT persistent teams of 32 -- with a quarter of a tile's rows on chip (312 in the LDS of every
@@ -293,7 +295,7 @@ def _irregular_graph(n, s, seed, heavy=False):
 
 @pytest.mark.parametrize("n,s,members,heavy", [(4096, 2048, 8, False), (16384, 8192, 32, False), (16384, 8192, 32, True), (1000, 700, 3, True)])
 def test_irregular_graph_tables_describe_the_graph(n, s, members, heavy):
-    """Whole checks of an IRREGULAR graph in the LDS of their owners (ldpc_mi355x.hip team_irr_tables(); bp_team_kernels.hpp,
+    """Whole checks of an IRREGULAR graph in the LDS of their owners (team_plan.cpp team_irr_tables(); bp_team_kernels.hpp,
     IRR), checked without a GPU: the dealt bit order is a permutation; a position's edge list is its bit's (checks
     ascending), every entry either the CSR row itself or an LDS row of the member that owns the position; a check in LDS is
     there WHOLE, consecutively, with its owner, and every one of its bits sits in a position of that member (so nobody
@@ -347,3 +349,22 @@ def test_irregular_graph_tables_describe_the_graph(n, s, members, heavy):
     # worth having: a random graph of mean bit degree 3.5 packs ~1 check in 4 (the bound is n / mean check degree), unless the
     # members' LDS is what limits it (312 rows each)
     assert in_lds >= min(0.08 * nnz, 0.7 * RMAX * members), (in_lds, nnz)
+
+
+def test_team_plan_under_sanitizers(tmp_path):
+    """team_plan.cpp built with AddressSanitizer + UBSan (CPU only; the GPU pool offers no sanitizers) and driven by
+    tests/native/team_plan_sanitize.cpp: the row tables of six regular graphs, the whole-check tables of six irregular
+    ones and 180 plans, on the smallest shapes that reach every branch of the builders."""
+    import os
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    exe = str(tmp_path / "team_plan_sanitize")
+    subprocess.check_call(["g++", "-std=c++17", *san, "-o", exe, os.path.join(root, "tests", "native", "team_plan_sanitize.cpp"),
+                           os.path.join(root, "ldpcdecoders.jl_amd", "csrc", "team_plan.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
