@@ -490,6 +490,79 @@ ldpc_status ldpc_bitflip_decode_batch_device(ldpc_bitflip_decoder *dec, int64_t 
                                              const uint8_t *d_syndromes, uint8_t *d_errors, uint8_t *d_converged,
                                              int32_t *d_iters, uint8_t *d_stop_reason, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Monte-Carlo trials on the device: what surrounds every decode in the reference's own use (test/test_bp_decoder.jl:19-30,
+ * benchmark/benchmarks.jl:8-11) -- draw `errors = rand(n, B) .< per`, form `syndromes = H * errors .% 2`, decode, compare
+ * `guesses[:, i] == errors[:, i]`, count.  A trials handle owns the Tanner graph of H and an optional second sparse
+ * pattern L of nl x n "logical" rows, and offers the three steps around the decode with DEVICE pointers, so that the
+ * batch never leaves the GPU and a run over many batches reads back the four counts.
+ *
+ * The sampling rule (a CPU model equals the device in every element).  mix is the SplitMix64 finaliser of the bit-flip
+ * tie rule above; all arithmetic is uint64:
+ *     k_i  = mix(seed + 0x9E3779B97F4A7C15 * (column0 + i + 1))        i = column index in the call
+ *     r_ij = mix(k_i + j)                                              j = bit index
+ *     t    = (uint64)(per * 18446744073709551616.0)                    for 0 <= per < 1 (a power-of-two scaling, truncated)
+ *     error(i, j) = per >= 1 ? 1 : (r_ij < t)
+ * per NaN, < 0 or > 1: LDPC_ERR_INVALID_ARGUMENT.  No state is carried between calls: column i of a call with
+ * column0 = c equals column 0 of a call with column0 = c + i, whatever the tier, chunking or stream.
+ *
+ * Syndromes.  syndromes(i, r) = XOR over the stored entries (r, j) of H of errors(i, j) & 1.
+ *
+ * Score, per column i, with d = guesses(i, .) ^ errors(i, .) (low bits):
+ *     flag bit 0: d != 0                 (the reference's `guess != err`)
+ *     flag bit 1: H * d != 0             (the guess does not reproduce the error's syndrome)
+ *     flag bit 2: L * d != 0 in some row (a logical failure; never set when nl = 0)
+ * counts[0] += batch, counts[1..3] += the number of columns with each bit set.  Counts are ACCUMULATED, never zeroed by
+ * the library: the caller zeroes them once, a run over many batches reads them back once.
+ *
+ * Layouts as everywhere in this header: errors / guesses [batch][n] bytes, syndromes [batch][s] bytes, flags [batch]
+ * bytes.  H and L are zero-based CSC patterns with the checks of ldpc_bp_create (L has n columns); nl = 0 with NULL
+ * lcolptr / lrowval is legal.  No pointer needs an alignment; score is fastest where d_guesses and d_errors agree in
+ * address mod 16 (otherwise the guesses are read byte by byte: same result, 16 loads for one).  A call takes at most
+ * 2^36 columns (more: LDPC_ERR_UNSUPPORTED).
+ *
+ * ldpc_trials_kernel: 1 = on-chip bit image (a column's bits, or those of d, live in LDS while its checks are walked:
+ * n <= 1,302,497, i.e. 2 * ((n + 30) / 16 + 1) <= 159 KiB; columns of n <= 4096 bits take one wave each, four to a
+ * workgroup, longer ones a workgroup each); 2 = unlimited (the walks read the bytes from global memory); 0 for NULL.
+ * options->kernel_variant 0 = by size, 1 / 2 force a tier (1 where the image does not fit: LDPC_ERR_UNSUPPORTED).
+ *
+ * The *_device entries take DEVICE pointers and are asynchronous on `stream`; calls on one handle run in call order
+ * whatever streams they are given.  ldpc_trials_sample and ldpc_trials_score take HOST buffers and are synchronous
+ * (their waits are bounded by ldpc_set_wait_limit_ms); the host form's counts[4] is accumulated into as well.
+ * d_syndromes / syndromes may be NULL in sample (errors only), d_flags / flags may be NULL in score; every other
+ * pointer is required.  batch = 0: LDPC_OK, nothing touched.  A negative batch or column0, a per outside [0, 1], a NULL
+ * required pointer, a NULL handle: LDPC_ERR_INVALID_ARGUMENT before any device work.  Without a device,
+ * ldpc_trials_create returns LDPC_ERR_NO_DEVICE.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_trials ldpc_trials;
+
+/* Optional; pass NULL to ldpc_trials_create for defaults (current device, tier by size). */
+typedef struct ldpc_trials_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_trials_kernel */
+    int32_t reserved[14];
+} ldpc_trials_options;
+
+ldpc_status ldpc_trials_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
+                               int64_t nl, int64_t lnnz, const int64_t *lcolptr, const int64_t *lrowval,
+                               const ldpc_trials_options *options, ldpc_trials **out);
+ldpc_status ldpc_trials_destroy(ldpc_trials *t);
+int32_t ldpc_trials_kernel(const ldpc_trials *t);
+/* errors and (unless NULL) their syndromes in one pass */
+ldpc_status ldpc_trials_sample_device(ldpc_trials *t, int64_t batch, int64_t column0, double per, uint64_t seed,
+                                      uint8_t *d_errors, uint8_t *d_syndromes, void *stream);
+/* the syndromes of given errors */
+ldpc_status ldpc_trials_syndromes_device(ldpc_trials *t, int64_t batch, const uint8_t *d_errors,
+                                         uint8_t *d_syndromes, void *stream);
+ldpc_status ldpc_trials_score_device(ldpc_trials *t, int64_t batch, const uint8_t *d_guesses, const uint8_t *d_errors,
+                                     uint8_t *d_flags, int64_t *d_counts, void *stream);
+ldpc_status ldpc_trials_sample(ldpc_trials *t, int64_t batch, int64_t column0, double per, uint64_t seed,
+                               uint8_t *errors, uint8_t *syndromes);
+ldpc_status ldpc_trials_score(ldpc_trials *t, int64_t batch, const uint8_t *guesses, const uint8_t *errors,
+                              uint8_t *flags, int64_t counts[4]);
+
 /* Diagnostics: 100 MHz ticks spent in {check sweep, variable sweep, convergence test}
  * of that call, summed over workgroups (one sampling wave each). */
 ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *dec, int32_t calls_back, uint64_t ticks[3]);

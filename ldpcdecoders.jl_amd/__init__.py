@@ -26,10 +26,12 @@ from .decoder import (  # noqa: F401
 from .osd import BeliefPropagationOSDDecoder, OSDPostProcessor  # noqa: F401,E402
 from .bpots import BPOTSDecoder  # noqa: F401,E402
 from .bitflip import BitFlipDecoder, BitFlipScratchSpace  # noqa: F401,E402
+from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 
 __all__ = [
     "BeliefPropagationOSDDecoder", "OSDPostProcessor", "BPOTSDecoder", "BitFlipDecoder", "BitFlipScratchSpace",
     "decode_", "batchdecode_", "reset_", "AbstractDecoder", "BeliefPropagationDecoder",
     "BeliefPropagationScratchSpace", "parity_check_matrix", "save_pcm", "load_pcm",
     "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
+    "Trials", "TrialResult", "run_trials",
 ]

@@ -58,6 +58,24 @@ class BPOTSDecoder(AbstractDecoder):
                                                     conv.ctypes.data, its.ctypes.data), self._L)
         return err, conv, its
 
+    def decode_batch_device(self, syn, err, conv, iters=None, stream=None) -> None:
+        """HBM-resident batch (ldpc_bpots_decode_batch_device): torch tensors on the decoder's GPU, syn [B][s] u8,
+        err [B][n] u8, conv [B] u8, iters [B] i32 | None, all contiguous.  Asynchronous on `stream` (a hipStream_t as
+        int; default = torch's current stream)."""
+        import torch
+
+        B = int(syn.shape[0])
+        for x in (syn, err, conv):
+            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
+        if iters is not None:
+            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
+        if stream is None:
+            stream = torch.cuda.current_stream(syn.device).cuda_stream
+        _capi.check(self._L.ldpc_bpots_decode_batch_device(
+            self._h, B, syn.data_ptr(), err.data_ptr(), conv.data_ptr(),
+            iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)), self._L)
+
     def decode_(self, syndrome) -> Tuple[np.ndarray, bool]:
         """`decode!(decoder::BPOTSDecoder, syndrome)`: (best_decisions as Int vector, converged)."""
         syn = syndrome_bytes(np.asarray(syndrome).reshape(-1))

@@ -22,6 +22,7 @@ import LDPCDecoders
 import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 
 export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder, MI355XBitFlipDecoder
+export Trials, sample!, score!
 
 const libldpc = get(ENV, "LDPC_MI355X_LIB", "libldpc_mi355x.so")
 
@@ -410,5 +411,78 @@ function batchdecode!(d::MI355XBitFlipDecoder, syndromes::AbstractMatrix, errors
 end
 batchdecode!(d::MI355XBitFlipDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix) =
     batchdecode!(d, syndromes, errors, Vector{Bool}(undef, size(syndromes, 2)))
+
+# ---------------------------------------------------------------------------------------------
+# Monte-Carlo trials over ldpc_trials_* (host entries): what the reference's tests do around every decode
+# (test/test_bp_decoder.jl:19-30) -- errors = rand(n, B) .< per, syndromes = H * errors .% 2, guesses[:, i] == errors[:, i]
+# -- with the sampling, syndrome and score rules of include/ldpc_mi355x.h.  These symbols were added without a change of
+# the ABI version; `Libdl.dlsym(Libdl.dlopen(libldpc), :ldpc_trials_create; throw_error=false)` tells whether they exist.
+# ---------------------------------------------------------------------------------------------
+mutable struct Trials
+    s::Int; n::Int; nl::Int
+    handle::Ptr{Cvoid}
+end
+
+"""
+    Trials(H; logicals=nothing, device=-1, kernel_variant=0)
+
+`logicals`: an nl x n matrix whose rows are checked against `guess .⊻ error` (flag bit 2 of `score!`).
+"""
+function Trials(H; logicals=nothing, device::Integer=-1, kernel_variant::Integer=0)
+    s, n = size(H)
+    sp = dropzeros(SparseMatrixCSC{Bool,Int}(sparse(H)))
+    colptr = Int64.(sp.colptr .- 1); rowval = Int64.(rowvals(sp) .- 1)
+    nl = 0; lcolptr = Int64[]; lrowval = Int64[]
+    if logicals !== nothing && size(logicals, 1) > 0
+        size(logicals, 2) == n || throw(DimensionMismatch("logicals must have as many columns as H"))
+        lsp = dropzeros(SparseMatrixCSC{Bool,Int}(sparse(logicals)))
+        nl = size(logicals, 1); lcolptr = Int64.(lsp.colptr .- 1); lrowval = Int64.(rowvals(lsp) .- 1)
+    end
+    opts = zeros(Int32, 16); opts[1] = Int32(device); opts[2] = Int32(kernel_variant)   # ldpc_trials_options (64 bytes)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:ldpc_trials_create, libldpc), Cint,
+                (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                s, n, length(rowval), colptr, rowval, nl, length(lrowval), nl > 0 ? pointer(lcolptr) : C_NULL,
+                nl > 0 && !isempty(lrowval) ? pointer(lrowval) : C_NULL, opts, h))
+    t = Trials(s, n, nl, h[])
+    finalizer(t) do x
+        x.handle != C_NULL && ccall((:ldpc_trials_destroy, libldpc), Cint, (Ptr{Cvoid},), x.handle)
+        x.handle = C_NULL
+    end
+    return t
+end
+
+"""
+    sample!(t, errors, syndromes, per; seed=0, column0=0)
+
+Fills `errors` (n x B, `Matrix{UInt8}` or `Matrix{Bool}`) and `syndromes` (s x B) by the header's sampling rule; column
+`i` of the call is trial number `column0 + i - 1`.
+"""
+function sample!(t::Trials, errors::Union{Matrix{UInt8},Matrix{Bool}}, syndromes::Union{Matrix{UInt8},Matrix{Bool}},
+                 per::Float64; seed::Integer=0, column0::Integer=0)
+    size(errors, 1) == t.n && size(syndromes, 1) == t.s || throw(DimensionMismatch("errors / syndromes rows"))
+    @assert size(errors, 2) == size(syndromes, 2)
+    check(ccall((:ldpc_trials_sample, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Float64, UInt64, Ptr{UInt8}, Ptr{UInt8}),
+                t.handle, size(errors, 2), column0, per, UInt64(seed), errors, syndromes))
+    return errors, syndromes
+end
+
+"""
+    score!(t, guesses, errors, counts=zeros(Int64, 4)) -> (flags, counts)
+
+`flags[i]`: bit 0 `guesses[:, i] != errors[:, i]`, bit 1 the guess does not reproduce the syndrome, bit 2 a logical row
+is hit.  `counts` = (columns, block errors, syndrome mismatches, logical errors) is ADDED to.
+"""
+function score!(t::Trials, guesses::Union{Matrix{UInt8},Matrix{Bool}}, errors::Union{Matrix{UInt8},Matrix{Bool}},
+                counts::Vector{Int64}=zeros(Int64, 4))
+    size(guesses) == size(errors) && size(errors, 1) == t.n || throw(DimensionMismatch("guesses / errors"))
+    length(counts) == 4 || throw(DimensionMismatch("counts must hold 4 entries"))
+    flags = Vector{UInt8}(undef, size(errors, 2))
+    check(ccall((:ldpc_trials_score, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int64}),
+                t.handle, size(errors, 2), guesses, errors, flags, counts))
+    return flags, counts
+end
 
 end # module

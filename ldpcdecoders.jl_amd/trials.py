@@ -1,0 +1,247 @@
+"""Monte-Carlo trials on the device: the steps that surround every decode in the reference's own use
+(test/test_bp_decoder.jl:19-30, benchmark/benchmarks.jl:8-11) -- `errors = rand(n, B) .< per`,
+`syndromes = H * errors .% 2`, decode, `guesses[:, i] == errors[:, i]`, an error rate -- over the ldpc_trials_* entry
+points, so that the batch never leaves the GPU.  The sampling, syndrome and score rules are stated in
+include/ldpc_mi355x.h; `run_trials` loops sample -> a decoder's device entry -> score and reads back the four
+counts and the number of unconverged columns."""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _capi
+from .decoder import _pattern_of
+
+_M64 = (1 << 64) - 1
+
+
+def _current_device() -> Optional[int]:
+    """torch's current GPU, or None without one (ldpc_trials_create then answers LDPC_ERR_NO_DEVICE itself)."""
+    import torch
+
+    return int(torch.cuda.current_device()) if torch.cuda.is_available() else None
+
+
+class Trials:
+    """Owns the Tanner graph of `H` and the optional `logicals` (nl x n) on a device.  kernel_variant: 0 = by size,
+    1 = on-chip bit image, 2 = unlimited (`.kernel` tells which one the handle takes)."""
+
+    def __init__(self, H, logicals=None, device: Optional[int] = None, kernel_variant: int = 0):
+        M = _pattern_of(H)
+        self.s, self.n = int(M.shape[0]), int(M.shape[1])
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        self.nl = 0
+        lcolptr = lrowval = None
+        if logicals is not None:
+            Lm = _pattern_of(logicals)
+            if int(Lm.shape[1]) != self.n:
+                raise AssertionError("logicals must have as many columns as H")
+            self.nl = int(Lm.shape[0])
+            if self.nl:
+                lcolptr = np.ascontiguousarray(Lm.indptr, dtype=np.int64)
+                lrowval = np.ascontiguousarray(Lm.indices, dtype=np.int64)
+        if device is None:
+            # the current device NOW is the handle's for good: what `_torch_device` answers later must not follow a
+            # change of the current device between here and a `sample`
+            device = _current_device()
+        opts = _capi.TrialsOptions()
+        opts.device = -1 if device is None else int(device)
+        opts.kernel_variant = int(kernel_variant)
+        self._h = ctypes.c_void_p()
+        self._L = _capi.lib_for(None)
+        _capi.check(self._L.ldpc_trials_create(
+            self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, self.nl,
+            int(lrowval.size) if lrowval is not None else 0, lcolptr.ctypes.data if lcolptr is not None else None,
+            lrowval.ctypes.data if lrowval is not None else None, ctypes.byref(opts), ctypes.byref(self._h)), self._L)
+        self.device = device
+
+    @property
+    def kernel(self) -> int:
+        """1 = on-chip bit image, 2 = unlimited (ldpc_trials_kernel)."""
+        return int(self._L.ldpc_trials_kernel(self._h))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.ldpc_trials_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _torch_device(self):
+        import torch
+
+        return torch.device("cuda", int(self.device))
+
+    # -- device forms (torch tensors, asynchronous on `stream`: a hipStream_t as int, default torch's current stream) --
+    def sample(self, batch: int, per: float, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
+        """-> (errors [batch][n] u8, syndromes [batch][s] u8).  `out` = (errors, syndromes) to write into; a
+        syndromes of None there skips them (errors only)."""
+        import torch
+
+        B = int(batch)
+        if out is None:
+            dev = self._torch_device()
+            err = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
+            syn = torch.empty((B, self.s), dtype=torch.uint8, device=dev)
+        else:
+            err, syn = out
+        for x, cols in ((err, self.n), (syn, self.s)):
+            if x is not None:
+                assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, cols)
+        if stream is None:
+            stream = torch.cuda.current_stream(err.device).cuda_stream
+        _capi.check(self._L.ldpc_trials_sample_device(self._h, B, int(column0), float(per), int(seed) & _M64, err.data_ptr(),
+                                                      syn.data_ptr() if syn is not None else None, ctypes.c_void_p(stream)),
+                    self._L)
+        return err, syn
+
+    def syndromes(self, errors, out=None, stream: Optional[int] = None):
+        """errors [B][n] u8 -> syndromes [B][s] u8 (`H * errors .% 2`)."""
+        import torch
+
+        B = int(errors.shape[0])
+        syn = torch.empty((B, self.s), dtype=torch.uint8, device=errors.device) if out is None else out
+        for x, cols in ((errors, self.n), (syn, self.s)):
+            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, cols)
+        if stream is None:
+            stream = torch.cuda.current_stream(errors.device).cuda_stream
+        _capi.check(self._L.ldpc_trials_syndromes_device(self._h, B, errors.data_ptr(), syn.data_ptr(), ctypes.c_void_p(stream)),
+                    self._L)
+        return syn
+
+    def score(self, guesses, errors, flags=None, counts=None, stream: Optional[int] = None, want_flags: bool = True):
+        """guesses, errors [B][n] u8 -> (flags [B] u8, counts [4] i64).  `counts` is ACCUMULATED into (a fresh one
+        starts at zero): trials, block errors, syndrome mismatches, logical errors.  want_flags=False: no flags."""
+        import torch
+
+        B = int(errors.shape[0])
+        for x in (guesses, errors):
+            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, self.n)
+        if flags is None and want_flags:
+            flags = torch.empty(B, dtype=torch.uint8, device=errors.device)
+        if flags is not None:
+            assert flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() == B
+        if counts is None:
+            counts = torch.zeros(4, dtype=torch.int64, device=errors.device)
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 4
+        if stream is None:
+            stream = torch.cuda.current_stream(errors.device).cuda_stream
+        _capi.check(self._L.ldpc_trials_score_device(self._h, B, guesses.data_ptr(), errors.data_ptr(),
+                                                     flags.data_ptr() if flags is not None else None, counts.data_ptr(),
+                                                     ctypes.c_void_p(stream)), self._L)
+        return flags, counts
+
+    # -- host forms (numpy, synchronous) ---------------------------------------------------------------------------
+    def sample_host(self, batch: int, per: float, seed: int = 0, column0: int = 0):
+        B = int(batch)
+        err = np.empty((B, self.n), dtype=np.uint8)
+        syn = np.empty((B, self.s), dtype=np.uint8)
+        _capi.check(self._L.ldpc_trials_sample(self._h, B, int(column0), float(per), int(seed) & _M64, err.ctypes.data,
+                                               syn.ctypes.data), self._L)
+        return err, syn
+
+    def score_host(self, guesses, errors, counts=None):
+        """-> (flags [B] u8, counts [4] i64); `counts` (numpy int64[4]) is accumulated into."""
+        g = np.ascontiguousarray(guesses, dtype=np.uint8)
+        e = np.ascontiguousarray(errors, dtype=np.uint8)
+        B = int(e.shape[0])
+        assert g.shape == (B, self.n) and e.shape == (B, self.n)
+        flags = np.empty(B, dtype=np.uint8)
+        if counts is None:
+            counts = np.zeros(4, dtype=np.int64)
+        assert counts.dtype == np.int64 and counts.flags.c_contiguous and counts.size == 4
+        _capi.check(self._L.ldpc_trials_score(self._h, B, g.ctypes.data, e.ctypes.data, flags.ctypes.data, counts.ctypes.data),
+                    self._L)
+        return flags, counts
+
+
+@dataclass
+class TrialResult:
+    trials: int
+    block_errors: int          # guess != error (the reference's count)
+    syndrome_mismatches: int   # the guess does not reproduce the error's syndrome
+    logical_errors: int        # L * (guess ^ error) != 0; 0 without logicals
+    not_converged: int         # columns whose decoder flag was false
+
+    @property
+    def block_error_rate(self) -> float:
+        return self.block_errors / self.trials if self.trials else 0.0
+
+    @property
+    def syndrome_mismatch_rate(self) -> float:
+        return self.syndrome_mismatches / self.trials if self.trials else 0.0
+
+    @property
+    def logical_error_rate(self) -> float:
+        return self.logical_errors / self.trials if self.trials else 0.0
+
+    @property
+    def not_converged_rate(self) -> float:
+        return self.not_converged / self.trials if self.trials else 0.0
+
+
+def _device_decode(decoder, syn, err, conv, first_trial: int):
+    """One batch through the decoder's device entry; returns the error tensor that holds the guesses."""
+    from .bitflip import BitFlipDecoder
+    from .osd import BeliefPropagationOSDDecoder
+
+    if isinstance(decoder, BeliefPropagationOSDDecoder):
+        guesses, c, _ = decoder.batchdecode_device(syn)
+        conv.copy_(c)
+        return guesses
+    if isinstance(decoder, BitFlipDecoder):
+        decoder.decode_batch_device(syn, err, conv, column0=first_trial)
+        return err
+    decoder.decode_batch_device(syn, err, conv)   # BP, BP-OTS
+    return err
+
+
+def run_trials(decoder, trials: int, per: Optional[float] = None, batch: int = 65536, seed: int = 0, logicals=None) -> TrialResult:
+    """`trials` Monte-Carlo trials of `decoder` (BP, BP+OSD, BP-OTS or bit-flip) at physical error rate `per`
+    (default: the decoder's): sample -> decode -> score in batches of `batch` (the last one ragged) on torch's current
+    stream of the decoder's GPU; trial number c is column c of the sampling rule (and of the bit-flip tie rule), so the
+    result does not depend on `batch`.  Only the four counts and the number of unconverged columns are read back."""
+    import torch
+
+    from .osd import BeliefPropagationOSDDecoder
+
+    bp = decoder.bp_decoder if isinstance(decoder, BeliefPropagationOSDDecoder) else decoder
+    if per is None:
+        per = bp.per
+    device = bp.info().device if hasattr(bp, "info") else torch.cuda.current_device()
+    dev = torch.device("cuda", int(device))
+    total, batch = int(trials), int(batch)
+    assert total >= 0 and batch > 0
+    tr = Trials(bp.sparse_H, logicals, device=int(device))
+    try:
+        with torch.cuda.device(dev):
+            counts = torch.zeros(4, dtype=torch.int64, device=dev)
+            unconverged = torch.zeros((), dtype=torch.int64, device=dev)
+            B = min(batch, max(total, 1))
+            err = torch.empty((B, tr.n), dtype=torch.uint8, device=dev)
+            syn = torch.empty((B, tr.s), dtype=torch.uint8, device=dev)
+            guess = torch.empty((B, tr.n), dtype=torch.uint8, device=dev)
+            conv = torch.empty(B, dtype=torch.uint8, device=dev)
+            done = 0
+            while done < total:
+                b = min(B, total - done)
+                e, sy, gu, cv = err[:b], syn[:b], guess[:b], conv[:b]
+                tr.sample(b, per, seed=seed, column0=done, out=(e, sy))
+                guesses = _device_decode(decoder, sy, gu, cv, done)
+                tr.score(guesses, e, counts=counts, want_flags=False)
+                unconverged += (cv == 0).sum()
+                done += b
+            c = counts.cpu().tolist()
+            nc = int(unconverged.cpu())
+    finally:
+        tr.close()
+    return TrialResult(trials=int(c[0]), block_errors=int(c[1]), syndrome_mismatches=int(c[2]), logical_errors=int(c[3]),
+                       not_converged=nc)
