@@ -563,6 +563,96 @@ ldpc_status ldpc_trials_sample(ldpc_trials *t, int64_t batch, int64_t column0, d
 ldpc_status ldpc_trials_score(ldpc_trials *t, int64_t batch, const uint8_t *guesses, const uint8_t *errors,
                               uint8_t *flags, int64_t counts[4]);
 
+/* ------------------------------------------------------------------------
+ * Monte-Carlo trials of a CSS code on the device: two check matrices Hx (rows_x x n) and Hz (rows_z x n) over the same n
+ * qubits, Pauli errors (depolarizing or biased: the X part and the Z part of a qubit's error are correlated), two
+ * syndromes for two decoders, and a joint score that counts logical X and logical Z failures.  A CSS trials handle owns
+ * the Tanner graphs of Hx, Hz and of two optional patterns of logical rows Lx (nlx x n) and Lz (nlz x n).  The library
+ * does not require Hx * Hz' = 0.
+ *
+ * The sampling rule (a CPU model equals the device in every element), with mix, k_i and r_ij of the trials section:
+ *     k_i  = mix(seed + 0x9E3779B97F4A7C15 * (column0 + i + 1))        i = column index in the call
+ *     r_ij = mix(k_i + j)                                              j = qubit
+ *     tx, ty, tz = (uint64)(px * 2^64), (uint64)(py * 2^64), (uint64)(pz * 2^64)      each rate in [0, 1), truncated
+ *     a = tx, b = tx + ty, c = tx + ty + tz                            uint64
+ *     Pauli(i, j) = X if r < a, Y if a <= r < b, Z if b <= r < c, else I
+ *     ex(i, j) = X or Y = (r < b)          ez(i, j) = Y or Z = (a <= r < c)
+ * One mix per qubit feeds both arrays.  A rate that is NaN, negative or >= 1, or an overflow of either sum:
+ * LDPC_ERR_INVALID_ARGUMENT.  No state is carried between calls: column i of a call with column0 = c equals column 0 of
+ * a call with column0 = c + i, whatever the tier, batch or stream.  With py = pz = 0, ex equals the errors of
+ * ldpc_trials_sample at per = px and the same seed, and ez is zero.
+ *
+ * Syndromes.  sz(i, r) = XOR over the stored entries (r, j) of Hz of ex(i, j) & 1 (the Z checks see the X part);
+ *             sx(i, r) = XOR over the stored entries (r, j) of Hx of ez(i, j) & 1.
+ *
+ * Score, per column i, with dx = gx(i, .) ^ ex(i, .) and dz = gz(i, .) ^ ez(i, .) (low bits):
+ *     flag bit 0: dx != 0 or dz != 0
+ *     flag bit 1: Hz * dx != 0 or Hx * dz != 0
+ *     flag bit 2: Lz * dx != 0 in some row (a logical X failure; never set when nlz = 0)
+ *     flag bit 3: Lx * dz != 0 in some row (a logical Z failure; never set when nlx = 0)
+ * counts[0] += batch, counts[1] += columns with bit 0, counts[2] += columns with bit 1, counts[3] += columns with bit 2
+ * or bit 3, counts[4] += columns with bit 2, counts[5] += columns with bit 3.  Counts are ACCUMULATED, never zeroed by
+ * the library.
+ *
+ * Layouts: ex / ez / gx / gz [batch][n] bytes, sx [batch][rows_x] bytes, sz [batch][rows_z] bytes, flags [batch] bytes.
+ * Every pattern is a zero-based CSC pattern of n columns with the checks of ldpc_trials_create; lx / lz may be NULL or
+ * have rows = 0 (then colptr / rowval are not read).  No pointer needs an alignment.  The 16-byte pieces of a column
+ * are laid on its address in ex; every other array (ez; in score gx and gz) is fastest where it agrees with ex in
+ * address mod 16 and is otherwise accessed byte by byte: same result, 16 accesses for one.  A call takes at most 2^36
+ * columns (more: LDPC_ERR_UNSUPPORTED).
+ *
+ * ldpc_css_trials_kernel: 1 = on-chip bit images (a column's two images live in LDS while the checks are walked:
+ * n <= 651,233, i.e. 2 * 2 * ((n + 30) / 16 + 1) <= 159 KiB with an image rounded up to 16 bytes; columns of n <= 4096
+ * take one wave each, four to a workgroup, longer ones a workgroup each); 2 = unlimited (the walks read the bytes from
+ * global memory); 0 for NULL.  options->kernel_variant 0 = by size, 1 / 2 force a tier (1 where the images do not fit:
+ * LDPC_ERR_UNSUPPORTED).
+ *
+ * The *_device entries take DEVICE pointers and are asynchronous on `stream`; calls on one handle run in call order
+ * whatever streams they are given.  ldpc_css_trials_sample and ldpc_css_trials_score take HOST buffers and are
+ * synchronous (their waits are bounded by ldpc_set_wait_limit_ms); the host form's counts[6] is accumulated into as
+ * well.  In sample, d_sx / sx and d_sz / sz may both be NULL (errors only; one of them alone:
+ * LDPC_ERR_INVALID_ARGUMENT); d_flags / flags may be NULL in score; every other pointer is required.  batch = 0: LDPC_OK, nothing touched.  A negative batch or column0, a bad
+ * rate, a NULL required pointer, a NULL handle: LDPC_ERR_INVALID_ARGUMENT before any device work.  Without a device,
+ * ldpc_css_trials_create returns LDPC_ERR_NO_DEVICE.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_css_trials ldpc_css_trials;
+
+/* A zero-based CSC pattern of `rows` rows (its column count is the n of the call). */
+typedef struct ldpc_css_pattern {
+    int64_t rows, nnz;
+    const int64_t *colptr;   /* [n + 1] */
+    const int64_t *rowval;   /* [nnz] */
+} ldpc_css_pattern;
+
+/* Optional; pass NULL to ldpc_css_trials_create for defaults (current device, tier by size). */
+typedef struct ldpc_css_trials_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_css_trials_kernel */
+    int32_t reserved[14];
+} ldpc_css_trials_options;
+
+ldpc_status ldpc_css_trials_create(int64_t n, const ldpc_css_pattern *hx, const ldpc_css_pattern *hz,
+                                   const ldpc_css_pattern *lx, const ldpc_css_pattern *lz,
+                                   const ldpc_css_trials_options *options, ldpc_css_trials **out);
+ldpc_status ldpc_css_trials_destroy(ldpc_css_trials *t);
+int32_t ldpc_css_trials_kernel(const ldpc_css_trials *t);
+/* Pauli errors and (unless NULL) their two syndromes in one pass */
+ldpc_status ldpc_css_trials_sample_device(ldpc_css_trials *t, int64_t batch, int64_t column0, double px, double py,
+                                          double pz, uint64_t seed, uint8_t *d_ex, uint8_t *d_ez, uint8_t *d_sx,
+                                          uint8_t *d_sz, void *stream);
+/* the two syndromes of given errors */
+ldpc_status ldpc_css_trials_syndromes_device(ldpc_css_trials *t, int64_t batch, const uint8_t *d_ex,
+                                             const uint8_t *d_ez, uint8_t *d_sx, uint8_t *d_sz, void *stream);
+ldpc_status ldpc_css_trials_score_device(ldpc_css_trials *t, int64_t batch, const uint8_t *d_gx, const uint8_t *d_gz,
+                                         const uint8_t *d_ex, const uint8_t *d_ez, uint8_t *d_flags, int64_t *d_counts,
+                                         void *stream);
+ldpc_status ldpc_css_trials_sample(ldpc_css_trials *t, int64_t batch, int64_t column0, double px, double py, double pz,
+                                   uint64_t seed, uint8_t *ex, uint8_t *ez, uint8_t *sx, uint8_t *sz);
+ldpc_status ldpc_css_trials_score(ldpc_css_trials *t, int64_t batch, const uint8_t *gx, const uint8_t *gz,
+                                  const uint8_t *ex, const uint8_t *ez, uint8_t *flags, int64_t counts[6]);
+
 /* Diagnostics: 100 MHz ticks spent in {check sweep, variable sweep, convergence test}
  * of that call, summed over workgroups (one sampling wave each). */
 ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *dec, int32_t calls_back, uint64_t ticks[3]);

@@ -27,6 +27,7 @@ from .osd import BeliefPropagationOSDDecoder, OSDPostProcessor  # noqa: F401,E40
 from .bpots import BPOTSDecoder  # noqa: F401,E402
 from .bitflip import BitFlipDecoder, BitFlipScratchSpace  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
+from .css_trials import CSSTrialResult, CSSTrials, run_css_trials  # noqa: F401,E402
 
 __all__ = [
     "BeliefPropagationOSDDecoder", "OSDPostProcessor", "BPOTSDecoder", "BitFlipDecoder", "BitFlipScratchSpace",
@@ -34,4 +35,5 @@ __all__ = [
     "BeliefPropagationScratchSpace", "parity_check_matrix", "save_pcm", "load_pcm",
     "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
     "Trials", "TrialResult", "run_trials",
+    "CSSTrials", "CSSTrialResult", "run_css_trials",
 ]

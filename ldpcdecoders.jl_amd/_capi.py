@@ -79,6 +79,14 @@ EXPORTED_SYMBOLS = (
     "ldpc_trials_score_device",
     "ldpc_trials_sample",
     "ldpc_trials_score",
+    "ldpc_css_trials_create",
+    "ldpc_css_trials_destroy",
+    "ldpc_css_trials_kernel",
+    "ldpc_css_trials_sample_device",
+    "ldpc_css_trials_syndromes_device",
+    "ldpc_css_trials_score_device",
+    "ldpc_css_trials_sample",
+    "ldpc_css_trials_score",
 )
 # ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
 DEBUG_SYMBOLS = ("ldpc_debug_team_rows", "ldpc_debug_team_plan", "ldpc_debug_div_check", "ldpc_debug_process_state",
@@ -139,10 +147,19 @@ class TrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
 
+class CSSPattern(ctypes.Structure):
+    """ldpc_css_pattern: a zero-based CSC pattern of `rows` rows."""
+    _fields_ = [("rows", ctypes.c_int64), ("nnz", ctypes.c_int64), ("colptr", ctypes.c_void_p), ("rowval", ctypes.c_void_p)]
+
+
+class CSSTrialsOptions(ctypes.Structure):
+    _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_css_trials.hip", "css_trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -289,6 +306,23 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_trials_sample.argtypes = [vp, i64, i64, f64, u64, vp, vp]
     L.ldpc_trials_score.restype = i32
     L.ldpc_trials_score.argtypes = [vp, i64, vp, vp, vp, vp]
+    pat = ctypes.POINTER(CSSPattern)
+    L.ldpc_css_trials_create.restype = i32
+    L.ldpc_css_trials_create.argtypes = [i64, pat, pat, pat, pat, ctypes.POINTER(CSSTrialsOptions), ctypes.POINTER(vp)]
+    L.ldpc_css_trials_destroy.restype = i32
+    L.ldpc_css_trials_destroy.argtypes = [vp]
+    L.ldpc_css_trials_kernel.restype = i32
+    L.ldpc_css_trials_kernel.argtypes = [vp]
+    L.ldpc_css_trials_sample_device.restype = i32
+    L.ldpc_css_trials_sample_device.argtypes = [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp, vp]
+    L.ldpc_css_trials_syndromes_device.restype = i32
+    L.ldpc_css_trials_syndromes_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    L.ldpc_css_trials_score_device.restype = i32
+    L.ldpc_css_trials_score_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ldpc_css_trials_sample.restype = i32
+    L.ldpc_css_trials_sample.argtypes = [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp]
+    L.ldpc_css_trials_score.restype = i32
+    L.ldpc_css_trials_score.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
     L.ldpc_debug_process_state.restype = vp
     L.ldpc_debug_adopt_process_state.restype = i32
     L.ldpc_debug_adopt_process_state.argtypes = [vp]

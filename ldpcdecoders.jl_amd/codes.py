@@ -121,3 +121,118 @@ def syndromes_of(H, errors_bn: np.ndarray) -> np.ndarray:
     """syndrome = (H * e) .% 2 for every row of errors [B][n]; returns [B][s] uint8."""
     M = sp.csr_matrix(H, dtype=np.int32) if not sp.issparse(H) else sp.csr_matrix(H.astype(np.int32))
     return (np.asarray((M @ errors_bn.T.astype(np.int32))) % 2).T.astype(np.uint8).copy()
+
+
+# ---- CSS codes: a product family and the logical operators (host GF(2) elimination; run once per code) --------------
+def _dense_bits(H) -> np.ndarray:
+    """The pattern of H (its nonzero entries, as the decoders take it) as a dense 0/1 uint8 matrix."""
+    A = np.asarray(H.todense()) if sp.issparse(H) else np.asarray(H)
+    return (A != 0).astype(np.uint8)
+
+
+def _gf2_rref(A: np.ndarray):
+    """Reduced row echelon form over GF(2) of a dense 0/1 matrix -> (R [rank][n] uint8, pivot columns).  The rows are
+    eliminated bit-packed (numpy.packbits), one XOR of whole rows per pivot."""
+    r, n = A.shape
+    P = np.packbits(A, axis=1) if n else np.zeros((r, 0), dtype=np.uint8)
+    pivots, rank = [], 0
+    for c in range(n):
+        if rank == r:
+            break
+        byte, mask = c >> 3, 0x80 >> (c & 7)
+        hit = np.nonzero(P[rank:, byte] & mask)[0]
+        if hit.size == 0:
+            continue
+        p = rank + int(hit[0])
+        if p != rank:
+            P[[rank, p]] = P[[p, rank]]
+        rows = np.nonzero(P[:, byte] & mask)[0]
+        rows = rows[rows != rank]
+        P[rows] ^= P[rank]
+        pivots.append(c)
+        rank += 1
+    R = np.unpackbits(P[:rank], axis=1, count=n) if n else np.zeros((rank, 0), dtype=np.uint8)
+    return R, pivots
+
+
+def gf2_rank(A) -> int:
+    """Rank over GF(2)."""
+    return len(_gf2_rref(_dense_bits(A))[1])
+
+
+def _gf2_kernel(A: np.ndarray) -> np.ndarray:
+    """A basis (rows) of {v : A v = 0} over GF(2)."""
+    n = A.shape[1]
+    R, pivots = _gf2_rref(A)
+    free = np.setdiff1d(np.arange(n), np.asarray(pivots, dtype=np.int64))
+    K = np.zeros((free.size, n), dtype=np.uint8)
+    K[np.arange(free.size), free] = 1
+    if pivots:
+        K[:, pivots] = R[:, free].T
+    return K
+
+
+def _first_independent_rows(S: np.ndarray) -> list:
+    """Indices of the rows of S that are independent of the rows before them (the pivot columns of S')."""
+    return _gf2_rref(np.ascontiguousarray(S.T))[1]
+
+
+def _gf2_matmul(A: np.ndarray, B: np.ndarray) -> np.ndarray:
+    """A * B over GF(2) for 0/1 matrices (float32 products are exact: the inner dimension is far below 2^24)."""
+    assert A.shape[1] < (1 << 24)
+    return (np.rint(A.astype(np.float32) @ B.astype(np.float32)).astype(np.int64) & 1).astype(np.uint8)
+
+
+def _gf2_inverse(M: np.ndarray) -> np.ndarray:
+    k = M.shape[0]
+    R, pivots = _gf2_rref(np.concatenate([M, np.eye(k, dtype=np.uint8)], axis=1))
+    if pivots != list(range(k)):
+        raise AssertionError("matrix is singular over GF(2)")
+    return R[:, k:]
+
+
+def css_logicals(Hx, Hz) -> Tuple[np.ndarray, np.ndarray]:
+    """Logical operators of the CSS code (Hx, Hz), Hx * Hz' = 0 over GF(2): -> (Lx, Lz), each k x n uint8 with
+    k = n - rank(Hx) - rank(Hz).  The rows of Lx span ker(Hz) modulo rowspace(Hx), those of Lz span ker(Hx) modulo
+    rowspace(Hz), and they are paired: Lx * Lz' = I_k.  Host elimination in numpy, for create time."""
+    X, Z = _dense_bits(Hx), _dense_bits(Hz)
+    if X.shape[1] != Z.shape[1]:
+        raise AssertionError("Hx and Hz must have the same number of columns")
+    if _gf2_matmul(X, Z.T).any():
+        raise AssertionError("Hx * Hz' != 0 over GF(2): not a CSS code")
+
+    def quotient(H_kernel_of, H_modulo):
+        K = _gf2_kernel(H_kernel_of)
+        R, pivots = _gf2_rref(H_modulo)
+        if pivots:
+            K = K ^ _gf2_matmul(K[:, pivots], R)   # every row reduced modulo rowspace(H_modulo): zero in its pivot columns
+        return K[_first_independent_rows(K)]
+
+    Lx, Lz = quotient(Z, X), quotient(X, Z)
+    k = Lx.shape[0]
+    if Lz.shape[0] != k:
+        raise AssertionError("logical X and Z spaces differ in dimension")
+    if k:
+        # Lz <- inv(M)' * Lz with M = Lx * Lz', so that Lx * Lz' = M * inv(M) = I
+        Lz = _gf2_matmul(np.ascontiguousarray(_gf2_inverse(_gf2_matmul(Lx, Lz.T)).T), Lz)
+    return Lx, Lz
+
+
+def hypergraph_product(H1, H2=None) -> Tuple[sp.csc_matrix, sp.csc_matrix]:
+    """Hypergraph product (Tillich, Zemor 2014) of two classical parity-check matrices H1 (m1 x n1) and H2 (m2 x n2,
+    default H1): Hx = [H1 (x) I_n2 | I_m1 (x) H2'] (m1 n2 rows), Hz = [I_n1 (x) H2 | H1' (x) I_m2] (n1 m2 rows), on
+    n1 n2 + m1 m2 qubits; Hx * Hz' = 2 (H1 (x) H2') = 0 over GF(2).  Sparse uint8 patterns."""
+    A = sp.csr_matrix(_dense_bits(H1))
+    B = A if H2 is None else sp.csr_matrix(_dense_bits(H2))
+    (m1, n1), (m2, n2) = A.shape, B.shape
+    eye = lambda k: sp.identity(k, dtype=np.uint8, format="csr")   # noqa: E731
+    Hx = sp.hstack([sp.kron(A, eye(n2)), sp.kron(eye(m1), B.T)])
+    Hz = sp.hstack([sp.kron(eye(n1), B), sp.kron(A.T, eye(m2))])
+    out = []
+    for M in (Hx, Hz):
+        M = sp.csc_matrix(M).astype(np.uint8)
+        M.sum_duplicates()
+        M.eliminate_zeros()   # (kron stores the zeros of a dense block)
+        M.sort_indices()
+        out.append(M)
+    return out[0], out[1]

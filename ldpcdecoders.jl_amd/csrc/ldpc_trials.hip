@@ -70,7 +70,9 @@ static ldpc_status trials_launch(ldpc_trials *t, int mode, TrialParams p, int64_
     const size_t lds = image ? (size_t)cpb * t->image_stride * sizeof(unsigned short) : 0;
     trial_kernel_t k = trial_kernel_of(mode, t->wpc, image);
     if (!t->per_cu[mode]) {
-        if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // always the whole budget, never this handle's own size: the cap belongs to the kernel, not to the handle, and a
+        // later handle of a smaller n must not lower it under an earlier, larger one
+        if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrialsImageLds));
         t->per_cu[mode] = std::min(8, ldpc_detail::blocks_per_cu((const void *)k, kThreads, lds));
     }
     p.s = (int)t->s; p.n = (int)t->n; p.nl = (int)t->nl; p.cpl = t->cpl; p.image_stride = t->image_stride; p.batch = batch;

@@ -1,0 +1,288 @@
+"""Monte-Carlo trials of a CSS code on the device, over the ldpc_css_trials_* entry points: Pauli errors on n qubits
+(depolarizing or biased; one draw per qubit gives its X part `ex` and its Z part `ez`, so a Y error exists), the two
+syndromes `sz = Hz ex` and `sx = Hx ez`, and a joint score that counts logical X and logical Z failures.  The rules
+are stated in include/ldpc_mi355x.h; `run_css_trials` loops sample -> two decoders' device entries -> score and reads
+back the six counts and the two numbers of unconverged columns."""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _capi, codes
+from .decoder import _pattern_of
+from .trials import _M64, _current_device, _device_decode
+
+
+def pauli_rates(p):
+    """`p` -> (px, py, pz): a float is depolarizing noise of total rate p (px = py = pz = p / 3), a triple is itself."""
+    if isinstance(p, (tuple, list, np.ndarray)):
+        px, py, pz = (float(x) for x in p)
+        return px, py, pz
+    return (float(p) / 3.0,) * 3
+
+
+class CSSTrials:
+    """Owns the Tanner graphs of `Hx`, `Hz` and of the logical rows on a device.  logicals: None = `codes.css_logicals`,
+    False = no logical rows (flag bits 2 and 3 are then never set), or a pair (Lx, Lz).  check: assert Hx * Hz' = 0
+    over GF(2) (the library does not).  kernel_variant: 0 = by size, 1 = on-chip bit images, 2 = unlimited (`.kernel`
+    tells which one the handle takes)."""
+
+    def __init__(self, Hx, Hz, logicals=None, device: Optional[int] = None, kernel_variant: int = 0, check: bool = True):
+        self._h = None
+        Mx, Mz = _pattern_of(Hx), _pattern_of(Hz)
+        if int(Mx.shape[1]) != int(Mz.shape[1]):
+            raise AssertionError("Hx and Hz must have the same number of columns")
+        if check:
+            prod = Mx.astype(np.int64) @ Mz.astype(np.int64).T
+            if (prod.data % 2).any():
+                raise AssertionError("Hx * Hz' != 0 over GF(2): the X and Z checks do not commute")
+        self.n, self.rows_x, self.rows_z = int(Mx.shape[1]), int(Mx.shape[0]), int(Mz.shape[0])
+        if logicals is None:
+            logicals = codes.css_logicals(Mx, Mz)
+        mats = [Mx, Mz]
+        if logicals is not False:
+            Lx, Lz = logicals
+            for L in (Lx, Lz):
+                Lm = _pattern_of(L)
+                if int(Lm.shape[1]) != self.n:
+                    raise AssertionError("logicals must have as many columns as Hx and Hz")
+                mats.append(Lm)
+        self.nlx = int(mats[2].shape[0]) if len(mats) > 2 else 0
+        self.nlz = int(mats[3].shape[0]) if len(mats) > 3 else 0
+        keep, pats = [], []
+        for M in mats:
+            colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
+            rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+            keep += [colptr, rowval]
+            pat = _capi.CSSPattern()
+            pat.rows, pat.nnz, pat.colptr, pat.rowval = int(M.shape[0]), int(rowval.size), colptr.ctypes.data, rowval.ctypes.data
+            pats.append(ctypes.byref(pat))
+        pats += [None] * (4 - len(pats))
+        if device is None:
+            device = _current_device()   # (the current device NOW is the handle's for good, as in Trials)
+        opts = _capi.CSSTrialsOptions()
+        opts.device = -1 if device is None else int(device)
+        opts.kernel_variant = int(kernel_variant)
+        h = ctypes.c_void_p()
+        self._L = _capi.lib_for(None)
+        _capi.check(self._L.ldpc_css_trials_create(self.n, pats[0], pats[1], pats[2], pats[3], ctypes.byref(opts), ctypes.byref(h)),
+                    self._L)
+        self._h = h
+        self.device = device
+
+    @property
+    def kernel(self) -> int:
+        """1 = on-chip bit images, 2 = unlimited (ldpc_css_trials_kernel)."""
+        return int(self._L.ldpc_css_trials_kernel(self._h))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.ldpc_css_trials_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _torch_device(self):
+        import torch
+
+        return torch.device("cuda", int(self.device))
+
+    @staticmethod
+    def _is(x, shape) -> bool:
+        import torch
+
+        return x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == tuple(shape)
+
+    # -- device forms (torch tensors, asynchronous on `stream`: a hipStream_t as int, default torch's current stream) --
+    def sample(self, batch: int, p, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
+        """-> (ex [batch][n], ez [batch][n], sx [batch][rows_x], sz [batch][rows_z]), all u8.  `out` = (ex, ez, sx, sz) to
+        write into; None for both sx and sz there skips the syndromes (errors only)."""
+        import torch
+
+        B = int(batch)
+        px, py, pz = pauli_rates(p)
+        if out is None:
+            dev = self._torch_device()
+            ex, ez = (torch.empty((B, self.n), dtype=torch.uint8, device=dev) for _ in range(2))
+            sx = torch.empty((B, self.rows_x), dtype=torch.uint8, device=dev)
+            sz = torch.empty((B, self.rows_z), dtype=torch.uint8, device=dev)
+        else:
+            ex, ez, sx, sz = out
+        for x, cols in ((ex, self.n), (ez, self.n), (sx, self.rows_x), (sz, self.rows_z)):
+            assert x is None or self._is(x, (B, cols))
+        if stream is None:
+            stream = torch.cuda.current_stream(ex.device).cuda_stream
+        _capi.check(self._L.ldpc_css_trials_sample_device(
+            self._h, B, int(column0), px, py, pz, int(seed) & _M64, ex.data_ptr(), ez.data_ptr(),
+            sx.data_ptr() if sx is not None else None, sz.data_ptr() if sz is not None else None, ctypes.c_void_p(stream)), self._L)
+        return ex, ez, sx, sz
+
+    def syndromes(self, ex, ez, out=None, stream: Optional[int] = None):
+        """ex, ez [B][n] u8 -> (sx [B][rows_x], sz [B][rows_z]) u8: sx = Hx ez, sz = Hz ex (mod 2)."""
+        import torch
+
+        B = int(ex.shape[0])
+        if out is None:
+            sx = torch.empty((B, self.rows_x), dtype=torch.uint8, device=ex.device)
+            sz = torch.empty((B, self.rows_z), dtype=torch.uint8, device=ex.device)
+        else:
+            sx, sz = out
+        for x, cols in ((ex, self.n), (ez, self.n), (sx, self.rows_x), (sz, self.rows_z)):
+            assert self._is(x, (B, cols))
+        if stream is None:
+            stream = torch.cuda.current_stream(ex.device).cuda_stream
+        _capi.check(self._L.ldpc_css_trials_syndromes_device(self._h, B, ex.data_ptr(), ez.data_ptr(), sx.data_ptr(), sz.data_ptr(),
+                                                             ctypes.c_void_p(stream)), self._L)
+        return sx, sz
+
+    def score(self, gx, gz, ex, ez, flags=None, counts=None, stream: Optional[int] = None, want_flags: bool = True):
+        """gx, gz, ex, ez [B][n] u8 -> (flags [B] u8, counts [6] i64).  `counts` is ACCUMULATED into (a fresh one starts
+        at zero): trials, columns with dx or dz != 0, with a syndrome mismatch, with a logical failure, with a logical
+        X failure, with a logical Z failure.  want_flags=False: no flags."""
+        import torch
+
+        B = int(ex.shape[0])
+        for x in (gx, gz, ex, ez):
+            assert self._is(x, (B, self.n))
+        if flags is None and want_flags:
+            flags = torch.empty(B, dtype=torch.uint8, device=ex.device)
+        if flags is not None:
+            assert flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() == B
+        if counts is None:
+            counts = torch.zeros(6, dtype=torch.int64, device=ex.device)
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 6
+        if stream is None:
+            stream = torch.cuda.current_stream(ex.device).cuda_stream
+        _capi.check(self._L.ldpc_css_trials_score_device(
+            self._h, B, gx.data_ptr(), gz.data_ptr(), ex.data_ptr(), ez.data_ptr(), flags.data_ptr() if flags is not None else None,
+            counts.data_ptr(), ctypes.c_void_p(stream)), self._L)
+        return flags, counts
+
+    # -- host forms (numpy, synchronous) ---------------------------------------------------------------------------
+    def sample_host(self, batch: int, p, seed: int = 0, column0: int = 0):
+        B = int(batch)
+        px, py, pz = pauli_rates(p)
+        ex, ez = np.empty((B, self.n), dtype=np.uint8), np.empty((B, self.n), dtype=np.uint8)
+        sx, sz = np.empty((B, self.rows_x), dtype=np.uint8), np.empty((B, self.rows_z), dtype=np.uint8)
+        _capi.check(self._L.ldpc_css_trials_sample(self._h, B, int(column0), px, py, pz, int(seed) & _M64, ex.ctypes.data,
+                                                   ez.ctypes.data, sx.ctypes.data, sz.ctypes.data), self._L)
+        return ex, ez, sx, sz
+
+    def score_host(self, gx, gz, ex, ez, counts=None):
+        """-> (flags [B] u8, counts [6] i64); `counts` (numpy int64[6]) is accumulated into."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (gx, gz, ex, ez)]
+        B = int(arrs[2].shape[0])
+        assert all(a.shape == (B, self.n) for a in arrs)
+        flags = np.empty(B, dtype=np.uint8)
+        if counts is None:
+            counts = np.zeros(6, dtype=np.int64)
+        assert counts.dtype == np.int64 and counts.flags.c_contiguous and counts.size == 6
+        _capi.check(self._L.ldpc_css_trials_score(self._h, B, *(a.ctypes.data for a in arrs), flags.ctypes.data, counts.ctypes.data),
+                    self._L)
+        return flags, counts
+
+
+@dataclass
+class CSSTrialResult:
+    trials: int
+    block_errors: int            # gx != ex or gz != ez
+    syndrome_mismatches: int     # a guess does not reproduce its error's syndrome
+    logical_errors: int          # a logical X or a logical Z failure
+    logical_x_errors: int        # Lz * (gx ^ ex) != 0
+    logical_z_errors: int        # Lx * (gz ^ ez) != 0
+    not_converged_hx: int        # columns whose decoder on Hx reported false
+    not_converged_hz: int        # the same for the decoder on Hz
+
+    def _rate(self, k: int) -> float:
+        return k / self.trials if self.trials else 0.0
+
+    @property
+    def block_error_rate(self) -> float:
+        return self._rate(self.block_errors)
+
+    @property
+    def syndrome_mismatch_rate(self) -> float:
+        return self._rate(self.syndrome_mismatches)
+
+    @property
+    def logical_error_rate(self) -> float:
+        return self._rate(self.logical_errors)
+
+    @property
+    def logical_x_error_rate(self) -> float:
+        return self._rate(self.logical_x_errors)
+
+    @property
+    def logical_z_error_rate(self) -> float:
+        return self._rate(self.logical_z_errors)
+
+    @property
+    def not_converged_hx_rate(self) -> float:
+        return self._rate(self.not_converged_hx)
+
+    @property
+    def not_converged_hz_rate(self) -> float:
+        return self._rate(self.not_converged_hz)
+
+
+def _bp_of(decoder):
+    from .osd import BeliefPropagationOSDDecoder
+
+    return decoder.bp_decoder if isinstance(decoder, BeliefPropagationOSDDecoder) else decoder
+
+
+def run_css_trials(decoder_hx, decoder_hz, trials: int, p, batch: int = 65536, seed: int = 0, logicals=None) -> CSSTrialResult:
+    """`trials` Monte-Carlo trials of a CSS code under Pauli noise `p` (a float: depolarizing, px = py = pz = p / 3; or a
+    triple (px, py, pz)).  `decoder_hz` (BP, BP+OSD, BP-OTS or bit-flip, built on Hz) decodes sz = Hz ex into the guess
+    gx; `decoder_hx` (built on Hx) decodes sx = Hx ez into gz.  sample -> decode -> decode -> score run in batches of
+    `batch` (the last one ragged) on torch's current stream of the decoders' GPU; trial number c is column c of the
+    sampling rule (and of the bit-flip tie rule), so the result does not depend on `batch`.  Only the six counts and
+    the two numbers of unconverged columns are read back.  logicals: as in CSSTrials.
+
+    Each decoder sees one side of the noise only.  Under depolarizing noise of total rate p, the marginal rate of either
+    side is 2 p / 3 (an X part is an X or a Y); whether the decoders are built with that `per` is the caller's choice:
+    nothing here changes a decoder."""
+    import torch
+
+    bx, bz = _bp_of(decoder_hx), _bp_of(decoder_hz)
+    devices = [int(b.info().device) if hasattr(b, "info") else int(torch.cuda.current_device()) for b in (bx, bz)]
+    assert devices[0] == devices[1], f"the two decoders live on different GPUs ({devices[0]} and {devices[1]})"
+    assert int(bx.sparse_H.shape[1]) == int(bz.sparse_H.shape[1]), "decoder_hx and decoder_hz must have the same number of bits"
+    device = devices[1]
+    dev = torch.device("cuda", int(device))
+    total, batch = int(trials), int(batch)
+    assert total >= 0 and batch > 0
+    tr = CSSTrials(bx.sparse_H, bz.sparse_H, logicals, device=int(device))
+    try:
+        with torch.cuda.device(dev):
+            counts = torch.zeros(6, dtype=torch.int64, device=dev)
+            unconverged = torch.zeros(2, dtype=torch.int64, device=dev)
+            B = min(batch, max(total, 1))
+            ex, ez, gx, gz = (torch.empty((B, tr.n), dtype=torch.uint8, device=dev) for _ in range(4))
+            sx = torch.empty((B, tr.rows_x), dtype=torch.uint8, device=dev)
+            sz = torch.empty((B, tr.rows_z), dtype=torch.uint8, device=dev)
+            cx, cz = torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+            done = 0
+            while done < total:
+                b = min(B, total - done)
+                tr.sample(b, p, seed=seed, column0=done, out=(ex[:b], ez[:b], sx[:b], sz[:b]))
+                guess_x = _device_decode(decoder_hz, sz[:b], gx[:b], cz[:b], done)
+                guess_z = _device_decode(decoder_hx, sx[:b], gz[:b], cx[:b], done)
+                tr.score(guess_x, guess_z, ex[:b], ez[:b], counts=counts, want_flags=False)
+                unconverged[0] += (cx[:b] == 0).sum()
+                unconverged[1] += (cz[:b] == 0).sum()
+                done += b
+            c = counts.cpu().tolist()
+            nc = unconverged.cpu().tolist()
+    finally:
+        tr.close()
+    return CSSTrialResult(trials=int(c[0]), block_errors=int(c[1]), syndrome_mismatches=int(c[2]), logical_errors=int(c[3]),
+                          logical_x_errors=int(c[4]), logical_z_errors=int(c[5]), not_converged_hx=int(nc[0]),
+                          not_converged_hz=int(nc[1]))

@@ -23,6 +23,7 @@ import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 
 export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder, MI355XBitFlipDecoder
 export Trials, sample!, score!
+export CSSTrials
 
 const libldpc = get(ENV, "LDPC_MI355X_LIB", "libldpc_mi355x.so")
 
@@ -482,6 +483,91 @@ function score!(t::Trials, guesses::Union{Matrix{UInt8},Matrix{Bool}}, errors::U
     check(ccall((:ldpc_trials_score, libldpc), Cint,
                 (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int64}),
                 t.handle, size(errors, 2), guesses, errors, flags, counts))
+    return flags, counts
+end
+
+# ---------------------------------------------------------------------------------------------
+# Monte-Carlo trials of a CSS code over ldpc_css_trials_* (host entries): Pauli errors (ex, ez) by one draw per qubit,
+# sz = Hz * ex .% 2 and sx = Hx * ez .% 2, and the joint score with logical X / Z failures (include/ldpc_mi355x.h).
+# Symbols added without a change of the ABI version, as those of Trials.
+# ---------------------------------------------------------------------------------------------
+struct CSSPattern            # ldpc_css_pattern
+    rows::Int64; nnz::Int64
+    colptr::Ptr{Int64}; rowval::Ptr{Int64}
+end
+
+mutable struct CSSTrials
+    n::Int; rows_x::Int; rows_z::Int; nlx::Int; nlz::Int
+    handle::Ptr{Cvoid}
+end
+
+"""
+    CSSTrials(Hx, Hz; Lx=nothing, Lz=nothing, device=-1, kernel_variant=0)
+
+`Lx`, `Lz`: logical rows (flag bits 3 and 2 of `score!`).  The library does not require `Hx * Hz' == 0`.
+"""
+function CSSTrials(Hx, Hz; Lx=nothing, Lz=nothing, device::Integer=-1, kernel_variant::Integer=0)
+    n = size(Hx, 2)
+    size(Hz, 2) == n || throw(DimensionMismatch("Hx and Hz must have the same number of columns"))
+    mats = Any[Hx, Hz, Lx, Lz]
+    keep = Any[]; pats = Vector{Any}(undef, 4)
+    for (k, M) in enumerate(mats)
+        if M === nothing || size(M, 1) == 0
+            pats[k] = C_NULL
+            continue
+        end
+        size(M, 2) == n || throw(DimensionMismatch("logicals must have as many columns as Hx and Hz"))
+        sp = dropzeros(SparseMatrixCSC{Bool,Int}(sparse(M)))
+        colptr = Int64.(sp.colptr .- 1); rowval = Int64.(rowvals(sp) .- 1)
+        push!(keep, colptr, rowval)
+        pats[k] = Ref(CSSPattern(size(M, 1), length(rowval), pointer(colptr), isempty(rowval) ? C_NULL : pointer(rowval)))
+    end
+    opts = zeros(Int32, 16); opts[1] = Int32(device); opts[2] = Int32(kernel_variant)   # ldpc_css_trials_options (64 bytes)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve keep pats begin
+        check(ccall((:ldpc_css_trials_create, libldpc), Cint,
+                    (Int64, Ptr{CSSPattern}, Ptr{CSSPattern}, Ptr{CSSPattern}, Ptr{CSSPattern}, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                    n, pats[1], pats[2], pats[3], pats[4], opts, h))
+    end
+    nrows(M) = M === nothing ? 0 : size(M, 1)
+    t = CSSTrials(n, size(Hx, 1), size(Hz, 1), nrows(Lx), nrows(Lz), h[])
+    finalizer(t) do x
+        x.handle != C_NULL && ccall((:ldpc_css_trials_destroy, libldpc), Cint, (Ptr{Cvoid},), x.handle)
+        x.handle = C_NULL
+    end
+    return t
+end
+
+"""
+    sample!(t::CSSTrials, ex, ez, sx, sz, (px, py, pz); seed=0, column0=0)
+
+Fills `ex`, `ez` (n x B) and the syndromes `sx` (rows of Hx x B), `sz` (rows of Hz x B) by the header's Pauli rule.
+"""
+function sample!(t::CSSTrials, ex::Matrix{UInt8}, ez::Matrix{UInt8}, sx::Matrix{UInt8}, sz::Matrix{UInt8},
+                 p::NTuple{3,Float64}; seed::Integer=0, column0::Integer=0)
+    size(ex) == size(ez) && size(ex, 1) == t.n || throw(DimensionMismatch("ex / ez"))
+    size(sx, 1) == t.rows_x && size(sz, 1) == t.rows_z || throw(DimensionMismatch("sx / sz rows"))
+    @assert size(sx, 2) == size(ex, 2) == size(sz, 2)
+    check(ccall((:ldpc_css_trials_sample, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, UInt64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}),
+                t.handle, size(ex, 2), column0, p[1], p[2], p[3], UInt64(seed), ex, ez, sx, sz))
+    return ex, ez, sx, sz
+end
+
+"""
+    score!(t::CSSTrials, gx, gz, ex, ez, counts=zeros(Int64, 6)) -> (flags, counts)
+
+`flags[i]`: bit 0 a guess differs, bit 1 a syndrome is not reproduced, bit 2 a logical X failure, bit 3 a logical Z
+failure.  `counts` = (columns, bit 0, bit 1, bit 2 or 3, bit 2, bit 3) is ADDED to.
+"""
+function score!(t::CSSTrials, gx::Matrix{UInt8}, gz::Matrix{UInt8}, ex::Matrix{UInt8}, ez::Matrix{UInt8},
+                counts::Vector{Int64}=zeros(Int64, 6))
+    size(gx) == size(gz) == size(ex) == size(ez) && size(ex, 1) == t.n || throw(DimensionMismatch("guesses / errors"))
+    length(counts) == 6 || throw(DimensionMismatch("counts must hold 6 entries"))
+    flags = Vector{UInt8}(undef, size(ex, 2))
+    check(ccall((:ldpc_css_trials_score, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int64}),
+                t.handle, size(ex, 2), gx, gz, ex, ez, flags, counts))
     return flags, counts
 end
 
