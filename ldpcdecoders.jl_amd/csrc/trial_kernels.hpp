@@ -1,26 +1,37 @@
 // trial_kernels.hpp -- the steps around a decode in a Monte-Carlo run, gfx950: sample errors (+ their syndromes),
-// syndromes of given errors, score guesses against errors.  The rules are stated in include/ldpc_mi355x.h.
+// syndromes of given errors, score guesses against errors; for one check matrix (ldpc_trials_*) and for a CSS pair
+// (ldpc_css_trials_*).  The rules are stated in include/ldpc_mi355x.h.
 //
-// One kernel template serves the three steps (MODE) and the two tiers (IMAGE):
-//   phase A  the column's bytes are produced (sample) or read (syndromes, score), 16 contiguous bytes per lane and step:
-//            one 16-byte vector access, folded to 16 bits with the multiply of bit_io_kernels.hpp.  The 16-byte pieces
-//            are laid on the ADDRESS, not on the column: a column starts at byte i * n of the array, which is aligned
-//            only by chance, so piece c covers the bytes [16 c - shift, 16 c - shift + 16) of the column, shift = the
-//            column's address & 15.  The first and the last piece may hold fewer than 16 bytes of the column and go
-//            byte by byte; every piece between them is an aligned vector access.  (score lays the pieces on `errors`;
-//            where `guesses` differs from it in address mod 16 the guess of every piece is read as 16 single bytes:
-//            correct, and 16 load instructions for one.  Arrays whose starts agree mod 16 never meet it.)
-//            IMAGE: piece c becomes the 16-bit word c of the column's bit image in LDS (bit j of the column is bit
-//            j + shift of the image): plain 2-byte LDS stores, no two lanes write one word, nothing to clear.
+// A SIDE is a column of errors with the matrices that see it: its arrays (errors, guesses, syndromes), the CSR of its
+// checks and of its logical rows, and the window [lo, hi) of the draw in which a bit of it is set.  The one-matrix trial
+// is one side (errors / guesses / syndromes, H, L, window [0, threshold)); a CSS trial is two sides that share one draw
+// per qubit and one flag word: side 0 = (ex, gx, sz) seen by Hz and Lz, window [0, tb); side 1 = (ez, gz, sx) seen by Hx
+// and Lx, window [ta, tc).  Side 0's window starts at 0 in both uses and costs no compare.
+//
+// One kernel template serves the side counts (SIDES), the three steps (MODE) and the two tiers (IMAGE):
+//   phase A  the column's bytes are produced (sample: ONE mix per bit position feeds every side) or read (syndromes,
+//            score), 16 contiguous bytes per lane and step, folded to 16 bits with the multiply of bit_io_kernels.hpp.
+//            The 16-byte pieces are laid on the ADDRESS of side 0's column, not on the column: a column starts at byte
+//            i * n of the array, which is aligned only by chance, so piece c covers the bytes [16 c - shift,
+//            16 c - shift + 16) of the column, shift = the column's address & 15.  The first and the last piece may hold
+//            fewer than 16 bytes of the column and go byte by byte.  In every piece between them side 0's column is one
+//            aligned vector access; each other array (side 0's guesses, everything of side 1) is a vector access too
+//            where its column agrees with side 0's in address mod 16, and 16 single-byte accesses where it does not:
+//            correct, and 16 instructions for one.
+//            IMAGE: piece c becomes the 16-bit word c of each side's bit image in LDS (bit j of a column is bit
+//            j + shift of its image; a column owns SIDES neighbouring images): plain 2-byte LDS stores, no two lanes
+//            write one word, nothing to clear.
 //   barrier
-//   phase B  lanes walk the checks through the CSR and XOR the bits of their entries: out of the image (IMAGE), or the
-//            bytes themselves out of global memory (the unlimited tier; the workgroup wrote or read them in phase A).
-//            sample / syndromes: a lane takes `cpl` neighbouring checks (4 when there are enough checks to keep every
+//   phase B  lanes walk each side's checks through the CSR and XOR the bits of their entries: out of the side's image
+//            (IMAGE), or the bytes themselves out of global memory (the unlimited tier; the workgroup wrote or read them
+//            in phase A).
+//            sample / syndromes: a lane takes `cpl` neighbouring checks (4 when the side has enough checks to keep every
 //            lane busy, else 1) and stores them as one 4-byte word, laid on the address like the pieces of phase A.
-//            score: a lane ORs the parities of its checks of H and of L; the three flag bits of a column meet in an LDS
-//            word, the workgroup keeps running counts in LDS and adds them to the caller's counters when it is done:
-//            one 64-bit atomicAdd per workgroup and counter, from a vector lane.
-//   barrier  (the image and the flag word are reused by the next column)
+//            score: a lane ORs the parities of its checks (all sides together) and of each side's logical rows; the flag
+//            bits of a column (0: any side differs, 1: any side's checks violated, 2 + k: side k's logical rows
+//            violated) meet in an LDS word, the workgroup keeps running counts in LDS and adds them to the caller's
+//            counters when it is done: one 64-bit atomicAdd per workgroup and counter, from a vector lane.
+//   barrier  (the images and the flag word are reused by the next column)
 //
 // Geometry: WPC waves work on a column.  WPC = 1: four columns per 256-thread workgroup, one wave each (short columns:
 // BB-72 at batch 2^20 would otherwise be 2^20 workgroups of one busy wave); WPC = 4: the workgroup takes one column.
@@ -59,20 +70,27 @@ __device__ inline tu64 spread8(unsigned b)
 // 16-bit words a column's image takes: pieces 0 .. (shift + n + 15) / 16 - 1 with shift <= 15
 __host__ __device__ inline int image_words(long long n) { return (int)((n + 30) >> 4) + 1; }
 
-struct TrialParams {
-    int s, n, nl, cpl;
-    int image_stride;            // 16-bit words between the images of two columns of a workgroup
-    int all_ones;                // per >= 1
-    long long batch;
-    tu64 column0, seed, threshold;
+struct TrialSide {
     uint8_t *err_out;            // sample
     const uint8_t *err;          // syndromes, score
     const uint8_t *guess;        // score
-    uint8_t *syn;                // sample (may be NULL), syndromes
+    uint8_t *syn;                // sample (may be NULL), syndromes: what this side's checks say
+    int rows, nl, cpl;           // checks, logical rows; checks a lane takes in the syndrome walk (4 or 1)
+    const int *row_ptr, *csr_col;      // the checks that see this side -> bits
+    const int *lrow_ptr, *lcsr_col;    // the logical rows that see this side -> bits
+    tu64 lo, hi;                 // sample: the bit is set where lo <= r < hi (side 0: lo is 0 and is not read)
+};
+
+template <int SIDES>
+struct TrialParams {
+    int n;
+    int image_stride;            // 16-bit words of ONE image; a column owns SIDES neighbouring ones
+    int all_ones;                // per >= 1 (one matrix only)
+    long long batch;
+    tu64 column0, seed;
     uint8_t *flags;              // score (may be NULL)
-    tu64 *counts;                // score
-    const int *row_ptr, *csr_col;      // H, checks -> bits
-    const int *lrow_ptr, *lcsr_col;    // L, logical rows -> bits
+    tu64 *counts;                // score: [trials, b0, b1, b2] or [trials, b0, b1, b2|b3, b2, b3]
+    TrialSide side[SIDES];
 };
 
 __device__ inline unsigned fold16(uint4 x)
@@ -80,107 +98,166 @@ __device__ inline unsigned fold16(uint4 x)
     return fold8((tu64)x.x | ((tu64)x.y << 32)) | (fold8((tu64)x.z | ((tu64)x.w << 32)) << 8);
 }
 
-template <int WPC, int MODE, bool IMAGE>
-__global__ __launch_bounds__(kThreads) void trial_kernel(TrialParams p)
+// 16 bytes at q -> their 16 low bits; `vec` says that q is 16-byte aligned
+__device__ inline unsigned load16(const uint8_t *q, bool vec)
+{
+    if (vec) return fold16(*reinterpret_cast<const uint4 *>(q));
+    unsigned h = 0;
+    for (int b = 0; b < 16; ++b) h |= (unsigned)(q[b] & 1u) << b;
+    return h;
+}
+
+// the low bits of 16 bytes at e ^ those at g; two aligned pieces are XORed as vectors and folded once
+__device__ inline unsigned diff16(const uint8_t *e, bool evec, const uint8_t *g, bool gvec)
+{
+    if (!(evec && gvec)) return load16(e, evec) ^ load16(g, gvec);
+    uint4 x = *reinterpret_cast<const uint4 *>(e);
+    const uint4 y = *reinterpret_cast<const uint4 *>(g);
+    x.x ^= y.x; x.y ^= y.y; x.z ^= y.z; x.w ^= y.w;
+    return fold16(x);
+}
+
+// 16 bits -> 16 bytes (0 / 1) at q
+__device__ inline void store16(uint8_t *q, unsigned h, bool vec)
+{
+    const tu64 lo = spread8(h), hi = spread8(h >> 8);
+    if (vec) {
+        uint4 o;
+        o.x = (unsigned)lo; o.y = (unsigned)(lo >> 32); o.z = (unsigned)hi; o.w = (unsigned)(hi >> 32);
+        *reinterpret_cast<uint4 *>(q) = o;
+    } else {
+        for (int b = 0; b < 8; ++b) {
+            q[b] = (uint8_t)((lo >> (8 * b)) & 0xffu);
+            q[8 + b] = (uint8_t)((hi >> (8 * b)) & 0xffu);
+        }
+    }
+}
+
+// Every loop over the sides below is unrolled, so `k` is a constant wherever it indexes p.side[] or a per-side local.
+// The two-sided score at one wave per column on the image tier asks for 8 waves/SIMD: left alone the scheduler spreads
+// the byte path of a misaligned load16 over 69 VGPRs (7 waves, and a smaller persistent grid); asked, it takes 59 and
+// keeps 12 SGPRs in the lanes of one VGPR outside the inner loops.  Every other instantiation gets the default (1).
+template <int SIDES, int WPC, int MODE, bool IMAGE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SIDES == 2 && WPC == 1 && MODE == kScore && IMAGE ? 8 : 1)))
+void trial_kernel(TrialParams<SIDES> p)
 {
     constexpr int GT = 64 * WPC, CPB = kThreads / GT;   // lanes per column, columns per workgroup
+    constexpr int NRUN = SIDES == 1 ? 3 : 3 + SIDES;    // running counts: b0, b1, any logical; then each side's logical
     extern __shared__ unsigned short image_all[];
-    __shared__ unsigned int colflags[4], running[3];
+    __shared__ unsigned int colflags[4], running[NRUN];
     const int slot = threadIdx.x / GT, gl = threadIdx.x % GT;
-    unsigned short *img = image_all + (size_t)slot * p.image_stride;
-    const int n = p.n, s = p.s;
+    unsigned short *img[SIDES];                         // a column owns SIDES neighbouring images
+#pragma unroll
+    for (int k = 0; k < SIDES; ++k) img[k] = image_all + ((size_t)slot * SIDES + k) * p.image_stride;
+    const int n = p.n;
     if (MODE == kScore) {
         if (threadIdx.x < 4) colflags[threadIdx.x] = 0;
-        if (threadIdx.x < 3) running[threadIdx.x] = 0;
+        if (threadIdx.x < NRUN) running[threadIdx.x] = 0;
         __syncthreads();
     }
+    bool walk = MODE == kScore;                         // (the same for every thread of the grid)
+#pragma unroll
+    for (int k = 0; k < SIDES; ++k) walk |= p.side[k].syn != nullptr;
     const long long ngroups = (p.batch + CPB - 1) / CPB;
     for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
         const long long col = g * CPB + slot;
         const bool live = col < p.batch;
-        // the column's bytes; `piece0` is the 16-byte boundary at or below its first byte (only bytes of the column are touched)
-        const uint8_t *ecol = (MODE == kSample ? (const uint8_t *)p.err_out : p.err) + (live ? col : 0) * (long long)n;
-        const uint8_t *gcol = MODE == kScore ? p.guess + (live ? col : 0) * (long long)n : nullptr;
-        const int shift = (int)((uintptr_t)ecol & 15);
-        const uint8_t *piece0 = ecol - shift;
+        const long long base = (live ? col : 0) * (long long)n;
+        // the column in every array (only bytes of the column are touched); the pieces are laid on ecol[0]
+        const uint8_t *ecol[SIDES], *gcol[SIDES];
+#pragma unroll
+        for (int k = 0; k < SIDES; ++k) {
+            ecol[k] = (MODE == kSample ? (const uint8_t *)p.side[k].err_out : p.side[k].err) + base;
+            gcol[k] = MODE == kScore ? p.side[k].guess + base : nullptr;
+        }
+        const int shift = (int)((uintptr_t)ecol[0] & 15);
         unsigned nonzero = 0;
         if (live && (IMAGE || MODE != kSyndromes)) {
+            bool evec[SIDES], gvec[SIDES];              // an array's column agrees with ecol[0] in address mod 16
+#pragma unroll
+            for (int k = 0; k < SIDES; ++k) evec[k] = k == 0 || (((uintptr_t)ecol[k] - (uintptr_t)ecol[0]) & 15) == 0;
+#pragma unroll
+            for (int k = 0; k < SIDES; ++k) gvec[k] = MODE == kScore && (((uintptr_t)gcol[k] - (uintptr_t)ecol[0]) & 15) == 0;
             const int npieces = (shift + n + 15) >> 4;
-            const tu64 k = MODE == kSample ? mix(p.seed + kGolden * (p.column0 + (tu64)col + 1)) : 0;
-            const bool guess_aligned = MODE == kScore && (((uintptr_t)gcol - (uintptr_t)ecol) & 15) == 0;
+            const tu64 key = MODE == kSample ? mix(p.seed + kGolden * (p.column0 + (tu64)col + 1)) : 0;
             for (int c = gl; c < npieces; c += GT) {
                 const int j = 16 * c - shift;
-                unsigned h = 0;
+                unsigned h[SIDES] = {};
                 if (j >= 0 && j + 16 <= n) {
                     if (MODE == kSample) {
 #pragma unroll
-                        for (int b = 0; b < 16; ++b) h |= (unsigned)(mix(k + (tu64)(j + b)) < p.threshold) << b;
-                        if (p.all_ones) h = 0xffffu;
-                        const tu64 lo = spread8(h), hi = spread8(h >> 8);
-                        uint4 o;
-                        o.x = (unsigned)lo; o.y = (unsigned)(lo >> 32); o.z = (unsigned)hi; o.w = (unsigned)(hi >> 32);
-                        *reinterpret_cast<uint4 *>(p.err_out + col * (long long)n + j) = o;
-                    } else {
-                        uint4 x = *reinterpret_cast<const uint4 *>(piece0 + 16 * (long long)c);
-                        if (MODE == kScore) {
-                            if (guess_aligned) {
-                                const uint4 y = *reinterpret_cast<const uint4 *>(gcol + j);
-                                x.x ^= y.x; x.y ^= y.y; x.z ^= y.z; x.w ^= y.w;
-                                h = fold16(x);
-                            } else {
-                                h = fold16(x);
-                                for (int b = 0; b < 16; ++b) h ^= (unsigned)(gcol[j + b] & 1u) << b;
-                            }
-                        } else {
-                            h = fold16(x);
+                        for (int b = 0; b < 16; ++b) {
+                            const tu64 r = mix(key + (tu64)(j + b));
+#pragma unroll
+                            for (int k = 0; k < SIDES; ++k)
+                                h[k] |= (unsigned)((k == 0 || r >= p.side[k].lo) && r < p.side[k].hi) << b;
                         }
+                        if (SIDES == 1 && p.all_ones) h[0] = 0xffffu;
+#pragma unroll
+                        for (int k = 0; k < SIDES; ++k) store16(p.side[k].err_out + base + j, h[k], evec[k]);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < SIDES; ++k)
+                            h[k] = MODE == kScore ? diff16(ecol[k] + j, evec[k], gcol[k] + j, gvec[k]) : load16(ecol[k] + j, evec[k]);
                     }
                 } else {
                     for (int b = 0; b < 16; ++b) {
                         const int jb = j + b;
                         if (jb < 0 || jb >= n) continue;
-                        unsigned bit;
-                        if (MODE == kSample) {
-                            bit = p.all_ones ? 1u : (unsigned)(mix(k + (tu64)jb) < p.threshold);
-                            p.err_out[col * (long long)n + jb] = (uint8_t)bit;
-                        } else if (MODE == kScore) {
-                            bit = (unsigned)((ecol[jb] ^ gcol[jb]) & 1u);
-                        } else {
-                            bit = (unsigned)(ecol[jb] & 1u);
+                        const tu64 r = MODE == kSample ? mix(key + (tu64)jb) : 0;
+#pragma unroll
+                        for (int k = 0; k < SIDES; ++k) {
+                            unsigned bit;
+                            if (MODE == kSample) {
+                                bit = (unsigned)((k == 0 || r >= p.side[k].lo) && r < p.side[k].hi);
+                                if (SIDES == 1 && p.all_ones) bit = 1u;
+                                p.side[k].err_out[base + jb] = (uint8_t)bit;
+                            } else if (MODE == kScore) {
+                                bit = (unsigned)((ecol[k][jb] ^ gcol[k][jb]) & 1u);
+                            } else {
+                                bit = (unsigned)(ecol[k][jb] & 1u);
+                            }
+                            h[k] |= bit << b;
                         }
-                        h |= bit << b;
                     }
                 }
-                if (IMAGE) img[c] = (unsigned short)h;
-                nonzero |= h;
+#pragma unroll
+                for (int k = 0; k < SIDES; ++k) {
+                    if (IMAGE) img[k][c] = (unsigned short)h[k];
+                    nonzero |= h[k];
+                }
             }
         }
-        const bool walk = MODE == kScore || p.syn != nullptr;
-        if (!walk) continue;                      // (the same for every thread of the grid)
+        if (!walk) continue;
         __syncthreads();
-        auto bit_of = [&](int j) -> unsigned {
+        // bit j of side k, and row r of a CSR over side k's bits (k is a constant at every call)
+        auto bit_of = [&](int k, int j) -> unsigned {
             if (IMAGE) {
                 const int q = j + shift;
-                return ((unsigned)img[q >> 4] >> (q & 15)) & 1u;
+                return ((unsigned)img[k][q >> 4] >> (q & 15)) & 1u;
             }
-            if (MODE == kScore) return (unsigned)((ecol[j] ^ gcol[j]) & 1u);
-            return (unsigned)(ecol[j] & 1u);
+            if (MODE == kScore) return (unsigned)((ecol[k][j] ^ gcol[k][j]) & 1u);
+            return (unsigned)(ecol[k][j] & 1u);
         };
-        auto parity_of = [&](const int *row_ptr, const int *csr_col, int r) -> unsigned {
+        auto parity_of = [&](int k, const int *row_ptr, const int *csr_col, int r) -> unsigned {
             unsigned par = 0;
-            for (int e = row_ptr[r], e1 = row_ptr[r + 1]; e < e1; ++e) par ^= bit_of(csr_col[e]);
+            for (int e = row_ptr[r], e1 = row_ptr[r + 1]; e < e1; ++e) par ^= bit_of(k, csr_col[e]);
             return par;
         };
         if (MODE != kScore) {
-            if (live) {
-                uint8_t *scol = p.syn + col * (long long)s;
-                const int cpl = p.cpl, sshift = (int)((uintptr_t)scol & (uintptr_t)(cpl - 1));
+#pragma unroll
+            for (int k = 0; k < SIDES; ++k) {
+                const TrialSide &sd = p.side[k];
+                if (!live || (SIDES > 1 && !sd.syn)) continue;   // (one side: walk says that syn is there)
+                const int s = sd.rows, cpl = sd.cpl;
+                uint8_t *scol = sd.syn + col * (long long)s;
+                const int sshift = (int)((uintptr_t)scol & (uintptr_t)(cpl - 1));
                 const int nwords = (sshift + s + cpl - 1) / cpl;
                 for (int c = gl; c < nwords; c += GT) {
                     const int r0 = c * cpl - sshift;
                     unsigned w = 0;
                     for (int b = 0; b < cpl; ++b)
-                        if (r0 + b >= 0 && r0 + b < s) w |= parity_of(p.row_ptr, p.csr_col, r0 + b) << (8 * b);
+                        if (r0 + b >= 0 && r0 + b < s) w |= parity_of(k, sd.row_ptr, sd.csr_col, r0 + b) << (8 * b);
                     if (cpl == 4 && r0 >= 0 && r0 + 4 <= s) {
                         *reinterpret_cast<unsigned *>(scol + r0) = w;
                     } else {
@@ -190,12 +267,18 @@ __global__ __launch_bounds__(kThreads) void trial_kernel(TrialParams p)
                 }
             }
         } else {
-            unsigned bad = 0, badl = 0;
+            unsigned bad = 0, badl[SIDES] = {};
             if (live) {
-                for (int r = gl; r < s; r += GT) bad |= parity_of(p.row_ptr, p.csr_col, r);
-                for (int r = gl; r < p.nl; r += GT) badl |= parity_of(p.lrow_ptr, p.lcsr_col, r);
+#pragma unroll
+                for (int k = 0; k < SIDES; ++k)
+                    for (int r = gl; r < p.side[k].rows; r += GT) bad |= parity_of(k, p.side[k].row_ptr, p.side[k].csr_col, r);
+#pragma unroll
+                for (int k = 0; k < SIDES; ++k)
+                    for (int r = gl; r < p.side[k].nl; r += GT) badl[k] |= parity_of(k, p.side[k].lrow_ptr, p.side[k].lcsr_col, r);
             }
-            const unsigned f = (__any((int)nonzero) ? 1u : 0u) | (__any((int)bad) ? 2u : 0u) | (__any((int)badl) ? 4u : 0u);
+            unsigned f = (__any((int)nonzero) ? 1u : 0u) | (__any((int)bad) ? 2u : 0u);
+#pragma unroll
+            for (int k = 0; k < SIDES; ++k) f |= __any((int)badl[k]) ? 4u << k : 0u;
             if ((threadIdx.x & 63) == 0 && f) atomicOr(&colflags[slot], f);
             __syncthreads();
             if (gl == 0 && live) {
@@ -204,7 +287,10 @@ __global__ __launch_bounds__(kThreads) void trial_kernel(TrialParams p)
                 if (p.flags) p.flags[col] = (uint8_t)cf;
                 if (cf & 1u) atomicAdd(&running[0], 1u);
                 if (cf & 2u) atomicAdd(&running[1], 1u);
-                if (cf & 4u) atomicAdd(&running[2], 1u);
+                if (cf & (((1u << SIDES) - 1u) << 2)) atomicAdd(&running[2], 1u);
+#pragma unroll
+                for (int k = 0; k < NRUN - 3; ++k)
+                    if (cf & (4u << k)) atomicAdd(&running[3 + k], 1u);
             }
         }
         __syncthreads();
@@ -213,8 +299,8 @@ __global__ __launch_bounds__(kThreads) void trial_kernel(TrialParams p)
         __syncthreads();
         // running[] is 32-bit: a call takes at most 2^36 columns and its grid has 32 workgroups or more once there are 32
         // column groups (ldpc_trials.hip), so a workgroup sees at most 2^31 + 4 columns
-        if (threadIdx.x < 3 && running[threadIdx.x]) atomicAdd(&p.counts[1 + threadIdx.x], (tu64)running[threadIdx.x]);
-        if (threadIdx.x == 3 && blockIdx.x == 0) atomicAdd(&p.counts[0], (tu64)p.batch);
+        if (threadIdx.x < NRUN && running[threadIdx.x]) atomicAdd(&p.counts[1 + threadIdx.x], (tu64)running[threadIdx.x]);
+        if (threadIdx.x == NRUN && blockIdx.x == 0) atomicAdd(&p.counts[0], (tu64)p.batch);
     }
 }
 

@@ -125,6 +125,26 @@ def test_x_only_noise_equals_the_one_matrix_sampler(ldpc, gpu):
     t.close(); one.close()
 
 
+CROSS = [("bb72", 1027), ("hgp", 5)]   # the one-matrix cross-checks: one wave per column, a workgroup per column
+
+
+@pytest.mark.parametrize("name,B", CROSS)
+def test_z_only_noise_equals_the_one_matrix_sampler_on_hx(ldpc, gpu, name, B):
+    """px = py = 0: ez is Trials(Hx).sample's errors at per = pz and the same seed, sx its syndromes, ex is zero."""
+    Hx = _code(name)[0]
+    for variant in (1, 2):
+        t, one = _handle(ldpc, name, variant), ldpc.Trials(Hx, kernel_variant=variant)
+        assert t.kernel == one.kernel == variant
+        for pz, seed, c0 in ((0.02, 5, 0), (0.5, 0xDEADBEEFCAFE1234, BIG0)):
+            ex, ez, sx, _ = t.sample(B, (0.0, 0.0, pz), seed=seed, column0=c0)
+            e, s = one.sample(B, pz, seed=seed, column0=c0)
+            assert bool(e.any())
+            _same(_np(ez), _np(e), f"{name} tier {variant} pz {pz} ez vs Trials.sample")
+            _same(_np(sx), _np(s), f"{name} tier {variant} pz {pz} sx vs Trials.sample")
+            assert not bool(ex.any())
+        t.close(); one.close()
+
+
 def test_a_call_split_at_an_odd_column_equals_the_single_call(ldpc, gpu):
     import torch
 
@@ -306,6 +326,60 @@ def test_score_at_the_batches_of_the_sample_test(ldpc, gpu, name):
             _same(_np(counts), wc, f"{name} tier {t.kernel} batch {B} counts")
     for t in handles:
         t.close()
+
+
+@pytest.mark.parametrize("name,B", CROSS)
+def test_score_with_one_side_clean_equals_the_one_matrix_score(ldpc, gpu, name, B):
+    """gz = ez: the joint score is Trials(Hz, Lz).score(gx, ex) (bits 0-2, counts 0, 1, 2, 4; bit 3 never set).  The mirror,
+    gx = ex: bits 0 and 1 are those of Trials(Hx, Lx).score(gz, ez), bit 3 is its bit 2 and bit 2 is never set.  On BB-72
+    the first runs once more with gx one byte off a 16-byte boundary and ex on one."""
+    import torch
+
+    Hx, Hz, Lx, Lz = _code(name)
+    n = Hx.shape[1]
+    ex, ez = cm.sample(n, B, 0.06, seed=31, column0=BIG0)
+    rng = np.random.default_rng(32)
+
+    def guesses(e, stabilizers, logicals):
+        """Column i % 5: 0 equal; 1 one flip; 2 ^ a logical row; 3 ^ a stabilizer; 4 a flip and a logical row."""
+        g = e.copy()
+        for i in range(B):
+            if i % 5 in (1, 4):
+                g[i, int(rng.integers(0, n))] ^= 1
+            if i % 5 in (2, 4):
+                g[i] ^= logicals[int(rng.integers(0, logicals.shape[0]))]
+            if i % 5 == 3:
+                g[i] ^= np.asarray(stabilizers[int(rng.integers(0, stabilizers.shape[0]))].todense()).astype(np.uint8)[0]
+        return g
+
+    gx, gz = guesses(ex, sp.csr_matrix(Hx), Lx), guesses(ez, sp.csr_matrix(Hz), Lz)
+    d_ex, d_ez, d_gx, d_gz = (torch.from_numpy(a).cuda() for a in (ex, ez, gx, gz))
+    gx_off = _offset_view(torch, (B, n), 1, src=d_gx)[1]
+    assert d_ex.data_ptr() % 16 == 0 and gx_off.data_ptr() % 16 == 1
+    for variant in (1, 2):
+        t = _handle(ldpc, name, variant)
+        one_z, one_x = ldpc.Trials(Hz, logicals=Lz, kernel_variant=variant), ldpc.Trials(Hx, logicals=Lx, kernel_variant=variant)
+        assert t.kernel == one_z.kernel == one_x.kernel == variant
+        what = f"{name} tier {variant}"
+        wf, wc = one_z.score(d_gx, d_ex)
+        wf, wc = _np(wf), _np(wc)
+        assert wc[0] == B and all(wc[1:] > 0)                       # every bit of the one-matrix score occurs
+        for g in (d_gx, gx_off) if name == "bb72" else (d_gx,):
+            flags, counts = t.score(g, d_ez, d_ex, d_ez)
+            _same(_np(flags), wf, f"{what} gz = ez, gx at {g.data_ptr() % 16} mod 16: flags vs Trials(Hz, Lz).score")
+            _same(_np(counts)[[0, 1, 2, 4]], wc, f"{what} gz = ez: counts 0, 1, 2, 4 vs the one-matrix four")
+            assert _np(counts)[5] == 0
+        wf, wc = one_x.score(d_gz, d_ez)
+        wf, wc = _np(wf), _np(wc)
+        assert wc[0] == B and all(wc[1:] > 0)
+        flags, counts = t.score(d_ex, d_gz, d_ex, d_ez)
+        flags = _np(flags)
+        _same(flags & 3, wf & 3, f"{what} gx = ex: bits 0 and 1 vs Trials(Hx, Lx).score")
+        _same((flags >> 3) & 1, (wf >> 2) & 1, f"{what} gx = ex: bit 3 vs the one-matrix bit 2")
+        assert not (flags & 4).any()
+        _same(_np(counts)[[0, 1, 2, 5]], wc, f"{what} gx = ex: counts 0, 1, 2, 5 vs the one-matrix four")
+        for h in (t, one_z, one_x):
+            h.close()
 
 
 def test_host_forms_equal_the_device_forms(ldpc, gpu):
