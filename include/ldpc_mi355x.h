@@ -653,6 +653,77 @@ ldpc_status ldpc_css_trials_sample(ldpc_css_trials *t, int64_t batch, int64_t co
 ldpc_status ldpc_css_trials_score(ldpc_css_trials *t, int64_t batch, const uint8_t *gx, const uint8_t *gz,
                                   const uint8_t *ex, const uint8_t *ez, uint8_t *flags, int64_t counts[6]);
 
+/* ------------------------------------------------------------------------
+ * Normalised min-sum decoder with one channel LLR per bit.  Not a decoder of the reference: it is what the uniform
+ * `per` of every other create cannot express (biased noise, the two sides of a CSS code, soft input, detector-error-model
+ * columns), and it has no division and no transcendental function, so THE RULE below has one legal outcome in IEEE
+ * binary32 and a numpy model equals the device in every bit, LLRs included.
+ *
+ * Inputs.  H as a zero-based CSC pattern with the checks of ldpc_bp_create.  channel_llr[n] binary32 =
+ * log(P(bit = 0) / P(bit = 1)), each finite; the library calls no log or exp, the caller computes the array.
+ * alpha binary32 in (0, 1] (default 0.75), clip binary32 finite and > 0 (default 1.0e6f), max_iters >= 0.  A syndrome
+ * entry that is not 0 counts as 1.
+ *
+ * THE RULE.  All arithmetic is binary32, every operation rounded once (no fused multiply-add), subnormals kept.
+ * State per syndrome: L[j], initially channel_llr[j]; the check-to-bit messages c[i][j], initially +0.
+ * For t = 1 .. max_iters:
+ *   1. Check sweep.  For check i with its bits j_0 < j_1 < ... (ascending):
+ *        b_k = min(max(L[j_k] - c[i][j_k], -clip), clip);   neg_k = (b_k < 0);   mag_k = |b_k|
+ *        m1 = m2 = clip, a = none; for k ascending: if mag_k < m1 { m2 = m1; m1 = mag_k; a = k } else if mag_k < m2 { m2 = mag_k }
+ *        par = syndrome_i XOR neg_0 XOR neg_1 XOR ...
+ *        new c[i][j_k]: the value alpha * (k == a ? m2 : m1), with its sign bit set iff par XOR neg_k (a zero product
+ *        with the sign set is -0).  All b_k are formed from the old messages before any is replaced.  A check with no
+ *        bits sends nothing.
+ *   2. Bit sweep.  L[j] = channel_llr[j] + c[i_0][j] + c[i_1][j] + ..., added one after another from the left in ascending
+ *      check order; err[j] = (L[j] <= 0).
+ *   3. Stop test.  If H * err == syndrome (an empty check is matched only by a 0 entry): converged = 1, iters = t, stop;
+ *      L and err stay as they are.
+ * Not stopped after max_iters: converged = 0, iters = max_iters.  With finite inputs no NaN or infinity can arise.
+ * The form "L - c" (total minus own message) is part of the rule: it lets a kernel keep L and, per check, only
+ * (alpha m1, alpha m2, a, the sign bits).
+ *
+ * Outputs.  errors [batch][n] uint8; converged [batch] uint8; llr [batch][n] DOUBLE (may be NULL): L widened exactly,
+ * so it feeds ldpc_osd_postprocess_batch[_device] as it is; iters [batch] int32 (may be NULL).  max_iters = 0: zeros,
+ * converged = 0, llr = 0, iters = 0.  batch = 0: LDPC_OK, nothing touched.
+ *
+ * ldpc_minsum_kernel: 1 = on-chip (L and the check records of the S <= 64 syndromes a workgroup holds live in LDS for
+ * the whole decode; needs (4 (n + record words) + s) bytes <= 159 KiB for one syndrome, a record being 4 words for a
+ * check of degree <= 32, 5 up to 64, one word per edge beyond); 2 = unlimited (tiles of 64 syndromes in a workspace the
+ * handle owns, sized by the resident workgroups; any H with nnz < 2^28); 0 for NULL.  options->kernel_variant 0 = by
+ * size, 1 / 2 force a tier (1 where the state does not fit: LDPC_ERR_UNSUPPORTED).
+ *
+ * ldpc_minsum_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL or non-finite channel_llr,
+ * alpha outside (0, 1], clip not in (0, inf), a kernel_variant outside 0..2 and a pattern ldpc_bp_create rejects;
+ * without a device LDPC_ERR_NO_DEVICE.  The decode entries reject a NULL handle, a negative batch and a NULL required
+ * pointer the same way.  ldpc_minsum_decode_batch takes HOST buffers and is synchronous (its wait is bounded by
+ * ldpc_set_wait_limit_ms); ldpc_minsum_decode_batch_device takes DEVICE pointers and is asynchronous on `stream`; calls
+ * on one handle run in call order whatever streams they are given.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_minsum_decoder ldpc_minsum_decoder;
+
+/* Optional; pass NULL to ldpc_minsum_create for defaults.  A zeroed struct means defaults too, except `device` (0 is
+ * device 0; -1 = the current one): alpha = 0 / clip = 0 select 0.75 / 1.0e6f. */
+typedef struct ldpc_minsum_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    float alpha;             /* normalisation factor in (0, 1]; 0 = default 0.75 */
+    float clip;              /* clamp of the bit-to-check values, finite, > 0; 0 = default 1.0e6f */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_minsum_kernel */
+    int32_t reserved[12];
+} ldpc_minsum_options;
+
+ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
+                               const float *channel_llr, int64_t max_iters, const ldpc_minsum_options *options,
+                               ldpc_minsum_decoder **out);
+ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *dec);
+int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *dec);
+ldpc_status ldpc_minsum_decode_batch(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *syndromes, uint8_t *errors,
+                                     uint8_t *converged, double *llr, int32_t *iters);
+ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *d_syndromes,
+                                            uint8_t *d_errors, uint8_t *d_converged, double *d_llr, int32_t *d_iters,
+                                            void *stream);
+
 /* Diagnostics: 100 MHz ticks spent in {check sweep, variable sweep, convergence test}
  * of that call, summed over workgroups (one sampling wave each). */
 ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *dec, int32_t calls_back, uint64_t ticks[3]);

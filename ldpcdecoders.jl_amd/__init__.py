@@ -26,6 +26,7 @@ from .decoder import (  # noqa: F401
 from .osd import BeliefPropagationOSDDecoder, OSDPostProcessor  # noqa: F401,E402
 from .bpots import BPOTSDecoder  # noqa: F401,E402
 from .bitflip import BitFlipDecoder, BitFlipScratchSpace  # noqa: F401,E402
+from .minsum import MinSumDecoder, MinSumScratchSpace  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 from .css_trials import CSSTrialResult, CSSTrials, run_css_trials  # noqa: F401,E402
 
@@ -34,6 +35,7 @@ __all__ = [
     "decode_", "batchdecode_", "reset_", "AbstractDecoder", "BeliefPropagationDecoder",
     "BeliefPropagationScratchSpace", "parity_check_matrix", "save_pcm", "load_pcm",
     "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
+    "MinSumDecoder", "MinSumScratchSpace",
     "Trials", "TrialResult", "run_trials",
     "CSSTrials", "CSSTrialResult", "run_css_trials",
 ]

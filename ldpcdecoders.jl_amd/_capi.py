@@ -71,6 +71,11 @@ EXPORTED_SYMBOLS = (
     "ldpc_bitflip_kernel",
     "ldpc_bitflip_decode_batch",
     "ldpc_bitflip_decode_batch_device",
+    "ldpc_minsum_create",
+    "ldpc_minsum_destroy",
+    "ldpc_minsum_kernel",
+    "ldpc_minsum_decode_batch",
+    "ldpc_minsum_decode_batch_device",
     "ldpc_trials_create",
     "ldpc_trials_destroy",
     "ldpc_trials_kernel",
@@ -143,6 +148,14 @@ class BitFlipOptions(ctypes.Structure):
     ]
 
 
+class MinSumOptions(ctypes.Structure):
+    """ldpc_minsum_options: alpha = 0 / clip = 0 select the defaults (0.75, 1e6)."""
+    _fields_ = [
+        ("device", ctypes.c_int32), ("alpha", ctypes.c_float), ("clip", ctypes.c_float),
+        ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 12),
+    ]
+
+
 class TrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
@@ -159,7 +172,7 @@ class CSSTrialsOptions(ctypes.Structure):
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -289,6 +302,16 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_bitflip_decode_batch.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp]
     L.ldpc_bitflip_decode_batch_device.restype = i32
     L.ldpc_bitflip_decode_batch_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_minsum_create.restype = i32
+    L.ldpc_minsum_create.argtypes = [i64, i64, i64, vp, vp, vp, i64, ctypes.POINTER(MinSumOptions), ctypes.POINTER(vp)]
+    L.ldpc_minsum_destroy.restype = i32
+    L.ldpc_minsum_destroy.argtypes = [vp]
+    L.ldpc_minsum_kernel.restype = i32
+    L.ldpc_minsum_kernel.argtypes = [vp]
+    L.ldpc_minsum_decode_batch.restype = i32
+    L.ldpc_minsum_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    L.ldpc_minsum_decode_batch_device.restype = i32
+    L.ldpc_minsum_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
     u64 = ctypes.c_uint64
     L.ldpc_trials_create.restype = i32
     L.ldpc_trials_create.argtypes = [i64, i64, i64, vp, vp, i64, i64, vp, vp, ctypes.POINTER(TrialsOptions), ctypes.POINTER(vp)]

@@ -1,0 +1,219 @@
+// ldpc_minsum.hip -- host side of the normalised min-sum decoder with per-bit channel LLRs: the ldpc_minsum_* entry
+// points of include/ldpc_mi355x.h (the rule is stated there).  Device code: minsum_kernels.hpp.  Tiers (ldpc_minsum_kernel):
+//   1  on-chip: the state of the S syndromes a workgroup holds lives in LDS for the whole decode (S = 64, 32, ... 1:
+//      the largest that leaves room for two workgroups a CU, else the largest that fits one)
+//   2  unlimited: tiles of 64 syndromes, the state in a global workspace, one slot per workgroup of a persistent grid
+// No CPU path.
+#include "../../include/ldpc_mi355x.h"
+#include "minsum_kernels.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+#include <vector>
+
+using namespace ldpc;
+
+#include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
+using ldpc_detail::set_error;
+
+static constexpr size_t kMsLdsTwo = (size_t)79 * 1024, kMsLdsOne = (size_t)159 * 1024;   // two / one workgroup a CU
+static constexpr int kMsLdsWaves = 8, kMsGlobalWaves = 16;   // (16 waves: 2.2x the speed of 4 at n = 16384, the sweeps are latency-bound)
+static constexpr size_t kMsWorkspaceCap = (size_t)6 << 30;   // the unlimited tier's grid shrinks to keep its slots below this
+static constexpr float kMsAlphaDefault = 0.75f, kMsClipDefault = 1.0e6f;
+
+struct ldpc_minsum_decoder {
+    int64_t s = 0, n = 0, nnz = 0, max_iters = 0;
+    float alpha = kMsAlphaDefault, clip = kMsClipDefault;
+    int device = 0, num_cus = 0, tier = 0, S = 64, shift = 6, rec_words = 0;
+    int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *edge_rec = nullptr, *edge_pos = nullptr;
+    float *prior = nullptr;
+    void *stage = nullptr;      // device staging for the host-pointer entry
+    size_t stage_cap = 0;
+    unsigned char *ws = nullptr;   // tier 2: [grid][slot]
+    size_t ws_cap = 0;
+    bool kernel_ready = false;
+    int per_cu = 1;
+    ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (they share the workspace)
+    ~ldpc_minsum_decoder()
+    {
+        if (ldpc_detail::device_stalled(device)) return;   // (host_wait.hpp: nothing a stalled device may still use is freed)
+        void *all[] = {row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, prior, stage, ws};
+        for (void *q : all)
+            if (q) (void)hipFree(q);
+        calls.destroy();
+    }
+};
+
+typedef void (*ms_kernel_t)(MsParams);
+static ms_kernel_t ms_kernel_of(int tier) { return tier == 1 ? minsum_kernel<kMsLdsWaves, false> : minsum_kernel<kMsGlobalWaves, true>; }
+
+// syndromes per workgroup of the on-chip tier: the largest power of two <= 64 whose state fits `budget`; 0 = none
+static int ms_lds_tile(int64_t s, int64_t n, int64_t rec_words, size_t budget)
+{
+    for (int S = 64; S >= 1; S >>= 1)
+        if (ms_state_bytes(s, n, rec_words, S) <= budget) return S;
+    return 0;
+}
+
+extern "C" {
+
+ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
+                               const float *channel_llr, int64_t max_iters, const ldpc_minsum_options *options,
+                               ldpc_minsum_decoder **out)
+{
+    if (!out) return set_error(LDPC_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, max_iters);
+    if (st != LDPC_OK) return st;
+    if (n > 0 && !channel_llr) return set_error(LDPC_ERR_INVALID_ARGUMENT, "channel_llr is NULL");
+    const float alpha = options && options->alpha != 0.0f ? options->alpha : kMsAlphaDefault;   // a zeroed struct: defaults
+    const float clip = options && options->clip != 0.0f ? options->clip : kMsClipDefault;
+    const int variant = options ? options->kernel_variant : 0;
+    int device = options ? options->device : -1;
+    if (!(alpha > 0.0f && alpha <= 1.0f)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "alpha must lie in (0, 1]");
+    if (!(clip > 0.0f) || std::isinf(clip)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "clip must be finite and > 0");
+    if (variant < 0 || variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
+    for (int64_t j = 0; j < n; ++j)
+        if (!std::isfinite(channel_llr[j]))
+            return set_error(LDPC_ERR_INVALID_ARGUMENT, "channel_llr[" + std::to_string(j) + "] is not finite");
+    if ((st = ldpc_detail::check_csc_pattern(s, n, nnz, colptr, rowval)) != LDPC_OK) return st;
+    hipDeviceProp_t prop;
+    if ((st = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (this library has no CPU fallback)")) != LDPC_OK)
+        return st;
+    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
+        return set_error(LDPC_ERR_UNSUPPORTED, "min-sum kernels: graph too large for 32-bit edge indexing");
+
+    ldpc_minsum_decoder *d = new (std::nothrow) ldpc_minsum_decoder();
+    if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
+    d->s = s; d->n = n; d->nnz = nnz; d->max_iters = max_iters; d->alpha = alpha; d->clip = clip;
+    d->device = device; d->num_cus = prop.multiProcessorCount;
+    // CSR (checks -> bits, ascending) next to the caller's CSC; a record per check; per CSC edge its record and position
+    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
+    std::vector<int> rec_off((size_t)std::max<int64_t>(s, 1), 0), edge_rec(g.csc_row.size(), 0), edge_pos(g.csc_row.size(), 0);
+    int64_t words = 0;
+    for (int64_t i = 0; i < s; ++i) {
+        rec_off[(size_t)i] = (int)words;
+        words += ms_record_words(g.row_ptr[(size_t)i + 1] - g.row_ptr[(size_t)i]);   // <= 4 nnz + ... < 2^31
+    }
+    for (int64_t e = 0; e < nnz; ++e) {
+        const int i = g.csc_row[(size_t)e], k = g.csc2csr[(size_t)e] - g.row_ptr[(size_t)i];
+        edge_rec[(size_t)e] = rec_off[(size_t)i];
+        edge_pos[(size_t)e] = g.row_ptr[(size_t)i + 1] - g.row_ptr[(size_t)i] > 64 ? (k | kMsPosEdge) : k;
+    }
+    d->rec_words = (int)words;
+    int S = ms_lds_tile(s, n, words, kMsLdsTwo);
+    if (!S) S = ms_lds_tile(s, n, words, kMsLdsOne);
+    if (variant == 1 && !S) {
+        delete d;
+        return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
+    }
+    d->tier = variant ? variant : S ? 1 : 2;
+    d->S = d->tier == 1 ? S : 64;
+    for (d->shift = 0; (1 << d->shift) < d->S; d->shift++) {}
+    using ldpc_detail::upload_ints;
+    bool ok = upload_ints(&d->row_ptr, g.row_ptr) && upload_ints(&d->csr_col, g.csr_col) && upload_ints(&d->rec_off, rec_off) &&
+              upload_ints(&d->col_ptr, g.col_ptr) && upload_ints(&d->edge_rec, edge_rec) && upload_ints(&d->edge_pos, edge_pos) &&
+              hipMalloc((void **)&d->prior, (size_t)std::max<int64_t>(n, 1) * sizeof(float)) == hipSuccess &&
+              (n == 0 || hipMemcpy(d->prior, channel_llr, (size_t)n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) &&
+              d->calls.create() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        delete d;
+        return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the Tanner graph failed");
+    }
+    *out = d;
+    return LDPC_OK;
+}
+
+int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *d) { return d ? d->tier : 0; }
+
+ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *d)
+{
+    if (!d) return LDPC_OK;
+    (void)hipSetDevice(d->device);
+    const ldpc_status st = ldpc_detail::wait_device(d->device, "ldpc_minsum_destroy (device synchronise)");
+    delete d;
+    return st;
+}
+
+ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *d_syn, uint8_t *d_err,
+                                            uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)
+{
+    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
+    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (batch == 0) return LDPC_OK;
+    if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
+    if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
+    hipStream_t stream = (hipStream_t)stream_v;
+    LDPC_HIP_TRY(hipSetDevice(d->device));
+    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
+    ldpc_status st = d->calls.enter(stream);
+    if (st != LDPC_OK) return st;
+    if (d->max_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
+        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
+        if (d_llr && d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * d->n * sizeof(double), stream));
+        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
+    } else {
+        const bool global = d->tier == 2;
+        const int threads = (global ? kMsGlobalWaves : kMsLdsWaves) * 64;
+        const size_t state = ms_state_bytes(d->s, d->n, d->rec_words, d->S);
+        const size_t lds = global ? 0 : state;
+        ms_kernel_t k = ms_kernel_of(d->tier);
+        if (!d->kernel_ready) {
+            // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
+            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMsLdsOne));
+            d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, threads, lds);
+            d->kernel_ready = true;
+        }
+        const int64_t tiles = (batch + d->S - 1) >> d->shift;
+        int64_t grid = std::min<int64_t>(tiles, (int64_t)d->per_cu * d->num_cus);
+        if (global) {
+            grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMsWorkspaceCap / state)));
+            st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
+                                                 "min-sum workspace regrow (device synchronise before the free)");
+            if (st != LDPC_OK) return st;
+        }
+        MsParams p{};
+        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = d->S; p.shift = d->shift;
+        p.batch = batch; p.alpha = d->alpha; p.clip = d->clip;
+        p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
+        p.prior = d->prior; p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
+        p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
+        p.ws = d->ws; p.slot_bytes = (long long)state;
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
+        LDPC_HIP_TRY(hipGetLastError());
+    }
+    return d->calls.leave(stream);
+}
+
+ldpc_status ldpc_minsum_decode_batch(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *syn, uint8_t *err, uint8_t *conv,
+                                     double *llr, int32_t *iters)
+{
+    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
+    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (batch == 0) return LDPC_OK;
+    if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
+    LDPC_HIP_TRY(hipSetDevice(d->device));
+    const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
+    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][LLRs]
+    image.take(B * s);
+    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4);
+    const size_t o_llr = image.take(llr ? B * n * sizeof(double) : 0), total = image.at;
+    ldpc_status st = ldpc_detail::grow_device_buffer(&d->stage, &d->stage_cap, total, d->device, "min-sum staging regrow (device synchronise before the free)");
+    if (st != LDPC_OK) return st;
+    char *dp = (char *)d->stage;
+    if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
+    st = ldpc_minsum_decode_batch_device(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
+                                         llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it), nullptr);
+    if (st != LDPC_OK) return st;
+    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
+    LDPC_HIP_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
+    if (iters) LDPC_HIP_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
+    if (llr && n > 0) LDPC_HIP_TRY(hipMemcpyAsync(llr, dp + o_llr, B * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    return ldpc_detail::wait_stream(nullptr, d->device, "ldpc_minsum_decode_batch (stream synchronise)");
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@ import LDPCDecoders
 import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 
 export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder, MI355XBitFlipDecoder
+export MI355XMinSumDecoder
 export Trials, sample!, score!
 export CSSTrials
 
@@ -411,6 +412,96 @@ function batchdecode!(d::MI355XBitFlipDecoder, syndromes::AbstractMatrix, errors
     return errors, converged
 end
 batchdecode!(d::MI355XBitFlipDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix) =
+    batchdecode!(d, syndromes, errors, Vector{Bool}(undef, size(syndromes, 2)))
+
+# ---------------------------------------------------------------------------------------------
+# Normalised min-sum with one channel LLR per bit over ldpc_minsum_* (not a decoder of the reference; the rule is stated
+# in include/ldpc_mi355x.h).  The library computes no logarithm: the Float32 prior LLRs log((1 - p) / p) are formed here.
+# These symbols were added without a change of the ABI version; look them up with Libdl.dlsym as for the trials entries.
+# ---------------------------------------------------------------------------------------------
+mutable struct MI355XMinSumDecoder <: AbstractDecoder
+    per::Union{Float64,Nothing}; max_iters::Int; s::Int; n::Int
+    sparse_H::SparseMatrixCSC{Bool,Int}
+    channel_llr::Vector{Float32}
+    err::Vector{Float64}
+    log_probabs::Vector{Float64}
+    handle::Ptr{Cvoid}
+end
+
+"ldpc_minsum_options: int32 device, float alpha, float clip, int32 kernel_variant, int32 reserved[12] (64 bytes)"
+function minsum_options(device::Integer, alpha::Real, clip::Real, kernel_variant::Integer)
+    opts = zeros(Int32, 16)
+    opts[1] = Int32(device); opts[4] = Int32(kernel_variant)
+    opts[2] = reinterpret(Int32, Float32(alpha)); opts[3] = reinterpret(Int32, Float32(clip))
+    return opts
+end
+
+minsum_llr(p) = Float32(log((1.0 - Float64(p)) / Float64(p)))
+
+"""
+    MI355XMinSumDecoder(H, per, max_iters; alpha=0.75, clip=1e6, device=-1, kernel_variant=0)
+    MI355XMinSumDecoder(H, max_iters; channel_probs=..., ...)   or   channel_llr=...
+
+One prior per bit: a uniform `per`, error probabilities strictly inside (0, 1), or finite LLRs log(P(0) / P(1)).
+"""
+function MI355XMinSumDecoder(H, per::Union{Float64,Nothing}, max_iters::Int; channel_probs=nothing, channel_llr=nothing,
+                             alpha::Real=0.75, clip::Real=1e6, device::Integer=-1, kernel_variant::Integer=0)
+    s, n = size(H)
+    count(!isnothing, (per, channel_probs, channel_llr)) == 1 ||
+        throw(ArgumentError("give exactly one of per, channel_probs and channel_llr"))
+    probs = per !== nothing ? fill(per, n) : channel_probs
+    probs === nothing || all(p -> 0 < p < 1, probs) || throw(DomainError(probs, "probabilities must lie strictly inside (0, 1)"))
+    llr = probs !== nothing ? Float32[minsum_llr(p) for p in probs] : Vector{Float32}(channel_llr)
+    length(llr) == n || throw(DimensionMismatch("one prior per bit"))
+    (Float32(alpha) == 0 || Float32(clip) == 0) && throw(ArgumentError("alpha and clip must not be zero"))   # (0 = default in the C struct)
+    sp = dropzeros(SparseMatrixCSC{Bool,Int}(sparse(H)))
+    colptr = Int64.(sp.colptr .- 1); rowval = Int64.(rowvals(sp) .- 1)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:ldpc_minsum_create, libldpc), Cint,
+                (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float32}, Int64, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                s, n, length(rowval), colptr, rowval, llr, max_iters, minsum_options(device, alpha, clip, kernel_variant), h))
+    d = MI355XMinSumDecoder(per, max_iters, s, n, sp, llr, zeros(n), zeros(n), h[])
+    finalizer(d) do x
+        x.handle != C_NULL && ccall((:ldpc_minsum_destroy, libldpc), Cint, (Ptr{Cvoid},), x.handle)
+        x.handle = C_NULL
+    end
+    return d
+end
+MI355XMinSumDecoder(H, max_iters::Int; kwargs...) = MI355XMinSumDecoder(H, nothing, max_iters; kwargs...)
+
+reset!(d::MI355XMinSumDecoder) = d      # the device state is reset inside every decode call
+
+minsum_call(handle, B, syn, err, conv, llr) =
+    check(ccall((:ldpc_minsum_decode_batch, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                handle, B, syn, err, conv, llr, C_NULL))
+
+function decode!(d::MI355XMinSumDecoder, syndrome::AbstractVector)
+    length(syndrome) == d.s || throw(BoundsError(syndrome, d.s))
+    syn = UInt8[syndrome_byte(x) for x in syndrome]
+    err = Vector{UInt8}(undef, d.n); conv = Vector{UInt8}(undef, 1)
+    minsum_call(d.handle, 1, syn, err, conv, d.log_probabs)
+    d.err .= err
+    return d.err, conv[1] != 0
+end
+
+function batchdecode!(d::MI355XMinSumDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix,
+                      converged::AbstractVector{Bool})                                 # one device call
+    @assert size(syndromes, 2) == size(errors, 2)
+    @assert size(syndromes, 2) == length(converged)
+    size(syndromes, 1) == d.s && size(errors, 1) == d.n || throw(DimensionMismatch("syndromes / errors rows"))
+    B = size(syndromes, 2)
+    B == 0 && return errors, converged
+    direct = errors isa Matrix{UInt8} || errors isa Matrix{Bool}
+    err = direct ? reinterpret(UInt8, errors) : Matrix{UInt8}(undef, d.n, B)
+    conv = Vector{UInt8}(undef, B)
+    minsum_call(d.handle, B, bitflip_image(syndromes), err, conv, C_NULL)
+    direct || (errors .= err)
+    converged .= conv .!= 0
+    d.err .= view(err, :, B)
+    return errors, converged
+end
+batchdecode!(d::MI355XMinSumDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix) =
     batchdecode!(d, syndromes, errors, Vector{Bool}(undef, size(syndromes, 2)))
 
 # ---------------------------------------------------------------------------------------------

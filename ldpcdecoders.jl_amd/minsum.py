@@ -1,0 +1,172 @@
+"""Normalised min-sum decoder with one channel LLR per bit, over the ldpc_minsum_* entry points (the rule is stated in
+include/ldpc_mi355x.h).  Not a decoder of the reference: it takes what the uniform `per` of the other decoders cannot
+express -- biased noise, the two sides of a CSS code, soft input -- and its argument order matches
+`BeliefPropagationDecoder`, so `run_trials`, `run_css_trials` and `BeliefPropagationOSDDecoder(bp_decoder=...)` drive it
+unchanged.  The library computes no logarithm: the prior LLRs are formed here with numpy (float64 `log((1 - p) / p)`,
+rounded once to float32) and `.channel_llr` is the array actually handed over."""
+from __future__ import annotations
+
+import ctypes
+from types import SimpleNamespace
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _capi
+from .decoder import AbstractDecoder, _pattern_of, syndrome_bytes
+
+
+def llr_of_probs(probs) -> np.ndarray:
+    """log(P(0) / P(1)) of error probabilities strictly inside (0, 1), as float32."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.size and not np.all((p > 0.0) & (p < 1.0)):   # (False for NaN as well)
+        raise ValueError("probabilities must lie strictly inside (0, 1)")
+    return np.log((1.0 - p) / p).astype(np.float32)
+
+
+class MinSumScratchSpace:
+    """What a caller of the reference's decoders reads after a decode: `err` and `log_probabs` of the last column."""
+
+    def __init__(self, n: int):
+        self.err = np.zeros(n, dtype=np.float64)
+        self.log_probabs = np.zeros(n, dtype=np.float64)
+
+
+class MinSumDecoder(AbstractDecoder):
+    """`MinSumDecoder(H, per, max_iters)` with a uniform prior, or one of `channel_probs=` (error probability per bit) /
+    `channel_llr=` (log(P(0) / P(1)) per bit, finite) instead of `per`: exactly one of the three.  alpha in (0, 1]
+    scales every check-to-bit message, clip > 0 clamps the bit-to-check values.  kernel_variant: 0 = by size, 1 = on-chip,
+    2 = unlimited (`.kernel` tells which tier the handle takes)."""
+
+    def __init__(self, H, per: Optional[float] = None, max_iters: int = 50, *, channel_llr=None, channel_probs=None,
+                 alpha: float = 0.75, clip: float = 1e6, device: Optional[int] = None, kernel_variant: int = 0):
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
+            raise TypeError("max_iters must be an Int")
+        if (per is not None) + (channel_llr is not None) + (channel_probs is not None) != 1:
+            raise TypeError("give exactly one of per, channel_probs and channel_llr")
+        M = _pattern_of(H)
+        self.s, self.n = int(M.shape[0]), int(M.shape[1])
+        self.sparse_H = M
+        self.per = None
+        if per is not None:
+            if isinstance(per, bool) or not isinstance(per, (float, np.floating)):
+                raise TypeError("per must be a Float64")
+            self.per = float(per)
+            llr = llr_of_probs(np.full(self.n, self.per))
+        elif channel_probs is not None:
+            llr = llr_of_probs(channel_probs)
+        else:
+            llr = np.array(channel_llr, dtype=np.float32)
+        if llr.shape != (self.n,):
+            raise ValueError(f"one prior per bit: expected {self.n} entries, got shape {llr.shape}")
+        self.channel_llr = np.ascontiguousarray(llr, dtype=np.float32)
+        self.max_iters, self.alpha, self.clip = int(max_iters), float(alpha), float(clip)
+        if np.float32(self.alpha) == 0.0 or np.float32(self.clip) == 0.0:
+            # a zero in ldpc_minsum_options selects the default there; here a default is spelled by leaving the keyword
+            # out, so a zero gets the status the library gives every other value outside the range
+            raise _capi.LdpcError(1, "alpha must lie in (0, 1] and clip must be finite and > 0 (got a zero)")
+        self.scratch = MinSumScratchSpace(self.n)
+        if device is None:
+            device = _current_device()   # the current device NOW is the handle's for good (what info() answers)
+        self.device = device
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        opts = _capi.MinSumOptions()
+        opts.device = -1 if device is None else int(device)
+        opts.alpha, opts.clip = self.alpha, self.clip
+        opts.kernel_variant = int(kernel_variant)
+        self._h = ctypes.c_void_p()
+        self._L = _capi.lib_for(None)
+        _capi.check(self._L.ldpc_minsum_create(self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
+                                               self.channel_llr.ctypes.data, self.max_iters, ctypes.byref(opts),
+                                               ctypes.byref(self._h)), self._L)
+
+    @property
+    def kernel(self) -> int:
+        """1 = on-chip (state in LDS), 2 = unlimited (state in a global workspace) (ldpc_minsum_kernel)."""
+        return int(self._L.ldpc_minsum_kernel(self._h))
+
+    def info(self):
+        """`.device`: the GPU the handle lives on; `.kernel`: its tier."""
+        return SimpleNamespace(device=self.device, kernel=self.kernel)
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.ldpc_minsum_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decode_batch_host(self, syn_bs, want_llr: bool = False):
+        """syn [B][s] uint8 -> (errors [B][n] u8, converged [B] u8, llr [B][n] f64 | None, iters [B] i32)."""
+        syn = np.ascontiguousarray(syn_bs, dtype=np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.s:
+            raise AssertionError("syndrome length does not match the number of checks")
+        B = int(syn.shape[0])
+        err = np.empty((B, self.n), dtype=np.uint8)
+        conv = np.empty(B, dtype=np.uint8)
+        llr = np.empty((B, self.n), dtype=np.float64) if want_llr else None
+        its = np.empty(B, dtype=np.int32)
+        _capi.check(self._L.ldpc_minsum_decode_batch(self._h, B, syn.ctypes.data, err.ctypes.data, conv.ctypes.data,
+                                                     llr.ctypes.data if want_llr else None, its.ctypes.data), self._L)
+        return err, conv, llr, its
+
+    def decode_batch_device(self, syn, err, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
+        """HBM-resident batch: torch tensors on the decoder's GPU, syn [B][s] u8, err [B][n] u8, conv [B] u8,
+        llr [B][n] f64 | None, iters [B] i32 | None, all contiguous.  Asynchronous on `stream` (a hipStream_t as int;
+        default = torch's current stream)."""
+        import torch
+
+        B = int(syn.shape[0])
+        for x in (syn, err, conv):
+            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
+        if llr is not None:
+            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
+        if iters is not None:
+            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
+        if stream is None:
+            stream = torch.cuda.current_stream(syn.device).cuda_stream
+        _capi.check(self._L.ldpc_minsum_decode_batch_device(
+            self._h, B, syn.data_ptr(), err.data_ptr(), conv.data_ptr(), llr.data_ptr() if llr is not None else None,
+            iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)), self._L)
+
+    def decode_(self, syndrome) -> Tuple[np.ndarray, bool]:
+        """One syndrome: (scratch.err, converged); scratch.log_probabs holds its LLRs."""
+        syn = syndrome_bytes(np.asarray(syndrome).reshape(-1))
+        if syn.size != self.s:
+            raise IndexError(f"syndrome has length {syn.size}, decoder has {self.s} checks")
+        err, conv, llr, _ = self.decode_batch_host(syn.reshape(1, -1), want_llr=True)
+        self.scratch.err[:] = err[0]
+        self.scratch.log_probabs[:] = llr[0]
+        return self.scratch.err, bool(conv[0])
+
+    def batchdecode_(self, syndromes, errors, success=None):
+        """syndromes s x B, errors n x B (overwritten), success [B]: one device call."""
+        syndromes = np.asarray(syndromes)
+        B = syndromes.shape[1]
+        if success is None:
+            success = np.empty(B, dtype=np.bool_)
+        assert syndromes.shape[1] == errors.shape[1]
+        assert syndromes.shape[1] == len(success)
+        err, conv, llr, _ = self.decode_batch_host(np.ascontiguousarray(syndrome_bytes(syndromes).T), want_llr=True)
+        errors[:, :] = err.T
+        success[:] = conv.astype(np.bool_)
+        if B > 0:
+            self.scratch.err[:] = err[-1]
+            self.scratch.log_probabs[:] = llr[-1]
+        return errors, success
+
+
+def _current_device() -> Optional[int]:
+    """torch's current GPU, or None without one (ldpc_minsum_create then answers LDPC_ERR_NO_DEVICE itself)."""
+    try:
+        import torch
+
+        return int(torch.cuda.current_device()) if torch.cuda.is_available() else None
+    except Exception:
+        return None

@@ -96,12 +96,28 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
     osd="host" (default): the ordered-statistics step in host threads; osd="device": in HIP kernels on the BP
     decoder's GPU (`OSDPostProcessor.postprocess_device`), so that `batchdecode_device` never leaves the device."""
 
-    def __init__(self, H, per: float, max_iters: int, *, osd_order: int = 0, osd: str = "host", **bp_kwargs):
+    def __init__(self, H, per: float = None, max_iters: int = None, *, osd_order: int = 0, osd: str = "host",
+                 bp_decoder=None, **bp_kwargs):
+        """bp_decoder: a decoder object to use as `self.bp_decoder` instead of constructing a BeliefPropagationDecoder --
+        anything with `decode_batch_host(syn, want_llr=True)`, `decode_batch_device(syn, err, conv, llr, iters)`,
+        `.s`, `.n`, `.sparse_H`, `.scratch` and `info().device`, such as a MinSumDecoder.  Its pattern must equal H's
+        (ValueError otherwise); `per` and `max_iters` are then IGNORED (the object carries its own priors and iteration
+        count) and no other decoder keyword may be given."""
         if osd not in ("host", "device"):
             raise ValueError('osd must be "host" or "device"')
-        # (exact LLRs: OSD orders the bits by reliability, :53-55 -- two that differ beyond the 21st bit must not tie)
-        bp_kwargs.setdefault("llr_exact", True)
-        self.bp_decoder = BeliefPropagationDecoder(H, per, max_iters, **bp_kwargs)   # :27
+        if bp_decoder is not None:
+            if bp_kwargs:
+                raise TypeError("decoder keywords (%s) have no meaning next to bp_decoder=" % ", ".join(sorted(bp_kwargs)))
+            M, D = _pattern_of(H), bp_decoder.sparse_H
+            if M.shape != D.shape or not (np.array_equal(M.indptr, D.indptr) and np.array_equal(M.indices, D.indices)):
+                raise ValueError("bp_decoder was built on another parity-check matrix than H")
+            self.bp_decoder = bp_decoder
+        else:
+            if per is None or max_iters is None:
+                raise TypeError("per and max_iters are required without bp_decoder=")
+            # (exact LLRs: OSD orders the bits by reliability, :53-55 -- two that differ beyond the 21st bit must not tie)
+            bp_kwargs.setdefault("llr_exact", True)
+            self.bp_decoder = BeliefPropagationDecoder(H, per, max_iters, **bp_kwargs)   # :27
         self.H = H                                                                    # :21
         self.osd_order = int(osd_order)                                               # :23
         self._osd = OSDPostProcessor(H, osd_order)
