@@ -724,6 +724,91 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *dec, int64_t ba
                                             uint8_t *d_errors, uint8_t *d_converged, double *d_llr, int32_t *d_iters,
                                             void *stream);
 
+/* ------------------------------------------------------------------------
+ * Relay min-sum decoder: normalised min-sum with a per-bit MEMORY, run as a chain of LEGS, returning the solution of
+ * lowest prior weight among the first `stop_after` it finds.  For the degenerate, short-cycle graphs of quantum LDPC
+ * codes, where plain min-sum stalls.  Like ldpc_minsum_* it has no division and no transcendental function, so THE
+ * RULE below has one legal outcome in IEEE binary32 and a numpy model equals the device in every bit.
+ *
+ * Inputs.  H, channel_llr[n], alpha, clip: as ldpc_minsum_create takes them.  legs >= 1; gammas[legs][n] binary32, the
+ * memory strengths, each finite with -1 < gamma < 1 (negative values are meaningful); leg_iters[legs] int32, each >= 0,
+ * their sum at most INT32_MAX; stop_after >= 1 (default 1).  The library draws no random number: the caller supplies
+ * gammas.  A syndrome entry that is not 0 counts as 1.
+ *
+ * THE RULE.  All arithmetic is binary32, every operation rounded once (no fused multiply-add), subnormals kept.
+ * Derived once per handle:
+ *   g0[r][j] = (1.0f - gammas[r][j]) * channel_llr[j]                  (one subtraction, one multiplication)
+ *   q[j]     = (int64) rint(clamp((double) channel_llr[j], -2^24, 2^24) * 2^16)      (the product is exact in double)
+ * n > 2^22 answers LDPC_ERR_UNSUPPORTED, so a weight (a sum of q[j]) always fits int64.
+ * State per syndrome: the posterior M[j], initially channel_llr[j]; X[j]; the check-to-bit messages c[i][j];
+ * found = 0, iters = 0; best, an error pattern, and its weight best_w.
+ * For leg r = 0 .. legs - 1 (a leg with leg_iters[r] = 0 is skipped):
+ *   Leg start.  Every c <- +0;  X[j] = g0[r][j] + gammas[r][j] * M[j]   (multiply, then add).
+ *   For t = 1 .. leg_iters[r]:
+ *     1. Check sweep: step 1 of the min-sum rule above with X in the place of L -- b_k = min(max(X[j_k] - c[i][j_k],
+ *        -clip), clip), the same ascending scan for m1, m2, a, the same par and the same signed alpha * (k == a ? m2 : m1),
+ *        -0 included; all b_k of a check are formed from the old messages.
+ *     2. Bit sweep, for every j:  Lambda = g0[r][j] + gammas[r][j] * M[j] with the OLD M;
+ *        M[j] = Lambda + c[i_0][j] + c[i_1][j] + ... from the left, checks ascending;  then with the NEW M:
+ *        Lambda' = g0[r][j] + gammas[r][j] * M[j],  X[j] = Lambda' + c[i_0][j] + c[i_1][j] + ... in the same order.
+ *        err[j] = (M[j] <= 0);  iters += 1.
+ *     3. Test.  If H * err == syndrome (an empty check is matched only by a 0 entry):  w = sum over j of err[j] * q[j]
+ *        in int64 (exact, so any summation order is legal);  if found == 0 or w < best_w: best = err, best_w = w (a tie
+ *        keeps the earlier solution);  found += 1;  if found == stop_after the syndrome stops, otherwise the leg ends
+ *        and the next leg starts from this M.
+ *   A leg that uses up leg_iters[r] without a solution ends, and the next starts from its M.
+ * After the last leg the syndrome stops.
+ *
+ * Outputs.  errors [batch][n] uint8 = best if found > 0, else (M <= 0) as it stands; converged [batch] uint8 =
+ * (found > 0); iters [batch] int32 (may be NULL): the total over all legs; solutions [batch] int32 (may be NULL) = found;
+ * llr [batch][n] DOUBLE (may be NULL): M as it stands when the syndrome stops, widened exactly -- with found > 1 that is
+ * the M of the LAST solution (or of the last iteration), not necessarily the M of `best`.  Every leg of 0 iterations:
+ * zeros, converged = 0, llr = 0, iters = 0, solutions = 0, as max_iters = 0 of min-sum.  batch = 0: LDPC_OK, nothing
+ * touched.
+ *
+ * Consequence.  With legs = 1, gammas all 0, stop_after = 1 and no channel_llr equal to -0, every output equals
+ * ldpc_minsum_* with max_iters = leg_iters[0] in every bit:  (1 - 0) * p = p  and  p + (+-0) = p.
+ *
+ * ldpc_relay_kernel: 1 = on-chip (X, M, the check records, best and the syndromes of the S <= 64 syndromes a workgroup
+ * holds live in LDS for the whole decode; needs (4 (2 n + record words + ceil(n / 32)) + s) bytes <= 159 KiB for one
+ * syndrome, records as in ldpc_minsum_kernel); 2 = unlimited (tiles of 64 syndromes in a workspace the handle owns,
+ * sized by the resident workgroups; any H with nnz < 2^28); 0 for NULL.  options->kernel_variant 0 = by size, 1 / 2 force
+ * a tier (1 where the state does not fit: LDPC_ERR_UNSUPPORTED).
+ *
+ * ldpc_relay_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL channel_llr, gammas or
+ * leg_iters, a non-finite channel_llr, a gamma that is not finite or outside (-1, 1), legs < 1, a negative leg_iters
+ * entry, a leg_iters sum beyond INT32_MAX, stop_after < 0 (0 = default 1), alpha or clip outside their min-sum ranges,
+ * a kernel_variant outside 0..2 and a pattern ldpc_bp_create rejects; without a device LDPC_ERR_NO_DEVICE.  The decode
+ * entries behave as those of ldpc_minsum_*: ldpc_relay_decode_batch takes HOST buffers and is synchronous (its wait is
+ * bounded by ldpc_set_wait_limit_ms); ldpc_relay_decode_batch_device takes DEVICE pointers and is asynchronous on
+ * `stream`; calls on one handle run in call order whatever streams they are given.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_relay_decoder ldpc_relay_decoder;
+
+/* Optional; pass NULL to ldpc_relay_create for defaults.  A zeroed struct means defaults too, except `device` (0 is
+ * device 0; -1 = the current one): alpha = 0 / clip = 0 / stop_after = 0 select 0.75 / 1.0e6f / 1. */
+typedef struct ldpc_relay_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    float alpha;             /* normalisation factor in (0, 1]; 0 = default 0.75 */
+    float clip;              /* clamp of the bit-to-check values, finite, > 0; 0 = default 1.0e6f */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_relay_kernel */
+    int32_t stop_after;      /* solutions to collect before a syndrome stops; 0 = default 1 */
+    int32_t reserved[11];
+} ldpc_relay_options;
+
+ldpc_status ldpc_relay_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
+                              const float *channel_llr, int64_t legs, const float *gammas, const int32_t *leg_iters,
+                              const ldpc_relay_options *options, ldpc_relay_decoder **out);
+ldpc_status ldpc_relay_destroy(ldpc_relay_decoder *dec);
+int32_t ldpc_relay_kernel(const ldpc_relay_decoder *dec);
+ldpc_status ldpc_relay_decode_batch(ldpc_relay_decoder *dec, int64_t batch, const uint8_t *syndromes, uint8_t *errors,
+                                    uint8_t *converged, double *llr, int32_t *iters, int32_t *solutions);
+ldpc_status ldpc_relay_decode_batch_device(ldpc_relay_decoder *dec, int64_t batch, const uint8_t *d_syndromes,
+                                           uint8_t *d_errors, uint8_t *d_converged, double *d_llr, int32_t *d_iters,
+                                           int32_t *d_solutions, void *stream);
+
 /* Diagnostics: 100 MHz ticks spent in {check sweep, variable sweep, convergence test}
  * of that call, summed over workgroups (one sampling wave each). */
 ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *dec, int32_t calls_back, uint64_t ticks[3]);

@@ -27,6 +27,7 @@ from .osd import BeliefPropagationOSDDecoder, OSDPostProcessor  # noqa: F401,E40
 from .bpots import BPOTSDecoder  # noqa: F401,E402
 from .bitflip import BitFlipDecoder, BitFlipScratchSpace  # noqa: F401,E402
 from .minsum import MinSumDecoder, MinSumScratchSpace  # noqa: F401,E402
+from .relay import RelayMinSumDecoder  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 from .css_trials import CSSTrialResult, CSSTrials, run_css_trials  # noqa: F401,E402
 
@@ -35,7 +36,7 @@ __all__ = [
     "decode_", "batchdecode_", "reset_", "AbstractDecoder", "BeliefPropagationDecoder",
     "BeliefPropagationScratchSpace", "parity_check_matrix", "save_pcm", "load_pcm",
     "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
-    "MinSumDecoder", "MinSumScratchSpace",
+    "MinSumDecoder", "MinSumScratchSpace", "RelayMinSumDecoder",
     "Trials", "TrialResult", "run_trials",
     "CSSTrials", "CSSTrialResult", "run_css_trials",
 ]

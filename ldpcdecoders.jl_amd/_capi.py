@@ -76,6 +76,11 @@ EXPORTED_SYMBOLS = (
     "ldpc_minsum_kernel",
     "ldpc_minsum_decode_batch",
     "ldpc_minsum_decode_batch_device",
+    "ldpc_relay_create",
+    "ldpc_relay_destroy",
+    "ldpc_relay_kernel",
+    "ldpc_relay_decode_batch",
+    "ldpc_relay_decode_batch_device",
     "ldpc_trials_create",
     "ldpc_trials_destroy",
     "ldpc_trials_kernel",
@@ -156,6 +161,14 @@ class MinSumOptions(ctypes.Structure):
     ]
 
 
+class RelayOptions(ctypes.Structure):
+    """ldpc_relay_options: alpha = 0 / clip = 0 / stop_after = 0 select the defaults (0.75, 1e6, 1)."""
+    _fields_ = [
+        ("device", ctypes.c_int32), ("alpha", ctypes.c_float), ("clip", ctypes.c_float),
+        ("kernel_variant", ctypes.c_int32), ("stop_after", ctypes.c_int32), ("reserved", ctypes.c_int32 * 11),
+    ]
+
+
 class TrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
@@ -172,7 +185,7 @@ class CSSTrialsOptions(ctypes.Structure):
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -312,6 +325,16 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_minsum_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     L.ldpc_minsum_decode_batch_device.restype = i32
     L.ldpc_minsum_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_relay_create.restype = i32
+    L.ldpc_relay_create.argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, vp, ctypes.POINTER(RelayOptions), ctypes.POINTER(vp)]
+    L.ldpc_relay_destroy.restype = i32
+    L.ldpc_relay_destroy.argtypes = [vp]
+    L.ldpc_relay_kernel.restype = i32
+    L.ldpc_relay_kernel.argtypes = [vp]
+    L.ldpc_relay_decode_batch.restype = i32
+    L.ldpc_relay_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_relay_decode_batch_device.restype = i32
+    L.ldpc_relay_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
     u64 = ctypes.c_uint64
     L.ldpc_trials_create.restype = i32
     L.ldpc_trials_create.argtypes = [i64, i64, i64, vp, vp, i64, i64, vp, vp, ctypes.POINTER(TrialsOptions), ctypes.POINTER(vp)]

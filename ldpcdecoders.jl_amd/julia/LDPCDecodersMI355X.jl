@@ -18,11 +18,13 @@ module LDPCDecodersMI355X
 
 using SparseArrays
 import Libdl
+import Random
 import LDPCDecoders
 import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 
 export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder, MI355XBitFlipDecoder
 export MI355XMinSumDecoder
+export MI355XRelayDecoder
 export Trials, sample!, score!
 export CSSTrials
 
@@ -502,6 +504,108 @@ function batchdecode!(d::MI355XMinSumDecoder, syndromes::AbstractMatrix, errors:
     return errors, converged
 end
 batchdecode!(d::MI355XMinSumDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix) =
+    batchdecode!(d, syndromes, errors, Vector{Bool}(undef, size(syndromes, 2)))
+
+# ---------------------------------------------------------------------------------------------
+# Relay min-sum over ldpc_relay_* (not a decoder of the reference; the rule is stated in include/ldpc_mi355x.h): min-sum
+# with a per-bit memory strength gamma, run as a chain of legs, the lightest of the first `stop_after` solutions returned.
+# The library draws no random number: the gammas are formed here.  Symbols added without a change of the ABI version.
+# ---------------------------------------------------------------------------------------------
+mutable struct MI355XRelayDecoder <: AbstractDecoder
+    per::Union{Float64,Nothing}; max_iters::Int; s::Int; n::Int
+    sparse_H::SparseMatrixCSC{Bool,Int}
+    channel_llr::Vector{Float32}
+    gammas::Matrix{Float32}          # n x legs: column r is leg r (the C array [legs][n])
+    leg_iters::Vector{Int32}
+    err::Vector{Float64}
+    log_probabs::Vector{Float64}
+    handle::Ptr{Cvoid}
+end
+
+"ldpc_relay_options: int32 device, float alpha, float clip, int32 kernel_variant, int32 stop_after, int32 reserved[11] (64 bytes)"
+function relay_options(device::Integer, alpha::Real, clip::Real, kernel_variant::Integer, stop_after::Integer)
+    opts = minsum_options(device, alpha, clip, kernel_variant)
+    opts[5] = Int32(stop_after)
+    return opts
+end
+
+"""
+    MI355XRelayDecoder(H, per, max_iters; legs=9, leg_iters=20, gamma0=0.125, gamma_range=(-0.24, 0.66), gammas=nothing,
+                       rng=Random.default_rng(), stop_after=1, alpha=0.75, clip=1e6, device=-1, kernel_variant=0)
+    MI355XRelayDecoder(H, max_iters; channel_probs=..., ...)   or   channel_llr=...
+
+Leg 0 runs `max_iters` iterations with `gamma0` everywhere, every later leg `leg_iters` with gammas drawn uniformly in
+`gamma_range`; `gammas` (n x legs, each inside (-1, 1)) gives them outright.
+"""
+function MI355XRelayDecoder(H, per::Union{Float64,Nothing}, max_iters::Int; channel_probs=nothing, channel_llr=nothing,
+                            legs::Int=9, leg_iters::Int=20, gamma0::Real=0.125, gamma_range=(-0.24, 0.66), gammas=nothing,
+                            rng=Random.default_rng(), stop_after::Int=1, alpha::Real=0.75, clip::Real=1e6,
+                            device::Integer=-1, kernel_variant::Integer=0)
+    s, n = size(H)
+    count(!isnothing, (per, channel_probs, channel_llr)) == 1 ||
+        throw(ArgumentError("give exactly one of per, channel_probs and channel_llr"))
+    legs >= 1 && stop_after >= 1 || throw(ArgumentError("legs and stop_after must be >= 1"))
+    probs = per !== nothing ? fill(per, n) : channel_probs
+    probs === nothing || all(p -> 0 < p < 1, probs) || throw(DomainError(probs, "probabilities must lie strictly inside (0, 1)"))
+    llr = probs !== nothing ? Float32[minsum_llr(p) for p in probs] : Vector{Float32}(channel_llr)
+    length(llr) == n || throw(DimensionMismatch("one prior per bit"))
+    (Float32(alpha) == 0 || Float32(clip) == 0) && throw(ArgumentError("alpha and clip must not be zero"))   # (0 = default in the C struct)
+    g = if gammas !== nothing
+        Matrix{Float32}(gammas)
+    else
+        lo, hi = Float64.(gamma_range)
+        hcat(fill(Float32(gamma0), n, 1), Float32.(lo .+ (hi - lo) .* rand(rng, n, legs - 1)))
+    end
+    size(g) == (n, legs) || throw(DimensionMismatch("gammas must be n x legs"))
+    its = Int32[max_iters; fill(leg_iters, legs - 1)]
+    sp = dropzeros(SparseMatrixCSC{Bool,Int}(sparse(H)))
+    colptr = Int64.(sp.colptr .- 1); rowval = Int64.(rowvals(sp) .- 1)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:ldpc_relay_create, libldpc), Cint,
+                (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                s, n, length(rowval), colptr, rowval, llr, legs, g, its, relay_options(device, alpha, clip, kernel_variant, stop_after), h))
+    d = MI355XRelayDecoder(per, max_iters, s, n, sp, llr, g, its, zeros(n), zeros(n), h[])
+    finalizer(d) do x
+        x.handle != C_NULL && ccall((:ldpc_relay_destroy, libldpc), Cint, (Ptr{Cvoid},), x.handle)
+        x.handle = C_NULL
+    end
+    return d
+end
+MI355XRelayDecoder(H, max_iters::Int; kwargs...) = MI355XRelayDecoder(H, nothing, max_iters; kwargs...)
+
+reset!(d::MI355XRelayDecoder) = d      # the device state is reset inside every decode call
+
+relay_call(handle, B, syn, err, conv, llr) =
+    check(ccall((:ldpc_relay_decode_batch, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                handle, B, syn, err, conv, llr, C_NULL, C_NULL))
+
+function decode!(d::MI355XRelayDecoder, syndrome::AbstractVector)
+    length(syndrome) == d.s || throw(BoundsError(syndrome, d.s))
+    syn = UInt8[syndrome_byte(x) for x in syndrome]
+    err = Vector{UInt8}(undef, d.n); conv = Vector{UInt8}(undef, 1)
+    relay_call(d.handle, 1, syn, err, conv, d.log_probabs)
+    d.err .= err
+    return d.err, conv[1] != 0
+end
+
+function batchdecode!(d::MI355XRelayDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix,
+                      converged::AbstractVector{Bool})                                 # one device call
+    @assert size(syndromes, 2) == size(errors, 2)
+    @assert size(syndromes, 2) == length(converged)
+    size(syndromes, 1) == d.s && size(errors, 1) == d.n || throw(DimensionMismatch("syndromes / errors rows"))
+    B = size(syndromes, 2)
+    B == 0 && return errors, converged
+    direct = errors isa Matrix{UInt8} || errors isa Matrix{Bool}
+    err = direct ? reinterpret(UInt8, errors) : Matrix{UInt8}(undef, d.n, B)
+    conv = Vector{UInt8}(undef, B)
+    relay_call(d.handle, B, bitflip_image(syndromes), err, conv, C_NULL)
+    direct || (errors .= err)
+    converged .= conv .!= 0
+    d.err .= view(err, :, B)
+    return errors, converged
+end
+batchdecode!(d::MI355XRelayDecoder, syndromes::AbstractMatrix, errors::AbstractMatrix) =
     batchdecode!(d, syndromes, errors, Vector{Bool}(undef, size(syndromes, 2)))
 
 # ---------------------------------------------------------------------------------------------
