@@ -692,6 +692,12 @@ ldpc_status ldpc_css_trials_score(ldpc_css_trials *t, int64_t batch, const uint8
  * handle owns, sized by the resident workgroups; any H with nnz < 2^28); 0 for NULL.  options->kernel_variant 0 = by
  * size, 1 / 2 force a tier (1 where the state does not fit: LDPC_ERR_UNSUPPORTED).
  *
+ * ldpc_minsum_tile_syndromes: the S of the handle -- on-chip the largest power of two <= 64 whose state fits 79 KiB (two
+ * workgroups a CU), else the largest that fits 159 KiB; 64 in the unlimited tier; 0 for NULL.  ldpc_minsum_last_grid: the
+ * workgroups of the handle's most recent kernel launch (each takes tile after tile of S syndromes in the same LDS block
+ * or workspace slot, so a value below ceil(batch / S) means slots were reused); 0 before any launch and for NULL.  Both
+ * only report what ran; neither has a reference counterpart.
+ *
  * ldpc_minsum_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL or non-finite channel_llr,
  * alpha outside (0, 1], clip not in (0, inf), a kernel_variant outside 0..2 and a pattern ldpc_bp_create rejects;
  * without a device LDPC_ERR_NO_DEVICE.  The decode entries reject a NULL handle, a negative batch and a NULL required
@@ -718,6 +724,8 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
                                ldpc_minsum_decoder **out);
 ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *dec);
 int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *dec);
+int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *dec);
+int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *dec);
 ldpc_status ldpc_minsum_decode_batch(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *syndromes, uint8_t *errors,
                                      uint8_t *converged, double *llr, int32_t *iters);
 ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *d_syndromes,
@@ -775,6 +783,9 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *dec, int64_t ba
  * sized by the resident workgroups; any H with nnz < 2^28); 0 for NULL.  options->kernel_variant 0 = by size, 1 / 2 force
  * a tier (1 where the state does not fit: LDPC_ERR_UNSUPPORTED).
  *
+ * ldpc_relay_tile_syndromes, ldpc_relay_last_grid: as ldpc_minsum_tile_syndromes and ldpc_minsum_last_grid -- the S of
+ * the handle, and the workgroups of its most recent kernel launch (0 before any launch); 0 for NULL.
+ *
  * ldpc_relay_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL channel_llr, gammas or
  * leg_iters, a non-finite channel_llr, a gamma that is not finite or outside (-1, 1), legs < 1, a negative leg_iters
  * entry, a leg_iters sum beyond INT32_MAX, stop_after < 0 (0 = default 1), alpha or clip outside their min-sum ranges,
@@ -803,6 +814,8 @@ ldpc_status ldpc_relay_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
                               const ldpc_relay_options *options, ldpc_relay_decoder **out);
 ldpc_status ldpc_relay_destroy(ldpc_relay_decoder *dec);
 int32_t ldpc_relay_kernel(const ldpc_relay_decoder *dec);
+int32_t ldpc_relay_tile_syndromes(const ldpc_relay_decoder *dec);
+int32_t ldpc_relay_last_grid(const ldpc_relay_decoder *dec);
 ldpc_status ldpc_relay_decode_batch(ldpc_relay_decoder *dec, int64_t batch, const uint8_t *syndromes, uint8_t *errors,
                                     uint8_t *converged, double *llr, int32_t *iters, int32_t *solutions);
 ldpc_status ldpc_relay_decode_batch_device(ldpc_relay_decoder *dec, int64_t batch, const uint8_t *d_syndromes,

@@ -2,7 +2,8 @@
  * ldpc_mi355x_debug.h -- test hooks of libldpc_mi355x.so.  NOT part of the drop-in boundary (include/ldpc_mi355x.h):
  * nothing here replaces a reference interface; the CPU test-suite uses these entries to check, without a GPU, the
  * host-side planning the team kernel relies on (ldpcdecoders.jl_amd/csrc/team_plan.cpp: team_plan_pure(),
- * team_rows_tables(), team_irr_tables()).  Pure host code; no device is needed or touched.
+ * team_rows_tables(), team_irr_tables()) and the tier / tile-width choice of the min-sum and relay decoders
+ * (csrc/tile_plan.hpp).  Pure host code; no device is needed or touched.
  */
 #ifndef LDPC_MI355X_DEBUG_H
 #define LDPC_MI355X_DEBUG_H
@@ -51,6 +52,18 @@ ldpc_status ldpc_debug_team_rows(int64_t s, int64_t n, const int64_t *colptr, co
 ldpc_status ldpc_debug_team_irr(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t members,
                                 int32_t dc_bucket, int32_t dv_bucket, int32_t *shape, int32_t *ctab2, int32_t *ptab, int32_t *ploc,
                                 int32_t *lds_edge, int32_t *posmap);
+
+/* The tier and the tile width ldpc_minsum_create (relay = 0) / ldpc_relay_create (relay != 0) choose for a graph of s
+   checks and n bits whose check records take rec_words words (4 per check of degree 1 ... 32, 5 up to 64, the degree
+   beyond; 0 for an empty check) -- csrc/tile_plan.hpp tile_plan(), the function both call.  A tile of S syndromes has a
+   state of  S (4 (n + rec_words) + s)  bytes (min-sum) or  S (4 (2 n + rec_words + ceil(n / 32)) + s)  bytes (relay),
+   rounded up to 256.  tier 1 (on-chip) with the largest power of two S <= 64 whose state fits 79 KiB (two workgroups a
+   CU), else the largest that fits 159 KiB; else tier 2 (unlimited) with S = 64.  kernel_variant 1 / 2 force a tier (2:
+   S = 64 always; 1 where not even S = 1 fits 159 KiB: LDPC_ERR_UNSUPPORTED, as create answers); 0 = by size.  Out (each
+   may be NULL): the tier, S, and the bytes of the state of one tile.  Negative sizes, sizes create refuses and a
+   kernel_variant outside 0 .. 2: LDPC_ERR_INVALID_ARGUMENT.  No reference counterpart. */
+ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t relay, int32_t kernel_variant, int32_t *tier,
+                                 int32_t *tile_syndromes, int64_t *state_bytes);
 
 /* Two builds of the library in one process (the product and the -DLDPC_EXPERIMENTS build: the Python host of the tests)
    must not run team grids on one device at the same time -- every member of a team has to be resident.  Each build

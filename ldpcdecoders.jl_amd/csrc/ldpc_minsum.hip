@@ -5,20 +5,22 @@
 //   2  unlimited: tiles of 64 syndromes, the state in a global workspace, one slot per workgroup of a persistent grid
 // No CPU path.
 #include "../../include/ldpc_mi355x.h"
+#include "../../include/ldpc_mi355x_debug.h"
 #include "minsum_kernels.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <new>
 #include <string>
 #include <vector>
 
 using namespace ldpc;
 
+#include "host_env.hpp"      // exp_env: LDPC_MS_GRID_MAX, experiments build only
 #include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
 using ldpc_detail::set_error;
 
-static constexpr size_t kMsLdsTwo = (size_t)79 * 1024, kMsLdsOne = (size_t)159 * 1024;   // two / one workgroup a CU
 static constexpr int kMsLdsWaves = 8, kMsGlobalWaves = 16;   // (16 waves: 2.2x the speed of 4 at n = 16384, the sweeps are latency-bound)
 static constexpr size_t kMsWorkspaceCap = (size_t)6 << 30;   // the unlimited tier's grid shrinks to keep its slots below this
 static constexpr float kMsAlphaDefault = 0.75f, kMsClipDefault = 1.0e6f;
@@ -35,6 +37,8 @@ struct ldpc_minsum_decoder {
     size_t ws_cap = 0;
     bool kernel_ready = false;
     int per_cu = 1;
+    int grid_max = 0;    // LDPC_MS_GRID_MAX (experiments build): workgroups a launch takes at most; 0 = no cap
+    int last_grid = 0;   // workgroups of the most recent launch
     ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (they share the workspace)
     ~ldpc_minsum_decoder()
     {
@@ -48,14 +52,6 @@ struct ldpc_minsum_decoder {
 
 typedef void (*ms_kernel_t)(MsParams);
 static ms_kernel_t ms_kernel_of(int tier) { return tier == 1 ? minsum_kernel<kMsLdsWaves, false> : minsum_kernel<kMsGlobalWaves, true>; }
-
-// syndromes per workgroup of the on-chip tier: the largest power of two <= 64 whose state fits `budget`; 0 = none
-static int ms_lds_tile(int64_t s, int64_t n, int64_t rec_words, size_t budget)
-{
-    for (int S = 64; S >= 1; S >>= 1)
-        if (ms_state_bytes(s, n, rec_words, S) <= budget) return S;
-    return 0;
-}
 
 extern "C" {
 
@@ -103,15 +99,13 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
         edge_pos[(size_t)e] = g.row_ptr[(size_t)i + 1] - g.row_ptr[(size_t)i] > 64 ? (k | kMsPosEdge) : k;
     }
     d->rec_words = (int)words;
-    int S = ms_lds_tile(s, n, words, kMsLdsTwo);
-    if (!S) S = ms_lds_tile(s, n, words, kMsLdsOne);
-    if (variant == 1 && !S) {
+    TilePlan plan;   // the tier and the tile width (tile_plan.hpp)
+    if (!tile_plan(s, n, words, false, variant, &plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
-    d->tier = variant ? variant : S ? 1 : 2;
-    d->S = d->tier == 1 ? S : 64;
-    for (d->shift = 0; (1 << d->shift) < d->S; d->shift++) {}
+    d->tier = plan.tier; d->S = plan.S; d->shift = plan.shift;
+    if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
     using ldpc_detail::upload_ints;
     bool ok = upload_ints(&d->row_ptr, g.row_ptr) && upload_ints(&d->csr_col, g.csr_col) && upload_ints(&d->rec_off, rec_off) &&
               upload_ints(&d->col_ptr, g.col_ptr) && upload_ints(&d->edge_rec, edge_rec) && upload_ints(&d->edge_pos, edge_pos) &&
@@ -127,7 +121,25 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
     return LDPC_OK;
 }
 
+// (include/ldpc_mi355x_debug.h) the choice both create routines make, without a device
+ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t relay, int32_t kernel_variant, int32_t *tier,
+                                 int32_t *tile_syndromes, int64_t *state_bytes)
+{
+    if (s < 0 || n < 0 || rec_words < 0 || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28) || rec_words >= ((int64_t)1 << 31))
+        return set_error(LDPC_ERR_INVALID_ARGUMENT, "s, n and rec_words must be >= 0 and within what create accepts");
+    if (kernel_variant < 0 || kernel_variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
+    TilePlan plan;
+    if (!tile_plan(s, n, rec_words, relay != 0, kernel_variant, &plan))
+        return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
+    if (tier) *tier = plan.tier;
+    if (tile_syndromes) *tile_syndromes = plan.S;
+    if (state_bytes) *state_bytes = (int64_t)plan.state_bytes;
+    return LDPC_OK;
+}
+
 int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *d) { return d ? d->tier : 0; }
+int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *d) { return d ? d->S : 0; }
+int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *d) { return d ? d->last_grid : 0; }
 
 ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *d)
 {
@@ -164,12 +176,13 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batc
         ms_kernel_t k = ms_kernel_of(d->tier);
         if (!d->kernel_ready) {
             // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
-            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMsLdsOne));
+            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
             d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, threads, lds);
             d->kernel_ready = true;
         }
         const int64_t tiles = (batch + d->S - 1) >> d->shift;
         int64_t grid = std::min<int64_t>(tiles, (int64_t)d->per_cu * d->num_cus);
+        if (d->grid_max > 0) grid = std::min<int64_t>(grid, d->grid_max);
         if (global) {
             grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMsWorkspaceCap / state)));
             st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
@@ -185,6 +198,7 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batc
         p.ws = d->ws; p.slot_bytes = (long long)state;
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
         LDPC_HIP_TRY(hipGetLastError());
+        d->last_grid = (int)grid;
     }
     return d->calls.leave(stream);
 }

@@ -9,16 +9,17 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <new>
 #include <string>
 #include <vector>
 
 using namespace ldpc;
 
+#include "host_env.hpp"      // exp_env: LDPC_MS_GRID_MAX, experiments build only
 #include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
 using ldpc_detail::set_error;
 
-static constexpr size_t kRlLdsTwo = (size_t)79 * 1024, kRlLdsOne = (size_t)159 * 1024;   // two / one workgroup a CU
 static constexpr int kRlLdsWaves = 8, kRlGlobalWaves = 16;   // as min-sum
 static constexpr size_t kRlWorkspaceCap = (size_t)6 << 30;   // the unlimited tier's grid shrinks to keep its slots below this
 static constexpr float kRlAlphaDefault = 0.75f, kRlClipDefault = 1.0e6f;
@@ -39,6 +40,8 @@ struct ldpc_relay_decoder {
     size_t ws_cap = 0;
     bool kernel_ready = false;
     int per_cu = 1;
+    int grid_max = 0;    // LDPC_MS_GRID_MAX (experiments build): workgroups a launch takes at most; 0 = no cap
+    int last_grid = 0;   // workgroups of the most recent launch
     ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (they share the workspace)
     ~ldpc_relay_decoder()
     {
@@ -52,14 +55,6 @@ struct ldpc_relay_decoder {
 
 typedef void (*relay_kernel_t)(RelayParams);
 static relay_kernel_t relay_kernel_of(int tier) { return tier == 1 ? relay_kernel<kRlLdsWaves, false> : relay_kernel<kRlGlobalWaves, true>; }
-
-// syndromes per workgroup of the on-chip tier: the largest power of two <= 64 whose state fits `budget`; 0 = none
-static int relay_lds_tile(int64_t s, int64_t n, int64_t rec_words, size_t budget)
-{
-    for (int S = 64; S >= 1; S >>= 1)
-        if (relay_state_bytes(s, n, rec_words, S) <= budget) return S;
-    return 0;
-}
 
 template <class V>
 static bool upload(V **dst, const std::vector<V> &v)   // hipMalloc (at least one element) + hipMemcpy
@@ -149,15 +144,13 @@ ldpc_status ldpc_relay_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
         edge_pos[(size_t)e] = g.row_ptr[(size_t)i + 1] - g.row_ptr[(size_t)i] > 64 ? (k | kMsPosEdge) : k;
     }
     d->rec_words = (int)words;
-    int S = relay_lds_tile(s, n, words, kRlLdsTwo);
-    if (!S) S = relay_lds_tile(s, n, words, kRlLdsOne);
-    if (variant == 1 && !S) {
+    TilePlan plan;   // the tier and the tile width (tile_plan.hpp)
+    if (!tile_plan(s, n, words, true, variant, &plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
-    d->tier = variant ? variant : S ? 1 : 2;
-    d->S = d->tier == 1 ? S : 64;
-    for (d->shift = 0; (1 << d->shift) < d->S; d->shift++) {}
+    d->tier = plan.tier; d->S = plan.S; d->shift = plan.shift;
+    if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
     using ldpc_detail::upload_ints;
     const std::vector<float> h_prior(channel_llr, channel_llr + n);
     bool ok = upload_ints(&d->row_ptr, g.row_ptr) && upload_ints(&d->csr_col, g.csr_col) && upload_ints(&d->rec_off, rec_off) &&
@@ -174,6 +167,8 @@ ldpc_status ldpc_relay_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
 }
 
 int32_t ldpc_relay_kernel(const ldpc_relay_decoder *d) { return d ? d->tier : 0; }
+int32_t ldpc_relay_tile_syndromes(const ldpc_relay_decoder *d) { return d ? d->S : 0; }
+int32_t ldpc_relay_last_grid(const ldpc_relay_decoder *d) { return d ? d->last_grid : 0; }
 
 ldpc_status ldpc_relay_destroy(ldpc_relay_decoder *d)
 {
@@ -211,12 +206,13 @@ ldpc_status ldpc_relay_decode_batch_device(ldpc_relay_decoder *d, int64_t batch,
         relay_kernel_t k = relay_kernel_of(d->tier);
         if (!d->kernel_ready) {
             // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
-            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRlLdsOne));
+            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
             d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, threads, lds);
             d->kernel_ready = true;
         }
         const int64_t tiles = (batch + d->S - 1) >> d->shift;
         int64_t grid = std::min<int64_t>(tiles, (int64_t)d->per_cu * d->num_cus);
+        if (d->grid_max > 0) grid = std::min<int64_t>(grid, d->grid_max);
         if (global) {
             grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kRlWorkspaceCap / state)));
             st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
@@ -233,6 +229,7 @@ ldpc_status ldpc_relay_decode_batch_device(ldpc_relay_decoder *d, int64_t batch,
         p.ws = d->ws; p.slot_bytes = (long long)state;
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
         LDPC_HIP_TRY(hipGetLastError());
+        d->last_grid = (int)grid;
     }
     return d->calls.leave(stream);
 }

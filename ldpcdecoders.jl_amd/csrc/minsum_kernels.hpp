@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_plan.hpp"
+
 namespace ldpc {
 
 constexpr unsigned kMsNone = 0xffffffffu;
@@ -50,13 +52,7 @@ struct MsParams {
     long long slot_bytes;
 };
 
-// words of check records for a check of degree `deg`
-__host__ __device__ inline int ms_record_words(int deg) { return deg == 0 ? 0 : deg <= 32 ? 4 : deg <= 64 ? 5 : deg; }
-// bytes of a tile's state: S lanes of (n + rec_words) words and s bytes, rounded up to 256
-__host__ __device__ inline size_t ms_state_bytes(long long s, long long n, long long rec_words, int S)
-{
-    return (((size_t)(n + rec_words) * 4 + (size_t)s) * (size_t)S + 255) & ~(size_t)255;
-}
+// (ms_record_words(), ms_state_bytes() -- the words of a check record, the bytes of a tile's state: tile_plan.hpp, host code)
 
 __device__ inline float ms_clamp(float x, float clip)
 {

@@ -48,11 +48,7 @@ struct RelayParams {
     long long slot_bytes;
 };
 
-// bytes of a tile's state: S lanes of (2 n + rec_words + ceil(n / 32)) words and s bytes, rounded up to 256
-__host__ __device__ inline size_t relay_state_bytes(long long s, long long n, long long rec_words, int S)
-{
-    return (((size_t)(2 * n + rec_words + ((n + 31) >> 5)) * 4 + (size_t)s) * (size_t)S + 255) & ~(size_t)255;
-}
+// (relay_state_bytes() -- the bytes of a tile's state, S lanes of (2 n + rec_words + ceil(n / 32)) words and s bytes: tile_plan.hpp)
 
 // the message of a bit's edge out of its check's record (minsum_kernel's bit sweep)
 __device__ inline float relay_message(const unsigned *rec, int k, int sh)

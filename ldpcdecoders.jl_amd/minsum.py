@@ -87,8 +87,12 @@ class MinSumDecoder(AbstractDecoder):
         return int(self._L.ldpc_minsum_kernel(self._h))
 
     def info(self):
-        """`.device`: the GPU the handle lives on; `.kernel`: its tier."""
-        return SimpleNamespace(device=self.device, kernel=self.kernel)
+        """`.device`: the GPU the handle lives on; `.kernel`: its tier; `.tile_syndromes`: the syndromes a workgroup decodes
+        at a time (S); `.last_grid`: the workgroups of the most recent launch (0 before any) -- fewer than ceil(batch / S)
+        means that a workgroup took a further tile in the same LDS block or workspace slot."""
+        return SimpleNamespace(device=self.device, kernel=self.kernel,
+                               tile_syndromes=int(self._L.ldpc_minsum_tile_syndromes(self._h)),
+                               last_grid=int(self._L.ldpc_minsum_last_grid(self._h)))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

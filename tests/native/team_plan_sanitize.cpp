@@ -4,8 +4,9 @@
 // tests/test_team_rows_cpu.py::test_team_plan_under_sanitizers.  What the tables must SAY about the graph is that
 // file's business; here only what is cheap: every call succeeds, the tables have the sizes the layout promises, the
 // write-back lists name edges of the graph, the bit order is a permutation, a plan never asks for more workgroups than
-// the chip hosts.  Exit code 0 and "OK ..." = nothing found.
+// the chip hosts; the tile plans of the min-sum and relay decoders (tile_plan.hpp) stay inside the LDS budgets.  Exit code 0 and "OK ..." = nothing found.
 #include "../../ldpcdecoders.jl_amd/csrc/team_plan.hpp"
+#include "../../ldpcdecoders.jl_amd/csrc/tile_plan.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -103,9 +104,32 @@ static bool plans(int *count)
     return true;
 }
 
+// The tier and the tile width of the min-sum and relay decoders (tile_plan.hpp) over sizes from nothing to the largest
+// create accepts, every variant: a plan is tier 1 with a power of two S <= 64 inside 159 KiB or tier 2 with S = 64, and
+// variant 1 is refused exactly where one syndrome does not fit.
+static bool tile_plans(int *count)
+{
+    for (int64_t n : {(int64_t)0, (int64_t)1, (int64_t)72, (int64_t)96, (int64_t)6144, (int64_t)6480, (int64_t)13824, ((int64_t)1 << 28) - 1})
+        for (int64_t s : {(int64_t)0, n / 2, n})
+            for (int64_t rec : {(int64_t)0, 4 * s, ((int64_t)1 << 31) - 1})
+                for (int relay = 0; relay < 2; ++relay)
+                    for (int variant = 0; variant < 3; ++variant) {
+                        TilePlan pl;
+                        const size_t one = relay ? relay_state_bytes(s, n, rec, 1) : ms_state_bytes(s, n, rec, 1);
+                        const bool ok = tile_plan(s, n, rec, relay != 0, variant, &pl);
+                        CHECK(ok == !(variant == 1 && one > kTileLdsOne));
+                        ++*count;
+                        if (!ok) continue;
+                        CHECK(pl.S == 1 << pl.shift && pl.S >= 1 && pl.S <= 64 && (pl.tier == 1 || (pl.tier == 2 && pl.S == 64)));
+                        CHECK(pl.tier == 2 || pl.state_bytes <= kTileLdsOne);
+                        CHECK(pl.state_bytes % 256 == 0 && pl.state_bytes >= one);
+                    }
+    return true;
+}
+
 int main()
 {
-    int nplans = 0;
+    int nplans = 0, ntile = 0;
     const bool ok = regular(1024, 3, 8, 4, 32, 3) && regular(1008, 5, 6, 3, 0, 3) && regular(3990, 6, 7, 3, 12, 3) &&
                     regular(4000, 7, 10, 5, 20, 3) &&
                     regular(4096, 8, 8, 4, 32, 0) &&    // no static quarters: a wave's first chunk only (static = W)
@@ -113,8 +137,8 @@ int main()
                     irregular(1000, 500, 3, 8, 4) && irregular(1000, 500, 3, 16, 16) && irregular(1000, 500, 32, 8, 4) &&
                     irregular(1000, 500, 32, 16, 16) &&
                     irregular(96, 64, 32, 8, 4) && irregular(96, 64, 32, 16, 16) &&   // 24 position chunks: members without a position
-                    plans(&nplans);
+                    plans(&nplans) && tile_plans(&ntile);
     if (!ok) return 1;
-    std::printf("OK 6 regular and 6 irregular table sets, %d plans\n", nplans);
+    std::printf("OK 6 regular and 6 irregular table sets, %d plans, %d tile plans\n", nplans, ntile);
     return 0;
 }

@@ -42,7 +42,7 @@ def test_product_build_reads_no_environment_and_has_no_fault_injection():
     prod = open(ldpc._capi.LIB_PATH, "rb").read()
     exp = open(ldpc._capi.EXP_LIB_PATH, "rb").read()
     for knob in (b"LDPC_TEAM_INJECT_FAULT", b"LDPC_TEAM_CACHE_MIB", b"LDPC_DEFER_T0", b"LDPC_VMM_HINT_TIB", b"LDPC_NODE_MSG_LDS",
-                 b"LDPC_BPOTS_FORCE_NODE", b"LDPC_WS_ALLOC"):
+                 b"LDPC_BPOTS_FORCE_NODE", b"LDPC_WS_ALLOC", b"LDPC_MS_GRID_MAX"):
         assert knob not in prod, knob
         assert knob in exp, knob
     undefined = subprocess.run(["nm", "-D", "--undefined-only", ldpc._capi.LIB_PATH], capture_output=True, text=True).stdout
