@@ -534,6 +534,23 @@ ldpc_status ldpc_bitflip_decode_batch_device(ldpc_bitflip_decoder *dec, int64_t 
  * required pointer, a NULL handle: LDPC_ERR_INVALID_ARGUMENT before any device work.  Without a device,
  * ldpc_trials_create returns LDPC_ERR_NO_DEVICE.
  *
+ * Per-bit rates (biased noise, the columns of a detector error model: one rate per error mechanism).  A handle may hold
+ * a table of n rates, set by ldpc_trials_set_rates; ldpc_trials_sample_rates[_device] then draws bit j at rates[j] by the
+ * same stateless rule, with k_i, r_ij and mix exactly those above.  For rates[j], a double in [0, 1]:
+ *     t_j         = (uint64)(rates[j] * 18446744073709551616.0)       for rates[j] < 1
+ *     error(i, j) = rates[j] >= 1 ? 1 : (r_ij < t_j)
+ * With rates[j] = per for all j, every element equals ldpc_trials_sample at that per, seed and column0 (per = 0 and
+ * per = 1 included).  On the device the table is one uint64 threshold per bit; the largest double below 1 gives
+ * t = 2^64 - 2^11, so the all-ones word never occurs for a rate below 1 and marks "always".
+ * ldpc_trials_set_rates takes a HOST pointer and is synchronous: it validates, converts and uploads, ordered after every
+ * earlier call on the handle (a sample still in flight keeps the table it was launched with; the wait for it is
+ * bounded).  n must equal the handle's n; a rate that is NaN, < 0 or > 1: LDPC_ERR_INVALID_ARGUMENT, the message names
+ * the first offending index, nothing is uploaded and the table set before stays in force.  rates = NULL clears the
+ * table.  The two sample entries are ldpc_trials_sample[_device] without `per` in every other respect (d_syndromes may be
+ * NULL, batch = 0 touches nothing, the 2^36 column limit, bounded waits, call order whatever the streams); without a
+ * table they answer LDPC_ERR_INVALID_ARGUMENT before any device work.  ldpc_trials_syndromes* and ldpc_trials_score*
+ * serve both kinds of sample.
+ *
  * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
  * ------------------------------------------------------------------------ */
 typedef struct ldpc_trials ldpc_trials;
@@ -562,6 +579,12 @@ ldpc_status ldpc_trials_sample(ldpc_trials *t, int64_t batch, int64_t column0, d
                                uint8_t *errors, uint8_t *syndromes);
 ldpc_status ldpc_trials_score(ldpc_trials *t, int64_t batch, const uint8_t *guesses, const uint8_t *errors,
                               uint8_t *flags, int64_t counts[4]);
+/* per-bit rates: rates [n] doubles on the HOST, NULL clears the table */
+ldpc_status ldpc_trials_set_rates(ldpc_trials *t, int64_t n, const double *rates);
+ldpc_status ldpc_trials_sample_rates_device(ldpc_trials *t, int64_t batch, int64_t column0, uint64_t seed,
+                                            uint8_t *d_errors, uint8_t *d_syndromes, void *stream);
+ldpc_status ldpc_trials_sample_rates(ldpc_trials *t, int64_t batch, int64_t column0, uint64_t seed,
+                                     uint8_t *errors, uint8_t *syndromes);
 
 /* ------------------------------------------------------------------------
  * Monte-Carlo trials of a CSS code on the device: two check matrices Hx (rows_x x n) and Hz (rows_z x n) over the same n

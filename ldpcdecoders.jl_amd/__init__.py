@@ -30,6 +30,7 @@ from .minsum import MinSumDecoder, MinSumScratchSpace  # noqa: F401,E402
 from .relay import RelayMinSumDecoder  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 from .css_trials import CSSTrialResult, CSSTrials, run_css_trials  # noqa: F401,E402
+from .dem import DetectorErrorModel, phenomenological, run_dem_trials  # noqa: F401,E402
 
 __all__ = [
     "BeliefPropagationOSDDecoder", "OSDPostProcessor", "BPOTSDecoder", "BitFlipDecoder", "BitFlipScratchSpace",
@@ -39,4 +40,5 @@ __all__ = [
     "MinSumDecoder", "MinSumScratchSpace", "RelayMinSumDecoder",
     "Trials", "TrialResult", "run_trials",
     "CSSTrials", "CSSTrialResult", "run_css_trials",
+    "DetectorErrorModel", "phenomenological", "run_dem_trials",
 ]

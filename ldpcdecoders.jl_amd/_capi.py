@@ -93,6 +93,9 @@ EXPORTED_SYMBOLS = (
     "ldpc_trials_score_device",
     "ldpc_trials_sample",
     "ldpc_trials_score",
+    "ldpc_trials_set_rates",
+    "ldpc_trials_sample_rates_device",
+    "ldpc_trials_sample_rates",
     "ldpc_css_trials_create",
     "ldpc_css_trials_destroy",
     "ldpc_css_trials_kernel",
@@ -366,6 +369,12 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_trials_sample.argtypes = [vp, i64, i64, f64, u64, vp, vp]
     L.ldpc_trials_score.restype = i32
     L.ldpc_trials_score.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.ldpc_trials_set_rates.restype = i32
+    L.ldpc_trials_set_rates.argtypes = [vp, i64, vp]
+    L.ldpc_trials_sample_rates_device.restype = i32
+    L.ldpc_trials_sample_rates_device.argtypes = [vp, i64, i64, u64, vp, vp, vp]
+    L.ldpc_trials_sample_rates.restype = i32
+    L.ldpc_trials_sample_rates.argtypes = [vp, i64, i64, u64, vp, vp]
     pat = ctypes.POINTER(CSSPattern)
     L.ldpc_css_trials_create.restype = i32
     L.ldpc_css_trials_create.argtypes = [i64, pat, pat, pat, pat, ctypes.POINTER(CSSTrialsOptions), ctypes.POINTER(vp)]

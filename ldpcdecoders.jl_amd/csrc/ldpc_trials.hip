@@ -5,7 +5,8 @@
 // sx = Hx ez, and the joint score with logical X and logical Z failures.  Device code: trial_kernels.hpp, whose sides
 // are filled here: one matrix = one side (H, L); CSS = side 0 (ex, gx, sz; Hz, Lz) and side 1 (ez, gz, sx; Hx, Lx).
 // Tiers (ldpc_trials_kernel, ldpc_css_trials_kernel): 1 = a column's bit images in LDS while its checks are walked,
-// 2 = unlimited.  No CPU path.
+// 2 = unlimited.  No CPU path.  A one-matrix handle may hold a table of per-bit thresholds (ldpc_trials_set_rates) for
+// the per-bit sample, a fourth step of the same kernel template.
 #include "../../include/ldpc_mi355x.h"
 #include "trial_kernels.hpp"
 
@@ -34,7 +35,8 @@ struct TrialsCore {
     int device = 0, num_cus = 0, tier = 0, wpc = 1, image_stride = 0;
     void *stage = nullptr;      // device staging for the host-pointer entries
     size_t stage_cap = 0;
-    int per_cu[3] = {0, 0, 0};  // workgroups a CU holds, per step (0 = not asked yet)
+    int per_cu[4] = {0, 0, 0, 0};  // workgroups a CU holds, per step (0 = not asked yet)
+    tu64 *rates = nullptr;      // one matrix: the threshold of every bit (trial_kernels.hpp), while a table is set
     ldpc_detail::CallOrder calls;
     ~TrialsCore()
     {
@@ -43,6 +45,7 @@ struct TrialsCore {
             for (void *q : {(void *)s.row_ptr, (void *)s.csr_col, (void *)s.lrow_ptr, (void *)s.lcsr_col})
                 if (q) (void)hipFree(q);
         if (stage) (void)hipFree(stage);
+        if (rates) (void)hipFree(rates);
         calls.destroy();
     }
 };
@@ -56,6 +59,10 @@ static auto trial_kernel_of(int mode, int wpc, bool image) -> void (*)(TrialPara
 #define LDPC_TRIAL_STEP(MODE) {{trial_kernel<SIDES, 1, MODE, false>, trial_kernel<SIDES, 1, MODE, true>}, \
                                {trial_kernel<SIDES, 4, MODE, false>, trial_kernel<SIDES, 4, MODE, true>}}
     static void (*const table[3][2][2])(TrialParams<SIDES>) = {LDPC_TRIAL_STEP(kSample), LDPC_TRIAL_STEP(kSyndromes), LDPC_TRIAL_STEP(kScore)};
+    if constexpr (SIDES == 1) {   // the per-bit sample exists for one matrix only
+        static void (*const by_rates[2][2])(TrialParams<1>) = LDPC_TRIAL_STEP(kSampleRates);
+        if (mode == kSampleRates) return by_rates[wpc == 4][image];
+    }
 #undef LDPC_TRIAL_STEP
     return table[mode][wpc == 4][image];
 }
@@ -81,7 +88,7 @@ static ldpc_status trials_launch(TrialsCore *t, int mode, TrialParams<SIDES> p, 
         if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrialsImageLds));
         t->per_cu[mode] = std::min(8, ldpc_detail::blocks_per_cu((const void *)k, kThreads, lds));
     }
-    p.n = (int)t->n; p.image_stride = t->image_stride; p.batch = batch;
+    p.n = (int)t->n; p.image_stride = t->image_stride; p.batch = batch; p.rates = t->rates;
     for (int i = 0; i < SIDES; ++i) {
         const TrialsCore::Side &s = t->side[i];
         TrialSide &d = p.side[i];
@@ -166,6 +173,38 @@ static ldpc_status check_sample_args(int64_t batch, int64_t column0, double per,
     if (!(per >= 0.0 && per <= 1.0)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "per must lie in [0, 1] (and not be NaN)");
     if (batch > 0 && !errors) return set_error(LDPC_ERR_INVALID_ARGUMENT, "errors pointer is NULL");
     return LDPC_OK;
+}
+
+// the per-bit sample: its rates were checked by ldpc_trials_set_rates, and without a table there is nothing to draw from
+static ldpc_status check_sample_rates_args(const ldpc_trials *t, int64_t batch, int64_t column0, const void *errors)
+{
+    const ldpc_status st = check_sample_args(batch, column0, 0.0, errors);
+    if (st != LDPC_OK) return st;
+    if (!t) return set_error(LDPC_ERR_INVALID_ARGUMENT, "trials handle is NULL");
+    if (!t->rates) return set_error(LDPC_ERR_INVALID_ARGUMENT, "no rates are set (ldpc_trials_set_rates)");
+    return LDPC_OK;
+}
+
+// The host form of either sample: the device form `sample_device(d_errors, d_syndromes)` into the staging buffer, then
+// the copies out.  The arguments are checked, the handle is not NULL, batch > 0.
+template <class F>
+static ldpc_status sample_to_host(ldpc_trials *t, int64_t batch, uint8_t *errors, uint8_t *syndromes, const char *what, F sample_device)
+{
+    LDPC_HIP_TRY(hipSetDevice(t->device));
+    const size_t s = (size_t)t->side[0].rows, n = (size_t)t->n, B = (size_t)batch;
+    ldpc_detail::Carve image;   // [errors][syndromes]
+    image.take(B * n);
+    const size_t o_syn = image.take(B * s);
+    ldpc_status st = ldpc_detail::grow_device_buffer(&t->stage, &t->stage_cap, std::max<size_t>(image.at, 256), t->device,
+                                                     "trials staging regrow (device synchronise before the free)");
+    if (st != LDPC_OK) return st;
+    uint8_t *dp = (uint8_t *)t->stage;
+    const bool want_syn = syndromes && s > 0;
+    st = sample_device(dp, want_syn ? dp + o_syn : nullptr);
+    if (st != LDPC_OK) return st;
+    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(errors, dp, B * n, hipMemcpyDeviceToHost, nullptr));
+    if (want_syn) LDPC_HIP_TRY(hipMemcpyAsync(syndromes, dp + o_syn, B * s, hipMemcpyDeviceToHost, nullptr));
+    return ldpc_detail::wait_stream(nullptr, t->device, what);
 }
 
 static ldpc_status check_score_args(int64_t batch, const void *guesses, const void *errors, const void *counts)
@@ -314,25 +353,70 @@ ldpc_status ldpc_trials_score_device(ldpc_trials *t, int64_t batch, const uint8_
 ldpc_status ldpc_trials_sample(ldpc_trials *t, int64_t batch, int64_t column0, double per, uint64_t seed, uint8_t *errors,
                                uint8_t *syndromes)
 {
-    ldpc_status st = check_sample_args(batch, column0, per, errors);
+    const ldpc_status st = check_sample_args(batch, column0, per, errors);
     if (st != LDPC_OK) return st;
     if (!t) return set_error(LDPC_ERR_INVALID_ARGUMENT, "trials handle is NULL");
     if (batch == 0) return LDPC_OK;
+    return sample_to_host(t, batch, errors, syndromes, "ldpc_trials_sample (stream synchronise)", [&](uint8_t *d_errors, uint8_t *d_syndromes) {
+        return ldpc_trials_sample_device(t, batch, column0, per, seed, d_errors, d_syndromes, nullptr);
+    });
+}
+
+ldpc_status ldpc_trials_set_rates(ldpc_trials *t, int64_t n, const double *rates)
+{
+    if (!t) return set_error(LDPC_ERR_INVALID_ARGUMENT, "trials handle is NULL");
+    if (n != t->n) return set_error(LDPC_ERR_INVALID_ARGUMENT, "n is not the handle's n (one rate per bit)");
+    std::vector<tu64> table;
+    if (rates) {
+        table.resize((size_t)std::max<int64_t>(n, 1), 0);
+        for (int64_t j = 0; j < n; ++j) {
+            if (!(rates[j] >= 0.0 && rates[j] <= 1.0))
+                return set_error(LDPC_ERR_INVALID_ARGUMENT, "rates[" + std::to_string(j) + "] must lie in [0, 1] (and not be NaN)");
+            // below 1 the threshold is at most 2^64 - 2^11, so all ones is free as the mark of "always"
+            table[(size_t)j] = rates[j] >= 1.0 ? ~0ull : (tu64)(rates[j] * 18446744073709551616.0);
+        }
+    }
     LDPC_HIP_TRY(hipSetDevice(t->device));
-    const size_t s = (size_t)t->side[0].rows, n = (size_t)t->n, B = (size_t)batch;
-    ldpc_detail::Carve image;   // [errors][syndromes]
-    image.take(B * n);
-    const size_t o_syn = image.take(B * s);
-    st = ldpc_detail::grow_device_buffer(&t->stage, &t->stage_cap, std::max<size_t>(image.at, 256), t->device,
-                                         "trials staging regrow (device synchronise before the free)");
+    if (ldpc_detail::device_stalled(t->device)) return ldpc_detail::stalled_error(t->device);
+    // after every earlier call on the handle: a sample still in flight reads the table it was launched with to its end
+    if (t->calls.have) {
+        const ldpc_status st = ldpc_detail::wait_event(t->calls.done, t->device, "ldpc_trials_set_rates (wait for the earlier calls)");
+        if (st != LDPC_OK) return st;
+    }
+    if (!rates) {
+        if (t->rates) LDPC_HIP_TRY(hipFree(t->rates));
+        t->rates = nullptr;
+        return LDPC_OK;
+    }
+    tu64 *fresh = t->rates;
+    if (!fresh) LDPC_HIP_TRY(hipMalloc((void **)&fresh, table.size() * sizeof(tu64)));
+    const hipError_t e = hipMemcpy(fresh, table.data(), table.size() * sizeof(tu64), hipMemcpyHostToDevice);
+    if (e != hipSuccess && !t->rates) (void)hipFree(fresh);
+    LDPC_HIP_TRY(e);
+    t->rates = fresh;
+    return LDPC_OK;
+}
+
+ldpc_status ldpc_trials_sample_rates_device(ldpc_trials *t, int64_t batch, int64_t column0, uint64_t seed, uint8_t *d_errors,
+                                            uint8_t *d_syndromes, void *stream)
+{
+    const ldpc_status st = check_sample_rates_args(t, batch, column0, d_errors);
     if (st != LDPC_OK) return st;
-    uint8_t *dp = (uint8_t *)t->stage;
-    const bool want_syn = syndromes && s > 0;
-    st = ldpc_trials_sample_device(t, batch, column0, per, seed, dp, want_syn ? dp + o_syn : nullptr, nullptr);
+    if (batch == 0) return LDPC_OK;
+    TrialParams<1> p{};
+    p.column0 = (tu64)column0; p.seed = seed;
+    p.side[0].err_out = d_errors; p.side[0].syn = t->side[0].rows > 0 ? d_syndromes : nullptr;
+    return trials_launch(t, kSampleRates, p, batch, (hipStream_t)stream);
+}
+
+ldpc_status ldpc_trials_sample_rates(ldpc_trials *t, int64_t batch, int64_t column0, uint64_t seed, uint8_t *errors, uint8_t *syndromes)
+{
+    const ldpc_status st = check_sample_rates_args(t, batch, column0, errors);
     if (st != LDPC_OK) return st;
-    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(errors, dp, B * n, hipMemcpyDeviceToHost, nullptr));
-    if (want_syn) LDPC_HIP_TRY(hipMemcpyAsync(syndromes, dp + o_syn, B * s, hipMemcpyDeviceToHost, nullptr));
-    return ldpc_detail::wait_stream(nullptr, t->device, "ldpc_trials_sample (stream synchronise)");
+    if (batch == 0) return LDPC_OK;
+    return sample_to_host(t, batch, errors, syndromes, "ldpc_trials_sample_rates (stream synchronise)", [&](uint8_t *d_errors, uint8_t *d_syndromes) {
+        return ldpc_trials_sample_rates_device(t, batch, column0, seed, d_errors, d_syndromes, nullptr);
+    });
 }
 
 ldpc_status ldpc_trials_score(ldpc_trials *t, int64_t batch, const uint8_t *guesses, const uint8_t *errors, uint8_t *flags,

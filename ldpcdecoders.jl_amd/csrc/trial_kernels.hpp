@@ -8,7 +8,8 @@
 // per qubit and one flag word: side 0 = (ex, gx, sz) seen by Hz and Lz, window [0, tb); side 1 = (ez, gz, sx) seen by Hx
 // and Lx, window [ta, tc).  Side 0's window starts at 0 in both uses and costs no compare.
 //
-// One kernel template serves the side counts (SIDES), the three steps (MODE) and the two tiers (IMAGE):
+// One kernel template serves the side counts (SIDES), the steps (MODE: sample, syndromes, score, and for one side the
+// sample with a rate per bit) and the two tiers (IMAGE):
 //   phase A  the column's bytes are produced (sample: ONE mix per bit position feeds every side) or read (syndromes,
 //            score), 16 contiguous bytes per lane and step, folded to 16 bits with the multiply of bit_io_kernels.hpp.
 //            The 16-byte pieces are laid on the ADDRESS of side 0's column, not on the column: a column starts at byte
@@ -18,6 +19,11 @@
 //            aligned vector access; each other array (side 0's guesses, everything of side 1) is a vector access too
 //            where its column agrees with side 0's in address mod 16, and 16 single-byte accesses where it does not:
 //            correct, and 16 instructions for one.
+//            The per-bit sample (kSampleRates) compares the draw of bit j with entry j of a table of 64-bit thresholds
+//            instead of side 0's `hi`: the 16 entries of a piece are 128 contiguous bytes at 8 j, read as eight 16-byte
+//            loads where j is even and entry by entry where it is odd (8-byte aligned only: the compiler pairs the
+//            inner fourteen into 16-byte loads all the same); the first and the last piece go entry by entry as they
+//            go byte by byte.  Still one mix per bit.
 //            IMAGE: piece c becomes the 16-bit word c of each side's bit image in LDS (bit j of a column is bit
 //            j + shift of its image; a column owns SIDES neighbouring images): plain 2-byte LDS stores, no two lanes
 //            write one word, nothing to clear.
@@ -47,7 +53,7 @@ namespace ldpc_trials_k {
 typedef unsigned long long tu64;
 constexpr int kThreads = 256;
 constexpr tu64 kGolden = 0x9E3779B97F4A7C15ull;
-enum { kSample = 0, kSyndromes = 1, kScore = 2 };
+enum { kSample = 0, kSyndromes = 1, kScore = 2, kSampleRates = 3 };   // kSampleRates: sample, bit j at its own rate (one side only)
 
 // the SplitMix64 finaliser (include/ldpc_mi355x.h)
 __host__ __device__ inline tu64 mix(tu64 z)
@@ -91,6 +97,7 @@ struct TrialParams {
     uint8_t *flags;              // score (may be NULL)
     tu64 *counts;                // score: [trials, b0, b1, b2] or [trials, b0, b1, b2|b3, b2, b3]
     TrialSide side[SIDES];
+    const tu64 *rates;           // kSampleRates: the threshold of every bit, [n]; all ones = always set (no rate below 1 gives it)
 };
 
 __device__ inline unsigned fold16(uint4 x)
@@ -116,6 +123,24 @@ __device__ inline unsigned diff16(const uint8_t *e, bool evec, const uint8_t *g,
     x.x ^= y.x; x.y ^= y.y; x.z ^= y.z; x.w ^= y.w;
     return fold16(x);
 }
+
+// the thresholds of the 16 bits from bit j on: 128 contiguous bytes at 8 j; `vec` says that they are 16-byte aligned (j even)
+__device__ inline void load_thresholds(const tu64 *q, bool vec, tu64 th[16])
+{
+    if (vec) {
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const ulonglong2 v = reinterpret_cast<const ulonglong2 *>(q)[b];
+            th[2 * b] = v.x; th[2 * b + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int b = 0; b < 16; ++b) th[b] = q[b];
+    }
+}
+
+// is a bit of draw r set under threshold t of the rates table
+__device__ inline unsigned under(tu64 r, tu64 t) { return (unsigned)(r < t) | (unsigned)(t == ~0ull); }
 
 // 16 bits -> 16 bytes (0 / 1) at q
 __device__ inline void store16(uint8_t *q, unsigned h, bool vec)
@@ -143,6 +168,8 @@ void trial_kernel(TrialParams<SIDES> p)
 {
     constexpr int GT = 64 * WPC, CPB = kThreads / GT;   // lanes per column, columns per workgroup
     constexpr int NRUN = SIDES == 1 ? 3 : 3 + SIDES;    // running counts: b0, b1, any logical; then each side's logical
+    constexpr bool RATES = MODE == kSampleRates, SAMPLE = MODE == kSample || RATES;
+    static_assert(!RATES || SIDES == 1, "per-bit rates: one side only");
     extern __shared__ unsigned short image_all[];
     __shared__ unsigned int colflags[4], running[NRUN];
     const int slot = threadIdx.x / GT, gl = threadIdx.x % GT;
@@ -167,7 +194,7 @@ void trial_kernel(TrialParams<SIDES> p)
         const uint8_t *ecol[SIDES], *gcol[SIDES];
 #pragma unroll
         for (int k = 0; k < SIDES; ++k) {
-            ecol[k] = (MODE == kSample ? (const uint8_t *)p.side[k].err_out : p.side[k].err) + base;
+            ecol[k] = (SAMPLE ? (const uint8_t *)p.side[k].err_out : p.side[k].err) + base;
             gcol[k] = MODE == kScore ? p.side[k].guess + base : nullptr;
         }
         const int shift = (int)((uintptr_t)ecol[0] & 15);
@@ -179,12 +206,18 @@ void trial_kernel(TrialParams<SIDES> p)
 #pragma unroll
             for (int k = 0; k < SIDES; ++k) gvec[k] = MODE == kScore && (((uintptr_t)gcol[k] - (uintptr_t)ecol[0]) & 15) == 0;
             const int npieces = (shift + n + 15) >> 4;
-            const tu64 key = MODE == kSample ? mix(p.seed + kGolden * (p.column0 + (tu64)col + 1)) : 0;
+            const tu64 key = SAMPLE ? mix(p.seed + kGolden * (p.column0 + (tu64)col + 1)) : 0;
             for (int c = gl; c < npieces; c += GT) {
                 const int j = 16 * c - shift;
                 unsigned h[SIDES] = {};
                 if (j >= 0 && j + 16 <= n) {
-                    if (MODE == kSample) {
+                    if constexpr (RATES) {
+                        tu64 th[16];
+                        load_thresholds(p.rates + j, (j & 1) == 0, th);
+#pragma unroll
+                        for (int b = 0; b < 16; ++b) h[0] |= under(mix(key + (tu64)(j + b)), th[b]) << b;
+                        store16(p.side[0].err_out + base + j, h[0], true);
+                    } else if (MODE == kSample) {
 #pragma unroll
                         for (int b = 0; b < 16; ++b) {
                             const tu64 r = mix(key + (tu64)(j + b));
@@ -204,11 +237,14 @@ void trial_kernel(TrialParams<SIDES> p)
                     for (int b = 0; b < 16; ++b) {
                         const int jb = j + b;
                         if (jb < 0 || jb >= n) continue;
-                        const tu64 r = MODE == kSample ? mix(key + (tu64)jb) : 0;
+                        const tu64 r = SAMPLE ? mix(key + (tu64)jb) : 0;
 #pragma unroll
                         for (int k = 0; k < SIDES; ++k) {
                             unsigned bit;
-                            if (MODE == kSample) {
+                            if constexpr (RATES) {
+                                bit = under(r, p.rates[jb]);
+                                p.side[0].err_out[base + jb] = (uint8_t)bit;
+                            } else if (MODE == kSample) {
                                 bit = (unsigned)((k == 0 || r >= p.side[k].lo) && r < p.side[k].hi);
                                 if (SIDES == 1 && p.all_ones) bit = 1u;
                                 p.side[k].err_out[base + jb] = (uint8_t)bit;

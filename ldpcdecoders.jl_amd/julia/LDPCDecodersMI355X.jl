@@ -25,7 +25,7 @@ import LDPCDecoders: AbstractDecoder, decode!, batchdecode!, reset!
 export MI355XBeliefPropagationDecoder, MI355XBeliefPropagationOSDDecoder, MI355XBPOTSDecoder, MI355XBitFlipDecoder
 export MI355XMinSumDecoder
 export MI355XRelayDecoder
-export Trials, sample!, score!
+export Trials, sample!, score!, set_rates!, sample_rates!, sample_rates_device!
 export CSSTrials
 
 const libldpc = get(ENV, "LDPC_MI355X_LIB", "libldpc_mi355x.so")
@@ -662,6 +662,50 @@ function sample!(t::Trials, errors::Union{Matrix{UInt8},Matrix{Bool}}, syndromes
                 (Ptr{Cvoid}, Int64, Int64, Float64, UInt64, Ptr{UInt8}, Ptr{UInt8}),
                 t.handle, size(errors, 2), column0, per, UInt64(seed), errors, syndromes))
     return errors, syndromes
+end
+
+"""
+    set_rates!(t, rates)
+
+One rate per bit (`rates[j]` in [0, 1], length n) for `sample_rates!`; `nothing` clears them.  Synchronous, and ordered
+after every earlier call on the handle.
+"""
+function set_rates!(t::Trials, rates::Union{Nothing,AbstractVector{<:Real}})
+    if rates === nothing
+        check(ccall((:ldpc_trials_set_rates, libldpc), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), t.handle, t.n, C_NULL))
+        return t
+    end
+    length(rates) == t.n || throw(DimensionMismatch("one rate per bit"))
+    check(ccall((:ldpc_trials_set_rates, libldpc), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), t.handle, t.n, Vector{Float64}(rates)))
+    return t
+end
+
+"""
+    sample_rates!(t, errors, syndromes; seed=0, column0=0)
+
+`sample!` with bit `j` drawn at `rates[j]` (`set_rates!`): equal to `sample!` in every element where all rates are equal.
+"""
+function sample_rates!(t::Trials, errors::Union{Matrix{UInt8},Matrix{Bool}}, syndromes::Union{Matrix{UInt8},Matrix{Bool}};
+                       seed::Integer=0, column0::Integer=0)
+    size(errors, 1) == t.n && size(syndromes, 1) == t.s || throw(DimensionMismatch("errors / syndromes rows"))
+    @assert size(errors, 2) == size(syndromes, 2)
+    check(ccall((:ldpc_trials_sample_rates, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Int64, UInt64, Ptr{UInt8}, Ptr{UInt8}),
+                t.handle, size(errors, 2), column0, UInt64(seed), errors, syndromes))
+    return errors, syndromes
+end
+
+"""
+    sample_rates_device!(t, batch, d_errors, d_syndromes; seed=0, column0=0, stream=C_NULL)
+
+The same with DEVICE pointers (`d_syndromes` may be `C_NULL`), asynchronous on `stream`.
+"""
+function sample_rates_device!(t::Trials, batch::Integer, d_errors::Ptr{UInt8}, d_syndromes::Ptr{UInt8};
+                              seed::Integer=0, column0::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    check(ccall((:ldpc_trials_sample_rates_device, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Int64, UInt64, Ptr{UInt8}, Ptr{UInt8}, Ptr{Cvoid}),
+                t.handle, batch, column0, UInt64(seed), d_errors, d_syndromes, stream))
+    return nothing
 end
 
 """

@@ -3,7 +3,8 @@
 `syndromes = H * errors .% 2`, decode, `guesses[:, i] == errors[:, i]`, an error rate -- over the ldpc_trials_* entry
 points, so that the batch never leaves the GPU.  The sampling, syndrome and score rules are stated in
 include/ldpc_mi355x.h; `run_trials` loops sample -> a decoder's device entry -> score and reads back the four
-counts and the number of unconverged columns."""
+counts and the number of unconverged columns.  A handle may hold one rate per bit (`set_rates`; `sample_rates` then
+draws bit j at its own rate by the same rule): biased noise, the columns of a detector error model (dem.py)."""
 from __future__ import annotations
 
 import ctypes
@@ -58,6 +59,7 @@ class Trials:
             int(lrowval.size) if lrowval is not None else 0, lcolptr.ctypes.data if lcolptr is not None else None,
             lrowval.ctypes.data if lrowval is not None else None, ctypes.byref(opts), ctypes.byref(self._h)), self._L)
         self.device = device
+        self.rates = None   # the array handed to set_rates, or None
 
     @property
     def kernel(self) -> int:
@@ -81,12 +83,10 @@ class Trials:
         return torch.device("cuda", int(self.device))
 
     # -- device forms (torch tensors, asynchronous on `stream`: a hipStream_t as int, default torch's current stream) --
-    def sample(self, batch: int, per: float, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
-        """-> (errors [batch][n] u8, syndromes [batch][s] u8).  `out` = (errors, syndromes) to write into; a
-        syndromes of None there skips them (errors only)."""
+    def _sample_out(self, B: int, out, stream):
+        """The (errors, syndromes) tensors of a sample and its stream."""
         import torch
 
-        B = int(batch)
         if out is None:
             dev = self._torch_device()
             err = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
@@ -98,8 +98,37 @@ class Trials:
                 assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, cols)
         if stream is None:
             stream = torch.cuda.current_stream(err.device).cuda_stream
+        return err, syn, stream
+
+    def sample(self, batch: int, per: float, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
+        """-> (errors [batch][n] u8, syndromes [batch][s] u8).  `out` = (errors, syndromes) to write into; a
+        syndromes of None there skips them (errors only)."""
+        B = int(batch)
+        err, syn, stream = self._sample_out(B, out, stream)
         _capi.check(self._L.ldpc_trials_sample_device(self._h, B, int(column0), float(per), int(seed) & _M64, err.data_ptr(),
                                                       syn.data_ptr() if syn is not None else None, ctypes.c_void_p(stream)),
+                    self._L)
+        return err, syn
+
+    def set_rates(self, rates) -> None:
+        """One rate per bit (array-like of n floats in [0, 1]) for `sample_rates`; None clears them.  Synchronous, and
+        ordered after every earlier call on the handle."""
+        if rates is None:
+            _capi.check(self._L.ldpc_trials_set_rates(self._h, self.n, None), self._L)
+            self.rates = None
+            return
+        r = np.ascontiguousarray(rates, dtype=np.float64)
+        if r.shape != (self.n,):
+            raise ValueError(f"one rate per bit: expected {self.n} entries, got shape {r.shape}")
+        _capi.check(self._L.ldpc_trials_set_rates(self._h, self.n, r.ctypes.data), self._L)
+        self.rates = r
+
+    def sample_rates(self, batch: int, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
+        """`sample` with bit j drawn at rates[j] (`set_rates`); equal to `sample` in every element where all rates are equal."""
+        B = int(batch)
+        err, syn, stream = self._sample_out(B, out, stream)
+        _capi.check(self._L.ldpc_trials_sample_rates_device(self._h, B, int(column0), int(seed) & _M64, err.data_ptr(),
+                                                            syn.data_ptr() if syn is not None else None, ctypes.c_void_p(stream)),
                     self._L)
         return err, syn
 
@@ -146,6 +175,14 @@ class Trials:
         syn = np.empty((B, self.s), dtype=np.uint8)
         _capi.check(self._L.ldpc_trials_sample(self._h, B, int(column0), float(per), int(seed) & _M64, err.ctypes.data,
                                                syn.ctypes.data), self._L)
+        return err, syn
+
+    def sample_rates_host(self, batch: int, seed: int = 0, column0: int = 0):
+        B = int(batch)
+        err = np.empty((B, self.n), dtype=np.uint8)
+        syn = np.empty((B, self.s), dtype=np.uint8)
+        _capi.check(self._L.ldpc_trials_sample_rates(self._h, B, int(column0), int(seed) & _M64, err.ctypes.data, syn.ctypes.data),
+                    self._L)
         return err, syn
 
     def score_host(self, guesses, errors, counts=None):
@@ -204,24 +241,33 @@ def _device_decode(decoder, syn, err, conv, first_trial: int):
     return err
 
 
-def run_trials(decoder, trials: int, per: Optional[float] = None, batch: int = 65536, seed: int = 0, logicals=None) -> TrialResult:
+def run_trials(decoder, trials: int, per=None, batch: int = 65536, seed: int = 0, logicals=None) -> TrialResult:
     """`trials` Monte-Carlo trials of `decoder` (BP, BP+OSD, BP-OTS or bit-flip) at physical error rate `per`
     (default: the decoder's): sample -> decode -> score in batches of `batch` (the last one ragged) on torch's current
     stream of the decoder's GPU; trial number c is column c of the sampling rule (and of the bit-flip tie rule), so the
-    result does not depend on `batch`.  Only the four counts and the number of unconverged columns are read back."""
+    result does not depend on `batch`.  Only the four counts and the number of unconverged columns are read back.
+    `per` may be an array-like of one rate per bit instead: the rates are set once and every batch is drawn with
+    `sample_rates`."""
     import torch
 
     from .osd import BeliefPropagationOSDDecoder
 
     bp = decoder.bp_decoder if isinstance(decoder, BeliefPropagationOSDDecoder) else decoder
+    rates = None
     if per is None:
         per = bp.per
+    elif np.ndim(per) > 0:
+        rates = np.ascontiguousarray(per, dtype=np.float64)
+        if rates.shape != (int(bp.sparse_H.shape[1]),):
+            raise ValueError(f"one rate per bit: expected {int(bp.sparse_H.shape[1])} entries, got shape {rates.shape}")
     device = bp.info().device if hasattr(bp, "info") else torch.cuda.current_device()
     dev = torch.device("cuda", int(device))
     total, batch = int(trials), int(batch)
     assert total >= 0 and batch > 0
     tr = Trials(bp.sparse_H, logicals, device=int(device))
     try:
+        if rates is not None:
+            tr.set_rates(rates)
         with torch.cuda.device(dev):
             counts = torch.zeros(4, dtype=torch.int64, device=dev)
             unconverged = torch.zeros((), dtype=torch.int64, device=dev)
@@ -234,7 +280,10 @@ def run_trials(decoder, trials: int, per: Optional[float] = None, batch: int = 6
             while done < total:
                 b = min(B, total - done)
                 e, sy, gu, cv = err[:b], syn[:b], guess[:b], conv[:b]
-                tr.sample(b, per, seed=seed, column0=done, out=(e, sy))
+                if rates is None:
+                    tr.sample(b, per, seed=seed, column0=done, out=(e, sy))
+                else:
+                    tr.sample_rates(b, seed=seed, column0=done, out=(e, sy))
                 guesses = _device_decode(decoder, sy, gu, cv, done)
                 tr.score(guesses, e, counts=counts, want_flags=False)
                 unconverged += (cv == 0).sum()
