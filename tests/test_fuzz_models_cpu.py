@@ -1,0 +1,68 @@
+"""tools/fuzz_models.py without a GPU: the draws of the committed seeds are reproducible, together they contain the shapes
+the tool is there for, and the models run a case to the end."""
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOOL = os.path.join(ROOT, "tools", "fuzz_models.py")
+CASES, SEEDS = 40, (20, 21)      # what tests/test_gpu_fuzz_models.py runs on the GPU
+
+CASE = re.compile(r"^case (\d+): kind (\d) shape \((\d+), (\d+)\) nnz (\d+) B (\d+) checks<=32 (\d+) checks33-64 (\d+) checks>64 (\d+) "
+                  r"empty_checks (\d+) empty_bits (\d+) max_bit_degree (\d+)$")
+
+
+def _tool(args, **env):
+    out = subprocess.run([sys.executable, TOOL] + [str(a) for a in args], capture_output=True, text=True, cwd=ROOT, timeout=600,
+                         env={**os.environ, **env})
+    assert out.returncode == 0 and "fuzz ok" in out.stdout.splitlines()[-1], out.stdout[-2000:] + out.stderr[-2000:]
+    return out.stdout
+
+
+def coverage(listing):
+    """The properties of the issue that the cases of a FUZZ_DRY listing have, as a set of names."""
+    have = set()
+    for line in listing.splitlines():
+        m = CASE.match(line)
+        if not m:
+            continue
+        _, _, s, n, _, B, c32, c64, cbig, ec, eb, bdeg = (int(x) for x in m.groups())
+        have |= {name for name, yes in (
+            ("check of degree <= 32", c32 > 0), ("check of degree 33 ... 64", c64 > 0), ("check of degree > 64", cbig > 0),
+            ("empty check", ec > 0), ("empty bit", eb > 0), ("bit of degree > 64", bdeg > 64), ("n % 64 == 0", n % 64 == 0),
+            ("n % 64 == 1", n % 64 == 1), ("n % 64 == 63", n % 64 == 63), ("n % 32 == 1", n % 32 == 1), ("batch 1", B == 1),
+            ("batch 65", B == 65)) if yes}
+    return have
+
+
+WANTED = {"check of degree <= 32", "check of degree 33 ... 64", "check of degree > 64", "empty check", "empty bit", "bit of degree > 64",
+          "n % 64 == 0", "n % 64 == 1", "n % 64 == 63", "n % 32 == 1", "batch 1", "batch 65"}
+
+
+def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_the_boundary_shapes():
+    have = set()
+    for seed in SEEDS:
+        first = _tool([CASES, seed], FUZZ_DRY="1")
+        again = _tool([CASES, seed], FUZZ_DRY="1")
+        strip = lambda text: "\n".join(text.splitlines()[:-1])   # noqa: E731  (the last line carries seconds)
+        assert strip(first) == strip(again), f"seed {seed}: two dry runs list different cases"
+        assert len([ln for ln in first.splitlines() if CASE.match(ln)]) == CASES
+        # every leg of every case is listed: the draws do not depend on what ran
+        for leg in ("bitflip", "minsum", "relay", "osd", "trials", "css"):
+            assert len([ln for ln in first.splitlines() if ln.startswith(f"   {leg} ")]) == CASES, leg
+        have |= coverage(first)
+    assert have == WANTED, f"the committed seeds never draw: {sorted(WANTED - have)}"
+
+
+def test_a_window_of_cases_draws_what_the_whole_run_draws():
+    """FUZZ_FROM / FUZZ_TO skip cases without changing the later draws."""
+    whole = _tool([6, SEEDS[0]], FUZZ_DRY="1", FUZZ_VERBOSE="1")
+    window = _tool([6, SEEDS[0]], FUZZ_MODEL_ONLY="1", FUZZ_VERBOSE="1", FUZZ_FROM="4", FUZZ_TO="4")
+    listed = lambda text: [ln for ln in text.splitlines() if ln.startswith(("case ", "   "))]   # noqa: E731
+    assert listed(whole) == listed(window)
+
+
+def test_one_case_runs_through_the_models_to_the_end():
+    out = _tool([3, SEEDS[0]], FUZZ_MODEL_ONLY="1", FUZZ_FROM="2", FUZZ_TO="2")
+    assert "model seconds: bitflip" in out and "through the models only" in out.splitlines()[-1]

@@ -1,0 +1,543 @@
+#!/usr/bin/env python3
+"""Randomised model-parity fuzz (GPU box) of the kernels that tools/fuzz_parity.py does not reach: the bit-flip decoder,
+min-sum, relay min-sum, the device OSD step, and the one-matrix and CSS trial steps.  Random Tanner graphs (irregular with
+empty and heavy nodes and sizes around the word boundaries, or small Gallager codes), ragged batches, every
+`kernel_variant` that create accepts, every result compared in every element with the numpy models of tests/ (min-sum
+and relay: the LLR bit patterns too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
+
+FUZZ_DRY=1: draw the cases and print them without touching the GPU or a model (no draw depends on a result, so this lists
+what a run with the same seed decodes); FUZZ_FROM / FUZZ_TO: only run the cases with these indices (the others are drawn
+and skipped); FUZZ_VERBOSE=1: one line per leg BEFORE it runs; FUZZ_MODEL_ONLY=1: no GPU, the models alone, with their
+seconds.  A leg is skipped only when create answers UNSUPPORTED for an on-chip tier; every component decodes every case on
+its unlimited tier.  The leg in hand is kept in fuzz_models_current.txt and, on a mismatch (exit status 1), the inputs in
+fuzz_models_failure.npz, both in the directory FUZZ_OUT (default: fuzz_out/ in the repository root, which git ignores)."""
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))     # the models are test infrastructure
+import ldpcdecoders_jl_amd as ldpc  # noqa: E402
+import css_trials_model as cm  # noqa: E402
+import dem_model as dm  # noqa: E402
+import trials_model as tm  # noqa: E402
+from bitflip_model import BitFlipModel  # noqa: E402
+from minsum_model import MinSumModel, llr_of_probs  # noqa: E402
+from osd_model import osd_model_postprocess  # noqa: E402
+from relay_model import RelayModel  # noqa: E402
+
+DRY = os.environ.get("FUZZ_DRY") == "1"
+FROM, TO = int(os.environ.get("FUZZ_FROM", "0")), int(os.environ.get("FUZZ_TO", str(1 << 60)))
+VERBOSE = os.environ.get("FUZZ_VERBOSE") == "1"
+MODEL_ONLY = os.environ.get("FUZZ_MODEL_ONLY") == "1"
+GPU = not (DRY or MODEL_ONLY)
+OUT = os.environ.get("FUZZ_OUT") or os.path.join(ROOT, "fuzz_out")
+UNSUPPORTED = 5
+# tiers a component can take here; the last one is its unlimited tier.  (Bit-flip tier 4, the 64-bit votes, needs
+# max_iters * max bit degree >= 2^31 and is held by test_unlimited_tier_with_64_bit_votes.)
+TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2)}
+BOUNDARY = (31, 32, 33, 63, 64, 65, 127, 128, 129)
+
+if GPU:
+    import torch
+
+    # every host-side wait of the library is bounded (host_wait.hpp): on these small graphs no leg needs more than
+    # seconds, so a stall names itself after 40 s instead of sitting silent until the runner's limit
+    for exp_build in (False, True):
+        ldpc._capi.check(ldpc._capi.lib(exp_build).ldpc_set_wait_limit_ms(int(os.environ.get("FUZZ_WAIT_LIMIT_MS", "40000"))),
+                         ldpc._capi.lib(exp_build))
+
+ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+rng = np.random.default_rng(seed)
+t0 = time.time()
+ran = {c: set() for c in TIERS}          # tiers that decoded
+legs_run = {c: 0 for c in TIERS}
+skipped = {c: 0 for c in TIERS}
+model_s = {c: 0.0 for c in TIERS}
+case = -1
+
+
+def note(component, text):
+    """What is about to run, where a run that stalls leaves it behind."""
+    if VERBOSE:
+        print(f"   {component}: {text}", flush=True)
+    try:
+        os.makedirs(OUT, exist_ok=True)
+        with open(os.path.join(OUT, "fuzz_models_current.txt"), "w") as fh:
+            fh.write(f"seed {seed} case {case} after {time.time() - t0:.0f} s: {component}: {text}\n")
+    except OSError:
+        pass
+
+
+def fail(component, text, **arrays):
+    try:
+        os.makedirs(OUT, exist_ok=True)
+        np.savez(os.path.join(OUT, "fuzz_models_failure.npz"), component=component, text=text, seed=seed, case=case,
+                 **{k: np.asarray(v) for k, v in arrays.items() if v is not None})
+    except OSError:
+        pass
+    print(f"MISMATCH seed {seed} case {case} {component}: {text}", flush=True)
+    sys.exit(1)
+
+
+def same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+def same_bits(llr64, model32):
+    """The library's float64 LLRs against the model's float32 ones, as bit patterns."""
+    return llr64.dtype == np.float64 and np.array_equal(llr64.view(np.int64), model32.astype(np.float64).view(np.int64))
+
+
+def timed_model(component, f):
+    t = time.time()
+    out = f()
+    model_s[component] += time.time() - t
+    return out
+
+
+def on_every_tier(component, variants, create, run, text):
+    """create(variant) -> handle (LdpcError UNSUPPORTED for an on-chip tier: the leg is skipped); run(handle, tier)
+    compares; the unlimited tier must run."""
+    unlimited = TIERS[component][-1]
+    for variant in variants:
+        note(component, f"kernel_variant {variant} {text}")
+        try:
+            h = create(variant)
+        except ldpc.LdpcError as e:
+            if e.status == UNSUPPORTED and variant != unlimited:
+                skipped[component] += 1
+                continue
+            raise
+        tier = int(h.kernel)
+        if tier != variant:
+            fail(component, f"kernel_variant {variant} gave tier {tier} {text}")
+        run(h, variant)
+        h.close()
+        ran[component].add(tier)
+        legs_run[component] += 1
+        if variant == unlimited:
+            break
+    else:
+        fail(component, f"the unlimited tier did not run {text}")
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+class Guarded:
+    """A [rows][cols] uint8 device array at byte offset `off` inside a larger buffer of guard bytes."""
+
+    def __init__(self, rows, cols, off, fill=0xA5):
+        self.off, self.size, self.fill = int(off), rows * cols, fill
+        self.buf = torch.full((self.off + self.size + 64,), fill, dtype=torch.uint8, device="cuda")
+        self.view = self.buf[self.off:self.off + self.size].view(rows, cols)
+
+    def put(self, a):
+        self.view.copy_(dev(np.ascontiguousarray(a, dtype=np.uint8)))
+        return self.view
+
+    def guards_intact(self):
+        return bool((self.buf[:self.off] == self.fill).all()) and bool((self.buf[self.off + self.size:] == self.fill).all())
+
+    def get(self):
+        return self.view.cpu().numpy()
+
+
+# ---- the draws ---------------------------------------------------------------------------------------------------------
+def draw_graph():
+    kind = int(rng.integers(0, 4))
+    if kind == 3:      # a small Gallager code
+        wr, wc = int(rng.choice([4, 6, 8])), int(rng.choice([2, 3, 4]))
+        n = wr * int(rng.integers(4, 40))
+        H = ldpc.codes.parity_check_csc(n, wr, wc, seed=int(rng.integers(1 << 30)))
+    else:              # irregular, with empty and heavy nodes and sizes at the word boundaries now and then
+        s, n = int(rng.integers(1, 81)), int(rng.integers(1, 161))
+        if rng.random() < 0.35:
+            n = int(rng.choice(BOUNDARY))
+        if rng.random() < 0.25:
+            s = int(rng.choice(BOUNDARY[:6]))
+        A = (rng.random((s, n)) < rng.uniform(0.02, 0.25)).astype(np.uint8)
+        if rng.random() < 0.3:
+            A[rng.integers(0, s), :] = 0
+        if rng.random() < 0.3:
+            A[:, rng.integers(0, n)] = 0
+        if rng.random() < 0.3 and n >= 33:        # a row of 33 ... 80 ones
+            A[rng.integers(0, s), rng.choice(n, size=min(n, int(rng.integers(33, 81))), replace=False)] = 1
+        if rng.random() < 0.3 and s >= 20:        # a column of 20 ... s ones
+            k = s if rng.random() < 0.4 else int(rng.integers(20, s + 1))
+            A[rng.choice(s, size=k, replace=False), rng.integers(0, n)] = 1
+        H = sp.csc_matrix(A)
+    H.sort_indices()
+    return kind, H
+
+
+def draw_syndromes(H, B):
+    """Syndromes of random errors, or arbitrary ones."""
+    s, n = H.shape
+    if rng.random() < 0.6:
+        return ldpc.codes.syndromes_of(H, (rng.random((B, n)) < rng.uniform(0.01, 0.2)).astype(np.uint8))
+    return rng.integers(0, 2, (B, s)).astype(np.uint8)
+
+
+def draw_priors(n):
+    """Per-bit prior LLRs with a few negative, +-0 and subnormal ones."""
+    prior = llr_of_probs(rng.uniform(0.005, 0.45, n))
+    for value in (None, 0.0, -0.0, 1e-40, -1e-41):
+        hit = rng.random(n) < 0.04
+        prior[hit] = -prior[hit] if value is None else np.float32(value)
+    return prior
+
+
+# ---- the legs ----------------------------------------------------------------------------------------------------------
+def leg_bitflip(H, B, run):
+    s, n = H.shape
+    rule = int(rng.integers(0, 3))
+    bf_seed = int(rng.integers(0, 1 << 64, dtype=np.uint64))
+    max_iters = int(rng.choice([0, 1, 5, 30]))
+    column0 = int(rng.choice([0, 5, (1 << 32) + 7, 1 << 40]))
+    device_entry = bool(rng.random() < 0.5)
+    syn = draw_syndromes(H, B)
+    if rng.random() < 0.25:
+        hit = rng.random(syn.shape) < 0.05
+        syn[hit] = rng.integers(2, 4, size=int(hit.sum()))
+    text = f"rule {rule} seed {bf_seed} max_iters {max_iters} column0 {column0} {'device' if device_entry else 'host'} entry"
+    if DRY or VERBOSE:
+        print(f"   bitflip {text}", flush=True)
+    if not run:
+        return
+    want = timed_model("bitflip", lambda: BitFlipModel(H, max_iters).decode_batch(syn, rule, seed=bf_seed, column0=column0))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if device_entry:
+            err = torch.full((B, n), 9, dtype=torch.uint8, device="cuda")
+            conv, stop = torch.full((B,), 9, dtype=torch.uint8, device="cuda"), torch.full((B,), 9, dtype=torch.uint8, device="cuda")
+            its = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+            dec.decode_batch_device(dev(syn), err, conv, its, stop, column0=column0)
+            torch.cuda.synchronize()
+            got = tuple(x.cpu().numpy() for x in (err, conv, its, stop))
+        else:
+            got = dec.decode_batch_host(syn, column0=column0)
+        for name, g, w in zip(("errors", "converged", "iters", "stop_reason"), got, want):
+            if not same(g, w):
+                fail("bitflip", f"{name} differ, kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape,
+                     syn=syn, got=g, want=w)
+
+    on_every_tier("bitflip", (1, 2, 3), lambda v: ldpc.BitFlipDecoder(H, 0.01, max_iters, tie_break=rule, seed=bf_seed, kernel_variant=v),
+                  go, text)
+
+
+def leg_minsum(H, B, run):
+    s, n = H.shape
+    alpha, clip = float(rng.choice([0.5, 0.75, 1.0])), float(rng.choice([4.0, 20.0, 1e6]))
+    max_iters = int(rng.choice([0, 1, 3, 20]))
+    prior = draw_priors(n)
+    device_entry = bool(rng.random() < 0.5)
+    syn = draw_syndromes(H, B)
+    text = f"alpha {alpha} clip {clip} max_iters {max_iters} {'device' if device_entry else 'host'} entry"
+    if DRY or VERBOSE:
+        print(f"   minsum {text}", flush=True)
+    if not run:
+        return
+    merr, mconv, mits, mL = timed_model("minsum", lambda: MinSumModel(H, prior, max_iters, alpha=alpha, clip=clip).decode(syn))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if device_entry:
+            err, conv = torch.full((B, n), 7, dtype=torch.uint8, device="cuda"), torch.full((B,), 7, dtype=torch.uint8, device="cuda")
+            llr = torch.full((B, n), 7.0, dtype=torch.float64, device="cuda")
+            its = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+            dec.decode_batch_device(dev(syn), err, conv, llr, its)
+            torch.cuda.synchronize()
+            err, conv, llr, its = (x.cpu().numpy() for x in (err, conv, llr, its))
+        else:
+            err, conv, llr, its = dec.decode_batch_host(syn, want_llr=True)
+        ok = same(err, merr) and same(conv, mconv) and same(its, mits) and same_bits(llr, mL)
+        if not ok:
+            fail("minsum", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, prior=prior,
+                 err=err, conv=conv, its=its, llr=llr, merr=merr, mconv=mconv, mits=mits, mL=mL)
+
+    on_every_tier("minsum", (1, 2), lambda v: ldpc.MinSumDecoder(H, None, max_iters, channel_llr=prior, alpha=alpha, clip=clip, kernel_variant=v),
+                  go, text)
+
+
+class RelayPerLeg(ldpc.RelayMinSumDecoder):
+    """A RelayMinSumDecoder with an iteration count of its own for every leg: ldpc_relay_create takes one per leg, the
+    class's constructor gives leg 0 one count and all later legs another.  The decode methods are the class's."""
+
+    def __init__(self, H, prior, gammas, leg_iters, stop_after, alpha, clip, kernel_variant):
+        import ctypes
+
+        capi = ldpc._capi
+        M = ldpc.decoder._pattern_of(H)
+        self.s, self.n, self.sparse_H = int(M.shape[0]), int(M.shape[1]), M
+        self.channel_llr = np.ascontiguousarray(prior, dtype=np.float32)
+        self.gammas = np.ascontiguousarray(gammas, dtype=np.float32)
+        self.leg_iters = np.ascontiguousarray(leg_iters, dtype=np.int32)
+        self.legs = int(self.leg_iters.size)
+        assert self.channel_llr.shape == (self.n,) and self.gammas.shape == (self.legs, self.n)
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        opts = capi.RelayOptions()
+        opts.device = 0
+        opts.alpha, opts.clip = float(alpha), float(clip)
+        opts.kernel_variant, opts.stop_after = int(kernel_variant), int(stop_after)
+        self.device = 0
+        self._h = ctypes.c_void_p()
+        self._L = capi.lib_for(None)
+        capi.check(self._L.ldpc_relay_create(self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
+                                             self.channel_llr.ctypes.data, self.legs, self.gammas.ctypes.data,
+                                             self.leg_iters.ctypes.data, ctypes.byref(opts), ctypes.byref(self._h)), self._L)
+
+
+def leg_relay(H, B, run):
+    s, n = H.shape
+    legs = int(rng.integers(1, 5))
+    leg_iters = [int(x) for x in rng.integers(0, 9, size=legs)]      # a leg of 0 iterations is skipped, wherever it stands
+    gammas = rng.uniform(-0.3, 0.9, size=(legs, n)).astype(np.float32)
+    stop_after = int(rng.integers(1, 4))
+    alpha, clip = float(rng.choice([0.5, 0.75, 1.0])), float(rng.choice([4.0, 20.0, 1e6]))
+    prior = draw_priors(n)
+    device_entry, want_solutions = bool(rng.random() < 0.5), bool(rng.random() < 0.5)
+    syn = draw_syndromes(H, B)
+    text = (f"leg_iters {leg_iters} stop_after {stop_after} alpha {alpha} clip {clip} {'device' if device_entry else 'host'} entry "
+            f"solutions={want_solutions}")
+    if DRY or VERBOSE:
+        print(f"   relay {text}", flush=True)
+    if not run:
+        return
+    merr, mconv, mits, msol, mM = timed_model(
+        "relay", lambda: RelayModel(H, prior, gammas, leg_iters, alpha=alpha, clip=clip, stop_after=stop_after).decode(syn))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if device_entry:
+            err, conv = torch.full((B, n), 7, dtype=torch.uint8, device="cuda"), torch.full((B,), 7, dtype=torch.uint8, device="cuda")
+            llr = torch.full((B, n), 7.0, dtype=torch.float64, device="cuda")
+            its = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+            sol = torch.full((B,), -7, dtype=torch.int32, device="cuda") if want_solutions else None
+            dec.decode_batch_device(dev(syn), err, conv, llr, its, sol)
+            torch.cuda.synchronize()
+            err, conv, llr, its = (x.cpu().numpy() for x in (err, conv, llr, its))
+            sol = sol.cpu().numpy() if want_solutions else None
+        else:
+            out = dec.decode_batch_host(syn, want_llr=True, want_solutions=want_solutions)
+            err, conv, llr, its = out[:4]
+            sol = out[4] if want_solutions else None
+        ok = same(err, merr) and same(conv, mconv) and same(its, mits) and same_bits(llr, mM) and (sol is None or same(sol, msol))
+        if not ok:
+            fail("relay", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, prior=prior,
+                 gammas=gammas, leg_iters=leg_iters, err=err, conv=conv, its=its, llr=llr, sol=sol, merr=merr, mconv=mconv, mits=mits,
+                 msol=msol, mM=mM)
+
+    on_every_tier("relay", (1, 2), lambda v: RelayPerLeg(H, prior, gammas, leg_iters, stop_after, alpha, clip, v), go, text)
+
+
+def leg_osd(H, B, run):
+    s, n = H.shape
+    order = int(rng.integers(0, 9))
+    inplace = bool(rng.random() < 0.5)
+    Bo = min(B, 65)      # (the model is one dense elimination and 2^order candidates per syndrome)
+    # consistent syndromes only: the estimate for a syndrome outside the column space of H is not specified
+    syn = ldpc.codes.syndromes_of(H, (rng.random((Bo, n)) < 0.1).astype(np.uint8))
+    bp_err = (rng.random((Bo, n)) < 0.1).astype(np.uint8)
+    llr = -np.exp(rng.uniform(-8, 1, (Bo, n)))
+    llr[rng.random((Bo, n)) < 0.3] = llr[0, 0]       # ties
+    if rng.random() < 0.3:
+        llr[rng.random((Bo, n)) < 0.05] = np.nan
+        llr[rng.random((Bo, n)) < 0.03] = -np.inf
+        llr[rng.random((Bo, n)) < 0.03] = np.inf
+    text = f"order {order} batch {Bo} {'in place' if inplace else 'out of place'}"
+    if DRY or VERBOSE:
+        print(f"   osd {text}", flush=True)
+    if not run:
+        return
+    Hd = np.asarray(H.todense()).astype(np.uint8)
+    want = timed_model("osd", lambda: np.stack([osd_model_postprocess(Hd, syn[b], bp_err[b], llr[b], order) for b in range(Bo)]))
+    if not GPU:
+        return
+
+    class Post:
+        def __init__(self, variant):
+            self.post = ldpc.OSDPostProcessor(H, order)
+            try:
+                self.post.prepare_device(0, variant)
+            except ldpc.LdpcError:
+                self.post.close()
+                raise
+            self.kernel = self.post.kernel
+
+        def close(self):
+            self.post.close()
+
+    def go(h, variant):
+        d_err = dev(bp_err)
+        out = h.post.postprocess_device(dev(syn), d_err, dev(llr), out=d_err if inplace else None)
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        if not same(got, want) or not (inplace or same(d_err.cpu().numpy(), bp_err)):
+            fail("osd", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, bp_err=bp_err,
+                 llr=llr, got=got, want=want)
+
+    on_every_tier("osd", (1, 2, 3), Post, go, text)
+
+
+def draw_offsets(k):
+    return [int(x) for x in rng.integers(0, 16, size=k)]
+
+
+def leg_trials(H, B, run):
+    s, n = H.shape
+    nl = int(rng.integers(0, 6))
+    L = sp.csc_matrix((rng.random((nl, n)) < rng.uniform(0.05, 0.5)).astype(np.uint8)) if nl else None
+    per = float(rng.choice([0.0, 1.0, 1e-12, 0.02, 0.3, 0.5]))
+    rates = rng.uniform(0.0, 1.0, n) ** 3
+    rates[rng.random(n) < 0.1] = 0.0
+    rates[rng.random(n) < 0.1] = 1.0
+    rates[rng.random(n) < 0.1] = 1e-12
+    tr_seed = int(rng.integers(0, 1 << 64, dtype=np.uint64))
+    column0 = int(rng.choice([0, 3, (1 << 32) + 1, 1 << 40]))
+    given = rng.integers(0, 2, (B, n)).astype(np.uint8)
+    if rng.random() < 0.3:
+        given |= (rng.integers(0, 128, (B, n)) << 1).astype(np.uint8)      # only the low bit of an error byte counts
+    guesses = given ^ (rng.random((B, n)) < rng.choice([0.0, 0.01, 0.2])).astype(np.uint8)
+    exact = rng.random(B) < 0.3
+    guesses[exact] = given[exact]
+    offs = draw_offsets(7)
+    text = f"nl {nl} per {per} seed {tr_seed} column0 {column0} offsets {offs}"
+    if DRY or VERBOSE:
+        print(f"   trials {text}", flush=True)
+    if not run:
+        return
+
+    def models():
+        e1 = tm.sample(n, B, per, tr_seed, column0)
+        e2 = dm.sample(rates, B, tr_seed, column0)
+        return e1, tm.syndromes(H, e1), e2, tm.syndromes(H, e2), tm.syndromes(H, given), tm.score(H, L, guesses, given)
+
+    e1, s1, e2, s2, s3, (flags, counts) = timed_model("trials", models)
+    if not GPU:
+        return
+
+    def go(t, variant):
+        def check(what, got, want, *bufs):
+            if not same(got, want) or not all(b.guards_intact() for b in bufs):
+                fail("trials", f"{what}, kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape,
+                     logicals=L.todense() if L is not None else None, rates=rates, given=given, guesses=guesses, got=got, want=want)
+
+        be, bs = Guarded(B, n, offs[0]), Guarded(B, s, offs[1])
+        t.sample(B, per, seed=tr_seed, column0=column0, out=(be.view, bs.view))
+        check("sample errors", be.get(), e1, be, bs)
+        check("sample syndromes", bs.get(), s1, be, bs)
+        be, bs = Guarded(B, n, offs[2]), Guarded(B, s, offs[3])
+        t.set_rates(rates)
+        t.sample_rates(B, seed=tr_seed, column0=column0, out=(be.view, bs.view))
+        check("sample_rates errors", be.get(), e2, be, bs)
+        check("sample_rates syndromes", bs.get(), s2, be, bs)
+        bg, bs = Guarded(B, n, offs[4]), Guarded(B, s, offs[3])
+        t.syndromes(bg.put(given), out=bs.view)
+        check("syndromes of given errors", bs.get(), s3, bg, bs)
+        bq, bf = Guarded(B, n, offs[5]), Guarded(B, 1, offs[6])
+        start = torch.tensor([5, 6, 7, 8], dtype=torch.int64, device="cuda")       # counts are accumulated into
+        _, c = t.score(bq.put(guesses), bg.view, flags=bf.view.view(B), counts=start)
+        check("score flags", bf.get().reshape(B), flags, bq, bg, bf)
+        check("score counts", c.cpu().numpy() - np.array([5, 6, 7, 8]), counts)
+
+    on_every_tier("trials", (1, 2), lambda v: ldpc.Trials(H, L, kernel_variant=v), go, text)
+
+
+def leg_css(B, run):
+    """The hypergraph product of two drawn small matrices."""
+    def small():
+        r, c = int(rng.integers(1, 5)), int(rng.integers(2, 7))
+        return (rng.random((r, c)) < 0.5).astype(np.uint8)
+
+    Hx, Hz = ldpc.codes.hypergraph_product(small(), small())
+    n = Hx.shape[1]
+    with_logicals = bool(rng.random() < 0.7)
+    p = [0.0, 0.05, 0.9, (0.01, 0.002, 0.03), (0.0, 0.0, 0.4), (0.3, 0.3, 0.3)][int(rng.integers(0, 6))]
+    tr_seed = int(rng.integers(0, 1 << 64, dtype=np.uint64))
+    column0 = int(rng.choice([0, 3, (1 << 32) + 1, 1 << 40]))
+    gex, gez = rng.integers(0, 2, (B, n)).astype(np.uint8), rng.integers(0, 2, (B, n)).astype(np.uint8)
+    flip = float(rng.choice([0.0, 0.01, 0.2]))
+    gx, gz = gex ^ (rng.random((B, n)) < flip).astype(np.uint8), gez ^ (rng.random((B, n)) < flip).astype(np.uint8)
+    offs = draw_offsets(10)
+    text = f"css Hx {Hx.shape} Hz {Hz.shape} logicals={with_logicals} p {p} seed {tr_seed} column0 {column0} offsets {offs}"
+    if DRY or VERBOSE:
+        print(f"   {text}", flush=True)
+    if not run:
+        return
+    Lx, Lz = ldpc.codes.css_logicals(Hx, Hz) if with_logicals else (None, None)
+
+    def models():
+        ex, ez = cm.sample(n, B, p, tr_seed, column0)
+        return ex, ez, cm.syndromes(Hx, Hz, ex, ez), cm.syndromes(Hx, Hz, gex, gez), cm.score(Hx, Hz, Lx, Lz, gx, gz, gex, gez)
+
+    ex, ez, (sx, sz), (gsx, gsz), (flags, counts) = timed_model("css", models)
+    if not GPU:
+        return
+    rx, rz = Hx.shape[0], Hz.shape[0]
+
+    def go(t, variant):
+        def check(what, got, want, *bufs):
+            if not same(got, want) or not all(b.guards_intact() for b in bufs):
+                fail("css", f"{what}, kernel_variant {variant} {text}", hx=Hx.todense(), hz=Hz.todense(), gex=gex, gez=gez, gx=gx, gz=gz,
+                     got=got, want=want)
+
+        b = [Guarded(B, n, offs[0]), Guarded(B, n, offs[1]), Guarded(B, rx, offs[2]), Guarded(B, rz, offs[3])]
+        t.sample(B, p, seed=tr_seed, column0=column0, out=tuple(x.view for x in b))
+        for what, buf, want in zip(("ex", "ez", "sx", "sz"), b, (ex, ez, sx, sz)):
+            check("sample " + what, buf.get(), want, *b)
+        be = [Guarded(B, n, offs[4]), Guarded(B, n, offs[5])]
+        bs = [Guarded(B, rx, offs[3]), Guarded(B, rz, offs[2])]
+        t.syndromes(be[0].put(gex), be[1].put(gez), out=(bs[0].view, bs[1].view))
+        check("syndromes sx", bs[0].get(), gsx, *be, *bs)
+        check("syndromes sz", bs[1].get(), gsz, *be, *bs)
+        bg = [Guarded(B, n, offs[6]), Guarded(B, n, offs[7])]
+        bf = Guarded(B, 1, offs[8])
+        start = torch.tensor([1, 2, 3, 4, 5, 6], dtype=torch.int64, device="cuda")
+        _, c = t.score(bg[0].put(gx), bg[1].put(gz), be[0].view, be[1].view, flags=bf.view.view(B), counts=start)
+        check("score flags", bf.get().reshape(B), flags, *bg, *be, bf)
+        check("score counts", c.cpu().numpy() - np.arange(1, 7), counts)
+
+    logicals = (Lx, Lz) if with_logicals else False
+    on_every_tier("css", (1, 2), lambda v: ldpc.CSSTrials(Hx, Hz, logicals, kernel_variant=v), go, text)
+
+
+# ---- the cases ---------------------------------------------------------------------------------------------------------
+last_note = t0
+for case in range(ncases):
+    run = (not DRY) and FROM <= case <= TO
+    kind, H = draw_graph()
+    B = int(rng.choice([1, 2, 63, 64, 65, 130]))
+    if DRY or VERBOSE:
+        cdeg, bdeg = np.diff(sp.csr_matrix(H).indptr), np.diff(H.indptr)
+        print(f"case {case}: kind {kind} shape {H.shape} nnz {H.nnz} B {B} checks<=32 {int(((cdeg > 0) & (cdeg <= 32)).sum())} "
+              f"checks33-64 {int(((cdeg > 32) & (cdeg <= 64)).sum())} checks>64 {int((cdeg > 64).sum())} empty_checks {int((cdeg == 0).sum())} "
+              f"empty_bits {int((bdeg == 0).sum())} max_bit_degree {int(bdeg.max())}", flush=True)
+    leg_bitflip(H, B, run)
+    leg_minsum(H, B, run)
+    leg_relay(H, B, run)
+    leg_osd(H, B, run)
+    leg_trials(H, B, run)
+    leg_css(B, run)
+    if time.time() - last_note > 60:   # a silent GPU job looks hung to the runner
+        last_note = time.time()
+        print(f"... {case + 1} cases, {time.time() - t0:.0f} s", flush=True)
+
+if MODEL_ONLY:
+    print("model seconds: " + ", ".join(f"{c} {model_s[c]:.2f}" for c in TIERS), flush=True)
+what = "drawn" if DRY else "through the models only" if MODEL_ONLY else "compared with the models on the GPU"
+print(f"fuzz ok: {ncases} random cases {what} in {time.time() - t0:.0f} s (models {sum(model_s.values()):.0f} s), seed {seed}; "
+      + "; ".join(f"{c} tiers {sorted(ran[c])} legs {legs_run[c]} skipped {skipped[c]}" for c in TIERS))
