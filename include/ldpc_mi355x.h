@@ -845,6 +845,69 @@ ldpc_status ldpc_relay_decode_batch_device(ldpc_relay_decoder *dec, int64_t batc
                                            uint8_t *d_errors, uint8_t *d_converged, double *d_llr, int32_t *d_iters,
                                            int32_t *d_solutions, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Sliding-window decoding: the step between two windows.  A model H (D detectors x N mechanisms, zero-based CSC) too
+ * long to decode in one piece is decoded window by window: window k sees the detectors det_k and the mechanisms mech_k,
+ * any decoder of this library decodes its syndromes against H[det_k, mech_k], the first mechanisms of its guess --
+ * commit_k, positions in mech_k -- are kept for good, their effect is XORed into the RESIDUAL syndrome (which starts as a
+ * copy of the syndromes), and the next window reads its syndromes out of the residual.  A handle holds K windows, given
+ * as three lists of lists (ptr[K + 1], idx[ptr[K]]): det_k = det_idx[det_ptr[k] .. det_ptr[k + 1]) and so on.  Which
+ * windows a model is cut into is the caller's business (the Python layer's window_plan does it by detector layers);
+ * this section only requires what makes the step well defined.
+ *
+ * Layouts as everywhere in this header: residual [batch][D], guess [batch][N], win_syndromes [batch][|det_k|],
+ * win_guess [batch][|mech_k|], next_syndromes [batch][|det_{k+1}|], conv and win_conv [batch], all uint8.  Entries are
+ * read by their low bit (flags: by "not 0"), and every entry written is 0 or 1.  The arrays of a call must not overlap.
+ *
+ * THE RULE, per column i of the call.
+ *   gather(k):   win_syndromes(i, r) = residual(i, det_k[r]) & 1.                      Nothing else is touched.
+ *   commit(k):
+ *     - for c in commit_k:  guess(i, mech_k[c]) = win_guess(i, c) & 1;
+ *     - for every detector d that has a stored entry in a committed column, i.e. (d, mech_k[c]) is stored in H for some
+ *       c in commit_k:  residual(i, d) = (residual(i, d) & 1) ^ XOR over those c of (win_guess(i, c) & 1).  The FULL
+ *       column of H counts, also its detectors outside det_k;
+ *     - where d_win_conv and d_conv are both given:  conv(i) = (k == 0 ? 1 : conv(i) != 0) & (win_conv(i) != 0);
+ *     - where d_next_syndromes is given:  next_syndromes(i, r) = the NEW residual(i, det_{k+1}[r]) & 1 -- gather(k + 1)
+ *       fused into the step;
+ *     - every other entry of residual and guess keeps its value.
+ *   Consequence: if every mechanism with a stored entry is committed by exactly one window, the windows are committed
+ *   in order 0 .. K - 1 on a residual that started as the syndromes, and guess is zero where no window commits, then
+ *   after the last commit residual = (syndromes & 1) ^ H * guess in every detector that H touches.
+ *
+ * ldpc_windows_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work, with a message that names the window
+ * and the index -- for a pattern ldpc_bp_create rejects, a NULL list, a ptr array that does not start at 0 or falls, an
+ * index out of range (det_idx in [0, D), mech_idx in [0, N), commit_idx in [0, |mech_k|)), a list that is not ascending
+ * and distinct, and a mechanism committed by two windows; D, N, nnz or K of 2^28 or more: LDPC_ERR_UNSUPPORTED; without
+ * a device LDPC_ERR_NO_DEVICE.  The tables are built once, on the host, and live in device memory as 32-bit indices.
+ * The two steps answer LDPC_ERR_INVALID_ARGUMENT for a NULL handle, k outside [0, K), a negative batch,
+ * d_next_syndromes with k = K - 1, and a NULL required pointer (d_win_conv, d_conv and d_next_syndromes are optional).
+ * batch = 0: LDPC_OK, nothing touched.  Both take DEVICE pointers and are asynchronous on `stream`; calls on one handle
+ * run in call order whatever streams they are given.  ldpc_windows_destroy waits for the device (bounded by
+ * ldpc_set_wait_limit_ms).  ldpc_windows_count: K; 0 for NULL.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_windows ldpc_windows;
+
+/* Optional; pass NULL to ldpc_windows_create for defaults (current device). */
+typedef struct ldpc_windows_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    int32_t reserved[15];
+} ldpc_windows_options;
+
+ldpc_status ldpc_windows_create(int64_t D, int64_t N, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
+                                int64_t K, const int64_t *det_ptr, const int64_t *det_idx,
+                                const int64_t *mech_ptr, const int64_t *mech_idx,
+                                const int64_t *commit_ptr, const int64_t *commit_idx,   /* positions in the window's mech list */
+                                const ldpc_windows_options *options, ldpc_windows **out);
+ldpc_status ldpc_windows_destroy(ldpc_windows *w);
+int64_t ldpc_windows_count(const ldpc_windows *w);
+ldpc_status ldpc_windows_gather_device(ldpc_windows *w, int64_t k, int64_t batch, const uint8_t *d_residual,
+                                       uint8_t *d_win_syndromes, void *stream);
+ldpc_status ldpc_windows_commit_device(ldpc_windows *w, int64_t k, int64_t batch, const uint8_t *d_win_guess,
+                                       const uint8_t *d_win_conv, uint8_t *d_residual, uint8_t *d_guess,
+                                       uint8_t *d_conv, uint8_t *d_next_syndromes, void *stream);
+
 /* Diagnostics: 100 MHz ticks spent in {check sweep, variable sweep, convergence test}
  * of that call, summed over workgroups (one sampling wave each). */
 ldpc_status ldpc_bp_call_phase_ticks(ldpc_bp_decoder *dec, int32_t calls_back, uint64_t ticks[3]);

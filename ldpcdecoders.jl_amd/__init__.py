@@ -31,6 +31,7 @@ from .relay import RelayMinSumDecoder  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 from .css_trials import CSSTrialResult, CSSTrials, run_css_trials  # noqa: F401,E402
 from .dem import DetectorErrorModel, phenomenological, run_dem_trials  # noqa: F401,E402
+from .windows import SlidingWindowDecoder, WindowPlan, WindowStep, phenomenological_layers, window_plan  # noqa: F401,E402
 
 __all__ = [
     "BeliefPropagationOSDDecoder", "OSDPostProcessor", "BPOTSDecoder", "BitFlipDecoder", "BitFlipScratchSpace",
@@ -41,4 +42,5 @@ __all__ = [
     "Trials", "TrialResult", "run_trials",
     "CSSTrials", "CSSTrialResult", "run_css_trials",
     "DetectorErrorModel", "phenomenological", "run_dem_trials",
+    "SlidingWindowDecoder", "WindowPlan", "WindowStep", "phenomenological_layers", "window_plan",
 ]

@@ -104,6 +104,11 @@ EXPORTED_SYMBOLS = (
     "ldpc_css_trials_score_device",
     "ldpc_css_trials_sample",
     "ldpc_css_trials_score",
+    "ldpc_windows_create",
+    "ldpc_windows_destroy",
+    "ldpc_windows_count",
+    "ldpc_windows_gather_device",
+    "ldpc_windows_commit_device",
 )
 # ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
 DEBUG_SYMBOLS = ("ldpc_debug_team_rows", "ldpc_debug_team_plan", "ldpc_debug_div_check", "ldpc_debug_process_state",
@@ -189,10 +194,14 @@ class CSSTrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
 
+class WindowsOptions(ctypes.Structure):
+    _fields_ = [("device", ctypes.c_int32), ("reserved", ctypes.c_int32 * 15)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_windows.hip", "window_kernels.hpp", "window_plan.cpp", "window_plan.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -392,6 +401,16 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_css_trials_sample.argtypes = [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp]
     L.ldpc_css_trials_score.restype = i32
     L.ldpc_css_trials_score.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_windows_create.restype = i32
+    L.ldpc_windows_create.argtypes = [i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(WindowsOptions), ctypes.POINTER(vp)]
+    L.ldpc_windows_destroy.restype = i32
+    L.ldpc_windows_destroy.argtypes = [vp]
+    L.ldpc_windows_count.restype = i64
+    L.ldpc_windows_count.argtypes = [vp]
+    L.ldpc_windows_gather_device.restype = i32
+    L.ldpc_windows_gather_device.argtypes = [vp, i64, i64, vp, vp, vp]
+    L.ldpc_windows_commit_device.restype = i32
+    L.ldpc_windows_commit_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.ldpc_debug_process_state.restype = vp
     L.ldpc_debug_adopt_process_state.restype = i32
     L.ldpc_debug_adopt_process_state.argtypes = [vp]
