@@ -705,6 +705,25 @@ ldpc_status ldpc_css_trials_score(ldpc_css_trials *t, int64_t batch, const uint8
  * The form "L - c" (total minus own message) is part of the rule: it lets a kernel keep L and, per check, only
  * (alpha m1, alpha m2, a, the sign bits).
  *
+ * THE LAYERED RULE (options->schedule = 1; the rule above is the flooding schedule, 0).  A check reads the L that the
+ * checks before it have just updated, so there is no bit sweep.  Same arithmetic: binary32, every operation rounded
+ * once, no fused multiply-add, subnormals kept.
+ *   Layers.  Go through the checks in ascending index.  A check with no bits belongs to no layer.  Every other check goes
+ *   into the lowest-numbered layer that so far holds no check sharing a bit with it (first fit).  K = the number of
+ *   layers; inside a layer the checks are in ascending order.  The assignment is part of the rule: the order of the
+ *   updates changes the result.
+ *   State per syndrome: L[j], initially channel_llr[j]; c[i][j], initially +0.  For t = 1 .. max_iters:
+ *   1. Go through the layers 0 .. K - 1 in order.  For every check i of the layer with its bits j_0 < j_1 < ...:
+ *        b_k = min(max(L[j_k] - c[i][j_k], -clip), clip);  neg_k, mag_k, m1, m2, a and par exactly as in step 1 above;
+ *        new c[i][j_k]: the value alpha * (k == a ? m2 : m1), with its sign bit set iff par XOR neg_k;
+ *        then L[j_k] = b_k + c[i][j_k], with the clamped b_k and the new message.
+ *      All b_k of a check are formed before any of its L or c is replaced.  The checks of one layer share no bit, so
+ *      their order is free.
+ *   2. After the last layer err[j] = (L[j] <= 0).  If H * err == syndrome (an empty check is matched only by a 0 entry):
+ *      converged = 1, iters = t, stop; L and err stay as they are.
+ * Not stopped after max_iters: converged = 0, iters = max_iters.  max_iters = 0 as below.  A bit of degree 0 keeps its
+ * prior.  ldpc_minsum_layers: K of a layered handle; 0 for a flooding handle and for NULL.
+ *
  * Outputs.  errors [batch][n] uint8; converged [batch] uint8; llr [batch][n] DOUBLE (may be NULL): L widened exactly,
  * so it feeds ldpc_osd_postprocess_batch[_device] as it is; iters [batch] int32 (may be NULL).  max_iters = 0: zeros,
  * converged = 0, llr = 0, iters = 0.  batch = 0: LDPC_OK, nothing touched.
@@ -722,7 +741,8 @@ ldpc_status ldpc_css_trials_score(ldpc_css_trials *t, int64_t batch, const uint8
  * only report what ran; neither has a reference counterpart.
  *
  * ldpc_minsum_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL or non-finite channel_llr,
- * alpha outside (0, 1], clip not in (0, inf), a kernel_variant outside 0..2 and a pattern ldpc_bp_create rejects;
+ * alpha outside (0, 1], clip not in (0, inf), a kernel_variant outside 0..2, a schedule outside 0..1 and a pattern
+ * ldpc_bp_create rejects;
  * without a device LDPC_ERR_NO_DEVICE.  The decode entries reject a NULL handle, a negative batch and a NULL required
  * pointer the same way.  ldpc_minsum_decode_batch takes HOST buffers and is synchronous (its wait is bounded by
  * ldpc_set_wait_limit_ms); ldpc_minsum_decode_batch_device takes DEVICE pointers and is asynchronous on `stream`; calls
@@ -739,7 +759,8 @@ typedef struct ldpc_minsum_options {
     float alpha;             /* normalisation factor in (0, 1]; 0 = default 0.75 */
     float clip;              /* clamp of the bit-to-check values, finite, > 0; 0 = default 1.0e6f */
     int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_minsum_kernel */
-    int32_t reserved[12];
+    int32_t schedule;        /* 0 = flooding, 1 = layered (THE LAYERED RULE above); took reserved[0], the struct stays 64 bytes */
+    int32_t reserved[11];
 } ldpc_minsum_options;
 
 ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval,
@@ -749,6 +770,7 @@ ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *dec);
 int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *dec);
 int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *dec);
 int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *dec);
+int32_t ldpc_minsum_layers(const ldpc_minsum_decoder *dec);
 ldpc_status ldpc_minsum_decode_batch(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *syndromes, uint8_t *errors,
                                      uint8_t *converged, double *llr, int32_t *iters);
 ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *d_syndromes,

@@ -3,7 +3,8 @@
  * nothing here replaces a reference interface; the CPU test-suite uses these entries to check, without a GPU, the
  * host-side planning the team kernel relies on (ldpcdecoders.jl_amd/csrc/team_plan.cpp: team_plan_pure(),
  * team_rows_tables(), team_irr_tables()) and the tier / tile-width choice of the min-sum and relay decoders
- * (csrc/tile_plan.hpp).  Pure host code; no device is needed or touched.
+ * (csrc/tile_plan.hpp) and the layers of the layered min-sum schedule (csrc/layer_plan.hpp).  Pure host code; no device
+ * is needed or touched.
  */
 #ifndef LDPC_MI355X_DEBUG_H
 #define LDPC_MI355X_DEBUG_H
@@ -64,6 +65,15 @@ ldpc_status ldpc_debug_team_irr(int64_t s, int64_t n, const int64_t *colptr, con
    kernel_variant outside 0 .. 2: LDPC_ERR_INVALID_ARGUMENT.  No reference counterpart. */
 ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t relay, int32_t kernel_variant, int32_t *tier,
                                  int32_t *tile_syndromes, int64_t *state_bytes);
+
+/* The layers ldpc_minsum_create gives a handle of the layered schedule (options->schedule = 1; THE LAYERED RULE of
+   include/ldpc_mi355x.h) -- csrc/layer_plan.hpp layer_plan_build(), the function create calls, followed by the same
+   verification (no two checks of a layer share a bit, every non-empty check in exactly one layer).  H as the zero-based
+   CSC pattern create takes.  Out (each may be NULL): layer_of [s] = the layer of every check, -1 for a check with no
+   bits; K = the number of layers (0 for a graph without edges).  A pattern create refuses: LDPC_ERR_INVALID_ARGUMENT.
+   No reference counterpart. */
+ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t *layer_of,
+                                  int32_t *K);
 
 /* Two builds of the library in one process (the product and the -DLDPC_EXPERIMENTS build: the Python host of the tests)
    must not run team grids on one device at the same time -- every member of a team has to be resident.  Each build

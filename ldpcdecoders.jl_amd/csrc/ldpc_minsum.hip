@@ -1,5 +1,6 @@
 // ldpc_minsum.hip -- host side of the normalised min-sum decoder with per-bit channel LLRs: the ldpc_minsum_* entry
-// points of include/ldpc_mi355x.h (the rule is stated there).  Device code: minsum_kernels.hpp.  Tiers (ldpc_minsum_kernel):
+// points of include/ldpc_mi355x.h (the rule is stated there).  Device code: minsum_kernels.hpp (the flooding schedule) and
+// layered_kernels.hpp (the layered one, over the layers of layer_plan.hpp).  Tiers (ldpc_minsum_kernel), of both schedules:
 //   1  on-chip: the state of the S syndromes a workgroup holds lives in LDS for the whole decode (S = 64, 32, ... 1:
 //      the largest that leaves room for two workgroups a CU, else the largest that fits one)
 //   2  unlimited: tiles of 64 syndromes, the state in a global workspace, one slot per workgroup of a persistent grid
@@ -7,6 +8,8 @@
 #include "../../include/ldpc_mi355x.h"
 #include "../../include/ldpc_mi355x_debug.h"
 #include "minsum_kernels.hpp"
+#include "layered_kernels.hpp"
+#include "layer_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -29,6 +32,8 @@ struct ldpc_minsum_decoder {
     int64_t s = 0, n = 0, nnz = 0, max_iters = 0;
     float alpha = kMsAlphaDefault, clip = kMsClipDefault;
     int device = 0, num_cus = 0, tier = 0, S = 64, shift = 6, rec_words = 0;
+    int schedule = 0, layers = 0;   // 1 = layered: K layers, layer_ptr [K + 1] and layer_checks on the device
+    int *layer_ptr = nullptr, *layer_checks = nullptr;
     int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *edge_rec = nullptr, *edge_pos = nullptr;
     float *prior = nullptr;
     void *stage = nullptr;      // device staging for the host-pointer entry
@@ -43,7 +48,7 @@ struct ldpc_minsum_decoder {
     ~ldpc_minsum_decoder()
     {
         if (ldpc_detail::device_stalled(device)) return;   // (host_wait.hpp: nothing a stalled device may still use is freed)
-        void *all[] = {row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, prior, stage, ws};
+        void *all[] = {row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, layer_ptr, layer_checks, prior, stage, ws};
         for (void *q : all)
             if (q) (void)hipFree(q);
         calls.destroy();
@@ -52,6 +57,11 @@ struct ldpc_minsum_decoder {
 
 typedef void (*ms_kernel_t)(MsParams);
 static ms_kernel_t ms_kernel_of(int tier) { return tier == 1 ? minsum_kernel<kMsLdsWaves, false> : minsum_kernel<kMsGlobalWaves, true>; }
+typedef void (*layered_kernel_t)(LayeredParams);
+static layered_kernel_t layered_kernel_of(int tier)
+{
+    return tier == 1 ? layered_minsum_kernel<kMsLdsWaves, false> : layered_minsum_kernel<kMsGlobalWaves, true>;
+}
 
 extern "C" {
 
@@ -67,10 +77,12 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
     const float alpha = options && options->alpha != 0.0f ? options->alpha : kMsAlphaDefault;   // a zeroed struct: defaults
     const float clip = options && options->clip != 0.0f ? options->clip : kMsClipDefault;
     const int variant = options ? options->kernel_variant : 0;
+    const int schedule = options ? options->schedule : 0;
     int device = options ? options->device : -1;
     if (!(alpha > 0.0f && alpha <= 1.0f)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "alpha must lie in (0, 1]");
     if (!(clip > 0.0f) || std::isinf(clip)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "clip must be finite and > 0");
     if (variant < 0 || variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
+    if (schedule < 0 || schedule > 1) return set_error(LDPC_ERR_INVALID_ARGUMENT, "schedule must be 0 (flooding) or 1 (layered)");
     for (int64_t j = 0; j < n; ++j)
         if (!std::isfinite(channel_llr[j]))
             return set_error(LDPC_ERR_INVALID_ARGUMENT, "channel_llr[" + std::to_string(j) + "] is not finite");
@@ -84,7 +96,7 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
     ldpc_minsum_decoder *d = new (std::nothrow) ldpc_minsum_decoder();
     if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     d->s = s; d->n = n; d->nnz = nnz; d->max_iters = max_iters; d->alpha = alpha; d->clip = clip;
-    d->device = device; d->num_cus = prop.multiProcessorCount;
+    d->device = device; d->num_cus = prop.multiProcessorCount; d->schedule = schedule;
     // CSR (checks -> bits, ascending) next to the caller's CSC; a record per check; per CSC edge its record and position
     const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
     std::vector<int> rec_off((size_t)std::max<int64_t>(s, 1), 0), edge_rec(g.csc_row.size(), 0), edge_pos(g.csc_row.size(), 0);
@@ -105,10 +117,25 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
     d->tier = plan.tier; d->S = plan.S; d->shift = plan.shift;
+    LayerPlan layers;   // the layered schedule: first-fit layers (layer_plan.hpp), verified before they reach the device
+    if (schedule == 1) {
+        std::string why;
+        const LayerPlanStatus ls = layer_plan_build(s, n, g.row_ptr.data(), g.csr_col.data(), &layers, &why);
+        if (ls != kLayerPlanOk) {
+            delete d;
+            return set_error(ls == kLayerPlanNoMemory ? LDPC_ERR_OUT_OF_MEMORY : ls == kLayerPlanTooLarge ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_INVALID_ARGUMENT, why);
+        }
+        if (!layer_plan_verify(s, n, g.row_ptr.data(), g.csr_col.data(), layers, &why)) {   // (a slip would be a data race in the kernel)
+            delete d;
+            return set_error(LDPC_ERR_HIP, "internal error: " + why);
+        }
+        d->layers = layers.K;
+    }
     if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
     using ldpc_detail::upload_ints;
     bool ok = upload_ints(&d->row_ptr, g.row_ptr) && upload_ints(&d->csr_col, g.csr_col) && upload_ints(&d->rec_off, rec_off) &&
               upload_ints(&d->col_ptr, g.col_ptr) && upload_ints(&d->edge_rec, edge_rec) && upload_ints(&d->edge_pos, edge_pos) &&
+              (schedule == 0 || (upload_ints(&d->layer_ptr, layers.layer_ptr) && upload_ints(&d->layer_checks, layers.layer_checks))) &&
               hipMalloc((void **)&d->prior, (size_t)std::max<int64_t>(n, 1) * sizeof(float)) == hipSuccess &&
               (n == 0 || hipMemcpy(d->prior, channel_llr, (size_t)n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) &&
               d->calls.create() == hipSuccess;
@@ -137,9 +164,32 @@ ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_
     return LDPC_OK;
 }
 
+// (include/ldpc_mi355x_debug.h) the layers create uploads for a layered handle, without a device
+ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t *layer_of, int32_t *K)
+{
+    if (s < 0 || n < 0 || !colptr) return set_error(LDPC_ERR_INVALID_ARGUMENT, "s and n must be >= 0 and colptr not NULL");
+    const int64_t nnz = n > 0 ? colptr[n] : 0;
+    ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, 0);
+    if (st != LDPC_OK || (st = ldpc_detail::check_csc_pattern(s, n, nnz, colptr, rowval)) != LDPC_OK) return st;
+    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
+        return set_error(LDPC_ERR_UNSUPPORTED, "min-sum kernels: graph too large for 32-bit edge indexing");
+    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
+    LayerPlan plan;
+    std::string why;
+    const LayerPlanStatus ls = layer_plan_build(s, n, g.row_ptr.data(), g.csr_col.data(), &plan, &why);
+    if (ls != kLayerPlanOk)
+        return set_error(ls == kLayerPlanNoMemory ? LDPC_ERR_OUT_OF_MEMORY : ls == kLayerPlanTooLarge ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_INVALID_ARGUMENT, why);
+    if (!layer_plan_verify(s, n, g.row_ptr.data(), g.csr_col.data(), plan, &why)) return set_error(LDPC_ERR_HIP, "internal error: " + why);
+    if (layer_of)
+        for (int64_t i = 0; i < s; ++i) layer_of[i] = plan.layer_of[(size_t)i];
+    if (K) *K = plan.K;
+    return LDPC_OK;
+}
+
 int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *d) { return d ? d->tier : 0; }
 int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *d) { return d ? d->S : 0; }
 int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *d) { return d ? d->last_grid : 0; }
+int32_t ldpc_minsum_layers(const ldpc_minsum_decoder *d) { return d && d->schedule == 1 ? d->layers : 0; }
 
 ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *d)
 {
@@ -173,11 +223,12 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batc
         const int threads = (global ? kMsGlobalWaves : kMsLdsWaves) * 64;
         const size_t state = ms_state_bytes(d->s, d->n, d->rec_words, d->S);
         const size_t lds = global ? 0 : state;
-        ms_kernel_t k = ms_kernel_of(d->tier);
+        const bool layered = d->schedule == 1;
+        const void *k = layered ? (const void *)layered_kernel_of(d->tier) : (const void *)ms_kernel_of(d->tier);
         if (!d->kernel_ready) {
             // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
-            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
-            d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, threads, lds);
+            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
+            d->per_cu = ldpc_detail::blocks_per_cu(k, threads, lds);
             d->kernel_ready = true;
         }
         const int64_t tiles = (batch + d->S - 1) >> d->shift;
@@ -196,7 +247,13 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batc
         p.prior = d->prior; p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
         p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
         p.ws = d->ws; p.slot_bytes = (long long)state;
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
+        if (layered) {
+            LayeredParams lp{};
+            lp.ms = p; lp.K = d->layers; lp.layer_ptr = d->layer_ptr; lp.layer_checks = d->layer_checks;
+            hipLaunchKernelGGL(layered_kernel_of(d->tier), dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, lp);
+        } else {
+            hipLaunchKernelGGL(ms_kernel_of(d->tier), dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
+        }
         LDPC_HIP_TRY(hipGetLastError());
         d->last_grid = (int)grid;
     }

@@ -430,10 +430,10 @@ mutable struct MI355XMinSumDecoder <: AbstractDecoder
     handle::Ptr{Cvoid}
 end
 
-"ldpc_minsum_options: int32 device, float alpha, float clip, int32 kernel_variant, int32 reserved[12] (64 bytes)"
-function minsum_options(device::Integer, alpha::Real, clip::Real, kernel_variant::Integer)
+"ldpc_minsum_options: int32 device, float alpha, float clip, int32 kernel_variant, int32 schedule (0 = flooding, 1 = layered), int32 reserved[11] (64 bytes)"
+function minsum_options(device::Integer, alpha::Real, clip::Real, kernel_variant::Integer, schedule::Integer=0)
     opts = zeros(Int32, 16)
-    opts[1] = Int32(device); opts[4] = Int32(kernel_variant)
+    opts[1] = Int32(device); opts[4] = Int32(kernel_variant); opts[5] = Int32(schedule)
     opts[2] = reinterpret(Int32, Float32(alpha)); opts[3] = reinterpret(Int32, Float32(clip))
     return opts
 end
@@ -441,14 +441,18 @@ end
 minsum_llr(p) = Float32(log((1.0 - Float64(p)) / Float64(p)))
 
 """
-    MI355XMinSumDecoder(H, per, max_iters; alpha=0.75, clip=1e6, device=-1, kernel_variant=0)
+    MI355XMinSumDecoder(H, per, max_iters; alpha=0.75, clip=1e6, device=-1, kernel_variant=0, schedule=:flooding)
     MI355XMinSumDecoder(H, max_iters; channel_probs=..., ...)   or   channel_llr=...
 
 One prior per bit: a uniform `per`, error probabilities strictly inside (0, 1), or finite LLRs log(P(0) / P(1)).
+`schedule`: `:flooding`, or `:layered` (a check reads the posteriors the checks before it have just updated: THE
+LAYERED RULE of include/ldpc_mi355x.h; `minsum_layers(d)` tells the number of layers); anything else is an ArgumentError.
 """
 function MI355XMinSumDecoder(H, per::Union{Float64,Nothing}, max_iters::Int; channel_probs=nothing, channel_llr=nothing,
-                             alpha::Real=0.75, clip::Real=1e6, device::Integer=-1, kernel_variant::Integer=0)
+                             alpha::Real=0.75, clip::Real=1e6, device::Integer=-1, kernel_variant::Integer=0,
+                             schedule::Symbol=:flooding)
     s, n = size(H)
+    schedule in (:flooding, :layered) || throw(ArgumentError("schedule must be :flooding or :layered"))
     count(!isnothing, (per, channel_probs, channel_llr)) == 1 ||
         throw(ArgumentError("give exactly one of per, channel_probs and channel_llr"))
     probs = per !== nothing ? fill(per, n) : channel_probs
@@ -461,7 +465,7 @@ function MI355XMinSumDecoder(H, per::Union{Float64,Nothing}, max_iters::Int; cha
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:ldpc_minsum_create, libldpc), Cint,
                 (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float32}, Int64, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
-                s, n, length(rowval), colptr, rowval, llr, max_iters, minsum_options(device, alpha, clip, kernel_variant), h))
+                s, n, length(rowval), colptr, rowval, llr, max_iters, minsum_options(device, alpha, clip, kernel_variant, schedule === :layered ? 1 : 0), h))
     d = MI355XMinSumDecoder(per, max_iters, s, n, sp, llr, zeros(n), zeros(n), h[])
     finalizer(d) do x
         x.handle != C_NULL && ccall((:ldpc_minsum_destroy, libldpc), Cint, (Ptr{Cvoid},), x.handle)
@@ -472,6 +476,8 @@ end
 MI355XMinSumDecoder(H, max_iters::Int; kwargs...) = MI355XMinSumDecoder(H, nothing, max_iters; kwargs...)
 
 reset!(d::MI355XMinSumDecoder) = d      # the device state is reset inside every decode call
+"the number of layers of a layered handle, 0 for the flooding schedule (ldpc_minsum_layers)"
+minsum_layers(d::MI355XMinSumDecoder) = Int(ccall((:ldpc_minsum_layers, libldpc), Int32, (Ptr{Cvoid},), d.handle))
 
 minsum_call(handle, B, syn, err, conv, llr) =
     check(ccall((:ldpc_minsum_decode_batch, libldpc), Cint,

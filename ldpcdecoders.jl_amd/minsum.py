@@ -36,10 +36,18 @@ class MinSumDecoder(AbstractDecoder):
     """`MinSumDecoder(H, per, max_iters)` with a uniform prior, or one of `channel_probs=` (error probability per bit) /
     `channel_llr=` (log(P(0) / P(1)) per bit, finite) instead of `per`: exactly one of the three.  alpha in (0, 1]
     scales every check-to-bit message, clip > 0 clamps the bit-to-check values.  kernel_variant: 0 = by size, 1 = on-chip,
-    2 = unlimited (`.kernel` tells which tier the handle takes)."""
+    2 = unlimited (`.kernel` tells which tier the handle takes).  schedule: "flooding" (every check reads the posteriors
+    of the previous iteration) or "layered" (a check reads what the checks before it have just updated: THE LAYERED RULE
+    of include/ldpc_mi355x.h; `.layers` tells the number of layers); anything else is a ValueError."""
+
+    SCHEDULES = {"flooding": 0, "layered": 1}
 
     def __init__(self, H, per: Optional[float] = None, max_iters: int = 50, *, channel_llr=None, channel_probs=None,
-                 alpha: float = 0.75, clip: float = 1e6, device: Optional[int] = None, kernel_variant: int = 0):
+                 alpha: float = 0.75, clip: float = 1e6, device: Optional[int] = None, kernel_variant: int = 0,
+                 schedule: str = "flooding"):
+        if not isinstance(schedule, str) or schedule not in self.SCHEDULES:
+            raise ValueError(f'schedule must be "flooding" or "layered", got {schedule!r}')
+        self.schedule = schedule
         if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
             raise TypeError("max_iters must be an Int")
         if (per is not None) + (channel_llr is not None) + (channel_probs is not None) != 1:
@@ -75,6 +83,7 @@ class MinSumDecoder(AbstractDecoder):
         opts.device = -1 if device is None else int(device)
         opts.alpha, opts.clip = self.alpha, self.clip
         opts.kernel_variant = int(kernel_variant)
+        opts.schedule = self.SCHEDULES[schedule]
         self._h = ctypes.c_void_p()
         self._L = _capi.lib_for(None)
         _capi.check(self._L.ldpc_minsum_create(self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
@@ -86,11 +95,17 @@ class MinSumDecoder(AbstractDecoder):
         """1 = on-chip (state in LDS), 2 = unlimited (state in a global workspace) (ldpc_minsum_kernel)."""
         return int(self._L.ldpc_minsum_kernel(self._h))
 
+    @property
+    def layers(self) -> int:
+        """The number of layers K of a layered handle; 0 for the flooding schedule (ldpc_minsum_layers)."""
+        return int(self._L.ldpc_minsum_layers(self._h))
+
     def info(self):
         """`.device`: the GPU the handle lives on; `.kernel`: its tier; `.tile_syndromes`: the syndromes a workgroup decodes
         at a time (S); `.last_grid`: the workgroups of the most recent launch (0 before any) -- fewer than ceil(batch / S)
-        means that a workgroup took a further tile in the same LDS block or workspace slot."""
-        return SimpleNamespace(device=self.device, kernel=self.kernel,
+        means that a workgroup took a further tile in the same LDS block or workspace slot; `.schedule` and `.layers`:
+        the schedule and its number of layers (0 for flooding)."""
+        return SimpleNamespace(device=self.device, kernel=self.kernel, schedule=self.schedule, layers=self.layers,
                                tile_syndromes=int(self._L.ldpc_minsum_tile_syndromes(self._h)),
                                last_grid=int(self._L.ldpc_minsum_last_grid(self._h)))
 
