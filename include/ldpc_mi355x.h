@@ -748,6 +748,32 @@ ldpc_status ldpc_css_trials_score(ldpc_css_trials *t, int64_t batch, const uint8
  * ldpc_set_wait_limit_ms); ldpc_minsum_decode_batch_device takes DEVICE pointers and is asynchronous on `stream`; calls
  * on one handle run in call order whatever streams they are given.
  *
+ * PER-SYNDROME PRIORS (ldpc_minsum_decode_batch_priors*, ldpc_minsum_decode_batch_given*).  Column i of the call is
+ * decoded exactly by THE RULE (or THE LAYERED RULE, by the handle's schedule) with every occurrence of channel_llr[j] --
+ * the initial L[j] and the left-most addend of the bit sweep -- replaced by priors[i][j].  Same arithmetic: binary32,
+ * every operation rounded once, no fused multiply-add, subnormals kept; a numpy model equals the device in every bit,
+ * LLRs included.  The handle's channel_llr plays no part in these entries.  Two sources of priors[i][j]:
+ *   Floats.  priors [batch][n] binary32, laid out like every other batch array; no alignment is asked for.
+ *   Given bits.  The handle holds two tables llr_if0[n], llr_if1[n], binary32 and finite, set by
+ *     ldpc_minsum_set_conditional_priors (host arrays; may be called again: it waits for the earlier calls on the handle
+ *     and takes effect for the calls after it); the call brings given [batch][n] uint8 and
+ *     priors[i][j] = (given[i][j] & 1) ? llr_if1[j] : llr_if0[j]  -- the low bit, as the trial scores read a guess.  This
+ *     is the second stage of a correlated decode of a CSS code (given = the other side's guess) at one byte per bit.
+ * A column that holds a non-finite prior (only the floats form can) is not decoded: errors zeros, converged 0, iters 0,
+ * llr 0 -- what max_iters = 0 writes; no other column is affected.  +-0 and subnormal priors are ordinary values.
+ * max_iters = 0 and batch = 0 as above.
+ * The flooding schedule keeps a tile's priors beside its state, 4 n more bytes per syndrome (the layered one reads them
+ * only when a tile starts and keeps nothing), so these entries have a plan of their own, chosen at create by the same
+ * policy: ldpc_minsum_priors_kernel and ldpc_minsum_priors_tile_syndromes report its tier and S (0 for NULL); for a
+ * layered handle they equal ldpc_minsum_kernel / ldpc_minsum_tile_syndromes.  On a handle forced on-chip
+ * (kernel_variant 1) whose state with the priors does not fit 159 KiB for one syndrome, create and the plain entries
+ * succeed, both getters answer 0 and these entries answer LDPC_ERR_UNSUPPORTED.  ldpc_minsum_last_grid reports the most
+ * recent launch of any entry.
+ * Before any device work: LDPC_ERR_INVALID_ARGUMENT for a NULL handle, a negative batch, a NULL required pointer
+ * (d_priors / d_given included), a NULL or non-finite table entry, and for a given entry on a handle without tables.
+ * The forms without _device take HOST buffers and are synchronous (bounded waits); calls on one handle run in call
+ * order whatever streams they are given, these entries included.
+ *
  * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
  * ------------------------------------------------------------------------ */
 typedef struct ldpc_minsum_decoder ldpc_minsum_decoder;
@@ -776,6 +802,22 @@ ldpc_status ldpc_minsum_decode_batch(ldpc_minsum_decoder *dec, int64_t batch, co
 ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *d_syndromes,
                                             uint8_t *d_errors, uint8_t *d_converged, double *d_llr, int32_t *d_iters,
                                             void *stream);
+/* per-syndrome priors (PER-SYNDROME PRIORS above) */
+int32_t ldpc_minsum_priors_kernel(const ldpc_minsum_decoder *dec);
+int32_t ldpc_minsum_priors_tile_syndromes(const ldpc_minsum_decoder *dec);
+ldpc_status ldpc_minsum_decode_batch_priors(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *syndromes,
+                                            const float *priors, uint8_t *errors, uint8_t *converged, double *llr,
+                                            int32_t *iters);
+ldpc_status ldpc_minsum_decode_batch_priors_device(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *d_syndromes,
+                                                   const float *d_priors, uint8_t *d_errors, uint8_t *d_converged,
+                                                   double *d_llr, int32_t *d_iters, void *stream);
+ldpc_status ldpc_minsum_set_conditional_priors(ldpc_minsum_decoder *dec, const float *llr_if0, const float *llr_if1);
+ldpc_status ldpc_minsum_decode_batch_given(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *syndromes,
+                                           const uint8_t *given, uint8_t *errors, uint8_t *converged, double *llr,
+                                           int32_t *iters);
+ldpc_status ldpc_minsum_decode_batch_given_device(ldpc_minsum_decoder *dec, int64_t batch, const uint8_t *d_syndromes,
+                                                  const uint8_t *d_given, uint8_t *d_errors, uint8_t *d_converged,
+                                                  double *d_llr, int32_t *d_iters, void *stream);
 
 /* ------------------------------------------------------------------------
  * Relay min-sum decoder: normalised min-sum with a per-bit MEMORY, run as a chain of LEGS, returning the solution of

@@ -66,6 +66,15 @@ ldpc_status ldpc_debug_team_irr(int64_t s, int64_t n, const int64_t *colptr, con
 ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t relay, int32_t kernel_variant, int32_t *tier,
                                  int32_t *tile_syndromes, int64_t *state_bytes);
 
+/* The second plan of a min-sum handle, for the entries with per-syndrome priors (ldpc_minsum_decode_batch_priors*,
+   ldpc_minsum_decode_batch_given*) -- csrc/tile_plan.hpp priors_tile_plan(), the function ldpc_minsum_create calls.
+   schedule 0 (flooding): a tile keeps its priors as a fourth block [n][S] f32, so its state is
+   round4(S (4 (n + rec_words) + s)) + 4 n S  bytes, rounded up to 256, and the policy of ldpc_debug_tile_plan runs over
+   that size.  schedule 1 (layered): no such block; the answer is ldpc_debug_tile_plan's with relay = 0.  Out and
+   statuses as there; a schedule outside 0 .. 1: LDPC_ERR_INVALID_ARGUMENT.  No reference counterpart. */
+ldpc_status ldpc_debug_priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t schedule, int32_t kernel_variant,
+                                        int32_t *tier, int32_t *tile_syndromes, int64_t *state_bytes);
+
 /* The layers ldpc_minsum_create gives a handle of the layered schedule (options->schedule = 1; THE LAYERED RULE of
    include/ldpc_mi355x.h) -- csrc/layer_plan.hpp layer_plan_build(), the function create calls, followed by the same
    verification (no two checks of a layer share a bit, every non-empty check in exactly one layer).  H as the zero-based

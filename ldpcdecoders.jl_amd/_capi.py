@@ -79,6 +79,13 @@ EXPORTED_SYMBOLS = (
     "ldpc_minsum_layers",
     "ldpc_minsum_decode_batch",
     "ldpc_minsum_decode_batch_device",
+    "ldpc_minsum_priors_kernel",
+    "ldpc_minsum_priors_tile_syndromes",
+    "ldpc_minsum_decode_batch_priors",
+    "ldpc_minsum_decode_batch_priors_device",
+    "ldpc_minsum_set_conditional_priors",
+    "ldpc_minsum_decode_batch_given",
+    "ldpc_minsum_decode_batch_given_device",
     "ldpc_relay_create",
     "ldpc_relay_destroy",
     "ldpc_relay_kernel",
@@ -113,7 +120,8 @@ EXPORTED_SYMBOLS = (
 )
 # ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
 DEBUG_SYMBOLS = ("ldpc_debug_team_rows", "ldpc_debug_team_plan", "ldpc_debug_div_check", "ldpc_debug_process_state",
-                 "ldpc_debug_adopt_process_state", "ldpc_debug_team_irr", "ldpc_debug_llr_check", "ldpc_debug_tile_plan", "ldpc_debug_layer_plan")
+                 "ldpc_debug_adopt_process_state", "ldpc_debug_team_irr", "ldpc_debug_llr_check", "ldpc_debug_tile_plan", "ldpc_debug_layer_plan",
+                 "ldpc_debug_priors_tile_plan")
 
 MULTI_MAX_DEVICES = 16
 EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_NONE = 0, 1, 2, 3
@@ -260,6 +268,8 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_debug_llr_check.argtypes = [i64, vp, vp, vp]
     L.ldpc_debug_tile_plan.restype = i32
     L.ldpc_debug_tile_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
+    L.ldpc_debug_priors_tile_plan.restype = i32
+    L.ldpc_debug_priors_tile_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
     L.ldpc_debug_layer_plan.restype = i32
     L.ldpc_debug_layer_plan.argtypes = [i64, i64, vp, vp, vp, ctypes.POINTER(i32)]
     L.ldpc_debug_team_irr.restype = i32
@@ -352,6 +362,20 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_minsum_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     L.ldpc_minsum_decode_batch_device.restype = i32
     L.ldpc_minsum_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_minsum_priors_kernel.restype = i32
+    L.ldpc_minsum_priors_kernel.argtypes = [vp]
+    L.ldpc_minsum_priors_tile_syndromes.restype = i32
+    L.ldpc_minsum_priors_tile_syndromes.argtypes = [vp]
+    L.ldpc_minsum_decode_batch_priors.restype = i32
+    L.ldpc_minsum_decode_batch_priors.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_minsum_decode_batch_priors_device.restype = i32
+    L.ldpc_minsum_decode_batch_priors_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ldpc_minsum_set_conditional_priors.restype = i32
+    L.ldpc_minsum_set_conditional_priors.argtypes = [vp, vp, vp]
+    L.ldpc_minsum_decode_batch_given.restype = i32
+    L.ldpc_minsum_decode_batch_given.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_minsum_decode_batch_given_device.restype = i32
+    L.ldpc_minsum_decode_batch_given_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.ldpc_relay_create.restype = i32
     L.ldpc_relay_create.argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, vp, ctypes.POINTER(RelayOptions), ctypes.POINTER(vp)]
     L.ldpc_relay_destroy.restype = i32

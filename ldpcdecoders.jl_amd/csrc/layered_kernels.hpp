@@ -29,13 +29,21 @@ struct LayeredParams {
     const int *layer_ptr;         // [K + 1]
     const int *layer_checks;      // [layer_ptr[K]]: the non-empty checks, layer by layer
 };
+struct LayeredPriorsParams : LayeredParams {   // (the table instantiations keep LayeredParams as their argument)
+    MsPriorSource src;
+};
+template <int SRC> struct LayeredParamsOf { typedef LayeredPriorsParams type; };
+template <> struct LayeredParamsOf<kMsPriorTable> { typedef LayeredParams type; };
 
-template <int TW, bool GLOBAL>
-__global__ __launch_bounds__(TW * 64) void layered_minsum_kernel(LayeredParams lp)
+// SRC (minsum_kernels.hpp): per-syndrome priors are read only here, when a tile starts, so they are staged straight into L
+// and the state of a tile is the same for every SRC.
+template <int TW, bool GLOBAL, int SRC = kMsPriorTable>
+__global__ __launch_bounds__(TW * 64) void layered_minsum_kernel(typename LayeredParamsOf<SRC>::type lp)
 {
     constexpr int T = TW * 64;
+    constexpr bool STAGED = SRC != kMsPriorTable;
     extern __shared__ __attribute__((aligned(16))) unsigned char ms_lds[];
-    __shared__ int sh_bad[64];
+    __shared__ int sh_bad[STAGED ? 128 : 64];   // STAGED: [64 + c] = column c of the tile holds a non-finite prior
     const MsParams &p = lp.ms;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int S = p.S, sh = p.shift, l = t & (S - 1), q = t >> sh, Q = T >> sh;
@@ -56,20 +64,33 @@ __global__ __launch_bounds__(TW * 64) void layered_minsum_kernel(LayeredParams l
         const long long col0 = tile << sh;
         const int valid = (int)((p.batch - col0) < (long long)S ? (p.batch - col0) : (long long)S);
         // ---- state of iteration 0: L = channel_llr, every message +0; the syndromes, a wave per column
-        for (int j = q; j < n; j += Q) L[((size_t)j << sh) + l] = prior[j];
+        if constexpr (!STAGED)
+            for (int j = q; j < n; j += Q) L[((size_t)j << sh) + l] = prior[j];
         for (int w = q; w < p.rec_words; w += Q) R[((size_t)w << sh) + l] = 0u;
         for (int c = wave; c < S; c += TW) {
             if (c < valid) {
                 const uint8_t *src = p.syn + (col0 + c) * s;
                 for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = src[i] != 0;
+                if constexpr (STAGED) {   // ... and the column's priors, all of L[.][c]
+                    const bool skip = ms_stage_priors<SRC>(lp.src, col0 + c, n, lane, [&](int j, float v) { L[((size_t)j << sh) + c] = v; });
+                    if (lane == 0) sh_bad[64 + c] = skip;
+                }
             } else {   // a lane past the batch reads nothing and never becomes active
                 for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = 0;
+                if constexpr (STAGED)
+                    for (int j = lane; j < n; j += 64) L[((size_t)j << sh) + c] = 0.0f;
             }
         }
         if (t < 64) sh_bad[t] = 0;
         bool active = l < valid;
         int my_iters = p.max_iters, my_conv = 0;
         __syncthreads();
+        if constexpr (STAGED) {
+            if (active && sh_bad[64 + l]) {   // a column with a non-finite prior stays out
+                active = false;
+                my_iters = 0;
+            }
+        }
 
         for (int it = 1; it <= p.max_iters; ++it) {
             // ---- the layers in order; the checks of a layer share no bit
@@ -190,6 +211,15 @@ __global__ __launch_bounds__(TW * 64) void layered_minsum_kernel(LayeredParams l
         for (int c = wave; c < valid; c += TW) {
             uint8_t *eo = p.err + (col0 + c) * n;
             double *lo = p.llr ? p.llr + (col0 + c) * n : nullptr;
+            if constexpr (STAGED) {
+                if (sh_bad[64 + c]) {   // not decoded: what max_iters = 0 writes
+                    for (int j = lane; j < n; j += 64) {
+                        eo[j] = 0;
+                        if (lo) lo[j] = 0.0;
+                    }
+                    continue;
+                }
+            }
             for (int j = lane; j < n; j += 64) {
                 const float v = L[((size_t)j << sh) + c];
                 eo[j] = v <= 0.0f;

@@ -4,7 +4,9 @@
 //   1  on-chip: the state of the S syndromes a workgroup holds lives in LDS for the whole decode (S = 64, 32, ... 1:
 //      the largest that leaves room for two workgroups a CU, else the largest that fits one)
 //   2  unlimited: tiles of 64 syndromes, the state in a global workspace, one slot per workgroup of a persistent grid
-// No CPU path.
+// The entries with per-syndrome priors (decode_batch_priors / decode_batch_given) run the same kernel templates with
+// another prior source and, in the flooding schedule, a larger state (the staged priors): a handle holds a second plan
+// for them (priors_tile_plan, tile_plan.hpp), computed at create.  No CPU path.
 #include "../../include/ldpc_mi355x.h"
 #include "../../include/ldpc_mi355x_debug.h"
 #include "minsum_kernels.hpp"
@@ -32,23 +34,25 @@ struct ldpc_minsum_decoder {
     int64_t s = 0, n = 0, nnz = 0, max_iters = 0;
     float alpha = kMsAlphaDefault, clip = kMsClipDefault;
     int device = 0, num_cus = 0, tier = 0, S = 64, shift = 6, rec_words = 0;
+    TilePlan pplan;             // the plan of the priors / given entries; tier 0: kernel_variant 1 and their state does not fit
     int schedule = 0, layers = 0;   // 1 = layered: K layers, layer_ptr [K + 1] and layer_checks on the device
     int *layer_ptr = nullptr, *layer_checks = nullptr;
     int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *edge_rec = nullptr, *edge_pos = nullptr;
     float *prior = nullptr;
+    float *cond = nullptr;      // [2][n]: llr_if0, llr_if1, once ldpc_minsum_set_conditional_priors has been called
     void *stage = nullptr;      // device staging for the host-pointer entry
     size_t stage_cap = 0;
     unsigned char *ws = nullptr;   // tier 2: [grid][slot]
     size_t ws_cap = 0;
-    bool kernel_ready = false;
-    int per_cu = 1;
+    bool kernel_ready[3] = {false, false, false};   // per prior source (kMsPrior*): each is a kernel function of its own
+    int per_cu[3] = {1, 1, 1};
     int grid_max = 0;    // LDPC_MS_GRID_MAX (experiments build): workgroups a launch takes at most; 0 = no cap
     int last_grid = 0;   // workgroups of the most recent launch
     ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (they share the workspace)
     ~ldpc_minsum_decoder()
     {
         if (ldpc_detail::device_stalled(device)) return;   // (host_wait.hpp: nothing a stalled device may still use is freed)
-        void *all[] = {row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, layer_ptr, layer_checks, prior, stage, ws};
+        void *all[] = {row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, layer_ptr, layer_checks, prior, cond, stage, ws};
         for (void *q : all)
             if (q) (void)hipFree(q);
         calls.destroy();
@@ -61,6 +65,138 @@ typedef void (*layered_kernel_t)(LayeredParams);
 static layered_kernel_t layered_kernel_of(int tier)
 {
     return tier == 1 ? layered_minsum_kernel<kMsLdsWaves, false> : layered_minsum_kernel<kMsGlobalWaves, true>;
+}
+// ... and with per-syndrome priors
+typedef void (*ms_priors_kernel_t)(MsPriorsParams);
+template <int SRC> static ms_priors_kernel_t ms_priors_kernel_of(int tier)
+{
+    return tier == 1 ? minsum_kernel<kMsLdsWaves, false, SRC> : minsum_kernel<kMsGlobalWaves, true, SRC>;
+}
+typedef void (*layered_priors_kernel_t)(LayeredPriorsParams);
+template <int SRC> static layered_priors_kernel_t layered_priors_kernel_of(int tier)
+{
+    return tier == 1 ? layered_minsum_kernel<kMsLdsWaves, false, SRC> : layered_minsum_kernel<kMsGlobalWaves, true, SRC>;
+}
+
+// One decode on `stream`, whatever the prior source: the plan and the state of the plain entries for the table, of the
+// priors entries otherwise.  The arguments are checked, batch > 0.
+static ldpc_status ms_launch(ldpc_minsum_decoder *d, int src_kind, const MsPriorSource &src, int64_t batch, const uint8_t *d_syn,
+                             uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters, hipStream_t stream)
+{
+    LDPC_HIP_TRY(hipSetDevice(d->device));
+    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
+    ldpc_status st = d->calls.enter(stream);
+    if (st != LDPC_OK) return st;
+    if (d->max_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
+        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
+        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
+        if (d_llr && d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * d->n * sizeof(double), stream));
+        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
+    } else {
+        const bool staged = src_kind != kMsPriorTable, layered = d->schedule == 1;
+        const int tier = staged ? d->pplan.tier : d->tier, S = staged ? d->pplan.S : d->S, shift = staged ? d->pplan.shift : d->shift;
+        const bool global = tier == 2;
+        const int threads = (global ? kMsGlobalWaves : kMsLdsWaves) * 64;
+        const size_t state = staged ? d->pplan.state_bytes : ms_state_bytes(d->s, d->n, d->rec_words, d->S);
+        const size_t lds = global ? 0 : state;
+        const void *k;
+        if (src_kind == kMsPriorFloats)
+            k = layered ? (const void *)layered_priors_kernel_of<kMsPriorFloats>(tier) : (const void *)ms_priors_kernel_of<kMsPriorFloats>(tier);
+        else if (src_kind == kMsPriorGiven)
+            k = layered ? (const void *)layered_priors_kernel_of<kMsPriorGiven>(tier) : (const void *)ms_priors_kernel_of<kMsPriorGiven>(tier);
+        else
+            k = layered ? (const void *)layered_kernel_of(tier) : (const void *)ms_kernel_of(tier);
+        if (!d->kernel_ready[src_kind]) {
+            // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
+            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
+            d->per_cu[src_kind] = ldpc_detail::blocks_per_cu(k, threads, lds);
+            d->kernel_ready[src_kind] = true;
+        }
+        const int64_t tiles = (batch + S - 1) >> shift;
+        int64_t grid = std::min<int64_t>(tiles, (int64_t)d->per_cu[src_kind] * d->num_cus);
+        if (d->grid_max > 0) grid = std::min<int64_t>(grid, d->grid_max);
+        if (global) {
+            grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMsWorkspaceCap / state)));
+            st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
+                                                 "min-sum workspace regrow (device synchronise before the free)");
+            if (st != LDPC_OK) return st;
+        }
+        MsParams p{};
+        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = S; p.shift = shift;
+        p.batch = batch; p.alpha = d->alpha; p.clip = d->clip;
+        p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
+        p.prior = d->prior; p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
+        p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
+        p.ws = d->ws; p.slot_bytes = (long long)state;
+        const dim3 g((unsigned)grid), b((unsigned)threads);
+        if (layered) {
+            LayeredPriorsParams lp{};
+            lp.ms = p; lp.K = d->layers; lp.layer_ptr = d->layer_ptr; lp.layer_checks = d->layer_checks; lp.src = src;
+            if (src_kind == kMsPriorFloats) hipLaunchKernelGGL(layered_priors_kernel_of<kMsPriorFloats>(tier), g, b, lds, stream, lp);
+            else if (src_kind == kMsPriorGiven) hipLaunchKernelGGL(layered_priors_kernel_of<kMsPriorGiven>(tier), g, b, lds, stream, lp);
+            else hipLaunchKernelGGL(layered_kernel_of(tier), g, b, lds, stream, (const LayeredParams &)lp);
+        } else {
+            MsPriorsParams pp{};
+            (MsParams &)pp = p; pp.src = src;
+            if (src_kind == kMsPriorFloats) hipLaunchKernelGGL(ms_priors_kernel_of<kMsPriorFloats>(tier), g, b, lds, stream, pp);
+            else if (src_kind == kMsPriorGiven) hipLaunchKernelGGL(ms_priors_kernel_of<kMsPriorGiven>(tier), g, b, lds, stream, pp);
+            else hipLaunchKernelGGL(ms_kernel_of(tier), g, b, lds, stream, p);
+        }
+        LDPC_HIP_TRY(hipGetLastError());
+        d->last_grid = (int)grid;
+    }
+    return d->calls.leave(stream);
+}
+
+// what every device entry checks before any device work; batch == 0 is the caller's to answer
+static ldpc_status ms_check_batch(const ldpc_minsum_decoder *d, int64_t batch, const void *syn, const void *err, const void *conv)
+{
+    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
+    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (batch == 0) return LDPC_OK;
+    if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
+    return LDPC_OK;
+}
+
+// ... and the priors / given entries on top: their own pointer, the tables of the given form, the second plan
+static ldpc_status ms_check_priors(const ldpc_minsum_decoder *d, int64_t batch, const void *syn, const void *per_syndrome, bool given,
+                                   const void *err, const void *conv)
+{
+    const ldpc_status st = ms_check_batch(d, batch, syn, err, conv);
+    if (st != LDPC_OK) return st;
+    if (given && !d->cond) return set_error(LDPC_ERR_INVALID_ARGUMENT, "no conditional priors are set (ldpc_minsum_set_conditional_priors)");
+    if (batch > 0 && d->n > 0 && !per_syndrome) return set_error(LDPC_ERR_INVALID_ARGUMENT, given ? "given pointer is NULL" : "priors pointer is NULL");
+    if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
+    if (d->pplan.tier == 0)
+        return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome with its priors does not fit the on-chip tier");
+    return LDPC_OK;
+}
+
+// The host form of every entry: the syndromes and `extra` (extra_bytes per syndrome: the priors or the given bits, or
+// nothing) into the staging buffer, `decode` on the null stream, the copies out.  The arguments are checked, batch > 0.
+template <class F>
+static ldpc_status ms_decode_to_host(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *syn, const void *extra, size_t extra_bytes,
+                                     uint8_t *err, uint8_t *conv, double *llr, int32_t *iters, const char *what, F decode)
+{
+    LDPC_HIP_TRY(hipSetDevice(d->device));
+    const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
+    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][LLRs][priors or given bits]
+    image.take(B * s);
+    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4);
+    const size_t o_llr = image.take(llr ? B * n * sizeof(double) : 0), o_extra = image.take(B * extra_bytes), total = image.at;
+    ldpc_status st = ldpc_detail::grow_device_buffer(&d->stage, &d->stage_cap, total, d->device, "min-sum staging regrow (device synchronise before the free)");
+    if (st != LDPC_OK) return st;
+    char *dp = (char *)d->stage;
+    if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
+    if (extra_bytes > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp + o_extra, extra, B * extra_bytes, hipMemcpyHostToDevice, nullptr));
+    st = decode((const uint8_t *)dp, (const void *)(dp + o_extra), (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
+                llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it));
+    if (st != LDPC_OK) return st;
+    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
+    LDPC_HIP_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
+    if (iters) LDPC_HIP_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
+    if (llr && n > 0) LDPC_HIP_TRY(hipMemcpyAsync(llr, dp + o_llr, B * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    return ldpc_detail::wait_stream(nullptr, d->device, what);
 }
 
 extern "C" {
@@ -117,6 +253,7 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
     d->tier = plan.tier; d->S = plan.S; d->shift = plan.shift;
+    if (!priors_tile_plan(s, n, words, schedule == 1, variant, &d->pplan)) d->pplan = TilePlan();   // (tier 0: those entries answer UNSUPPORTED)
     LayerPlan layers;   // the layered schedule: first-fit layers (layer_plan.hpp), verified before they reach the device
     if (schedule == 1) {
         std::string why;
@@ -164,6 +301,23 @@ ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_
     return LDPC_OK;
 }
 
+// (include/ldpc_mi355x_debug.h) ... and the second plan, of the entries with per-syndrome priors
+ldpc_status ldpc_debug_priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t schedule, int32_t kernel_variant, int32_t *tier,
+                                        int32_t *tile_syndromes, int64_t *state_bytes)
+{
+    if (s < 0 || n < 0 || rec_words < 0 || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28) || rec_words >= ((int64_t)1 << 31))
+        return set_error(LDPC_ERR_INVALID_ARGUMENT, "s, n and rec_words must be >= 0 and within what create accepts");
+    if (kernel_variant < 0 || kernel_variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
+    if (schedule < 0 || schedule > 1) return set_error(LDPC_ERR_INVALID_ARGUMENT, "schedule must be 0 (flooding) or 1 (layered)");
+    TilePlan plan;
+    if (!priors_tile_plan(s, n, rec_words, schedule == 1, kernel_variant, &plan))
+        return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome with its priors does not fit the on-chip tier");
+    if (tier) *tier = plan.tier;
+    if (tile_syndromes) *tile_syndromes = plan.S;
+    if (state_bytes) *state_bytes = (int64_t)plan.state_bytes;
+    return LDPC_OK;
+}
+
 // (include/ldpc_mi355x_debug.h) the layers create uploads for a layered handle, without a device
 ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t *layer_of, int32_t *K)
 {
@@ -188,6 +342,8 @@ ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, c
 
 int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *d) { return d ? d->tier : 0; }
 int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *d) { return d ? d->S : 0; }
+int32_t ldpc_minsum_priors_kernel(const ldpc_minsum_decoder *d) { return d ? d->pplan.tier : 0; }
+int32_t ldpc_minsum_priors_tile_syndromes(const ldpc_minsum_decoder *d) { return d && d->pplan.tier ? d->pplan.S : 0; }
 int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *d) { return d ? d->last_grid : 0; }
 int32_t ldpc_minsum_layers(const ldpc_minsum_decoder *d) { return d && d->schedule == 1 ? d->layers : 0; }
 
@@ -203,88 +359,96 @@ ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *d)
 ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *d_syn, uint8_t *d_err,
                                             uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)
 {
-    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    if (batch == 0) return LDPC_OK;
-    if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
+    const ldpc_status st = ms_check_batch(d, batch, d_syn, d_err, d_conv);
+    if (st != LDPC_OK || batch == 0) return st;
     if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-    hipStream_t stream = (hipStream_t)stream_v;
-    LDPC_HIP_TRY(hipSetDevice(d->device));
-    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
-    ldpc_status st = d->calls.enter(stream);
-    if (st != LDPC_OK) return st;
-    if (d->max_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
-        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
-        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_llr && d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * d->n * sizeof(double), stream));
-        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
-    } else {
-        const bool global = d->tier == 2;
-        const int threads = (global ? kMsGlobalWaves : kMsLdsWaves) * 64;
-        const size_t state = ms_state_bytes(d->s, d->n, d->rec_words, d->S);
-        const size_t lds = global ? 0 : state;
-        const bool layered = d->schedule == 1;
-        const void *k = layered ? (const void *)layered_kernel_of(d->tier) : (const void *)ms_kernel_of(d->tier);
-        if (!d->kernel_ready) {
-            // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
-            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
-            d->per_cu = ldpc_detail::blocks_per_cu(k, threads, lds);
-            d->kernel_ready = true;
-        }
-        const int64_t tiles = (batch + d->S - 1) >> d->shift;
-        int64_t grid = std::min<int64_t>(tiles, (int64_t)d->per_cu * d->num_cus);
-        if (d->grid_max > 0) grid = std::min<int64_t>(grid, d->grid_max);
-        if (global) {
-            grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMsWorkspaceCap / state)));
-            st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
-                                                 "min-sum workspace regrow (device synchronise before the free)");
-            if (st != LDPC_OK) return st;
-        }
-        MsParams p{};
-        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = d->S; p.shift = d->shift;
-        p.batch = batch; p.alpha = d->alpha; p.clip = d->clip;
-        p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
-        p.prior = d->prior; p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
-        p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
-        p.ws = d->ws; p.slot_bytes = (long long)state;
-        if (layered) {
-            LayeredParams lp{};
-            lp.ms = p; lp.K = d->layers; lp.layer_ptr = d->layer_ptr; lp.layer_checks = d->layer_checks;
-            hipLaunchKernelGGL(layered_kernel_of(d->tier), dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, lp);
-        } else {
-            hipLaunchKernelGGL(ms_kernel_of(d->tier), dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
-        }
-        LDPC_HIP_TRY(hipGetLastError());
-        d->last_grid = (int)grid;
-    }
-    return d->calls.leave(stream);
+    return ms_launch(d, kMsPriorTable, MsPriorSource{}, batch, d_syn, d_err, d_conv, d_llr, d_iters, (hipStream_t)stream_v);
 }
 
 ldpc_status ldpc_minsum_decode_batch(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *syn, uint8_t *err, uint8_t *conv,
                                      double *llr, int32_t *iters)
 {
+    const ldpc_status st = ms_check_batch(d, batch, syn, err, conv);
+    if (st != LDPC_OK || batch == 0) return st;
+    return ms_decode_to_host(d, batch, syn, nullptr, 0, err, conv, llr, iters, "ldpc_minsum_decode_batch (stream synchronise)",
+                             [&](const uint8_t *d_syn, const void *, uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters) {
+                                 return ldpc_minsum_decode_batch_device(d, batch, d_syn, d_err, d_conv, d_llr, d_iters, nullptr);
+                             });
+}
+
+// ---- per-syndrome priors ---------------------------------------------------------------------------------------------------
+
+ldpc_status ldpc_minsum_decode_batch_priors_device(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *d_syn, const float *d_priors,
+                                                   uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)
+{
+    const ldpc_status st = ms_check_priors(d, batch, d_syn, d_priors, false, d_err, d_conv);
+    if (st != LDPC_OK || batch == 0) return st;
+    MsPriorSource src{};
+    src.priors = d_priors;
+    return ms_launch(d, kMsPriorFloats, src, batch, d_syn, d_err, d_conv, d_llr, d_iters, (hipStream_t)stream_v);
+}
+
+ldpc_status ldpc_minsum_decode_batch_priors(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *syn, const float *priors, uint8_t *err,
+                                            uint8_t *conv, double *llr, int32_t *iters)
+{
+    const ldpc_status st = ms_check_priors(d, batch, syn, priors, false, err, conv);
+    if (st != LDPC_OK || batch == 0) return st;
+    return ms_decode_to_host(d, batch, syn, priors, (size_t)d->n * sizeof(float), err, conv, llr, iters,
+                             "ldpc_minsum_decode_batch_priors (stream synchronise)",
+                             [&](const uint8_t *d_syn, const void *d_extra, uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters) {
+                                 return ldpc_minsum_decode_batch_priors_device(d, batch, d_syn, (const float *)d_extra, d_err, d_conv, d_llr,
+                                                                               d_iters, nullptr);
+                             });
+}
+
+ldpc_status ldpc_minsum_set_conditional_priors(ldpc_minsum_decoder *d, const float *llr_if0, const float *llr_if1)
+{
     if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    if (batch == 0) return LDPC_OK;
-    if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
+    if (d->n > 0 && (!llr_if0 || !llr_if1)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "llr_if0 or llr_if1 is NULL");
+    const size_t n = (size_t)d->n;
+    std::vector<float> both(std::max<size_t>(2 * n, 1), 0.0f);
+    for (size_t j = 0; j < n; ++j) {
+        if (!std::isfinite(llr_if0[j])) return set_error(LDPC_ERR_INVALID_ARGUMENT, "llr_if0[" + std::to_string(j) + "] is not finite");
+        if (!std::isfinite(llr_if1[j])) return set_error(LDPC_ERR_INVALID_ARGUMENT, "llr_if1[" + std::to_string(j) + "] is not finite");
+        both[j] = llr_if0[j];
+        both[n + j] = llr_if1[j];
+    }
     LDPC_HIP_TRY(hipSetDevice(d->device));
-    const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][LLRs]
-    image.take(B * s);
-    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4);
-    const size_t o_llr = image.take(llr ? B * n * sizeof(double) : 0), total = image.at;
-    ldpc_status st = ldpc_detail::grow_device_buffer(&d->stage, &d->stage_cap, total, d->device, "min-sum staging regrow (device synchronise before the free)");
-    if (st != LDPC_OK) return st;
-    char *dp = (char *)d->stage;
-    if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
-    st = ldpc_minsum_decode_batch_device(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
-                                         llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it), nullptr);
-    if (st != LDPC_OK) return st;
-    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
-    LDPC_HIP_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
-    if (iters) LDPC_HIP_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
-    if (llr && n > 0) LDPC_HIP_TRY(hipMemcpyAsync(llr, dp + o_llr, B * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    return ldpc_detail::wait_stream(nullptr, d->device, "ldpc_minsum_decode_batch (stream synchronise)");
+    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
+    // after every earlier call on the handle: a decode still in flight reads the tables it was launched with to its end
+    if (d->calls.have) {
+        const ldpc_status st = ldpc_detail::wait_event(d->calls.done, d->device, "ldpc_minsum_set_conditional_priors (wait for the earlier calls)");
+        if (st != LDPC_OK) return st;
+    }
+    float *fresh = d->cond;
+    if (!fresh) LDPC_HIP_TRY(hipMalloc((void **)&fresh, both.size() * sizeof(float)));
+    const hipError_t e = hipMemcpy(fresh, both.data(), both.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess && !d->cond) (void)hipFree(fresh);
+    LDPC_HIP_TRY(e);
+    d->cond = fresh;
+    return LDPC_OK;
+}
+
+ldpc_status ldpc_minsum_decode_batch_given_device(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *d_syn, const uint8_t *d_given,
+                                                  uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)
+{
+    const ldpc_status st = ms_check_priors(d, batch, d_syn, d_given, true, d_err, d_conv);
+    if (st != LDPC_OK || batch == 0) return st;
+    MsPriorSource src{};
+    src.given = d_given; src.llr_if0 = d->cond; src.llr_if1 = d->cond + d->n;
+    return ms_launch(d, kMsPriorGiven, src, batch, d_syn, d_err, d_conv, d_llr, d_iters, (hipStream_t)stream_v);
+}
+
+ldpc_status ldpc_minsum_decode_batch_given(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *syn, const uint8_t *given, uint8_t *err,
+                                           uint8_t *conv, double *llr, int32_t *iters)
+{
+    const ldpc_status st = ms_check_priors(d, batch, syn, given, true, err, conv);
+    if (st != LDPC_OK || batch == 0) return st;
+    return ms_decode_to_host(d, batch, syn, given, (size_t)d->n, err, conv, llr, iters, "ldpc_minsum_decode_batch_given (stream synchronise)",
+                             [&](const uint8_t *d_syn, const void *d_extra, uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters) {
+                                 return ldpc_minsum_decode_batch_given_device(d, batch, d_syn, (const uint8_t *)d_extra, d_err, d_conv, d_llr,
+                                                                              d_iters, nullptr);
+                             });
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 //        below clip); bit k of signs: the message to the check's k-th bit is negative.  The message to bit k is
 //        (k == a ? m2a : m1a) with that sign -- what the rule's step 1 defines.  All-zero words are the initial +0.
 //   syn  [s][S]          u8   the syndrome entries as 0 / 1
+//   P    [n][S]          f32  only with per-syndrome priors (SRC below): the tile's priors, on the next word boundary
 // GLOBAL = false: the state is the workgroup's dynamic LDS and stays there for the whole decode.  GLOBAL = true: a slot
 // of a global workspace per workgroup of the persistent grid (S = 64); same code.
 //
@@ -54,18 +55,56 @@ struct MsParams {
 
 // (ms_record_words(), ms_state_bytes() -- the words of a check record, the bytes of a tile's state: tile_plan.hpp, host code)
 
+// Where a syndrome's prior comes from (the third template argument of both kernels).  kMsPriorTable: prior[n] of the
+// handle, shared by the batch -- the plain entries.  The other two are the per-syndrome priors of the header:
+// kMsPriorFloats reads priors [batch][n] f32, kMsPriorGiven forms (given[i][j] & 1) ? llr_if1[j] : llr_if0[j] from
+// given [batch][n] u8.  Both are staged once per tile, a wave per column with its lanes along j (a coalesced read, every
+// float or byte read once): into a fourth block P [n][S] f32 behind syn (at ms_priors_offset(), tile_plan.hpp) in the
+// flooding kernel, whose bit sweep reads the prior again in every iteration, and straight into L in the layered one.  A
+// column in which the staging meets a non-finite prior never becomes active and is written out as zeros.
+constexpr int kMsPriorTable = 0, kMsPriorFloats = 1, kMsPriorGiven = 2;
+
+struct MsPriorSource {
+    const float *priors;            // kMsPriorFloats: [batch][n]
+    const uint8_t *given;           // kMsPriorGiven: [batch][n]
+    const float *llr_if0, *llr_if1; // kMsPriorGiven: [n] each
+};
+struct MsPriorsParams : MsParams {   // (the table instantiations keep MsParams as their argument)
+    MsPriorSource src;
+};
+template <int SRC> struct MsParamsOf { typedef MsPriorsParams type; };
+template <> struct MsParamsOf<kMsPriorTable> { typedef MsParams type; };
+
+// One column's priors, lanes along j: store(j, value) for every bit; true in every lane if one of them is not finite.
+template <int SRC, class Store>
+__device__ inline bool ms_stage_priors(const MsPriorSource &src, long long column, int n, int lane, Store store)
+{
+    static_assert(SRC == kMsPriorFloats || SRC == kMsPriorGiven, "the table is not staged");
+    int bad = 0;
+    for (int j = lane; j < n; j += 64) {
+        float v;
+        if constexpr (SRC == kMsPriorFloats) v = src.priors[column * n + j];
+        else v = (src.given[column * n + j] & 1) ? src.llr_if1[j] : src.llr_if0[j];
+        bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;   // infinity or NaN
+        store(j, v);
+    }
+    return __any(bad) != 0;
+}
+
 __device__ inline float ms_clamp(float x, float clip)
 {
     x = x < -clip ? -clip : x;    // max(x, -clip)
     return x > clip ? clip : x;   // min(., clip)
 }
 
-template <int TW, bool GLOBAL>
-__global__ __launch_bounds__(TW * 64) void minsum_kernel(MsParams p)
+template <int TW, bool GLOBAL, int SRC = kMsPriorTable>
+__global__ __launch_bounds__(TW * 64) void minsum_kernel(typename MsParamsOf<SRC>::type kp)
 {
     constexpr int T = TW * 64;
+    constexpr bool STAGED = SRC != kMsPriorTable;
     extern __shared__ __attribute__((aligned(16))) unsigned char ms_lds[];
-    __shared__ int sh_bad[64];
+    __shared__ int sh_bad[STAGED ? 128 : 64];   // STAGED: [64 + c] = column c of the tile holds a non-finite prior
+    const MsParams &p = kp;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int S = p.S, sh = p.shift, l = t & (S - 1), q = t >> sh, Q = T >> sh;
     const int n = p.n, s = p.s;
@@ -76,6 +115,8 @@ __global__ __launch_bounds__(TW * 64) void minsum_kernel(MsParams p)
     float *L = (float *)base;
     unsigned *R = (unsigned *)base + ((size_t)n << sh);
     unsigned char *Y = base + (((size_t)n + (size_t)p.rec_words) << sh) * 4;
+    float *P = nullptr;   // STAGED: the tile's priors [n][S]
+    if constexpr (STAGED) P = (float *)(base + ((((((size_t)n + (size_t)p.rec_words) << sh) * 4 + ((size_t)s << sh)) + 3) & ~(size_t)3));
     const int *__restrict__ row_ptr = p.row_ptr, *__restrict__ csr_col = p.csr_col, *__restrict__ rec_off = p.rec_off;
     const int *__restrict__ col_ptr = p.col_ptr, *__restrict__ edge_rec = p.edge_rec, *__restrict__ edge_pos = p.edge_pos;
     const float *__restrict__ prior = p.prior;
@@ -85,20 +126,35 @@ __global__ __launch_bounds__(TW * 64) void minsum_kernel(MsParams p)
         const long long col0 = tile << sh;
         const int valid = (int)((p.batch - col0) < (long long)S ? (p.batch - col0) : (long long)S);
         // ---- state of iteration 0: L = channel_llr, every message +0; the syndromes, a wave per column
-        for (int j = q; j < n; j += Q) L[((size_t)j << sh) + l] = prior[j];
+        if constexpr (!STAGED)
+            for (int j = q; j < n; j += Q) L[((size_t)j << sh) + l] = prior[j];
         for (int w = q; w < p.rec_words; w += Q) R[((size_t)w << sh) + l] = 0u;
         for (int c = wave; c < S; c += TW) {
             if (c < valid) {
                 const uint8_t *src = p.syn + (col0 + c) * s;
                 for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = src[i] != 0;
+                if constexpr (STAGED) {   // ... and the column's priors, all of P[.][c] anew
+                    const bool skip = ms_stage_priors<SRC>(kp.src, col0 + c, n, lane, [&](int j, float v) { P[((size_t)j << sh) + c] = v; });
+                    if (lane == 0) sh_bad[64 + c] = skip;
+                }
             } else {   // a lane past the batch reads nothing and never becomes active
                 for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = 0;
+                if constexpr (STAGED)
+                    for (int j = lane; j < n; j += 64) P[((size_t)j << sh) + c] = 0.0f;
             }
         }
         if (t < 64) sh_bad[t] = 0;
         bool active = l < valid;
         int my_iters = p.max_iters, my_conv = 0;
         __syncthreads();
+        if constexpr (STAGED) {   // L = the staged priors, rows along the lanes; a column with a non-finite one stays out
+            for (int j = q; j < n; j += Q) L[((size_t)j << sh) + l] = P[((size_t)j << sh) + l];
+            if (active && sh_bad[64 + l]) {
+                active = false;
+                my_iters = 0;
+            }
+            __syncthreads();
+        }
 
         for (int it = 1;; ++it) {
             const bool test_only = it > p.max_iters;
@@ -195,7 +251,9 @@ __global__ __launch_bounds__(TW * 64) void minsum_kernel(MsParams p)
             // ---- bit sweep `it`: channel_llr plus the messages in ascending check order
             if (active) {
                 for (int j = q; j < n; j += Q) {
-                    float acc = prior[j];
+                    float acc;
+                    if constexpr (STAGED) acc = P[((size_t)j << sh) + l];
+                    else acc = prior[j];
                     const int eb = col_ptr[j + 1];
                     for (int e = col_ptr[j]; e < eb; ++e) {
                         const unsigned *rec = R + ((size_t)edge_rec[e] << sh) + l;
@@ -221,6 +279,15 @@ __global__ __launch_bounds__(TW * 64) void minsum_kernel(MsParams p)
         for (int c = wave; c < valid; c += TW) {
             uint8_t *eo = p.err + (col0 + c) * n;
             double *lo = p.llr ? p.llr + (col0 + c) * n : nullptr;
+            if constexpr (STAGED) {
+                if (sh_bad[64 + c]) {   // not decoded: what max_iters = 0 writes
+                    for (int j = lane; j < n; j += 64) {
+                        eo[j] = 0;
+                        if (lo) lo[j] = 0.0;
+                    }
+                    continue;
+                }
+            }
             for (int j = lane; j < n; j += 64) {
                 const float v = L[((size_t)j << sh) + c];
                 eo[j] = v <= 0.0f;

@@ -6,6 +6,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 
 namespace ldpc {
 
@@ -51,6 +52,40 @@ inline bool tile_plan(int64_t s, int64_t n, int64_t rec_words, bool relay, int v
     p.S = p.tier == 1 ? S : 64;
     for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
     p.state_bytes = relay ? relay_state_bytes(s, n, rec_words, p.S) : ms_state_bytes(s, n, rec_words, p.S);
+    *out = p;
+    return true;
+}
+
+// ---- per-syndrome priors (the ldpc_minsum_decode_batch_priors / _given entries) ------------------------------------------
+// The flooding schedule re-reads the prior in every bit sweep, so a tile keeps its priors as a fourth block P [n][S] f32
+// behind the three of ms_state_bytes(); the block starts on a word: the S s syndrome bytes before it are rounded up to 4.
+inline size_t ms_priors_offset(long long s, long long n, long long rec_words, int S)
+{
+    return (((size_t)(n + rec_words) * 4 + (size_t)s) * (size_t)S + 3) & ~(size_t)3;
+}
+// bytes of such a tile's state, rounded up to 256
+inline size_t ms_priors_state_bytes(long long s, long long n, long long rec_words, int S)
+{
+    return (ms_priors_offset(s, n, rec_words, S) + (size_t)n * 4 * (size_t)S + 255) & ~(size_t)255;
+}
+
+// The plan of the priors entries: the policy of tile_plan() over the larger state.  The layered schedule reads the prior
+// only when a tile starts and keeps no P, so its plan is tile_plan()'s.  false: variant 1 and nothing fits.
+inline bool priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, bool layered, int variant, TilePlan *out)
+{
+    if (layered) return tile_plan(s, n, rec_words, false, variant, out);
+    int S = 0;
+    for (size_t budget : {kTileLdsTwo, kTileLdsOne}) {
+        for (int w = 64; w >= 1 && !S; w >>= 1)
+            if (ms_priors_state_bytes(s, n, rec_words, w) <= budget) S = w;
+        if (S) break;
+    }
+    if (variant == 1 && !S) return false;
+    TilePlan p;
+    p.tier = variant ? variant : S ? 1 : 2;
+    p.S = p.tier == 1 ? S : 64;
+    for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
+    p.state_bytes = ms_priors_state_bytes(s, n, rec_words, p.S);
     *out = p;
     return true;
 }

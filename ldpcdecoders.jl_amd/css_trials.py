@@ -24,6 +24,21 @@ def pauli_rates(p):
     return (float(p) / 3.0,) * 3
 
 
+def conditional_probs(p):
+    """(p_if0, p_if1): the probability that a qubit's Z part is flipped given that its X part is not / is, under Pauli
+    noise `p` (as `pauli_rates` takes it), in float64.  An X part is an X or a Y and only the Y carries a Z part, so
+    p_if1 = py / (px + py); without an X part the qubit holds I or Z: p_if0 = pz / (1 - px - py).  ValueError where
+    either is not strictly inside (0, 1) -- px + py = 0 included."""
+    px, py, pz = (np.float64(x) for x in pauli_rates(p))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p_if1 = py / (px + py)
+        p_if0 = pz / (np.float64(1.0) - px - py)
+    for name, v in (("p_if0", p_if0), ("p_if1", p_if1)):
+        if not (0.0 < v < 1.0):   # (False for NaN as well)
+            raise ValueError(f"{name} = {v} is not strictly inside (0, 1) for the rates {(float(px), float(py), float(pz))}")
+    return float(p_if0), float(p_if1)
+
+
 class CSSTrials:
     """Owns the Tanner graphs of `Hx`, `Hz` and of the logical rows on a device.  logicals: None = `codes.css_logicals`,
     False = no logical rows (flag bits 2 and 3 are then never set), or a pair (Lx, Lz).  check: assert Hx * Hz' = 0
@@ -238,7 +253,8 @@ def _bp_of(decoder):
     return decoder.bp_decoder if isinstance(decoder, BeliefPropagationOSDDecoder) else decoder
 
 
-def run_css_trials(decoder_hx, decoder_hz, trials: int, p, batch: int = 65536, seed: int = 0, logicals=None) -> CSSTrialResult:
+def run_css_trials(decoder_hx, decoder_hz, trials: int, p, batch: int = 65536, seed: int = 0, logicals=None,
+                   correlated: bool = False) -> CSSTrialResult:
     """`trials` Monte-Carlo trials of a CSS code under Pauli noise `p` (a float: depolarizing, px = py = pz = p / 3; or a
     triple (px, py, pz)).  `decoder_hz` (BP, BP+OSD, BP-OTS or bit-flip, built on Hz) decodes sz = Hz ex into the guess
     gx; `decoder_hx` (built on Hx) decodes sx = Hx ez into gz.  sample -> decode -> decode -> score run in batches of
@@ -246,11 +262,27 @@ def run_css_trials(decoder_hx, decoder_hz, trials: int, p, batch: int = 65536, s
     sampling rule (and of the bit-flip tie rule), so the result does not depend on `batch`.  Only the six counts and
     the two numbers of unconverged columns are read back.  logicals: as in CSSTrials.
 
-    Each decoder sees one side of the noise only.  Under depolarizing noise of total rate p, the marginal rate of either
-    side is 2 p / 3 (an X part is an X or a Y); whether the decoders are built with that `per` is the caller's choice:
-    nothing here changes a decoder."""
+    correlated=False: each decoder sees one side of the noise only.  Under depolarizing noise of total rate p, the
+    marginal rate of either side is 2 p / 3 (an X part is an X or a Y); whether the decoders are built with that `per`
+    is the caller's choice: nothing here changes a decoder.
+
+    correlated=True: the two sides are decoded one after the other, because a Y error hits both.  `decoder_hz` decodes sz
+    into gx as before; `decoder_hx` -- which must be a `MinSumDecoder` of either schedule -- then decodes sx with the
+    prior of every qubit chosen by that guess: `conditional_probs(p)` gives P(Z part | X part not flipped / flipped), and
+    `decode_batch_given_device(sx, gx, ...)` selects between the two per trial and qubit on the device.  The logical-X
+    count is that of the uncorrelated run by construction.  The function sets the two tables on `decoder_hx`
+    (`set_conditional_priors`) once from `p`: that is the one thing it changes on a decoder; the prior `decoder_hx` was
+    built with plays no part."""
     import torch
 
+    if correlated:
+        from .minsum import MinSumDecoder
+
+        if not isinstance(decoder_hx, MinSumDecoder):
+            raise TypeError("correlated=True needs a MinSumDecoder as decoder_hx (only it has an entry with per-syndrome "
+                            f"priors), got {type(decoder_hx).__name__}")
+        p_if0, p_if1 = conditional_probs(p)
+        decoder_hx.set_conditional_priors(probs_if0=p_if0, probs_if1=p_if1)
     bx, bz = _bp_of(decoder_hx), _bp_of(decoder_hz)
     devices = [int(b.info().device) if hasattr(b, "info") else int(torch.cuda.current_device()) for b in (bx, bz)]
     assert devices[0] == devices[1], f"the two decoders live on different GPUs ({devices[0]} and {devices[1]})"
@@ -274,7 +306,11 @@ def run_css_trials(decoder_hx, decoder_hz, trials: int, p, batch: int = 65536, s
                 b = min(B, total - done)
                 tr.sample(b, p, seed=seed, column0=done, out=(ex[:b], ez[:b], sx[:b], sz[:b]))
                 guess_x = _device_decode(decoder_hz, sz[:b], gx[:b], cz[:b], done)
-                guess_z = _device_decode(decoder_hx, sx[:b], gz[:b], cx[:b], done)
+                if correlated:
+                    decoder_hx.decode_batch_given_device(sx[:b], guess_x, gz[:b], cx[:b])
+                    guess_z = gz[:b]
+                else:
+                    guess_z = _device_decode(decoder_hx, sx[:b], gz[:b], cx[:b], done)
                 tr.score(guess_x, guess_z, ex[:b], ez[:b], counts=counts, want_flags=False)
                 unconverged[0] += (cx[:b] == 0).sum()
                 unconverged[1] += (cz[:b] == 0).sum()

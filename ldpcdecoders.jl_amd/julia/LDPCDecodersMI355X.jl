@@ -484,6 +484,43 @@ minsum_call(handle, B, syn, err, conv, llr) =
                 (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
                 handle, B, syn, err, conv, llr, C_NULL))
 
+# Per-syndrome priors (PER-SYNDROME PRIORS of include/ldpc_mi355x.h): host entries; the batch arrays are column-major
+# n x B / s x B matrices, which is the library's [batch][n] layout.
+"tier and S of the entries with per-syndrome priors (0, 0: unsupported on this handle)"
+minsum_priors_plan(d::MI355XMinSumDecoder) =
+    (Int(ccall((:ldpc_minsum_priors_kernel, libldpc), Int32, (Ptr{Cvoid},), d.handle)),
+     Int(ccall((:ldpc_minsum_priors_tile_syndromes, libldpc), Int32, (Ptr{Cvoid},), d.handle)))
+
+"syndromes s x B UInt8, priors n x B Float32 (one prior LLR per syndrome and bit) -> (errors n x B UInt8, converged)"
+function minsum_decode_priors(d::MI355XMinSumDecoder, syndromes::Matrix{UInt8}, priors::Matrix{Float32})
+    B = size(syndromes, 2)
+    size(syndromes, 1) == d.s && size(priors) == (d.n, B) || throw(DimensionMismatch("syndromes / priors"))
+    err = Matrix{UInt8}(undef, d.n, B); conv = Vector{UInt8}(undef, B)
+    check(ccall((:ldpc_minsum_decode_batch_priors, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{Float32}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                d.handle, B, syndromes, priors, err, conv, C_NULL, C_NULL))
+    return err, conv .!= 0
+end
+
+"the two tables of the given-bits entry: the prior LLR of every bit where its given bit is 0 / 1 (finite)"
+function minsum_set_conditional_priors!(d::MI355XMinSumDecoder, llr_if0::Vector{Float32}, llr_if1::Vector{Float32})
+    length(llr_if0) == d.n && length(llr_if1) == d.n || throw(DimensionMismatch("one entry per bit"))
+    check(ccall((:ldpc_minsum_set_conditional_priors, libldpc), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}),
+                d.handle, llr_if0, llr_if1))
+    return d
+end
+
+"syndromes s x B UInt8, given n x B UInt8 (the low bit selects llr_if1 over llr_if0) -> (errors n x B UInt8, converged)"
+function minsum_decode_given(d::MI355XMinSumDecoder, syndromes::Matrix{UInt8}, given::Matrix{UInt8})
+    B = size(syndromes, 2)
+    size(syndromes, 1) == d.s && size(given) == (d.n, B) || throw(DimensionMismatch("syndromes / given"))
+    err = Matrix{UInt8}(undef, d.n, B); conv = Vector{UInt8}(undef, B)
+    check(ccall((:ldpc_minsum_decode_batch_given, libldpc), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}),
+                d.handle, B, syndromes, given, err, conv, C_NULL, C_NULL))
+    return err, conv .!= 0
+end
+
 function decode!(d::MI355XMinSumDecoder, syndrome::AbstractVector)
     length(syndrome) == d.s || throw(BoundsError(syndrome, d.s))
     syn = UInt8[syndrome_byte(x) for x in syndrome]

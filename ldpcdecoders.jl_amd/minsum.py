@@ -74,6 +74,7 @@ class MinSumDecoder(AbstractDecoder):
             # out, so a zero gets the status the library gives every other value outside the range
             raise _capi.LdpcError(1, "alpha must lie in (0, 1] and clip must be finite and > 0 (got a zero)")
         self.scratch = MinSumScratchSpace(self.n)
+        self.conditional_llr = None   # (llr_if0, llr_if1) once set_conditional_priors has been called
         if device is None:
             device = _current_device()   # the current device NOW is the handle's for good (what info() answers)
         self.device = device
@@ -104,10 +105,14 @@ class MinSumDecoder(AbstractDecoder):
         """`.device`: the GPU the handle lives on; `.kernel`: its tier; `.tile_syndromes`: the syndromes a workgroup decodes
         at a time (S); `.last_grid`: the workgroups of the most recent launch (0 before any) -- fewer than ceil(batch / S)
         means that a workgroup took a further tile in the same LDS block or workspace slot; `.schedule` and `.layers`:
-        the schedule and its number of layers (0 for flooding)."""
+        the schedule and its number of layers (0 for flooding); `.priors_kernel` and `.priors_tile_syndromes`: the tier
+        and S of the entries with per-syndrome priors (the flooding schedule keeps a tile's priors beside its state, so
+        they may differ from `.kernel` and `.tile_syndromes`; 0 where those entries are unsupported on the handle)."""
         return SimpleNamespace(device=self.device, kernel=self.kernel, schedule=self.schedule, layers=self.layers,
                                tile_syndromes=int(self._L.ldpc_minsum_tile_syndromes(self._h)),
-                               last_grid=int(self._L.ldpc_minsum_last_grid(self._h)))
+                               last_grid=int(self._L.ldpc_minsum_last_grid(self._h)),
+                               priors_kernel=int(self._L.ldpc_minsum_priors_kernel(self._h)),
+                               priors_tile_syndromes=int(self._L.ldpc_minsum_priors_tile_syndromes(self._h)))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -153,6 +158,87 @@ class MinSumDecoder(AbstractDecoder):
         _capi.check(self._L.ldpc_minsum_decode_batch_device(
             self._h, B, syn.data_ptr(), err.data_ptr(), conv.data_ptr(), llr.data_ptr() if llr is not None else None,
             iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)), self._L)
+
+    # -- per-syndrome priors (PER-SYNDROME PRIORS of include/ldpc_mi355x.h) ----------------------------------------------
+    def _host_outputs(self, syn_bs, want_llr):
+        syn = np.ascontiguousarray(syn_bs, dtype=np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.s:
+            raise AssertionError("syndrome length does not match the number of checks")
+        B = int(syn.shape[0])
+        return (syn, B, np.empty((B, self.n), dtype=np.uint8), np.empty(B, dtype=np.uint8),
+                np.empty((B, self.n), dtype=np.float64) if want_llr else None, np.empty(B, dtype=np.int32))
+
+    def _device_args(self, syn, extra, extra_dtype, err, conv, llr, iters, stream):
+        import torch
+
+        B = int(syn.shape[0])
+        for x in (syn, err, conv):
+            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        assert extra.is_cuda and extra.dtype == extra_dtype and extra.is_contiguous() and tuple(extra.shape) == (B, self.n)
+        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
+        if llr is not None:
+            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
+        if iters is not None:
+            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
+        if stream is None:
+            stream = torch.cuda.current_stream(syn.device).cuda_stream
+        return (self._h, B, syn.data_ptr(), extra.data_ptr(), err.data_ptr(), conv.data_ptr(),
+                llr.data_ptr() if llr is not None else None, iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream))
+
+    def decode_batch_priors_host(self, syn_bs, priors, want_llr: bool = False):
+        """syn [B][s] uint8, priors [B][n] float32 (one prior LLR per syndrome and bit, in place of `.channel_llr`) ->
+        (errors, converged, llr | None, iters) as `decode_batch_host`.  A row with a non-finite prior is not decoded:
+        zeros, converged 0, iters 0, llr 0."""
+        syn, B, err, conv, llr, its = self._host_outputs(syn_bs, want_llr)
+        pri = np.ascontiguousarray(priors, dtype=np.float32)
+        if pri.shape != (B, self.n):
+            raise ValueError(f"one prior per syndrome and bit: expected shape {(B, self.n)}, got {pri.shape}")
+        _capi.check(self._L.ldpc_minsum_decode_batch_priors(self._h, B, syn.ctypes.data, pri.ctypes.data, err.ctypes.data, conv.ctypes.data,
+                                                            llr.ctypes.data if want_llr else None, its.ctypes.data), self._L)
+        return err, conv, llr, its
+
+    def decode_batch_priors_device(self, syn, priors, err, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
+        """`decode_batch_device` with priors [B][n] float32 on the decoder's GPU, contiguous."""
+        import torch
+
+        _capi.check(self._L.ldpc_minsum_decode_batch_priors_device(*self._device_args(syn, priors, torch.float32, err, conv, llr, iters, stream)),
+                    self._L)
+
+    def set_conditional_priors(self, llr_if0=None, llr_if1=None, *, probs_if0=None, probs_if1=None) -> None:
+        """The two tables of the given-bits entries: the prior LLR of bit j where its given bit is 0 / 1.  Each as LLRs
+        (finite, float32) or as error probabilities strictly inside (0, 1) (`probs_if0=` / `probs_if1=`, through
+        `llr_of_probs`); a scalar stands for every bit.  May be called again: the next call decodes with the new tables.
+        `.conditional_llr` holds the pair actually handed over."""
+        tables = []
+        for llr, probs, name in ((llr_if0, probs_if0, "if0"), (llr_if1, probs_if1, "if1")):
+            if (llr is None) == (probs is None):
+                raise TypeError(f"give exactly one of llr_{name} and probs_{name}")
+            t = np.asarray(llr, dtype=np.float32) if llr is not None else llr_of_probs(probs)
+            if t.ndim == 0:
+                t = np.full(self.n, t, dtype=np.float32)
+            if t.shape != (self.n,):
+                raise ValueError(f"one entry per bit: expected {self.n} entries, got shape {t.shape}")
+            tables.append(np.ascontiguousarray(t, dtype=np.float32))
+        _capi.check(self._L.ldpc_minsum_set_conditional_priors(self._h, tables[0].ctypes.data, tables[1].ctypes.data), self._L)
+        self.conditional_llr = (tables[0], tables[1])
+
+    def decode_batch_given_host(self, syn_bs, given, want_llr: bool = False):
+        """syn [B][s] uint8, given [B][n] uint8: the prior of bit j of row i is llr_if1[j] where given[i][j] & 1, else
+        llr_if0[j] (`set_conditional_priors`) -> as `decode_batch_host`."""
+        syn, B, err, conv, llr, its = self._host_outputs(syn_bs, want_llr)
+        giv = np.ascontiguousarray(given, dtype=np.uint8)
+        if giv.shape != (B, self.n):
+            raise ValueError(f"one given bit per syndrome and bit: expected shape {(B, self.n)}, got {giv.shape}")
+        _capi.check(self._L.ldpc_minsum_decode_batch_given(self._h, B, syn.ctypes.data, giv.ctypes.data, err.ctypes.data, conv.ctypes.data,
+                                                           llr.ctypes.data if want_llr else None, its.ctypes.data), self._L)
+        return err, conv, llr, its
+
+    def decode_batch_given_device(self, syn, given, err, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
+        """`decode_batch_device` with given [B][n] uint8 on the decoder's GPU, contiguous."""
+        import torch
+
+        _capi.check(self._L.ldpc_minsum_decode_batch_given_device(*self._device_args(syn, given, torch.uint8, err, conv, llr, iters, stream)),
+                    self._L)
 
     def decode_(self, syndrome) -> Tuple[np.ndarray, bool]:
         """One syndrome: (scratch.err, converged); scratch.log_probabs holds its LLRs."""
