@@ -820,6 +820,91 @@ ldpc_status ldpc_minsum_decode_batch_given_device(ldpc_minsum_decoder *dec, int6
                                                   double *d_llr, int32_t *d_iters, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Joint X/Z (Pauli) min-sum decoder of a CSS code: ONE decoder over both check matrices.  Every other decoder here is
+ * binary and sees one side of the code; under depolarizing noise a Y error flips both sides, and two binary decoders
+ * throw that correlation away.  Here each qubit carries three beliefs (X, Y, Z against I) and both kinds of check send
+ * the scalar min-sum messages of ldpc_minsum_* (quaternary belief propagation with scalar messages, in its min-sum
+ * form).  Not a decoder of the reference.  Compare, add and one multiply in binary32, no division and no transcendental
+ * function, so THE RULE below has one legal outcome in IEEE binary32 and a numpy model equals the device in every bit,
+ * LLRs included.  Flooding schedule only.
+ *
+ * Inputs.  hx with rx rows and hz with rz rows, both zero-based CSC patterns over the same n qubits (ldpc_css_pattern, as
+ * ldpc_css_trials_create takes them), rx >= 1 and rz >= 1.  The checks are numbered Hx rows first (0 .. rx - 1), then Hz
+ * rows (rx .. rx + rz - 1).  prior_x[n], prior_y[n], prior_z[n] binary32, each finite: log(P(I) / P(W)) of the qubit for
+ * W = X, Y, Z; the library calls no log, the caller computes the arrays.  alpha, clip, max_iters: as ldpc_minsum_create
+ * takes them.  Syndromes sx [batch][rx] (= Hx ez: an Hx row sees the Z parts) and sz [batch][rz] (= Hz ex: an Hz row sees
+ * the X parts); an entry that is not 0 counts as 1.
+ *
+ * THE RULE.  All arithmetic is binary32, every operation rounded once (no fused multiply-add), subnormals kept.
+ * min(x, y) below means  x < y ? x : y  with the operands in the order given.
+ * State per syndrome: TX[j], TZ[j], initially +0; the check-to-qubit messages c[i][j], initially +0.
+ * Derived, wherever used:  GX[j] = prior_x[j] + TX[j];  GZ[j] = prior_z[j] + TZ[j];  GY[j] = (prior_y[j] + TX[j]) + TZ[j].
+ * For t = 1 .. max_iters:
+ *   1. Check sweep.  For check i with its qubits j_0 < j_1 < ... (ascending), with G of j_k:
+ *        an Hx row (sees Z parts):  u_k = min(GY, GZ);  w_k = GX < 0 ? GX : +0
+ *        an Hz row (sees X parts):  u_k = min(GY, GX);  w_k = GZ < 0 ? GZ : +0
+ *        b_k = min(max((u_k - c[i][j_k]) - w_k, -clip), clip);   neg_k = (b_k < 0);   mag_k = |b_k|
+ *        m1, m2, a, par and the new c[i][j_k] exactly as in step 1 of THE RULE of ldpc_minsum_*: par starts from the
+ *        check's own syndrome entry (sx_i or sz_{i - rx}); the new message is alpha * (k == a ? m2 : m1) with its sign
+ *        bit set iff par XOR neg_k.  All b_k are formed from the old state before any message is replaced.  A check with
+ *        no qubits sends nothing.
+ *   2. Bit sweep.  TX[j] = ((+0 + c[i_0][j]) + c[i_1][j]) + ... over the Hz checks of j in ascending order; TZ[j] the same
+ *      sum over the Hx checks of j.  Decision:  best = X, g = GX;  if GZ < g { best = Z, g = GZ };  if GY < g { best = Y,
+ *      g = GY };  E = (g <= 0) ? best : I;  ex[j] = (E is X or Y);  ez[j] = (E is Z or Y).
+ *   3. Stop test.  If Hz ex == sz and Hx ez == sx (an empty check is matched only by a 0 entry): converged = 1, iters = t,
+ *      stop; TX, TZ, ex and ez stay as they are.
+ * Not stopped after max_iters: converged = 0, iters = max_iters.  With finite inputs no NaN or infinity can arise.
+ * The form "total minus own message" (u_k contains c[i][j_k]; it is subtracted) is part of the rule: it lets a kernel
+ * keep TX, TZ and, per check, only (alpha m1, alpha m2, a, the sign bits).
+ *
+ * Outputs.  gx [batch][n] uint8 = ex and gz [batch][n] uint8 = ez (what ldpc_css_trials_score_device reads as guesses);
+ * converged [batch] uint8; iters [batch] int32 (may be NULL); llr [batch][3][n] DOUBLE (may be NULL): the planes GX, GY,
+ * GZ of the final state widened exactly.  max_iters = 0: zeros everywhere, llr included.  batch = 0: LDPC_OK, nothing
+ * touched.
+ *
+ * ldpc_pauli_minsum_kernel: 1 = on-chip (TX, TZ and the check records of the S <= 64 syndromes a workgroup holds live in
+ * LDS for the whole decode; needs (4 (2 n + record words) + rx + rz) bytes <= 159 KiB for one syndrome, records as in
+ * ldpc_minsum_kernel over the checks of both sides); 2 = unlimited (tiles of 64 syndromes in a workspace the handle owns);
+ * 0 for NULL.  options->kernel_variant 0 = by size, 1 / 2 force a tier (1 where the state does not fit:
+ * LDPC_ERR_UNSUPPORTED).  ldpc_pauli_minsum_tile_syndromes and ldpc_pauli_minsum_last_grid: as
+ * ldpc_minsum_tile_syndromes and ldpc_minsum_last_grid, by the same policy over that state.
+ *
+ * ldpc_pauli_minsum_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL or non-finite prior,
+ * alpha outside (0, 1], clip not in (0, inf), a kernel_variant outside 0..2, a NULL pattern or one ldpc_bp_create rejects
+ * on either side, and rx < 1 or rz < 1; without a device LDPC_ERR_NO_DEVICE.  The library does not check that Hx and Hz
+ * commute.  The decode entries reject a NULL handle, a negative batch and a NULL required pointer the same way.
+ * ldpc_pauli_minsum_decode_batch takes HOST buffers and is synchronous (its wait is bounded by ldpc_set_wait_limit_ms);
+ * ldpc_pauli_minsum_decode_batch_device takes DEVICE pointers and is asynchronous on `stream`; calls on one handle run in
+ * call order whatever streams they are given.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_pauli_minsum_decoder ldpc_pauli_minsum_decoder;
+
+/* Optional; pass NULL to ldpc_pauli_minsum_create for defaults.  A zeroed struct means defaults too, except `device` (0
+ * is device 0; -1 = the current one): alpha = 0 / clip = 0 select 0.75 / 1.0e6f. */
+typedef struct ldpc_pauli_minsum_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    float alpha;             /* normalisation factor in (0, 1]; 0 = default 0.75 */
+    float clip;              /* clamp of the qubit-to-check values, finite, > 0; 0 = default 1.0e6f */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_pauli_minsum_kernel */
+    int32_t reserved[12];
+} ldpc_pauli_minsum_options;
+
+ldpc_status ldpc_pauli_minsum_create(int64_t n, const ldpc_css_pattern *hx, const ldpc_css_pattern *hz,
+                                     const float *prior_x, const float *prior_y, const float *prior_z, int64_t max_iters,
+                                     const ldpc_pauli_minsum_options *options, ldpc_pauli_minsum_decoder **out);
+ldpc_status ldpc_pauli_minsum_destroy(ldpc_pauli_minsum_decoder *dec);
+int32_t ldpc_pauli_minsum_kernel(const ldpc_pauli_minsum_decoder *dec);
+int32_t ldpc_pauli_minsum_tile_syndromes(const ldpc_pauli_minsum_decoder *dec);
+int32_t ldpc_pauli_minsum_last_grid(const ldpc_pauli_minsum_decoder *dec);
+ldpc_status ldpc_pauli_minsum_decode_batch(ldpc_pauli_minsum_decoder *dec, int64_t batch, const uint8_t *sx, const uint8_t *sz,
+                                           uint8_t *gx, uint8_t *gz, uint8_t *converged, double *llr, int32_t *iters);
+ldpc_status ldpc_pauli_minsum_decode_batch_device(ldpc_pauli_minsum_decoder *dec, int64_t batch, const uint8_t *d_sx,
+                                                  const uint8_t *d_sz, uint8_t *d_gx, uint8_t *d_gz, uint8_t *d_converged,
+                                                  double *d_llr, int32_t *d_iters, void *stream);
+
+/* ------------------------------------------------------------------------
  * Relay min-sum decoder: normalised min-sum with a per-bit MEMORY, run as a chain of LEGS, returning the solution of
  * lowest prior weight among the first `stop_after` it finds.  For the degenerate, short-cycle graphs of quantum LDPC
  * codes, where plain min-sum stalls.  Like ldpc_minsum_* it has no division and no transcendental function, so THE

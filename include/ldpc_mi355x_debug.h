@@ -75,6 +75,14 @@ ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_
 ldpc_status ldpc_debug_priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t schedule, int32_t kernel_variant,
                                         int32_t *tier, int32_t *tile_syndromes, int64_t *state_bytes);
 
+/* The plan of a joint X/Z (Pauli) min-sum handle -- csrc/tile_plan.hpp pauli_tile_plan(), the function
+   ldpc_pauli_minsum_create calls.  s = rx + rz checks of both sides, n qubits, rec_words over the checks of both sides
+   (counted as for ldpc_debug_tile_plan).  A tile of S syndromes has a state of  S (4 (2 n + rec_words) + s)  bytes,
+   rounded up to 256, and the policy of ldpc_debug_tile_plan runs over that size.  Out and statuses as there.  No
+   reference counterpart. */
+ldpc_status ldpc_debug_pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t kernel_variant, int32_t *tier,
+                                       int32_t *tile_syndromes, int64_t *state_bytes);
+
 /* The layers ldpc_minsum_create gives a handle of the layered schedule (options->schedule = 1; THE LAYERED RULE of
    include/ldpc_mi355x.h) -- csrc/layer_plan.hpp layer_plan_build(), the function create calls, followed by the same
    verification (no two checks of a layer share a bit, every non-empty check in exactly one layer).  H as the zero-based

@@ -29,7 +29,8 @@ from .bitflip import BitFlipDecoder, BitFlipScratchSpace  # noqa: F401,E402
 from .minsum import MinSumDecoder, MinSumScratchSpace  # noqa: F401,E402
 from .relay import RelayMinSumDecoder  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
-from .css_trials import CSSTrialResult, CSSTrials, conditional_probs, run_css_trials  # noqa: F401,E402
+from .css_trials import CSSTrialResult, CSSTrials, conditional_probs, run_css_joint_trials, run_css_trials  # noqa: F401,E402
+from .pauli import PauliMinSumDecoder  # noqa: F401,E402
 from .dem import DetectorErrorModel, phenomenological, run_dem_trials  # noqa: F401,E402
 from .windows import SlidingWindowDecoder, WindowPlan, WindowStep, phenomenological_layers, window_plan  # noqa: F401,E402
 
@@ -40,7 +41,7 @@ __all__ = [
     "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
     "MinSumDecoder", "MinSumScratchSpace", "RelayMinSumDecoder",
     "Trials", "TrialResult", "run_trials",
-    "CSSTrials", "CSSTrialResult", "run_css_trials", "conditional_probs",
+    "CSSTrials", "CSSTrialResult", "run_css_trials", "run_css_joint_trials", "conditional_probs", "PauliMinSumDecoder",
     "DetectorErrorModel", "phenomenological", "run_dem_trials",
     "SlidingWindowDecoder", "WindowPlan", "WindowStep", "phenomenological_layers", "window_plan",
 ]

@@ -93,6 +93,13 @@ EXPORTED_SYMBOLS = (
     "ldpc_relay_last_grid",
     "ldpc_relay_decode_batch",
     "ldpc_relay_decode_batch_device",
+    "ldpc_pauli_minsum_create",
+    "ldpc_pauli_minsum_destroy",
+    "ldpc_pauli_minsum_kernel",
+    "ldpc_pauli_minsum_tile_syndromes",
+    "ldpc_pauli_minsum_last_grid",
+    "ldpc_pauli_minsum_decode_batch",
+    "ldpc_pauli_minsum_decode_batch_device",
     "ldpc_trials_create",
     "ldpc_trials_destroy",
     "ldpc_trials_kernel",
@@ -121,7 +128,7 @@ EXPORTED_SYMBOLS = (
 # ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
 DEBUG_SYMBOLS = ("ldpc_debug_team_rows", "ldpc_debug_team_plan", "ldpc_debug_div_check", "ldpc_debug_process_state",
                  "ldpc_debug_adopt_process_state", "ldpc_debug_team_irr", "ldpc_debug_llr_check", "ldpc_debug_tile_plan", "ldpc_debug_layer_plan",
-                 "ldpc_debug_priors_tile_plan")
+                 "ldpc_debug_priors_tile_plan", "ldpc_debug_pauli_tile_plan")
 
 MULTI_MAX_DEVICES = 16
 EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_NONE = 0, 1, 2, 3
@@ -190,6 +197,14 @@ class RelayOptions(ctypes.Structure):
     ]
 
 
+class PauliMinSumOptions(ctypes.Structure):
+    """ldpc_pauli_minsum_options: alpha = 0 / clip = 0 select the defaults (0.75, 1e6)."""
+    _fields_ = [
+        ("device", ctypes.c_int32), ("alpha", ctypes.c_float), ("clip", ctypes.c_float),
+        ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 12),
+    ]
+
+
 class TrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
@@ -210,7 +225,7 @@ class WindowsOptions(ctypes.Structure):
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "layered_kernels.hpp", "layer_plan.hpp", "layer_plan.cpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_windows.hip", "window_kernels.hpp", "window_plan.cpp", "window_plan.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "layered_kernels.hpp", "layer_plan.hpp", "layer_plan.cpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_pauli.hip", "pauli_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_windows.hip", "window_kernels.hpp", "window_plan.cpp", "window_plan.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
@@ -270,6 +285,8 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_debug_tile_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
     L.ldpc_debug_priors_tile_plan.restype = i32
     L.ldpc_debug_priors_tile_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
+    L.ldpc_debug_pauli_tile_plan.restype = i32
+    L.ldpc_debug_pauli_tile_plan.argtypes = [i64, i64, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
     L.ldpc_debug_layer_plan.restype = i32
     L.ldpc_debug_layer_plan.argtypes = [i64, i64, vp, vp, vp, ctypes.POINTER(i32)]
     L.ldpc_debug_team_irr.restype = i32
@@ -430,6 +447,20 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
     L.ldpc_css_trials_sample.argtypes = [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp]
     L.ldpc_css_trials_score.restype = i32
     L.ldpc_css_trials_score.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ldpc_pauli_minsum_create.restype = i32
+    L.ldpc_pauli_minsum_create.argtypes = [i64, pat, pat, vp, vp, vp, i64, ctypes.POINTER(PauliMinSumOptions), ctypes.POINTER(vp)]
+    L.ldpc_pauli_minsum_destroy.restype = i32
+    L.ldpc_pauli_minsum_destroy.argtypes = [vp]
+    L.ldpc_pauli_minsum_kernel.restype = i32
+    L.ldpc_pauli_minsum_kernel.argtypes = [vp]
+    L.ldpc_pauli_minsum_tile_syndromes.restype = i32
+    L.ldpc_pauli_minsum_tile_syndromes.argtypes = [vp]
+    L.ldpc_pauli_minsum_last_grid.restype = i32
+    L.ldpc_pauli_minsum_last_grid.argtypes = [vp]
+    L.ldpc_pauli_minsum_decode_batch.restype = i32
+    L.ldpc_pauli_minsum_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ldpc_pauli_minsum_decode_batch_device.restype = i32
+    L.ldpc_pauli_minsum_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ldpc_windows_create.restype = i32
     L.ldpc_windows_create.argtypes = [i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(WindowsOptions), ctypes.POINTER(vp)]
     L.ldpc_windows_destroy.restype = i32

@@ -2,7 +2,8 @@
 // device code: minsum_kernels.hpp, relay_kernels.hpp), and the sizes of a tile's state they are chosen from.  Pure host
 // code over the standard library -- no HIP, no decoder handle, no environment -- so that it builds with a plain C++
 // compiler and runs under the sanitizers on the CPU (tests/native/team_plan_sanitize.cpp).  Both `create` routines call
-// tile_plan(); ldpc_debug_tile_plan (include/ldpc_mi355x_debug.h) hands it to the CPU tests.
+// tile_plan(); ldpc_debug_tile_plan (include/ldpc_mi355x_debug.h) hands it to the CPU tests.  At the end: the state size
+// and the plan of the joint X/Z (Pauli) min-sum decoder (ldpc_pauli.hip), the same policy over another size.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -86,6 +87,34 @@ inline bool priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, bool layer
     p.S = p.tier == 1 ? S : 64;
     for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
     p.state_bytes = ms_priors_state_bytes(s, n, rec_words, p.S);
+    *out = p;
+    return true;
+}
+
+// ---- the joint X/Z (Pauli) min-sum decoder (ldpc_pauli.hip; device code: pauli_kernels.hpp) ------------------------------
+// bytes of a Pauli tile's state: S lanes of (2 n + rec_words) words -- the two message totals TX, TZ and the check records of
+// both sides -- and s = rx + rz syndrome bytes, rounded up to 256
+inline size_t pauli_state_bytes(long long s, long long n, long long rec_words, int S)
+{
+    return (((size_t)(2 * n + rec_words) * 4 + (size_t)s) * (size_t)S + 255) & ~(size_t)255;
+}
+
+// Its plan: the policy of tile_plan() over that size (s = rx + rz, rec_words over the checks of both sides).  false:
+// variant 1 and nothing fits.
+inline bool pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, int variant, TilePlan *out)
+{
+    int S = 0;
+    for (size_t budget : {kTileLdsTwo, kTileLdsOne}) {
+        for (int w = 64; w >= 1 && !S; w >>= 1)
+            if (pauli_state_bytes(s, n, rec_words, w) <= budget) S = w;
+        if (S) break;
+    }
+    if (variant == 1 && !S) return false;
+    TilePlan p;
+    p.tier = variant ? variant : S ? 1 : 2;
+    p.S = p.tier == 1 ? S : 64;
+    for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
+    p.state_bytes = pauli_state_bytes(s, n, rec_words, p.S);
     *out = p;
     return true;
 }

@@ -322,3 +322,43 @@ def run_css_trials(decoder_hx, decoder_hz, trials: int, p, batch: int = 65536, s
     return CSSTrialResult(trials=int(c[0]), block_errors=int(c[1]), syndrome_mismatches=int(c[2]), logical_errors=int(c[3]),
                           logical_x_errors=int(c[4]), logical_z_errors=int(c[5]), not_converged_hx=int(nc[0]),
                           not_converged_hz=int(nc[1]))
+
+
+def run_css_joint_trials(decoder, trials: int, p, batch: int = 65536, seed: int = 0, logicals=None) -> CSSTrialResult:
+    """`run_css_trials` with ONE joint decoder in place of the two binary ones: `decoder` is a `PauliMinSumDecoder` built
+    on (Hx, Hz); every batch is sampled under Pauli noise `p`, decoded once from (sx, sz) into (gx, gz), and scored, all
+    on torch's current stream of the decoder's GPU.  Trial number c is column c of the sampling rule, so the result does
+    not depend on `batch`.  Only the six counts and the number of unconverged columns are read back; a joint decode
+    converges or not as a whole, so `not_converged_hx` and `not_converged_hz` both hold that number.  Nothing here
+    changes the decoder: whether its priors were built from the same `p` is the caller's choice.  logicals: as in
+    CSSTrials."""
+    import torch
+
+    device = int(decoder.info().device) if decoder.info().device is not None else int(torch.cuda.current_device())
+    dev = torch.device("cuda", device)
+    total, batch = int(trials), int(batch)
+    assert total >= 0 and batch > 0
+    tr = CSSTrials(decoder.sparse_Hx, decoder.sparse_Hz, logicals, device=device)
+    try:
+        with torch.cuda.device(dev):
+            counts = torch.zeros(6, dtype=torch.int64, device=dev)
+            unconverged = torch.zeros(1, dtype=torch.int64, device=dev)
+            B = min(batch, max(total, 1))
+            ex, ez, gx, gz = (torch.empty((B, tr.n), dtype=torch.uint8, device=dev) for _ in range(4))
+            sx = torch.empty((B, tr.rows_x), dtype=torch.uint8, device=dev)
+            sz = torch.empty((B, tr.rows_z), dtype=torch.uint8, device=dev)
+            conv = torch.empty(B, dtype=torch.uint8, device=dev)
+            done = 0
+            while done < total:
+                b = min(B, total - done)
+                tr.sample(b, p, seed=seed, column0=done, out=(ex[:b], ez[:b], sx[:b], sz[:b]))
+                decoder.decode_batch_device(sx[:b], sz[:b], gx[:b], gz[:b], conv[:b])
+                tr.score(gx[:b], gz[:b], ex[:b], ez[:b], counts=counts, want_flags=False)
+                unconverged[0] += (conv[:b] == 0).sum()
+                done += b
+            c = counts.cpu().tolist()
+            nc = int(unconverged.cpu().tolist()[0])
+    finally:
+        tr.close()
+    return CSSTrialResult(trials=int(c[0]), block_errors=int(c[1]), syndrome_mismatches=int(c[2]), logical_errors=int(c[3]),
+                          logical_x_errors=int(c[4]), logical_z_errors=int(c[5]), not_converged_hx=nc, not_converged_hz=nc)
