@@ -225,7 +225,7 @@ class WindowsOptions(ctypes.Structure):
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "layered_kernels.hpp", "layer_plan.hpp", "layer_plan.cpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_pauli.hip", "pauli_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_windows.hip", "window_kernels.hpp", "window_plan.cpp", "window_plan.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
+                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "layered_kernels.hpp", "layer_plan.hpp", "layer_plan.cpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_pauli.hip", "pauli_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_windows.hip", "window_kernels.hpp", "window_plan.cpp", "window_plan.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "tile_host.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
                                              "bpots_kernels.hpp", "portable_math.h", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))

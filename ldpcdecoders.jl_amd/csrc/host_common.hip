@@ -207,12 +207,6 @@ TannerGraph tanner_graph(int64_t s, int64_t n, int64_t nnz, const int64_t *colpt
     return g;
 }
 
-bool upload_ints(int **dst, const std::vector<int> &v)
-{
-    if (hipMalloc((void **)dst, std::max<size_t>(v.size(), 1) * sizeof(int)) != hipSuccess) return false;
-    return hipMemcpy(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-}
-
 ldpc_status grow_device_buffer(void **p, size_t *cap, size_t bytes, int device, const char *what)
 {
     if (*cap >= bytes) return LDPC_OK;

@@ -63,7 +63,12 @@ struct TannerGraph {
 };
 TannerGraph tanner_graph(int64_t s, int64_t n, int64_t nnz, const int64_t *colptr, const int64_t *rowval);   // host_common.hip (validated pattern)
 
-bool upload_ints(int **dst, const std::vector<int> &v);  // host_common.hip: hipMalloc (at least one element) + hipMemcpy
+template <class V>
+inline bool upload(V **dst, const std::vector<V> &v)   // hipMalloc (at least one element) + hipMemcpy
+{
+    if (hipMalloc((void **)dst, (v.empty() ? 1 : v.size()) * sizeof(V)) != hipSuccess) return false;
+    return v.empty() || hipMemcpy(*dst, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice) == hipSuccess;
+}
 
 // host_common.hip: *p holds at least `bytes` afterwards.  A buffer that has to grow is freed only once the device has
 // drained (bounded: `what` names that wait), and its contents are not kept.

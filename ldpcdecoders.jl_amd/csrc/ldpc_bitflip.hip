@@ -97,9 +97,9 @@ ldpc_status ldpc_bitflip_create(int64_t s, int64_t n, int64_t nnz, const int64_t
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant: the state of a syndrome does not fit that on-chip tier");
     }
     d->tier = wide_votes ? 4 : variant ? variant : fits1 ? 1 : fits2 ? 2 : 3;
-    using ldpc_detail::upload_ints;
-    if (!upload_ints(&d->row_ptr, g.row_ptr) || !upload_ints(&d->csr_col, g.csr_col) || !upload_ints(&d->col_ptr, g.col_ptr) ||
-        !upload_ints(&d->csc_row, g.csc_row) || d->calls.create() != hipSuccess) {
+    using ldpc_detail::upload;
+    if (!upload(&d->row_ptr, g.row_ptr) || !upload(&d->csr_col, g.csr_col) || !upload(&d->col_ptr, g.col_ptr) ||
+        !upload(&d->csc_row, g.csc_row) || d->calls.create() != hipSuccess) {
         (void)hipGetLastError();
         delete d;
         return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the Tanner graph failed");

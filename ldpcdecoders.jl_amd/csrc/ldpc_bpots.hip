@@ -111,9 +111,9 @@ ldpc_status ldpc_bpots_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
         // buckets: everything in the global slot, any degree (the reference's BPOTSDecoder has no limit either)
         d->big_mode = wide || force_node >= 2 || ots_node_lds_bytes((int)s, (int)n) + 1024 > (size_t)156 * 1024;
     }
-    using ldpc_detail::upload_ints;
-    if (!upload_ints(&d->row_ptr, g.row_ptr) || !upload_ints(&d->csc_row, g.csc_row) || !upload_ints(&d->col_ptr, g.col_ptr) ||
-        !upload_ints(&d->csc2csr, g.csc2csr) ||
+    using ldpc_detail::upload;
+    if (!upload(&d->row_ptr, g.row_ptr) || !upload(&d->csc_row, g.csc_row) || !upload(&d->col_ptr, g.col_ptr) ||
+        !upload(&d->csc2csr, g.csc2csr) ||
         hipMalloc((void **)&d->queue, 64) != hipSuccess || hipMalloc((void **)&d->done_ctr, 64) != hipSuccess ||
         hipMemset(d->done_ctr, 0, 64) != hipSuccess) {
         (void)hipGetLastError();

@@ -1,12 +1,10 @@
 // ldpc_minsum.hip -- host side of the normalised min-sum decoder with per-bit channel LLRs: the ldpc_minsum_* entry
 // points of include/ldpc_mi355x.h (the rule is stated there).  Device code: minsum_kernels.hpp (the flooding schedule) and
-// layered_kernels.hpp (the layered one, over the layers of layer_plan.hpp).  Tiers (ldpc_minsum_kernel), of both schedules:
-//   1  on-chip: the state of the S syndromes a workgroup holds lives in LDS for the whole decode (S = 64, 32, ... 1:
-//      the largest that leaves room for two workgroups a CU, else the largest that fits one)
-//   2  unlimited: tiles of 64 syndromes, the state in a global workspace, one slot per workgroup of a persistent grid
-// The entries with per-syndrome priors (decode_batch_priors / decode_batch_given) run the same kernel templates with
-// another prior source and, in the flooding schedule, a larger state (the staged priors): a handle holds a second plan
-// for them (priors_tile_plan, tile_plan.hpp), computed at create.  No CPU path.
+// layered_kernels.hpp (the layered one, over the layers of layer_plan.hpp).  The tiers (ldpc_minsum_kernel) and the tile
+// width of both schedules: tile_plan.hpp; the launch geometry, the staging of the host-pointer entries and the rest of
+// what the min-sum family shares on the host: tile_host.hpp.  The entries with per-syndrome priors (decode_batch_priors /
+// decode_batch_given) run the same kernel templates with another prior source and, in the flooding schedule, a larger
+// state (the staged priors): a handle holds a second plan for them (priors_tile_plan), computed at create.  No CPU path.
 #include "../../include/ldpc_mi355x.h"
 #include "../../include/ldpc_mi355x_debug.h"
 #include "minsum_kernels.hpp"
@@ -24,58 +22,44 @@ using namespace ldpc;
 
 #include "host_env.hpp"      // exp_env: LDPC_MS_GRID_MAX, experiments build only
 #include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
+#include "tile_host.hpp"
 using ldpc_detail::set_error;
-
-static constexpr int kMsLdsWaves = 8, kMsGlobalWaves = 16;   // (16 waves: 2.2x the speed of 4 at n = 16384, the sweeps are latency-bound)
-static constexpr size_t kMsWorkspaceCap = (size_t)6 << 30;   // the unlimited tier's grid shrinks to keep its slots below this
-static constexpr float kMsAlphaDefault = 0.75f, kMsClipDefault = 1.0e6f;
+using ldpc_detail::kTileLdsWaves;
+using ldpc_detail::kTileGlobalWaves;
 
 struct ldpc_minsum_decoder {
     int64_t s = 0, n = 0, nnz = 0, max_iters = 0;
-    float alpha = kMsAlphaDefault, clip = kMsClipDefault;
-    int device = 0, num_cus = 0, tier = 0, S = 64, shift = 6, rec_words = 0;
-    TilePlan pplan;             // the plan of the priors / given entries; tier 0: kernel_variant 1 and their state does not fit
+    float alpha = 0.0f, clip = 0.0f;
+    int rec_words = 0;
+    TilePlan plan;              // of the plain entries
+    TilePlan pplan;             // of the priors / given entries; tier 0: kernel_variant 1 and their state does not fit
     int schedule = 0, layers = 0;   // 1 = layered: K layers, layer_ptr [K + 1] and layer_checks on the device
     int *layer_ptr = nullptr, *layer_checks = nullptr;
     int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *edge_rec = nullptr, *edge_pos = nullptr;
     float *prior = nullptr;
     float *cond = nullptr;      // [2][n]: llr_if0, llr_if1, once ldpc_minsum_set_conditional_priors has been called
-    void *stage = nullptr;      // device staging for the host-pointer entry
-    size_t stage_cap = 0;
-    unsigned char *ws = nullptr;   // tier 2: [grid][slot]
-    size_t ws_cap = 0;
-    bool kernel_ready[3] = {false, false, false};   // per prior source (kMsPrior*): each is a kernel function of its own
-    int per_cu[3] = {1, 1, 1};
-    int grid_max = 0;    // LDPC_MS_GRID_MAX (experiments build): workgroups a launch takes at most; 0 = no cap
-    int last_grid = 0;   // workgroups of the most recent launch
-    ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (they share the workspace)
-    ~ldpc_minsum_decoder()
-    {
-        if (ldpc_detail::device_stalled(device)) return;   // (host_wait.hpp: nothing a stalled device may still use is freed)
-        void *all[] = {row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, layer_ptr, layer_checks, prior, cond, stage, ws};
-        for (void *q : all)
-            if (q) (void)hipFree(q);
-        calls.destroy();
-    }
+    ldpc_detail::TileHost tile;            // (grid_max: LDPC_MS_GRID_MAX of the experiments build)
+    ldpc_detail::TileKernel kernels[3];    // per prior source (kMsPrior*): each is a kernel function of its own
+    ~ldpc_minsum_decoder() { tile.release({row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, layer_ptr, layer_checks, prior, cond}); }
 };
 
 typedef void (*ms_kernel_t)(MsParams);
-static ms_kernel_t ms_kernel_of(int tier) { return tier == 1 ? minsum_kernel<kMsLdsWaves, false> : minsum_kernel<kMsGlobalWaves, true>; }
+static ms_kernel_t ms_kernel_of(int tier) { return tier == 1 ? minsum_kernel<kTileLdsWaves, false> : minsum_kernel<kTileGlobalWaves, true>; }
 typedef void (*layered_kernel_t)(LayeredParams);
 static layered_kernel_t layered_kernel_of(int tier)
 {
-    return tier == 1 ? layered_minsum_kernel<kMsLdsWaves, false> : layered_minsum_kernel<kMsGlobalWaves, true>;
+    return tier == 1 ? layered_minsum_kernel<kTileLdsWaves, false> : layered_minsum_kernel<kTileGlobalWaves, true>;
 }
 // ... and with per-syndrome priors
 typedef void (*ms_priors_kernel_t)(MsPriorsParams);
 template <int SRC> static ms_priors_kernel_t ms_priors_kernel_of(int tier)
 {
-    return tier == 1 ? minsum_kernel<kMsLdsWaves, false, SRC> : minsum_kernel<kMsGlobalWaves, true, SRC>;
+    return tier == 1 ? minsum_kernel<kTileLdsWaves, false, SRC> : minsum_kernel<kTileGlobalWaves, true, SRC>;
 }
 typedef void (*layered_priors_kernel_t)(LayeredPriorsParams);
 template <int SRC> static layered_priors_kernel_t layered_priors_kernel_of(int tier)
 {
-    return tier == 1 ? layered_minsum_kernel<kMsLdsWaves, false, SRC> : layered_minsum_kernel<kMsGlobalWaves, true, SRC>;
+    return tier == 1 ? layered_minsum_kernel<kTileLdsWaves, false, SRC> : layered_minsum_kernel<kTileGlobalWaves, true, SRC>;
 }
 
 // One decode on `stream`, whatever the prior source: the plan and the state of the plain entries for the table, of the
@@ -83,9 +67,9 @@ template <int SRC> static layered_priors_kernel_t layered_priors_kernel_of(int t
 static ldpc_status ms_launch(ldpc_minsum_decoder *d, int src_kind, const MsPriorSource &src, int64_t batch, const uint8_t *d_syn,
                              uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters, hipStream_t stream)
 {
-    LDPC_HIP_TRY(hipSetDevice(d->device));
-    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
-    ldpc_status st = d->calls.enter(stream);
+    LDPC_HIP_TRY(hipSetDevice(d->tile.device));
+    if (ldpc_detail::device_stalled(d->tile.device)) return ldpc_detail::stalled_error(d->tile.device);
+    ldpc_status st = d->tile.calls.enter(stream);
     if (st != LDPC_OK) return st;
     if (d->max_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
         if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
@@ -94,11 +78,8 @@ static ldpc_status ms_launch(ldpc_minsum_decoder *d, int src_kind, const MsPrior
         if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
     } else {
         const bool staged = src_kind != kMsPriorTable, layered = d->schedule == 1;
-        const int tier = staged ? d->pplan.tier : d->tier, S = staged ? d->pplan.S : d->S, shift = staged ? d->pplan.shift : d->shift;
-        const bool global = tier == 2;
-        const int threads = (global ? kMsGlobalWaves : kMsLdsWaves) * 64;
-        const size_t state = staged ? d->pplan.state_bytes : ms_state_bytes(d->s, d->n, d->rec_words, d->S);
-        const size_t lds = global ? 0 : state;
+        const TilePlan &plan = staged ? d->pplan : d->plan;
+        const int tier = plan.tier, threads = ldpc_detail::tile_threads(tier);
         const void *k;
         if (src_kind == kMsPriorFloats)
             k = layered ? (const void *)layered_priors_kernel_of<kMsPriorFloats>(tier) : (const void *)ms_priors_kernel_of<kMsPriorFloats>(tier);
@@ -106,28 +87,18 @@ static ldpc_status ms_launch(ldpc_minsum_decoder *d, int src_kind, const MsPrior
             k = layered ? (const void *)layered_priors_kernel_of<kMsPriorGiven>(tier) : (const void *)ms_priors_kernel_of<kMsPriorGiven>(tier);
         else
             k = layered ? (const void *)layered_kernel_of(tier) : (const void *)ms_kernel_of(tier);
-        if (!d->kernel_ready[src_kind]) {
-            // (the limit belongs to the kernel, not to the handle: every handle asks for the tier's maximum, so none lowers another's)
-            if (lds) LDPC_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLdsOne));
-            d->per_cu[src_kind] = ldpc_detail::blocks_per_cu(k, threads, lds);
-            d->kernel_ready[src_kind] = true;
-        }
-        const int64_t tiles = (batch + S - 1) >> shift;
-        int64_t grid = std::min<int64_t>(tiles, (int64_t)d->per_cu[src_kind] * d->num_cus);
-        if (d->grid_max > 0) grid = std::min<int64_t>(grid, d->grid_max);
-        if (global) {
-            grid = std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(kMsWorkspaceCap / state)));
-            st = ldpc_detail::grow_device_buffer((void **)&d->ws, &d->ws_cap, (size_t)grid * state, d->device,
-                                                 "min-sum workspace regrow (device synchronise before the free)");
-            if (st != LDPC_OK) return st;
-        }
+        int64_t grid;
+        size_t lds;
+        st = ldpc_detail::tile_geometry(&d->tile, &d->kernels[src_kind], k, threads, plan, batch,
+                                        "min-sum workspace regrow (device synchronise before the free)", &grid, &lds);
+        if (st != LDPC_OK) return st;
         MsParams p{};
-        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = S; p.shift = shift;
+        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = plan.S; p.shift = plan.shift;
         p.batch = batch; p.alpha = d->alpha; p.clip = d->clip;
         p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
         p.prior = d->prior; p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
         p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
-        p.ws = d->ws; p.slot_bytes = (long long)state;
+        p.ws = d->tile.ws; p.slot_bytes = (long long)plan.state_bytes;
         const dim3 g((unsigned)grid), b((unsigned)threads);
         if (layered) {
             LayeredPriorsParams lp{};
@@ -143,9 +114,9 @@ static ldpc_status ms_launch(ldpc_minsum_decoder *d, int src_kind, const MsPrior
             else hipLaunchKernelGGL(ms_kernel_of(tier), g, b, lds, stream, p);
         }
         LDPC_HIP_TRY(hipGetLastError());
-        d->last_grid = (int)grid;
+        d->tile.last_grid = (int)grid;
     }
-    return d->calls.leave(stream);
+    return d->tile.calls.leave(stream);
 }
 
 // what every device entry checks before any device work; batch == 0 is the caller's to answer
@@ -178,25 +149,13 @@ template <class F>
 static ldpc_status ms_decode_to_host(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *syn, const void *extra, size_t extra_bytes,
                                      uint8_t *err, uint8_t *conv, double *llr, int32_t *iters, const char *what, F decode)
 {
-    LDPC_HIP_TRY(hipSetDevice(d->device));
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][LLRs][priors or given bits]
-    image.take(B * s);
-    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4);
-    const size_t o_llr = image.take(llr ? B * n * sizeof(double) : 0), o_extra = image.take(B * extra_bytes), total = image.at;
-    ldpc_status st = ldpc_detail::grow_device_buffer(&d->stage, &d->stage_cap, total, d->device, "min-sum staging regrow (device synchronise before the free)");
-    if (st != LDPC_OK) return st;
-    char *dp = (char *)d->stage;
-    if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, syn, B * s, hipMemcpyHostToDevice, nullptr));
-    if (extra_bytes > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp + o_extra, extra, B * extra_bytes, hipMemcpyHostToDevice, nullptr));
-    st = decode((const uint8_t *)dp, (const void *)(dp + o_extra), (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
-                llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it));
-    if (st != LDPC_OK) return st;
-    if (n > 0) LDPC_HIP_TRY(hipMemcpyAsync(err, dp + o_err, B * n, hipMemcpyDeviceToHost, nullptr));
-    LDPC_HIP_TRY(hipMemcpyAsync(conv, dp + o_conv, B, hipMemcpyDeviceToHost, nullptr));
-    if (iters) LDPC_HIP_TRY(hipMemcpyAsync(iters, dp + o_it, B * 4, hipMemcpyDeviceToHost, nullptr));
-    if (llr && n > 0) LDPC_HIP_TRY(hipMemcpyAsync(llr, dp + o_llr, B * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    return ldpc_detail::wait_stream(nullptr, d->device, what);
+    ldpc_detail::StageRegion r[] = {{syn, nullptr, B * s}, {nullptr, err, B * n}, {nullptr, conv, B}, {nullptr, iters, B * 4},
+                                    {nullptr, llr, llr ? B * n * sizeof(double) : 0}, {extra, nullptr, B * extra_bytes}};
+    return ldpc_detail::staged_call(&d->tile, r, "min-sum staging regrow (device synchronise before the free)", what, [&](char *dp) {
+        return decode((const uint8_t *)dp, (const void *)(dp + r[5].at), (uint8_t *)(dp + r[1].at), (uint8_t *)(dp + r[2].at),
+                      llr ? (double *)(dp + r[4].at) : nullptr, (int32_t *)(dp + r[3].at));
+    });
 }
 
 extern "C" {
@@ -210,14 +169,10 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
     ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, max_iters);
     if (st != LDPC_OK) return st;
     if (n > 0 && !channel_llr) return set_error(LDPC_ERR_INVALID_ARGUMENT, "channel_llr is NULL");
-    const float alpha = options && options->alpha != 0.0f ? options->alpha : kMsAlphaDefault;   // a zeroed struct: defaults
-    const float clip = options && options->clip != 0.0f ? options->clip : kMsClipDefault;
-    const int variant = options ? options->kernel_variant : 0;
+    float alpha, clip;
+    int variant, device;
+    if ((st = ldpc_detail::tile_options(options, &alpha, &clip, &variant, &device)) != LDPC_OK) return st;
     const int schedule = options ? options->schedule : 0;
-    int device = options ? options->device : -1;
-    if (!(alpha > 0.0f && alpha <= 1.0f)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "alpha must lie in (0, 1]");
-    if (!(clip > 0.0f) || std::isinf(clip)) return set_error(LDPC_ERR_INVALID_ARGUMENT, "clip must be finite and > 0");
-    if (variant < 0 || variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
     if (schedule < 0 || schedule > 1) return set_error(LDPC_ERR_INVALID_ARGUMENT, "schedule must be 0 (flooding) or 1 (layered)");
     for (int64_t j = 0; j < n; ++j)
         if (!std::isfinite(channel_llr[j]))
@@ -232,28 +187,16 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
     ldpc_minsum_decoder *d = new (std::nothrow) ldpc_minsum_decoder();
     if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     d->s = s; d->n = n; d->nnz = nnz; d->max_iters = max_iters; d->alpha = alpha; d->clip = clip;
-    d->device = device; d->num_cus = prop.multiProcessorCount; d->schedule = schedule;
+    d->tile.device = device; d->tile.num_cus = prop.multiProcessorCount; d->schedule = schedule;
     // CSR (checks -> bits, ascending) next to the caller's CSC; a record per check; per CSC edge its record and position
     const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
-    std::vector<int> rec_off((size_t)std::max<int64_t>(s, 1), 0), edge_rec(g.csc_row.size(), 0), edge_pos(g.csc_row.size(), 0);
-    int64_t words = 0;
-    for (int64_t i = 0; i < s; ++i) {
-        rec_off[(size_t)i] = (int)words;
-        words += ms_record_words(g.row_ptr[(size_t)i + 1] - g.row_ptr[(size_t)i]);   // <= 4 nnz + ... < 2^31
-    }
-    for (int64_t e = 0; e < nnz; ++e) {
-        const int i = g.csc_row[(size_t)e], k = g.csc2csr[(size_t)e] - g.row_ptr[(size_t)i];
-        edge_rec[(size_t)e] = rec_off[(size_t)i];
-        edge_pos[(size_t)e] = g.row_ptr[(size_t)i + 1] - g.row_ptr[(size_t)i] > 64 ? (k | kMsPosEdge) : k;
-    }
-    d->rec_words = (int)words;
-    TilePlan plan;   // the tier and the tile width (tile_plan.hpp)
-    if (!tile_plan(s, n, words, false, variant, &plan)) {
+    const MsRecords rec = ms_records(s, nnz, g.row_ptr.data(), g.csc_row.data(), g.csc2csr.data());   // words <= 4 s + nnz < 2^31
+    d->rec_words = (int)rec.words;
+    if (!tile_plan(s, n, rec.words, false, variant, &d->plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
-    d->tier = plan.tier; d->S = plan.S; d->shift = plan.shift;
-    if (!priors_tile_plan(s, n, words, schedule == 1, variant, &d->pplan)) d->pplan = TilePlan();   // (tier 0: those entries answer UNSUPPORTED)
+    if (!priors_tile_plan(s, n, rec.words, schedule == 1, variant, &d->pplan)) d->pplan = TilePlan();   // (tier 0: those entries answer UNSUPPORTED)
     LayerPlan layers;   // the layered schedule: first-fit layers (layer_plan.hpp), verified before they reach the device
     if (schedule == 1) {
         std::string why;
@@ -268,14 +211,12 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
         }
         d->layers = layers.K;
     }
-    if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
-    using ldpc_detail::upload_ints;
-    bool ok = upload_ints(&d->row_ptr, g.row_ptr) && upload_ints(&d->csr_col, g.csr_col) && upload_ints(&d->rec_off, rec_off) &&
-              upload_ints(&d->col_ptr, g.col_ptr) && upload_ints(&d->edge_rec, edge_rec) && upload_ints(&d->edge_pos, edge_pos) &&
-              (schedule == 0 || (upload_ints(&d->layer_ptr, layers.layer_ptr) && upload_ints(&d->layer_checks, layers.layer_checks))) &&
-              hipMalloc((void **)&d->prior, (size_t)std::max<int64_t>(n, 1) * sizeof(float)) == hipSuccess &&
-              (n == 0 || hipMemcpy(d->prior, channel_llr, (size_t)n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) &&
-              d->calls.create() == hipSuccess;
+    if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->tile.grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
+    using ldpc_detail::upload;
+    bool ok = upload(&d->row_ptr, g.row_ptr) && upload(&d->csr_col, g.csr_col) && upload(&d->rec_off, rec.rec_off) &&
+              upload(&d->col_ptr, g.col_ptr) && upload(&d->edge_rec, rec.edge_rec) && upload(&d->edge_pos, rec.edge_pos) &&
+              (schedule == 0 || (upload(&d->layer_ptr, layers.layer_ptr) && upload(&d->layer_checks, layers.layer_checks))) &&
+              upload(&d->prior, std::vector<float>(channel_llr, channel_llr + n)) && d->tile.calls.create() == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         delete d;
@@ -289,33 +230,24 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
 ldpc_status ldpc_debug_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t relay, int32_t kernel_variant, int32_t *tier,
                                  int32_t *tile_syndromes, int64_t *state_bytes)
 {
-    if (s < 0 || n < 0 || rec_words < 0 || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28) || rec_words >= ((int64_t)1 << 31))
-        return set_error(LDPC_ERR_INVALID_ARGUMENT, "s, n and rec_words must be >= 0 and within what create accepts");
-    if (kernel_variant < 0 || kernel_variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
+    const ldpc_status st = ldpc_detail::tile_debug_args(s, n, rec_words, rec_words, kernel_variant);
+    if (st != LDPC_OK) return st;
     TilePlan plan;
-    if (!tile_plan(s, n, rec_words, relay != 0, kernel_variant, &plan))
-        return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
-    if (tier) *tier = plan.tier;
-    if (tile_syndromes) *tile_syndromes = plan.S;
-    if (state_bytes) *state_bytes = (int64_t)plan.state_bytes;
-    return LDPC_OK;
+    return ldpc_detail::tile_debug_answer(tile_plan(s, n, rec_words, relay != 0, kernel_variant, &plan), plan,
+                                          "kernel_variant 1: the state of one syndrome does not fit the on-chip tier", tier, tile_syndromes, state_bytes);
 }
 
 // (include/ldpc_mi355x_debug.h) ... and the second plan, of the entries with per-syndrome priors
 ldpc_status ldpc_debug_priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t schedule, int32_t kernel_variant, int32_t *tier,
                                         int32_t *tile_syndromes, int64_t *state_bytes)
 {
-    if (s < 0 || n < 0 || rec_words < 0 || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28) || rec_words >= ((int64_t)1 << 31))
-        return set_error(LDPC_ERR_INVALID_ARGUMENT, "s, n and rec_words must be >= 0 and within what create accepts");
-    if (kernel_variant < 0 || kernel_variant > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 or 2");
+    const ldpc_status st = ldpc_detail::tile_debug_args(s, n, rec_words, rec_words, kernel_variant);
+    if (st != LDPC_OK) return st;
     if (schedule < 0 || schedule > 1) return set_error(LDPC_ERR_INVALID_ARGUMENT, "schedule must be 0 (flooding) or 1 (layered)");
     TilePlan plan;
-    if (!priors_tile_plan(s, n, rec_words, schedule == 1, kernel_variant, &plan))
-        return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome with its priors does not fit the on-chip tier");
-    if (tier) *tier = plan.tier;
-    if (tile_syndromes) *tile_syndromes = plan.S;
-    if (state_bytes) *state_bytes = (int64_t)plan.state_bytes;
-    return LDPC_OK;
+    return ldpc_detail::tile_debug_answer(priors_tile_plan(s, n, rec_words, schedule == 1, kernel_variant, &plan), plan,
+                                          "kernel_variant 1: the state of one syndrome with its priors does not fit the on-chip tier", tier,
+                                          tile_syndromes, state_bytes);
 }
 
 // (include/ldpc_mi355x_debug.h) the layers create uploads for a layered handle, without a device
@@ -340,21 +272,14 @@ ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, c
     return LDPC_OK;
 }
 
-int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *d) { return d ? d->tier : 0; }
-int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *d) { return d ? d->S : 0; }
+int32_t ldpc_minsum_kernel(const ldpc_minsum_decoder *d) { return d ? d->plan.tier : 0; }
+int32_t ldpc_minsum_tile_syndromes(const ldpc_minsum_decoder *d) { return d ? d->plan.S : 0; }
 int32_t ldpc_minsum_priors_kernel(const ldpc_minsum_decoder *d) { return d ? d->pplan.tier : 0; }
 int32_t ldpc_minsum_priors_tile_syndromes(const ldpc_minsum_decoder *d) { return d && d->pplan.tier ? d->pplan.S : 0; }
-int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *d) { return d ? d->last_grid : 0; }
+int32_t ldpc_minsum_last_grid(const ldpc_minsum_decoder *d) { return d ? d->tile.last_grid : 0; }
 int32_t ldpc_minsum_layers(const ldpc_minsum_decoder *d) { return d && d->schedule == 1 ? d->layers : 0; }
 
-ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *d)
-{
-    if (!d) return LDPC_OK;
-    (void)hipSetDevice(d->device);
-    const ldpc_status st = ldpc_detail::wait_device(d->device, "ldpc_minsum_destroy (device synchronise)");
-    delete d;
-    return st;
-}
+ldpc_status ldpc_minsum_destroy(ldpc_minsum_decoder *d) { return ldpc_detail::tile_destroy(d, "ldpc_minsum_destroy (device synchronise)"); }
 
 ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batch, const uint8_t *d_syn, uint8_t *d_err,
                                             uint8_t *d_conv, double *d_llr, int32_t *d_iters, void *stream_v)
@@ -413,11 +338,11 @@ ldpc_status ldpc_minsum_set_conditional_priors(ldpc_minsum_decoder *d, const flo
         both[j] = llr_if0[j];
         both[n + j] = llr_if1[j];
     }
-    LDPC_HIP_TRY(hipSetDevice(d->device));
-    if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
+    LDPC_HIP_TRY(hipSetDevice(d->tile.device));
+    if (ldpc_detail::device_stalled(d->tile.device)) return ldpc_detail::stalled_error(d->tile.device);
     // after every earlier call on the handle: a decode still in flight reads the tables it was launched with to its end
-    if (d->calls.have) {
-        const ldpc_status st = ldpc_detail::wait_event(d->calls.done, d->device, "ldpc_minsum_set_conditional_priors (wait for the earlier calls)");
+    if (d->tile.calls.have) {
+        const ldpc_status st = ldpc_detail::wait_event(d->tile.calls.done, d->tile.device, "ldpc_minsum_set_conditional_priors (wait for the earlier calls)");
         if (st != LDPC_OK) return st;
     }
     float *fresh = d->cond;

@@ -107,7 +107,7 @@ static bool upload_graph(int64_t *rows, int **row_ptr, int **csr_col, const ldpc
     if (!m || m->rows == 0) return true;   // (no row is ever walked: the arrays stay NULL, also those of an H with no checks)
     *rows = m->rows;
     const ldpc_detail::TannerGraph tg = ldpc_detail::tanner_graph(m->rows, n, m->nnz, m->colptr, m->rowval);
-    return ldpc_detail::upload_ints(row_ptr, tg.row_ptr) && ldpc_detail::upload_ints(csr_col, tg.csr_col);
+    return ldpc_detail::upload(row_ptr, tg.row_ptr) && ldpc_detail::upload(csr_col, tg.csr_col);
 }
 
 // What a create of either kind does once its patterns are validated (checks[k], logicals[k]: what sees side k; a

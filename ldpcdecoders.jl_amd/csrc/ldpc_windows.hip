@@ -112,7 +112,7 @@ ldpc_status ldpc_windows_create(int64_t D, int64_t N, int64_t nnz, const int64_t
     w->image_stride = (ldpc_trials_k::image_words(tables.max_mech) + 7) & ~7;   // (16-byte granules)
     w->image = (size_t)(kThreads / (64 * w->wpc)) * w->image_stride * sizeof(unsigned short) <= kWindowImageLds;
     w->win = std::move(tables.win);
-    if (!ldpc_detail::upload_ints(&w->ints, tables.ints) || w->calls.create() != hipSuccess) {
+    if (!ldpc_detail::upload(&w->ints, tables.ints) || w->calls.create() != hipSuccess) {
         (void)hipGetLastError();
         delete w;
         return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the window tables failed");

@@ -31,7 +31,7 @@
 namespace ldpc {
 
 constexpr unsigned kMsNone = 0xffffffffu;
-constexpr int kMsPosEdge = (int)0x80000000;   // flag in edge_pos: the check keeps one message per edge
+// (kMsPosEdge, the flag in edge_pos of a check that keeps one message per edge: tile_plan.hpp, with the host code that sets it)
 
 struct MsParams {
     int s, n, max_iters;
@@ -95,6 +95,17 @@ __device__ inline float ms_clamp(float x, float clip)
 {
     x = x < -clip ? -clip : x;    // max(x, -clip)
     return x > clip ? clip : x;   // min(., clip)
+}
+
+// The message of a bit's edge out of its check's record (rec: the record's first word in the bit's lane; k: edge_pos): the
+// one reader of the record forms in the bit sweeps of the flooding, relay and Pauli kernels.
+__device__ inline float ms_message(const unsigned *rec, int k, int sh)
+{
+    if (k < 0) return __uint_as_float(rec[(size_t)(k & 0x7fffffff) << sh]);
+    const unsigned a = rec[(size_t)2 << sh];
+    const float cm = __uint_as_float(rec[(size_t)((unsigned)k == a ? 1 : 0) << sh]);
+    const unsigned sg = rec[(size_t)(3 + (k >> 5)) << sh];
+    return (sg >> (k & 31)) & 1u ? -cm : cm;
 }
 
 template <int TW, bool GLOBAL, int SRC = kMsPriorTable>
@@ -256,18 +267,7 @@ __global__ __launch_bounds__(TW * 64) void minsum_kernel(typename MsParamsOf<SRC
                     else acc = prior[j];
                     const int eb = col_ptr[j + 1];
                     for (int e = col_ptr[j]; e < eb; ++e) {
-                        const unsigned *rec = R + ((size_t)edge_rec[e] << sh) + l;
-                        const int k = edge_pos[e];
-                        float c;
-                        if (k < 0) {
-                            c = __uint_as_float(rec[(size_t)(k & 0x7fffffff) << sh]);
-                        } else {
-                            const unsigned a = rec[(size_t)2 << sh];
-                            const float cm = __uint_as_float(rec[(size_t)((unsigned)k == a ? 1 : 0) << sh]);
-                            const unsigned sg = rec[(size_t)(3 + (k >> 5)) << sh];
-                            c = (sg >> (k & 31)) & 1u ? -cm : cm;
-                        }
-                        acc = acc + c;
+                        acc = acc + ms_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
                     }
                     L[((size_t)j << sh) + l] = acc;
                 }

@@ -26,8 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "minsum_kernels.hpp"   // ms_clamp, kMsNone, kMsPosEdge
-#include "tile_plan.hpp"
+#include "minsum_kernels.hpp"   // ms_clamp, ms_message, kMsNone
 
 namespace ldpc {
 
@@ -203,20 +202,11 @@ __global__ __launch_bounds__(TW * 64) void pauli_minsum_kernel(PauliParams p)
             if (!any || test_only) break;
             // ---- bit sweep `it`: TZ over the qubit's Hx checks, TX over its Hz checks, each from +0 in ascending order
             if (active) {
-                auto message = [&](int e) -> float {
-                    const unsigned *rec = R + ((size_t)edge_rec[e] << sh) + l;
-                    const int k = edge_pos[e];
-                    if (k < 0) return __uint_as_float(rec[(size_t)(k & 0x7fffffff) << sh]);
-                    const unsigned a = rec[(size_t)2 << sh];
-                    const float cm = __uint_as_float(rec[(size_t)((unsigned)k == a ? 1 : 0) << sh]);
-                    const unsigned sg = rec[(size_t)(3 + (k >> 5)) << sh];
-                    return (sg >> (k & 31)) & 1u ? -cm : cm;
-                };
                 for (int j = q; j < n; j += Q) {
                     const int ea = col_ptr[j], em = col_mid[j], eb = col_ptr[j + 1];
                     float tz = 0.0f, tx = 0.0f;
-                    for (int e = ea; e < em; ++e) tz = tz + message(e);
-                    for (int e = em; e < eb; ++e) tx = tx + message(e);
+                    for (int e = ea; e < em; ++e) tz = tz + ms_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
+                    for (int e = em; e < eb; ++e) tx = tx + ms_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
                     TX[((size_t)j << sh) + l] = tx;
                     TZ[((size_t)j << sh) + l] = tz;
                 }

@@ -2,7 +2,7 @@
 // is stated; host side: ldpc_relay.hip).  Binary32 throughout, one rounding per operation, no contraction.
 //
 // A SYNDROME IN A LANE, tiles of S <= 64 syndromes, rows S words wide, check records (alpha m1, alpha m2, a, sign bits):
-// all as in minsum_kernels.hpp, whose ms_clamp and ms_record_words are used here.  State of a tile:
+// all as in minsum_kernels.hpp, whose ms_clamp and ms_message are used here.  State of a tile:
 //   X    [n][S]              f32  what the check sweep reads
 //   M    [n][S]              f32  the posterior
 //   rec  [rec_words][S]      u32  the check-to-bit messages (forms: minsum_kernels.hpp)
@@ -49,16 +49,6 @@ struct RelayParams {
 };
 
 // (relay_state_bytes() -- the bytes of a tile's state, S lanes of (2 n + rec_words + ceil(n / 32)) words and s bytes: tile_plan.hpp)
-
-// the message of a bit's edge out of its check's record (minsum_kernel's bit sweep)
-__device__ inline float relay_message(const unsigned *rec, int k, int sh)
-{
-    if (k < 0) return __uint_as_float(rec[(size_t)(k & 0x7fffffff) << sh]);
-    const unsigned a = rec[(size_t)2 << sh];
-    const float cm = __uint_as_float(rec[(size_t)((unsigned)k == a ? 1 : 0) << sh]);
-    const unsigned sg = rec[(size_t)(3 + (k >> 5)) << sh];
-    return (sg >> (k & 31)) & 1u ? -cm : cm;
-}
 
 template <int TW, bool GLOBAL>
 __global__ __launch_bounds__(TW * 64) void relay_kernel(RelayParams p)
@@ -259,14 +249,14 @@ __global__ __launch_bounds__(TW * 64) void relay_kernel(RelayParams p)
                         const float g = gammas[row + j], h = g0[row + j];
                         const int ea = col_ptr[j], eb = col_ptr[j + 1];
                         float acc = h + g * M[at];
-                        for (int e = ea; e < eb; ++e) acc = acc + relay_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
+                        for (int e = ea; e < eb; ++e) acc = acc + ms_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
                         M[at] = acc;
                         float x;
                         if (next) {
                             x = g0[row2 + j] + gammas[row2 + j] * acc;
                         } else {
                             x = h + g * acc;
-                            for (int e = ea; e < eb; ++e) x = x + relay_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
+                            for (int e = ea; e < eb; ++e) x = x + ms_message(R + ((size_t)edge_rec[e] << sh) + l, edge_pos[e], sh);
                         }
                         X[at] = x;
                     }

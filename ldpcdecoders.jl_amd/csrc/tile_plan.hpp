@@ -1,13 +1,16 @@
-// tile_plan.hpp -- the tier and the tile width of the min-sum and the relay decoder (ldpc_minsum.hip, ldpc_relay.hip;
-// device code: minsum_kernels.hpp, relay_kernels.hpp), and the sizes of a tile's state they are chosen from.  Pure host
+// tile_plan.hpp -- what the host of every decoder of the min-sum family (ldpc_minsum.hip, ldpc_relay.hip, ldpc_pauli.hip;
+// device code: minsum_kernels.hpp, layered_kernels.hpp, relay_kernels.hpp, pauli_kernels.hpp) derives from a graph's sizes
+// alone: the sizes of a tile's state, the tier and the tile width chosen from them (the policy: plan_tiles(), the one
+// place it is stated) and the check records of a Tanner graph (ms_records(), the one place they are laid out).  Pure host
 // code over the standard library -- no HIP, no decoder handle, no environment -- so that it builds with a plain C++
-// compiler and runs under the sanitizers on the CPU (tests/native/team_plan_sanitize.cpp).  Both `create` routines call
-// tile_plan(); ldpc_debug_tile_plan (include/ldpc_mi355x_debug.h) hands it to the CPU tests.  At the end: the state size
-// and the plan of the joint X/Z (Pauli) min-sum decoder (ldpc_pauli.hip), the same policy over another size.
+// compiler and runs under the sanitizers on the CPU (tests/native/team_plan_sanitize.cpp, priors_plan_sanitize.cpp,
+// records_sanitize.cpp).  The `create` routines call the plans; the ldpc_debug_*tile_plan entries
+// (include/ldpc_mi355x_debug.h) hand them to the CPU tests.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
+#include <vector>
 
 namespace ldpc {
 
@@ -32,29 +35,29 @@ struct TilePlan {
     size_t state_bytes = 0;   // of a tile of S syndromes: the dynamic LDS of tier 1, a workspace slot of tier 2
 };
 
-// syndromes per workgroup of the on-chip tier: the largest power of two <= 64 whose state fits `budget`; 0 = none
-inline int tile_lds_syndromes(int64_t s, int64_t n, int64_t rec_words, bool relay, size_t budget)
+// The choice, over bytes(S) = the state of a tile of S syndromes.  On-chip with the largest power of two S <= 64 that
+// leaves room for two workgroups a CU, else the largest that fits one; where not even one syndrome fits, the unlimited
+// tier with S = 64.  variant 1 / 2 force a tier (0 = by size).  false: variant 1 and nothing fits.
+template <class Bytes> inline bool plan_tiles(Bytes bytes, int variant, TilePlan *out)
 {
-    for (int S = 64; S >= 1; S >>= 1)
-        if ((relay ? relay_state_bytes(s, n, rec_words, S) : ms_state_bytes(s, n, rec_words, S)) <= budget) return S;
-    return 0;
-}
-
-// The choice.  On-chip with the largest S that leaves room for two workgroups a CU, else the largest that fits one; where
-// not even one syndrome fits, the unlimited tier with S = 64.  variant 1 / 2 force a tier (0 = by size).  false: variant 1
-// and nothing fits.
-inline bool tile_plan(int64_t s, int64_t n, int64_t rec_words, bool relay, int variant, TilePlan *out)
-{
-    int S = tile_lds_syndromes(s, n, rec_words, relay, kTileLdsTwo);
-    if (!S) S = tile_lds_syndromes(s, n, rec_words, relay, kTileLdsOne);
+    int S = 0;
+    for (size_t budget : {kTileLdsTwo, kTileLdsOne})
+        for (int w = 64; w >= 1 && !S; w >>= 1)
+            if (bytes(w) <= budget) S = w;
     if (variant == 1 && !S) return false;
     TilePlan p;
     p.tier = variant ? variant : S ? 1 : 2;
     p.S = p.tier == 1 ? S : 64;
     for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
-    p.state_bytes = relay ? relay_state_bytes(s, n, rec_words, p.S) : ms_state_bytes(s, n, rec_words, p.S);
+    p.state_bytes = bytes(p.S);
     *out = p;
     return true;
+}
+
+// the plan of the min-sum decoder (plain entries, both schedules) and of the relay decoder
+inline bool tile_plan(int64_t s, int64_t n, int64_t rec_words, bool relay, int variant, TilePlan *out)
+{
+    return plan_tiles([=](int S) { return relay ? relay_state_bytes(s, n, rec_words, S) : ms_state_bytes(s, n, rec_words, S); }, variant, out);
 }
 
 // ---- per-syndrome priors (the ldpc_minsum_decode_batch_priors / _given entries) ------------------------------------------
@@ -70,28 +73,15 @@ inline size_t ms_priors_state_bytes(long long s, long long n, long long rec_word
     return (ms_priors_offset(s, n, rec_words, S) + (size_t)n * 4 * (size_t)S + 255) & ~(size_t)255;
 }
 
-// The plan of the priors entries: the policy of tile_plan() over the larger state.  The layered schedule reads the prior
-// only when a tile starts and keeps no P, so its plan is tile_plan()'s.  false: variant 1 and nothing fits.
+// The plan of the priors entries.  The layered schedule reads the prior only when a tile starts and keeps no P, so its
+// plan is tile_plan()'s.
 inline bool priors_tile_plan(int64_t s, int64_t n, int64_t rec_words, bool layered, int variant, TilePlan *out)
 {
     if (layered) return tile_plan(s, n, rec_words, false, variant, out);
-    int S = 0;
-    for (size_t budget : {kTileLdsTwo, kTileLdsOne}) {
-        for (int w = 64; w >= 1 && !S; w >>= 1)
-            if (ms_priors_state_bytes(s, n, rec_words, w) <= budget) S = w;
-        if (S) break;
-    }
-    if (variant == 1 && !S) return false;
-    TilePlan p;
-    p.tier = variant ? variant : S ? 1 : 2;
-    p.S = p.tier == 1 ? S : 64;
-    for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
-    p.state_bytes = ms_priors_state_bytes(s, n, rec_words, p.S);
-    *out = p;
-    return true;
+    return plan_tiles([=](int S) { return ms_priors_state_bytes(s, n, rec_words, S); }, variant, out);
 }
 
-// ---- the joint X/Z (Pauli) min-sum decoder (ldpc_pauli.hip; device code: pauli_kernels.hpp) ------------------------------
+// ---- the joint X/Z (Pauli) min-sum decoder --------------------------------------------------------------------------------
 // bytes of a Pauli tile's state: S lanes of (2 n + rec_words) words -- the two message totals TX, TZ and the check records of
 // both sides -- and s = rx + rz syndrome bytes, rounded up to 256
 inline size_t pauli_state_bytes(long long s, long long n, long long rec_words, int S)
@@ -99,24 +89,40 @@ inline size_t pauli_state_bytes(long long s, long long n, long long rec_words, i
     return (((size_t)(2 * n + rec_words) * 4 + (size_t)s) * (size_t)S + 255) & ~(size_t)255;
 }
 
-// Its plan: the policy of tile_plan() over that size (s = rx + rz, rec_words over the checks of both sides).  false:
-// variant 1 and nothing fits.
+// Its plan (s = rx + rz, rec_words over the checks of both sides).
 inline bool pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, int variant, TilePlan *out)
 {
-    int S = 0;
-    for (size_t budget : {kTileLdsTwo, kTileLdsOne}) {
-        for (int w = 64; w >= 1 && !S; w >>= 1)
-            if (pauli_state_bytes(s, n, rec_words, w) <= budget) S = w;
-        if (S) break;
+    return plan_tiles([=](int S) { return pauli_state_bytes(s, n, rec_words, S); }, variant, out);
+}
+
+// ---- the check records of a graph ------------------------------------------------------------------------------------------
+constexpr int kMsPosEdge = (int)0x80000000;   // flag in edge_pos: the check keeps one message per edge (degree > 64)
+
+struct MsRecords {
+    std::vector<int> rec_off;    // [max(s, 1)]: first word of the check's record
+    std::vector<int> edge_rec;   // [nnz], per CSC edge: rec_off of its check
+    std::vector<int> edge_pos;   // [nnz], per CSC edge: position of the bit in its check (| kMsPosEdge)
+    int64_t words = 0;           // of all records; a caller narrows it only after its own range check
+};
+
+// From the CSR row pointers [s + 1] and, per CSC edge, its check (csc_row) and its place in the CSR order (csc2csr): the
+// arrays of ldpc_detail::TannerGraph (host_common.hpp).  words <= 4 s + nnz.
+inline MsRecords ms_records(int64_t s, int64_t nnz, const int *row_ptr, const int *csc_row, const int *csc2csr)
+{
+    MsRecords r;
+    r.rec_off.assign((size_t)(s > 1 ? s : 1), 0);
+    r.edge_rec.assign((size_t)nnz, 0);
+    r.edge_pos.assign((size_t)nnz, 0);
+    for (int64_t i = 0; i < s; ++i) {
+        r.rec_off[(size_t)i] = (int)r.words;
+        r.words += ms_record_words(row_ptr[i + 1] - row_ptr[i]);
     }
-    if (variant == 1 && !S) return false;
-    TilePlan p;
-    p.tier = variant ? variant : S ? 1 : 2;
-    p.S = p.tier == 1 ? S : 64;
-    for (p.shift = 0; (1 << p.shift) < p.S; p.shift++) {}
-    p.state_bytes = pauli_state_bytes(s, n, rec_words, p.S);
-    *out = p;
-    return true;
+    for (int64_t e = 0; e < nnz; ++e) {
+        const int i = csc_row[e], k = csc2csr[e] - row_ptr[i];
+        r.edge_rec[(size_t)e] = r.rec_off[(size_t)i];
+        r.edge_pos[(size_t)e] = row_ptr[i + 1] - row_ptr[i] > 64 ? (k | kMsPosEdge) : k;
+    }
+    return r;
 }
 
 }  // namespace ldpc

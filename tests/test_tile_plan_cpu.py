@@ -7,8 +7,12 @@ never by calling the library for the sizes:
     S = the largest power of two <= 64 whose state fits 79 KiB (two workgroups a CU), else the largest that fits 159 KiB,
     else the unlimited tier with S = 64.
 
-tests/test_gpu_minsum_tiles.py runs every row of TABLE on the device and asserts the width read back from the handle."""
+tests/test_gpu_minsum_tiles.py runs every row of TABLE on the device and asserts the width read back from the handle.
+At the end: the builder of the check records (ms_records, the same header) under the sanitizers."""
 import ctypes
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -209,3 +213,17 @@ def test_getters_answer_zero_for_null():
         L = ldpc._capi.lib(experiments)
         assert L.ldpc_minsum_tile_syndromes(None) == 0 and L.ldpc_minsum_last_grid(None) == 0
         assert L.ldpc_relay_tile_syndromes(None) == 0 and L.ldpc_relay_last_grid(None) == 0
+
+
+def test_check_records_under_sanitizers(tmp_path):
+    """csrc/tile_plan.hpp (ms_records: rec_off, edge_rec, edge_pos and the word count that the three create routines
+    upload) built with AddressSanitizer + UBSan (CPU only) and driven by tests/native/records_sanitize.cpp."""
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    exe = str(tmp_path / "records_sanitize")
+    subprocess.check_call(["g++", "-std=c++17", *san, "-I", os.path.join(root, "ldpcdecoders.jl_amd", "csrc"), "-o", exe,
+                           os.path.join(root, "tests", "native", "records_sanitize.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("OK ") and "record sets" in out.stdout, out.stdout + out.stderr
