@@ -27,109 +27,6 @@ STATUS_NAMES = {
     5: "LDPC_ERR_UNSUPPORTED",
 }
 
-# every symbol include/ldpc_mi355x.h declares
-EXPORTED_SYMBOLS = (
-    "ldpc_abi_version",
-    "ldpc_build_target",
-    "ldpc_last_error",
-    "ldpc_device_count",
-    "ldpc_trim_memory",
-    "ldpc_set_wait_limit_ms",
-    "ldpc_get_wait_limit_ms",
-    "ldpc_bp_create",
-    "ldpc_bp_destroy",
-    "ldpc_bp_get_info",
-    "ldpc_bp_decode_batch",
-    "ldpc_bp_decode_batch_device",
-    "ldpc_bp_decode_batch_bits",
-    "ldpc_bp_decode_batch_bits_device",
-    "ldpc_bp_last_status",
-    "ldpc_bp_last_timing",
-    "ldpc_bp_call_timing",
-    "ldpc_bp_call_phase_ticks",
-    "ldpc_bp_create_multi",
-    "ldpc_bp_destroy_multi",
-    "ldpc_bp_multi_handle",
-    "ldpc_bp_decode_batch_multi",
-    "ldpc_bp_decode_batch_multi_bits",
-    "ldpc_bp_decode_batch_multi_device",
-    "ldpc_bp_multi_last_status",
-    "ldpc_bp_multi_get_info",
-    "ldpc_osd_create",
-    "ldpc_osd_destroy",
-    "ldpc_osd_postprocess_batch",
-    "ldpc_osd_device_prepare",
-    "ldpc_osd_device_kernel",
-    "ldpc_osd_postprocess_batch_device",
-    "ldpc_bpots_create",
-    "ldpc_bpots_destroy",
-    "ldpc_bpots_kernel",
-    "ldpc_bpots_decode_batch",
-    "ldpc_bpots_decode_batch_device",
-    "ldpc_bitflip_create",
-    "ldpc_bitflip_destroy",
-    "ldpc_bitflip_kernel",
-    "ldpc_bitflip_decode_batch",
-    "ldpc_bitflip_decode_batch_device",
-    "ldpc_minsum_create",
-    "ldpc_minsum_destroy",
-    "ldpc_minsum_kernel",
-    "ldpc_minsum_tile_syndromes",
-    "ldpc_minsum_last_grid",
-    "ldpc_minsum_layers",
-    "ldpc_minsum_decode_batch",
-    "ldpc_minsum_decode_batch_device",
-    "ldpc_minsum_priors_kernel",
-    "ldpc_minsum_priors_tile_syndromes",
-    "ldpc_minsum_decode_batch_priors",
-    "ldpc_minsum_decode_batch_priors_device",
-    "ldpc_minsum_set_conditional_priors",
-    "ldpc_minsum_decode_batch_given",
-    "ldpc_minsum_decode_batch_given_device",
-    "ldpc_relay_create",
-    "ldpc_relay_destroy",
-    "ldpc_relay_kernel",
-    "ldpc_relay_tile_syndromes",
-    "ldpc_relay_last_grid",
-    "ldpc_relay_decode_batch",
-    "ldpc_relay_decode_batch_device",
-    "ldpc_pauli_minsum_create",
-    "ldpc_pauli_minsum_destroy",
-    "ldpc_pauli_minsum_kernel",
-    "ldpc_pauli_minsum_tile_syndromes",
-    "ldpc_pauli_minsum_last_grid",
-    "ldpc_pauli_minsum_decode_batch",
-    "ldpc_pauli_minsum_decode_batch_device",
-    "ldpc_trials_create",
-    "ldpc_trials_destroy",
-    "ldpc_trials_kernel",
-    "ldpc_trials_sample_device",
-    "ldpc_trials_syndromes_device",
-    "ldpc_trials_score_device",
-    "ldpc_trials_sample",
-    "ldpc_trials_score",
-    "ldpc_trials_set_rates",
-    "ldpc_trials_sample_rates_device",
-    "ldpc_trials_sample_rates",
-    "ldpc_css_trials_create",
-    "ldpc_css_trials_destroy",
-    "ldpc_css_trials_kernel",
-    "ldpc_css_trials_sample_device",
-    "ldpc_css_trials_syndromes_device",
-    "ldpc_css_trials_score_device",
-    "ldpc_css_trials_sample",
-    "ldpc_css_trials_score",
-    "ldpc_windows_create",
-    "ldpc_windows_destroy",
-    "ldpc_windows_count",
-    "ldpc_windows_gather_device",
-    "ldpc_windows_commit_device",
-)
-# ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
-DEBUG_SYMBOLS = ("ldpc_debug_team_rows", "ldpc_debug_team_plan", "ldpc_debug_div_check", "ldpc_debug_process_state",
-                 "ldpc_debug_adopt_process_state", "ldpc_debug_team_irr", "ldpc_debug_llr_check", "ldpc_debug_tile_plan", "ldpc_debug_layer_plan",
-                 "ldpc_debug_priors_tile_plan", "ldpc_debug_pauli_tile_plan")
-
 MULTI_MAX_DEVICES = 16
 EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_NONE = 0, 1, 2, 3
 
@@ -222,19 +119,130 @@ class WindowsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("reserved", ctypes.c_int32 * 15)]
 
 
+# The prototypes, name -> (restype, argtypes): the one list of what the library exports.  ldpc_status is an int32_t; a
+# handle and every array is a void pointer, a structure or a fixed-size array goes by a typed pointer.
+vp, i32, i64, u64, f64, cstr, P = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double,
+                                   ctypes.c_char_p, ctypes.POINTER)
+# every function include/ldpc_mi355x.h declares
+API = {
+    "ldpc_abi_version": (i32, []),
+    "ldpc_build_target": (cstr, []),
+    "ldpc_last_error": (cstr, []),
+    "ldpc_device_count": (i32, []),
+    "ldpc_trim_memory": (i32, []),
+    "ldpc_set_wait_limit_ms": (i32, [i64]),
+    "ldpc_get_wait_limit_ms": (i64, []),
+    "ldpc_bp_create": (i32, [i64, i64, i64, vp, vp, f64, i64, P(BPOptions), P(vp)]),
+    "ldpc_bp_destroy": (i32, [vp]),
+    "ldpc_bp_get_info": (i32, [vp, P(BPInfo)]),
+    "ldpc_bp_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_bp_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_bp_decode_batch_bits": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+    "ldpc_bp_decode_batch_bits_device": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "ldpc_bp_last_status": (i32, [vp]),
+    "ldpc_bp_last_timing": (i32, [vp, P(f64), P(f64), P(i64)]),
+    "ldpc_bp_call_timing": (i32, [vp, i32, P(f64), P(f64), P(i64)]),
+    "ldpc_bp_call_phase_ticks": (i32, [vp, i32, P(u64 * 3)]),
+    "ldpc_bp_create_multi": (i32, [i32, P(i32), i32, i64, i64, i64, vp, vp, f64, i64, P(BPOptions), P(vp)]),
+    "ldpc_bp_destroy_multi": (i32, [vp]),
+    "ldpc_bp_multi_handle": (vp, [vp, i32]),
+    "ldpc_bp_decode_batch_multi": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_bp_decode_batch_multi_bits": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+    "ldpc_bp_decode_batch_multi_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_bp_multi_last_status": (i32, [vp]),
+    "ldpc_bp_multi_get_info": (i32, [vp, P(BPMultiInfo)]),
+    "ldpc_osd_create": (i32, [i64, i64, i64, vp, vp, i64, P(vp)]),
+    "ldpc_osd_destroy": (i32, [vp]),
+    "ldpc_osd_postprocess_batch": (i32, [vp, i64, vp, vp, vp, vp, i32]),
+    "ldpc_osd_device_prepare": (i32, [vp, i32, i32]),
+    "ldpc_osd_device_kernel": (i32, [vp]),
+    "ldpc_osd_postprocess_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_bpots_create": (i32, [i64, i64, i64, vp, vp, f64, i64, i64, f64, i32, P(vp)]),
+    "ldpc_bpots_destroy": (i32, [vp]),
+    "ldpc_bpots_kernel": (i32, [vp]),
+    "ldpc_bpots_decode_batch": (i32, [vp, i64, vp, vp, vp, vp]),
+    "ldpc_bpots_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_bitflip_create": (i32, [i64, i64, i64, vp, vp, f64, i64, P(BitFlipOptions), P(vp)]),
+    "ldpc_bitflip_destroy": (i32, [vp]),
+    "ldpc_bitflip_kernel": (i32, [vp]),
+    "ldpc_bitflip_decode_batch": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
+    "ldpc_bitflip_decode_batch_device": (i32, [vp, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_minsum_create": (i32, [i64, i64, i64, vp, vp, vp, i64, P(MinSumOptions), P(vp)]),
+    "ldpc_minsum_destroy": (i32, [vp]),
+    "ldpc_minsum_kernel": (i32, [vp]),
+    "ldpc_minsum_tile_syndromes": (i32, [vp]),
+    "ldpc_minsum_last_grid": (i32, [vp]),
+    "ldpc_minsum_layers": (i32, [vp]),
+    "ldpc_minsum_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_minsum_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_minsum_priors_kernel": (i32, [vp]),
+    "ldpc_minsum_priors_tile_syndromes": (i32, [vp]),
+    "ldpc_minsum_decode_batch_priors": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_minsum_decode_batch_priors_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_minsum_set_conditional_priors": (i32, [vp, vp, vp]),
+    "ldpc_minsum_decode_batch_given": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_minsum_decode_batch_given_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_relay_create": (i32, [i64, i64, i64, vp, vp, vp, i64, vp, vp, P(RelayOptions), P(vp)]),
+    "ldpc_relay_destroy": (i32, [vp]),
+    "ldpc_relay_kernel": (i32, [vp]),
+    "ldpc_relay_tile_syndromes": (i32, [vp]),
+    "ldpc_relay_last_grid": (i32, [vp]),
+    "ldpc_relay_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_relay_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_pauli_minsum_create": (i32, [i64, P(CSSPattern), P(CSSPattern), vp, vp, vp, i64, P(PauliMinSumOptions), P(vp)]),
+    "ldpc_pauli_minsum_destroy": (i32, [vp]),
+    "ldpc_pauli_minsum_kernel": (i32, [vp]),
+    "ldpc_pauli_minsum_tile_syndromes": (i32, [vp]),
+    "ldpc_pauli_minsum_last_grid": (i32, [vp]),
+    "ldpc_pauli_minsum_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_pauli_minsum_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_trials_create": (i32, [i64, i64, i64, vp, vp, i64, i64, vp, vp, P(TrialsOptions), P(vp)]),
+    "ldpc_trials_destroy": (i32, [vp]),
+    "ldpc_trials_kernel": (i32, [vp]),
+    "ldpc_trials_sample_device": (i32, [vp, i64, i64, f64, u64, vp, vp, vp]),
+    "ldpc_trials_syndromes_device": (i32, [vp, i64, vp, vp, vp]),
+    "ldpc_trials_score_device": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_trials_sample": (i32, [vp, i64, i64, f64, u64, vp, vp]),
+    "ldpc_trials_score": (i32, [vp, i64, vp, vp, vp, vp]),
+    "ldpc_trials_set_rates": (i32, [vp, i64, vp]),
+    "ldpc_trials_sample_rates_device": (i32, [vp, i64, i64, u64, vp, vp, vp]),
+    "ldpc_trials_sample_rates": (i32, [vp, i64, i64, u64, vp, vp]),
+    "ldpc_css_trials_create": (i32, [i64, P(CSSPattern), P(CSSPattern), P(CSSPattern), P(CSSPattern), P(CSSTrialsOptions), P(vp)]),
+    "ldpc_css_trials_destroy": (i32, [vp]),
+    "ldpc_css_trials_kernel": (i32, [vp]),
+    "ldpc_css_trials_sample_device": (i32, [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp, vp]),
+    "ldpc_css_trials_syndromes_device": (i32, [vp, i64, vp, vp, vp, vp, vp]),
+    "ldpc_css_trials_score_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_css_trials_sample": (i32, [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp]),
+    "ldpc_css_trials_score": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_windows_create": (i32, [i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, P(WindowsOptions), P(vp)]),
+    "ldpc_windows_destroy": (i32, [vp]),
+    "ldpc_windows_count": (i64, [vp]),
+    "ldpc_windows_gather_device": (i32, [vp, i64, i64, vp, vp, vp]),
+    "ldpc_windows_commit_device": (i32, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+}
+# ... and include/ldpc_mi355x_debug.h (test hooks, not part of the boundary)
+DEBUG_API = {
+    "ldpc_debug_team_rows": (i32, [i64, i64, vp, vp, i32, i32, i32, P(i32 * 2), P(i32 * 5), vp, vp, vp, vp]),
+    "ldpc_debug_team_plan": (i32, [i64, i64, i64, i32, i32, P(i32 * 6)]),
+    "ldpc_debug_div_check": (i32, [i64, vp, vp, vp, vp]),
+    "ldpc_debug_process_state": (vp, []),
+    "ldpc_debug_adopt_process_state": (i32, [vp]),
+    "ldpc_debug_team_irr": (i32, [i64, i64, vp, vp, i32, i32, i32, P(i32 * 2), vp, vp, vp, vp, vp]),
+    "ldpc_debug_llr_check": (i32, [i64, vp, vp, vp]),
+    "ldpc_debug_tile_plan": (i32, [i64, i64, i64, i32, i32, P(i32), P(i32), P(i64)]),
+    "ldpc_debug_layer_plan": (i32, [i64, i64, vp, vp, vp, P(i32)]),
+    "ldpc_debug_priors_tile_plan": (i32, [i64, i64, i64, i32, i32, P(i32), P(i32), P(i64)]),
+    "ldpc_debug_pauli_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
+}
+EXPORTED_SYMBOLS = tuple(API)
+DEBUG_SYMBOLS = tuple(DEBUG_API)
+
+
 def build(force: bool = False) -> str:
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("ldpc_mi355x.hip", "ldpc_multi.hip", "host_env.hpp", "host_wait.hpp", "host_common.hpp", "host_common.hip", "pick_tile.hip", "pick_lds.hip", "pick_node.hip", "pick_team.hip", "pickers.hpp",
-                                             "ldpc_bpots.hip", "ldpc_bitflip.hip", "bitflip_kernels.hpp", "ldpc_minsum.hip", "minsum_kernels.hpp", "layered_kernels.hpp", "layer_plan.hpp", "layer_plan.cpp", "ldpc_relay.hip", "relay_kernels.hpp", "ldpc_pauli.hip", "pauli_kernels.hpp", "ldpc_trials.hip", "trial_kernels.hpp", "ldpc_windows.hip", "window_kernels.hpp", "window_plan.cpp", "window_plan.hpp", "osd_host.cpp", "team_plan.cpp", "team_plan.hpp", "tile_plan.hpp", "tile_host.hpp", "team_layout.hpp", "ldpc_osd_device.hip", "osd_kernels.hpp", "osd_handle.hpp", "bp_kernels.hpp", "bp_lds_kernels.hpp", "bp_node_kernels.hpp", "bp_team_kernels.hpp", "bit_io_kernels.hpp", "latency_mode.hpp",
-                                             "bpots_kernels.hpp", "portable_math.h", "Makefile")]
-    srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "ldpc_mi355x_debug.h"))
-    for target in (LIB_PATH, EXP_LIB_PATH):
-        stale = (not os.path.exists(target)) or any(
-            os.path.getmtime(f) > os.path.getmtime(target) for f in srcs if os.path.exists(f))
-        if force or stale:
-            subprocess.check_call(["make", "-s", "-C", CSRC, "all"])
-            break
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  make decides what is stale: its
+    source list is the real one.  `force` asked for the make run that every call now does."""
+    subprocess.check_call(["make", "-s", "-C", CSRC, "all"])
     return LIB_PATH
 
 
@@ -266,214 +274,10 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
                            "or `make -C ldpcdecoders.jl_amd/csrc`. There is no CPU fallback.")
     _one_hip_runtime()
     L = ctypes.CDLL(path)
-    vp, i64, i32, f64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
-    L.ldpc_abi_version.restype = i32
-    L.ldpc_build_target.restype = ctypes.c_char_p
-    L.ldpc_last_error.restype = ctypes.c_char_p
-    L.ldpc_device_count.restype = i32
-    L.ldpc_trim_memory.restype = i32
-    L.ldpc_set_wait_limit_ms.restype = i32
-    L.ldpc_set_wait_limit_ms.argtypes = [i64]
-    L.ldpc_get_wait_limit_ms.restype = i64
-    L.ldpc_debug_team_plan.restype = i32
-    L.ldpc_debug_team_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32 * 6)]
-    L.ldpc_debug_div_check.restype = i32
-    L.ldpc_debug_div_check.argtypes = [i64, vp, vp, vp, vp]
-    L.ldpc_debug_llr_check.restype = i32
-    L.ldpc_debug_llr_check.argtypes = [i64, vp, vp, vp]
-    L.ldpc_debug_tile_plan.restype = i32
-    L.ldpc_debug_tile_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
-    L.ldpc_debug_priors_tile_plan.restype = i32
-    L.ldpc_debug_priors_tile_plan.argtypes = [i64, i64, i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
-    L.ldpc_debug_pauli_tile_plan.restype = i32
-    L.ldpc_debug_pauli_tile_plan.argtypes = [i64, i64, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
-    L.ldpc_debug_layer_plan.restype = i32
-    L.ldpc_debug_layer_plan.argtypes = [i64, i64, vp, vp, vp, ctypes.POINTER(i32)]
-    L.ldpc_debug_team_irr.restype = i32
-    L.ldpc_debug_team_irr.argtypes = [i64, i64, vp, vp, i32, i32, i32, ctypes.POINTER(i32 * 2), vp, vp, vp, vp, vp]
-    L.ldpc_debug_team_rows.restype = i32
-    L.ldpc_debug_team_rows.argtypes = [i64, i64, vp, vp, i32, i32, i32, ctypes.POINTER(i32 * 2), ctypes.POINTER(i32 * 5), vp, vp, vp, vp]
-    L.ldpc_bp_create_multi.restype = i32
-    L.ldpc_bp_create_multi.argtypes = [i32, ctypes.POINTER(i32), i32, i64, i64, i64, vp, vp, f64, i64, ctypes.POINTER(BPOptions), ctypes.POINTER(vp)]
-    L.ldpc_bp_destroy_multi.restype = i32
-    L.ldpc_bp_destroy_multi.argtypes = [vp]
-    L.ldpc_bp_multi_handle.restype = vp
-    L.ldpc_bp_multi_handle.argtypes = [vp, i32]
-    L.ldpc_bp_decode_batch_multi.restype = i32
-    L.ldpc_bp_decode_batch_multi.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_bp_decode_batch_multi_device.restype = i32
-    L.ldpc_bp_decode_batch_multi_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_bp_multi_last_status.restype = i32
-    L.ldpc_bp_multi_last_status.argtypes = [vp]
-    L.ldpc_bp_multi_get_info.restype = i32
-    L.ldpc_bp_multi_get_info.argtypes = [vp, ctypes.POINTER(BPMultiInfo)]
-    L.ldpc_bp_create.restype = i32
-    L.ldpc_bp_create.argtypes = [i64, i64, i64, vp, vp, f64, i64, ctypes.POINTER(BPOptions), ctypes.POINTER(vp)]
-    L.ldpc_bp_destroy.restype = i32
-    L.ldpc_bp_destroy.argtypes = [vp]
-    L.ldpc_bp_get_info.restype = i32
-    L.ldpc_bp_get_info.argtypes = [vp, ctypes.POINTER(BPInfo)]
-    L.ldpc_bp_decode_batch.restype = i32
-    L.ldpc_bp_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_bp_decode_batch_device.restype = i32
-    L.ldpc_bp_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_bp_decode_batch_bits.restype = i32
-    L.ldpc_bp_decode_batch_bits.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp]
-    L.ldpc_bp_decode_batch_bits_device.restype = i32
-    L.ldpc_bp_decode_batch_bits_device.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
-    L.ldpc_bp_decode_batch_multi_bits.restype = i32
-    L.ldpc_bp_decode_batch_multi_bits.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp]
-    L.ldpc_bp_last_status.restype = i32
-    L.ldpc_bp_last_status.argtypes = [vp]
-    L.ldpc_bp_last_timing.restype = i32
-    L.ldpc_bp_last_timing.argtypes = [vp, ctypes.POINTER(f64), ctypes.POINTER(f64), ctypes.POINTER(i64)]
-    L.ldpc_bp_call_timing.restype = i32
-    L.ldpc_bp_call_timing.argtypes = [vp, i32, ctypes.POINTER(f64), ctypes.POINTER(f64), ctypes.POINTER(i64)]
-    L.ldpc_bp_call_phase_ticks.restype = i32
-    L.ldpc_bp_call_phase_ticks.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64 * 3)]
-    L.ldpc_osd_create.restype = i32
-    L.ldpc_osd_create.argtypes = [i64, i64, i64, vp, vp, i64, ctypes.POINTER(vp)]
-    L.ldpc_osd_destroy.restype = i32
-    L.ldpc_osd_destroy.argtypes = [vp]
-    L.ldpc_osd_postprocess_batch.restype = i32
-    L.ldpc_osd_postprocess_batch.argtypes = [vp, i64, vp, vp, vp, vp, i32]
-    L.ldpc_osd_device_prepare.restype = i32
-    L.ldpc_osd_device_prepare.argtypes = [vp, i32, i32]
-    L.ldpc_osd_device_kernel.restype = i32
-    L.ldpc_osd_device_kernel.argtypes = [vp]
-    L.ldpc_osd_postprocess_batch_device.restype = i32
-    L.ldpc_osd_postprocess_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_bpots_create.restype = i32
-    L.ldpc_bpots_create.argtypes = [i64, i64, i64, vp, vp, f64, i64, i64, f64, i32, ctypes.POINTER(vp)]
-    L.ldpc_bpots_destroy.restype = i32
-    L.ldpc_bpots_destroy.argtypes = [vp]
-    L.ldpc_bpots_kernel.restype = i32
-    L.ldpc_bpots_kernel.argtypes = [vp]
-    L.ldpc_bpots_decode_batch.restype = i32
-    L.ldpc_bpots_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.ldpc_bpots_decode_batch_device.restype = i32
-    L.ldpc_bpots_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_bitflip_create.restype = i32
-    L.ldpc_bitflip_create.argtypes = [i64, i64, i64, vp, vp, f64, i64, ctypes.POINTER(BitFlipOptions), ctypes.POINTER(vp)]
-    L.ldpc_bitflip_destroy.restype = i32
-    L.ldpc_bitflip_destroy.argtypes = [vp]
-    L.ldpc_bitflip_kernel.restype = i32
-    L.ldpc_bitflip_kernel.argtypes = [vp]
-    L.ldpc_bitflip_decode_batch.restype = i32
-    L.ldpc_bitflip_decode_batch.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp]
-    L.ldpc_bitflip_decode_batch_device.restype = i32
-    L.ldpc_bitflip_decode_batch_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_minsum_create.restype = i32
-    L.ldpc_minsum_create.argtypes = [i64, i64, i64, vp, vp, vp, i64, ctypes.POINTER(MinSumOptions), ctypes.POINTER(vp)]
-    L.ldpc_minsum_destroy.restype = i32
-    L.ldpc_minsum_destroy.argtypes = [vp]
-    L.ldpc_minsum_kernel.restype = i32
-    L.ldpc_minsum_kernel.argtypes = [vp]
-    L.ldpc_minsum_tile_syndromes.restype = i32
-    L.ldpc_minsum_tile_syndromes.argtypes = [vp]
-    L.ldpc_minsum_last_grid.restype = i32
-    L.ldpc_minsum_last_grid.argtypes = [vp]
-    L.ldpc_minsum_layers.restype = i32
-    L.ldpc_minsum_layers.argtypes = [vp]
-    L.ldpc_minsum_decode_batch.restype = i32
-    L.ldpc_minsum_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_minsum_decode_batch_device.restype = i32
-    L.ldpc_minsum_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_minsum_priors_kernel.restype = i32
-    L.ldpc_minsum_priors_kernel.argtypes = [vp]
-    L.ldpc_minsum_priors_tile_syndromes.restype = i32
-    L.ldpc_minsum_priors_tile_syndromes.argtypes = [vp]
-    L.ldpc_minsum_decode_batch_priors.restype = i32
-    L.ldpc_minsum_decode_batch_priors.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_minsum_decode_batch_priors_device.restype = i32
-    L.ldpc_minsum_decode_batch_priors_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.ldpc_minsum_set_conditional_priors.restype = i32
-    L.ldpc_minsum_set_conditional_priors.argtypes = [vp, vp, vp]
-    L.ldpc_minsum_decode_batch_given.restype = i32
-    L.ldpc_minsum_decode_batch_given.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_minsum_decode_batch_given_device.restype = i32
-    L.ldpc_minsum_decode_batch_given_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.ldpc_relay_create.restype = i32
-    L.ldpc_relay_create.argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, vp, ctypes.POINTER(RelayOptions), ctypes.POINTER(vp)]
-    L.ldpc_relay_destroy.restype = i32
-    L.ldpc_relay_destroy.argtypes = [vp]
-    L.ldpc_relay_kernel.restype = i32
-    L.ldpc_relay_kernel.argtypes = [vp]
-    L.ldpc_relay_tile_syndromes.restype = i32
-    L.ldpc_relay_tile_syndromes.argtypes = [vp]
-    L.ldpc_relay_last_grid.restype = i32
-    L.ldpc_relay_last_grid.argtypes = [vp]
-    L.ldpc_relay_decode_batch.restype = i32
-    L.ldpc_relay_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_relay_decode_batch_device.restype = i32
-    L.ldpc_relay_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    u64 = ctypes.c_uint64
-    L.ldpc_trials_create.restype = i32
-    L.ldpc_trials_create.argtypes = [i64, i64, i64, vp, vp, i64, i64, vp, vp, ctypes.POINTER(TrialsOptions), ctypes.POINTER(vp)]
-    L.ldpc_trials_destroy.restype = i32
-    L.ldpc_trials_destroy.argtypes = [vp]
-    L.ldpc_trials_kernel.restype = i32
-    L.ldpc_trials_kernel.argtypes = [vp]
-    L.ldpc_trials_sample_device.restype = i32
-    L.ldpc_trials_sample_device.argtypes = [vp, i64, i64, f64, u64, vp, vp, vp]
-    L.ldpc_trials_syndromes_device.restype = i32
-    L.ldpc_trials_syndromes_device.argtypes = [vp, i64, vp, vp, vp]
-    L.ldpc_trials_score_device.restype = i32
-    L.ldpc_trials_score_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_trials_sample.restype = i32
-    L.ldpc_trials_sample.argtypes = [vp, i64, i64, f64, u64, vp, vp]
-    L.ldpc_trials_score.restype = i32
-    L.ldpc_trials_score.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.ldpc_trials_set_rates.restype = i32
-    L.ldpc_trials_set_rates.argtypes = [vp, i64, vp]
-    L.ldpc_trials_sample_rates_device.restype = i32
-    L.ldpc_trials_sample_rates_device.argtypes = [vp, i64, i64, u64, vp, vp, vp]
-    L.ldpc_trials_sample_rates.restype = i32
-    L.ldpc_trials_sample_rates.argtypes = [vp, i64, i64, u64, vp, vp]
-    pat = ctypes.POINTER(CSSPattern)
-    L.ldpc_css_trials_create.restype = i32
-    L.ldpc_css_trials_create.argtypes = [i64, pat, pat, pat, pat, ctypes.POINTER(CSSTrialsOptions), ctypes.POINTER(vp)]
-    L.ldpc_css_trials_destroy.restype = i32
-    L.ldpc_css_trials_destroy.argtypes = [vp]
-    L.ldpc_css_trials_kernel.restype = i32
-    L.ldpc_css_trials_kernel.argtypes = [vp]
-    L.ldpc_css_trials_sample_device.restype = i32
-    L.ldpc_css_trials_sample_device.argtypes = [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp, vp]
-    L.ldpc_css_trials_syndromes_device.restype = i32
-    L.ldpc_css_trials_syndromes_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    L.ldpc_css_trials_score_device.restype = i32
-    L.ldpc_css_trials_score_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.ldpc_css_trials_sample.restype = i32
-    L.ldpc_css_trials_sample.argtypes = [vp, i64, i64, f64, f64, f64, u64, vp, vp, vp, vp]
-    L.ldpc_css_trials_score.restype = i32
-    L.ldpc_css_trials_score.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    L.ldpc_pauli_minsum_create.restype = i32
-    L.ldpc_pauli_minsum_create.argtypes = [i64, pat, pat, vp, vp, vp, i64, ctypes.POINTER(PauliMinSumOptions), ctypes.POINTER(vp)]
-    L.ldpc_pauli_minsum_destroy.restype = i32
-    L.ldpc_pauli_minsum_destroy.argtypes = [vp]
-    L.ldpc_pauli_minsum_kernel.restype = i32
-    L.ldpc_pauli_minsum_kernel.argtypes = [vp]
-    L.ldpc_pauli_minsum_tile_syndromes.restype = i32
-    L.ldpc_pauli_minsum_tile_syndromes.argtypes = [vp]
-    L.ldpc_pauli_minsum_last_grid.restype = i32
-    L.ldpc_pauli_minsum_last_grid.argtypes = [vp]
-    L.ldpc_pauli_minsum_decode_batch.restype = i32
-    L.ldpc_pauli_minsum_decode_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.ldpc_pauli_minsum_decode_batch_device.restype = i32
-    L.ldpc_pauli_minsum_decode_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.ldpc_windows_create.restype = i32
-    L.ldpc_windows_create.argtypes = [i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(WindowsOptions), ctypes.POINTER(vp)]
-    L.ldpc_windows_destroy.restype = i32
-    L.ldpc_windows_destroy.argtypes = [vp]
-    L.ldpc_windows_count.restype = i64
-    L.ldpc_windows_count.argtypes = [vp]
-    L.ldpc_windows_gather_device.restype = i32
-    L.ldpc_windows_gather_device.argtypes = [vp, i64, i64, vp, vp, vp]
-    L.ldpc_windows_commit_device.restype = i32
-    L.ldpc_windows_commit_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.ldpc_debug_process_state.restype = vp
-    L.ldpc_debug_adopt_process_state.restype = i32
-    L.ldpc_debug_adopt_process_state.argtypes = [vp]
+    for group in (API, DEBUG_API):
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     # both builds in one process: the one loaded second orders its team grids through the first one's per-device events,
     # so that no two team grids of the process share a device (include/ldpc_mi355x_debug.h)
     other = _LIBS.get(not experiments)

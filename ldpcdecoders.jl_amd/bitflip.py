@@ -5,12 +5,13 @@ iteration), and this object numbers the columns it decodes."""
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Optional
 
 import numpy as np
 
-from . import _capi
-from .decoder import AbstractDecoder, _pattern_of, syndrome_bytes
+from . import _capi, _host
+from ._host import Handle, _pattern_of, as_int, csc_arrays, device_option, host_batch, stream_ptr, tensor_ptr
+from .decoder import AbstractDecoder
 
 TIE_BREAKS = {"random": _capi.BF_TIE_RANDOM, "first": _capi.BF_TIE_FIRST, "last": _capi.BF_TIE_LAST}
 
@@ -26,16 +27,20 @@ class BitFlipScratchSpace:
         self.error_checks = np.zeros(s, dtype=np.int64)
 
 
-class BitFlipDecoder(AbstractDecoder):
+class BitFlipDecoder(AbstractDecoder, Handle):
     """`BitFlipDecoder(H, per::Float64, max_iters::Int)`.  tie_break: "random" (default; seeded, reproducible), "first"
-    or "last" among the maximisers in ascending bit order.  kernel_variant forces a tier (0 = auto)."""
+    or "last" among the maximisers in ascending bit order.  kernel_variant forces a tier (0 = auto).  decode!/batchdecode!
+    (:116-201) leave the last column's `err` in the scratch."""
+
+    _destroy = "ldpc_bitflip_destroy"
+    _scratch_keeps = ("err",)
+    decode_, batchdecode_ = _host.decode_, _host.batchdecode_
 
     def __init__(self, H, per: float, max_iters: int, *, tie_break="random", seed: int = 0, device: Optional[int] = None,
                  kernel_variant: int = 0):
         if not isinstance(per, float):
             raise TypeError("per must be a Float64")
-        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
-            raise TypeError("max_iters must be an Int")
+        as_int(max_iters, "max_iters")
         M = _pattern_of(H)   # stored zeros dropped: only `true` entries of H count (`sparse_H[i, j]`, :135)
         self.per, self.max_iters = float(per), int(max_iters)
         self.s, self.n = int(M.shape[0]), int(M.shape[1])
@@ -44,34 +49,21 @@ class BitFlipDecoder(AbstractDecoder):
         self.tie_break = TIE_BREAKS[tie_break] if isinstance(tie_break, str) else int(tie_break)
         self.seed = int(seed)
         self.columns_decoded = 0   # column0 of the next call: repeated calls draw fresh tie-breaks, a seed replays a session
-        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        colptr, rowval = csc_arrays(M)
         opts = _capi.BitFlipOptions()
-        opts.device = -1 if device is None else int(device)
+        opts.device = device_option(device)
         opts.tie_break = self.tie_break
         opts.seed = self.seed & ((1 << 64) - 1)
         opts.kernel_variant = int(kernel_variant)
-        self._h = ctypes.c_void_p()
-        self._L = _capi.lib_for(None)
-        _capi.check(self._L.ldpc_bitflip_create(self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
-                                                self.per, self.max_iters, ctypes.byref(opts), ctypes.byref(self._h)), self._L)
+        L = _capi.lib_for(None)
+        self._create(L, L.ldpc_bitflip_create, self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
+                     self.per, self.max_iters, ctypes.byref(opts))
 
     @property
     def kernel(self) -> int:
         """1 / 2 = on-chip (one wave / one workgroup per syndrome), 3 = unlimited, 4 = unlimited with 64-bit votes
         (ldpc_bitflip_kernel)."""
         return int(self._L.ldpc_bitflip_kernel(self._h))
-
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ldpc_bitflip_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _column0(self, column0, batch: int) -> int:
         if column0 is not None:
@@ -83,13 +75,7 @@ class BitFlipDecoder(AbstractDecoder):
     def decode_batch_host(self, syn_bs, column0: Optional[int] = None):
         """syn [B][s] uint8 -> (errors [B][n] u8, converged [B] u8, iters [B] i32, stop_reason [B] u8).  column0=None:
         the columns continue the numbering of this object (`columns_decoded`, advanced by B)."""
-        syn = np.ascontiguousarray(syn_bs, dtype=np.uint8)
-        if syn.ndim != 2 or syn.shape[1] != self.s:
-            raise AssertionError("syndrome length does not match the number of checks")
-        B = int(syn.shape[0])
-        err = np.empty((B, self.n), dtype=np.uint8)
-        conv = np.empty(B, dtype=np.uint8)
-        its = np.empty(B, dtype=np.int32)
+        syn, B, err, conv, _, its = host_batch(syn_bs, self.s, self.n)
         stop = np.empty(B, dtype=np.uint8)
         _capi.check(self._L.ldpc_bitflip_decode_batch(self._h, B, self._column0(column0, B), syn.ctypes.data, err.ctypes.data,
                                                       conv.ctypes.data, its.ctypes.data, stop.ctypes.data), self._L)
@@ -103,39 +89,7 @@ class BitFlipDecoder(AbstractDecoder):
         import torch
 
         B = int(syn.shape[0])
-        for x in (syn, err, conv) + ((stop_reason,) if stop_reason is not None else ()):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
-        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
-        assert stop_reason is None or stop_reason.numel() == B
-        if iters is not None:
-            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
-        if stream is None:
-            stream = torch.cuda.current_stream(syn.device).cuda_stream
-        _capi.check(self._L.ldpc_bitflip_decode_batch_device(
-            self._h, B, self._column0(column0, B), syn.data_ptr(), err.data_ptr(), conv.data_ptr(),
-            iters.data_ptr() if iters is not None else None,
-            stop_reason.data_ptr() if stop_reason is not None else None, ctypes.c_void_p(stream)), self._L)
-
-    def decode_(self, syndrome) -> Tuple[np.ndarray, bool]:
-        """`decode!(decoder::BitFlipDecoder, syndrome)`: (scratch.err as Int vector, converged)."""
-        syn = syndrome_bytes(np.asarray(syndrome).reshape(-1))
-        if syn.size != self.s:
-            raise IndexError(f"syndrome has length {syn.size}, decoder has {self.s} checks")
-        err, conv, _, _ = self.decode_batch_host(syn.reshape(1, -1))
-        self.scratch.err[:] = err[0]
-        return self.scratch.err, bool(conv[0])
-
-    def batchdecode_(self, syndromes, errors, success=None):
-        """`batchdecode!(decoder::BitFlipDecoder, syndromes, errors, converged)` (:189-201): one device call."""
-        syndromes = np.asarray(syndromes)
-        B = syndromes.shape[1]
-        if success is None:
-            success = np.empty(B, dtype=np.bool_)
-        assert syndromes.shape[1] == errors.shape[1]                  # :190
-        assert syndromes.shape[1] == len(success)                     # :191
-        err, conv, _, _ = self.decode_batch_host(np.ascontiguousarray(syndrome_bytes(syndromes).T))
-        errors[:, :] = err.T
-        success[:] = conv.astype(np.bool_)
-        if B > 0:
-            self.scratch.err[:] = err[-1]
-        return errors, success
+        args = (tensor_ptr(syn, torch.uint8, (B, self.s)), tensor_ptr(err, torch.uint8, (B, self.n)), tensor_ptr(conv, torch.uint8, B),
+                tensor_ptr(iters, torch.int32, B, optional=True), tensor_ptr(stop_reason, torch.uint8, B, optional=True),
+                stream_ptr(stream, syn))
+        _capi.check(self._L.ldpc_bitflip_decode_batch_device(self._h, B, self._column0(column0, B), *args), self._L)

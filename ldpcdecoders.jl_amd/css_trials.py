@@ -12,8 +12,8 @@ from typing import Optional
 import numpy as np
 
 from . import _capi, codes
-from .decoder import _pattern_of
-from .trials import _M64, _current_device, _device_decode
+from ._host import Handle, _pattern_of, css_pattern, current_device, device_option, stream_ptr, tensor_ptr
+from .trials import _M64, _device_decode
 
 
 def pauli_rates(p):
@@ -39,14 +39,15 @@ def conditional_probs(p):
     return float(p_if0), float(p_if1)
 
 
-class CSSTrials:
+class CSSTrials(Handle):
     """Owns the Tanner graphs of `Hx`, `Hz` and of the logical rows on a device.  logicals: None = `codes.css_logicals`,
     False = no logical rows (flag bits 2 and 3 are then never set), or a pair (Lx, Lz).  check: assert Hx * Hz' = 0
     over GF(2) (the library does not).  kernel_variant: 0 = by size, 1 = on-chip bit images, 2 = unlimited (`.kernel`
     tells which one the handle takes)."""
 
+    _destroy = "ldpc_css_trials_destroy"
+
     def __init__(self, Hx, Hz, logicals=None, device: Optional[int] = None, kernel_variant: int = 0, check: bool = True):
-        self._h = None
         Mx, Mz = _pattern_of(Hx), _pattern_of(Hz)
         if int(Mx.shape[1]) != int(Mz.shape[1]):
             raise AssertionError("Hx and Hz must have the same number of columns")
@@ -67,25 +68,15 @@ class CSSTrials:
                 mats.append(Lm)
         self.nlx = int(mats[2].shape[0]) if len(mats) > 2 else 0
         self.nlz = int(mats[3].shape[0]) if len(mats) > 3 else 0
-        keep, pats = [], []
-        for M in mats:
-            colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-            rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
-            keep += [colptr, rowval]
-            pat = _capi.CSSPattern()
-            pat.rows, pat.nnz, pat.colptr, pat.rowval = int(M.shape[0]), int(rowval.size), colptr.ctypes.data, rowval.ctypes.data
-            pats.append(ctypes.byref(pat))
-        pats += [None] * (4 - len(pats))
+        pats = [css_pattern(M) for M in mats]
+        refs = [ctypes.byref(pat) for pat in pats] + [None] * (4 - len(pats))
         if device is None:
-            device = _current_device()   # (the current device NOW is the handle's for good, as in Trials)
+            device = current_device()   # (the current device NOW is the handle's for good, as in Trials)
         opts = _capi.CSSTrialsOptions()
-        opts.device = -1 if device is None else int(device)
+        opts.device = device_option(device)
         opts.kernel_variant = int(kernel_variant)
-        h = ctypes.c_void_p()
-        self._L = _capi.lib_for(None)
-        _capi.check(self._L.ldpc_css_trials_create(self.n, pats[0], pats[1], pats[2], pats[3], ctypes.byref(opts), ctypes.byref(h)),
-                    self._L)
-        self._h = h
+        L = _capi.lib_for(None)
+        self._create(L, L.ldpc_css_trials_create, self.n, *refs, ctypes.byref(opts))
         self.device = device
 
     @property
@@ -93,27 +84,10 @@ class CSSTrials:
         """1 = on-chip bit images, 2 = unlimited (ldpc_css_trials_kernel)."""
         return int(self._L.ldpc_css_trials_kernel(self._h))
 
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ldpc_css_trials_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _torch_device(self):
         import torch
 
         return torch.device("cuda", int(self.device))
-
-    @staticmethod
-    def _is(x, shape) -> bool:
-        import torch
-
-        return x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == tuple(shape)
 
     # -- device forms (torch tensors, asynchronous on `stream`: a hipStream_t as int, default torch's current stream) --
     def sample(self, batch: int, p, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
@@ -130,13 +104,11 @@ class CSSTrials:
             sz = torch.empty((B, self.rows_z), dtype=torch.uint8, device=dev)
         else:
             ex, ez, sx, sz = out
-        for x, cols in ((ex, self.n), (ez, self.n), (sx, self.rows_x), (sz, self.rows_z)):
-            assert x is None or self._is(x, (B, cols))
-        if stream is None:
-            stream = torch.cuda.current_stream(ex.device).cuda_stream
+        u8 = torch.uint8
         _capi.check(self._L.ldpc_css_trials_sample_device(
-            self._h, B, int(column0), px, py, pz, int(seed) & _M64, ex.data_ptr(), ez.data_ptr(),
-            sx.data_ptr() if sx is not None else None, sz.data_ptr() if sz is not None else None, ctypes.c_void_p(stream)), self._L)
+            self._h, B, int(column0), px, py, pz, int(seed) & _M64, tensor_ptr(ex, u8, (B, self.n)), tensor_ptr(ez, u8, (B, self.n)),
+            tensor_ptr(sx, u8, (B, self.rows_x), optional=True), tensor_ptr(sz, u8, (B, self.rows_z), optional=True),
+            stream_ptr(stream, ex)), self._L)
         return ex, ez, sx, sz
 
     def syndromes(self, ex, ez, out=None, stream: Optional[int] = None):
@@ -149,12 +121,10 @@ class CSSTrials:
             sz = torch.empty((B, self.rows_z), dtype=torch.uint8, device=ex.device)
         else:
             sx, sz = out
-        for x, cols in ((ex, self.n), (ez, self.n), (sx, self.rows_x), (sz, self.rows_z)):
-            assert self._is(x, (B, cols))
-        if stream is None:
-            stream = torch.cuda.current_stream(ex.device).cuda_stream
-        _capi.check(self._L.ldpc_css_trials_syndromes_device(self._h, B, ex.data_ptr(), ez.data_ptr(), sx.data_ptr(), sz.data_ptr(),
-                                                             ctypes.c_void_p(stream)), self._L)
+        u8 = torch.uint8
+        _capi.check(self._L.ldpc_css_trials_syndromes_device(
+            self._h, B, tensor_ptr(ex, u8, (B, self.n)), tensor_ptr(ez, u8, (B, self.n)), tensor_ptr(sx, u8, (B, self.rows_x)),
+            tensor_ptr(sz, u8, (B, self.rows_z)), stream_ptr(stream, ex)), self._L)
         return sx, sz
 
     def score(self, gx, gz, ex, ez, flags=None, counts=None, stream: Optional[int] = None, want_flags: bool = True):
@@ -164,20 +134,13 @@ class CSSTrials:
         import torch
 
         B = int(ex.shape[0])
-        for x in (gx, gz, ex, ez):
-            assert self._is(x, (B, self.n))
+        ptrs = [tensor_ptr(x, torch.uint8, (B, self.n)) for x in (gx, gz, ex, ez)]
         if flags is None and want_flags:
             flags = torch.empty(B, dtype=torch.uint8, device=ex.device)
-        if flags is not None:
-            assert flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() == B
         if counts is None:
             counts = torch.zeros(6, dtype=torch.int64, device=ex.device)
-        assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 6
-        if stream is None:
-            stream = torch.cuda.current_stream(ex.device).cuda_stream
-        _capi.check(self._L.ldpc_css_trials_score_device(
-            self._h, B, gx.data_ptr(), gz.data_ptr(), ex.data_ptr(), ez.data_ptr(), flags.data_ptr() if flags is not None else None,
-            counts.data_ptr(), ctypes.c_void_p(stream)), self._L)
+        _capi.check(self._L.ldpc_css_trials_score_device(self._h, B, *ptrs, tensor_ptr(flags, torch.uint8, B, optional=True),
+                                                         tensor_ptr(counts, torch.int64, 6), stream_ptr(stream, ex)), self._L)
         return flags, counts
 
     # -- host forms (numpy, synchronous) ---------------------------------------------------------------------------

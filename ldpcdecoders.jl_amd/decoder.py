@@ -23,6 +23,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _capi
+from ._host import Handle, _pattern_of, as_int, csc_arrays, device_option, host_syndromes, stream_ptr, syndrome_bytes, tensor_ptr
 from .bitmatrix import BitMatrix
 
 
@@ -48,47 +49,7 @@ class BeliefPropagationScratchSpace:
         self.err = np.zeros(n, dtype=np.float64)
 
 
-def _pattern_of(H) -> sp.csc_matrix:
-    """`sparse(H)` (belief_propagation.jl:63): CSC pattern, rows ascending per column."""
-    if sp.issparse(H):
-        M = sp.csc_matrix(H, copy=True)
-        M.sum_duplicates()
-        M.eliminate_zeros()
-    else:
-        A = np.asarray(H)
-        if A.ndim != 2:
-            raise ValueError("H must be a matrix")
-        M = sp.csc_matrix(A != 0)
-    M.sort_indices()
-    return M
-
-
-def syndrome_bytes(x) -> np.ndarray:
-    """Map syndrome entries to the ABI's uint8 alphabet.
-
-    0/1 (Bool, Int or integral Float) pass through.  Any other integer keeps
-    its parity -- ``(-1)^x`` at belief_propagation.jl:136 only depends on it --
-    and is encoded as 2 + parity so that it can never satisfy the ``==`` of the
-    convergence test (:181), exactly like an Int 2 or 3 in the reference.
-    A non-integral float is a DomainError in Julia; here a ValueError.
-    """
-    a = np.asarray(x)
-    if a.dtype == np.bool_:
-        return a.astype(np.uint8)
-    if a.dtype == np.uint8 and (a.size == 0 or a.max() <= 1):
-        return a
-    if np.issubdtype(a.dtype, np.floating):
-        if not np.all(np.isfinite(a)) or np.any(a != np.rint(a)):
-            raise ValueError("syndrome entries must be integral ((-1)^x is a DomainError otherwise)")
-        a = a.astype(np.int64)
-    elif not np.issubdtype(a.dtype, np.integer):
-        raise TypeError(f"unsupported syndrome element type {a.dtype}")
-    a64 = a.astype(np.int64)
-    out = np.where((a64 == 0) | (a64 == 1), a64, 2 + (a64 & 1))
-    return out.astype(np.uint8)
-
-
-class BeliefPropagationDecoder(AbstractDecoder):
+class BeliefPropagationDecoder(AbstractDecoder, Handle):
     """Drop-in for `BeliefPropagationDecoder(H, per::Float64, max_iters::Int)`.
 
     Extra keyword arguments select the device and tuning knobs; defaults give
@@ -100,14 +61,16 @@ class BeliefPropagationDecoder(AbstractDecoder):
     the library that reads the environment knobs (default: only when one of them is set).
     """
 
+    _destroy = "ldpc_bp_destroy"
+    _m = None   # the multi-device handle when devices= is given
+
     def __init__(self, H, per: float, max_iters: int, *, device: Optional[int] = None,
                  devices: Optional[Sequence[int]] = None, exchange: int = 0,
                  waves_per_tile: int = 0, resident_tiles: int = 0, kernel_variant: int = 0,
                  defer_threshold: int = 0, llr_exact: bool = False, experiments: Optional[bool] = None):
         if not isinstance(per, float):
             raise TypeError("per must be a Float64 (reference signature: per::Float64)")
-        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
-            raise TypeError("max_iters must be an Int (reference signature: max_iters::Int)")
+        as_int(max_iters, "max_iters", " (reference signature: max_iters::Int)")
         M = _pattern_of(H)
         self.per = float(per)
         self.max_iters = int(max_iters)
@@ -116,33 +79,25 @@ class BeliefPropagationDecoder(AbstractDecoder):
         self.sparse_HT = sp.csc_matrix(M.T)    # columns = checks    (:64)
         self.sparse_HT.sort_indices()
         self.scratch = BeliefPropagationScratchSpace(self.n, self.s, self.per)
-        self._colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-        self._rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        colptr, rowval = csc_arrays(M)
         opts = _capi.BPOptions()
-        opts.device = -1 if device is None else int(device)
+        opts.device = device_option(device)
         opts.waves_per_tile = int(waves_per_tile)
         opts.resident_tiles = int(resident_tiles)
         opts.kernel_variant = int(kernel_variant)   # 0 auto, 1 HBM-streaming, 2 LDS-resident, 3 node-parallel, 4 team
         opts.defer_threshold = int(defer_threshold)  # 0 auto (16), -1 off: straggler hand-off of the streaming kernel
         opts.llr_exact = 1 if llr_exact else 0       # LLRs from the full posterior odds (default: their upper 32 bits, within 5e-7)
-        self._h = ctypes.c_void_p()
-        self._m = None                         # the multi-device handle when devices= is given
-        self._L = L = _capi.lib_for(experiments)
+        L = _capi.lib_for(experiments)
+        graph = (self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, self.per, self.max_iters, ctypes.byref(opts))
         if devices is not None:
             if device is not None:
                 raise TypeError("give device= or devices=, not both")
             devs = (ctypes.c_int32 * len(devices))(*[int(x) for x in devices])
-            m = ctypes.c_void_p()
-            self._check(L.ldpc_bp_create_multi(len(devices), devs, int(exchange), self.s, self.n, int(self._rowval.size),
-                                               self._colptr.ctypes.data, self._rowval.ctypes.data, self.per, self.max_iters,
-                                               ctypes.byref(opts), ctypes.byref(m)))
-            self._m = m
-            self._h = ctypes.c_void_p(L.ldpc_bp_multi_handle(m, 0))   # info / timing: the root's handle
+            self._create(L, L.ldpc_bp_create_multi, len(devices), devs, int(exchange), *graph)
+            self._m, self._h = self._h, ctypes.c_void_p(L.ldpc_bp_multi_handle(self._h, 0))   # info / timing: the root's handle
             self.devices = [int(x) for x in devices]
         else:
-            self._check(L.ldpc_bp_create(self.s, self.n, int(self._rowval.size), self._colptr.ctypes.data,
-                                         self._rowval.ctypes.data, self.per, self.max_iters,
-                                         ctypes.byref(opts), ctypes.byref(self._h)))
+            self._create(L, L.ldpc_bp_create, *graph)
             self.devices = None
 
     def _check(self, status: int) -> None:
@@ -150,18 +105,13 @@ class BeliefPropagationDecoder(AbstractDecoder):
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        m, self._m = getattr(self, "_m", None), None
+        """With devices=, `_h` is the root's handle inside the multi-device one: destroying that one frees both."""
+        m, self._m = self._m, None
         if m:
+            self._h = None
             self._L.ldpc_bp_destroy_multi(m)
-        elif h:
-            self._L.ldpc_bp_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        else:
+            super().close()
 
     # -- introspection ------------------------------------------------------
     def info(self) -> _capi.BPInfo:
@@ -203,10 +153,8 @@ class BeliefPropagationDecoder(AbstractDecoder):
         """syn_bs: [B][s] uint8 C-contiguous.  Returns (errors [B][n] u8, converged [B] u8, llr|None, iters|None).
         `out` = (errors, converged) preallocated C-contiguous uint8 arrays to write into (a caller that
         reuses its buffers, like Julia's batchdecode!, avoids fresh-page faults on every call)."""
-        syn_bs = np.ascontiguousarray(syn_bs, dtype=np.uint8)
+        syn_bs = host_syndromes(syn_bs, self.s)
         B = int(syn_bs.shape[0])
-        if syn_bs.ndim != 2 or syn_bs.shape[1] != self.s:
-            raise AssertionError("syndrome length does not match the number of checks")
         if out is not None:
             err, conv = out
             assert err.dtype == np.uint8 and err.flags.c_contiguous and err.shape == (B, self.n)
@@ -228,21 +176,11 @@ class BeliefPropagationDecoder(AbstractDecoder):
         import torch
 
         B = int(syn.shape[0])
-        assert syn.is_cuda and err.is_cuda and conv.is_cuda
-        assert syn.dtype == torch.uint8 and err.dtype == torch.uint8 and conv.dtype == torch.uint8
-        assert syn.is_contiguous() and err.is_contiguous() and conv.is_contiguous()
-        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
-        if llr is not None:
-            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
-        if iters is not None:
-            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
-        if stream is None:
-            stream = torch.cuda.current_stream(syn.device).cuda_stream
         entry, handle = ((self._L.ldpc_bp_decode_batch_multi_device, self._m) if self._m
                          else (self._L.ldpc_bp_decode_batch_device, self._h))   # multi: the tensors live on devices[0]
-        self._check(entry(handle, B, syn.data_ptr(), err.data_ptr(), conv.data_ptr(),
-                          llr.data_ptr() if llr is not None else None,
-                          iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)))
+        self._check(entry(handle, B, tensor_ptr(syn, torch.uint8, (B, self.s)), tensor_ptr(err, torch.uint8, (B, self.n)),
+                          tensor_ptr(conv, torch.uint8, B), tensor_ptr(llr, torch.float64, (B, self.n), optional=True),
+                          tensor_ptr(iters, torch.int32, B, optional=True), stream_ptr(stream, syn)))
 
     # -- bit-packed (BitMatrix layout) entries --------------------------------
     def decode_batch_bits_words(self, batch: int, syn_words: np.ndarray, syn_bit0: int, err_words: np.ndarray,
@@ -298,17 +236,10 @@ class BeliefPropagationDecoder(AbstractDecoder):
             assert w.is_cuda and w.dim() == 1 and w.is_contiguous() and w.element_size() == 8 and not w.dtype.is_floating_point
         assert syn_bit0 >= 0 and int(syn_bit0) + B * self.s <= 64 * syn_words.numel()
         assert err_bit0 >= 0 and int(err_bit0) + B * self.n <= 64 * err_words.numel()
-        assert conv.is_cuda and conv.dtype == torch.uint8 and conv.is_contiguous() and conv.numel() == B
-        if llr is not None:
-            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
-        if iters is not None:
-            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
-        if stream is None:
-            stream = torch.cuda.current_stream(conv.device).cuda_stream
         self._check(self._L.ldpc_bp_decode_batch_bits_device(
-            self._h, B, syn_words.data_ptr(), int(syn_bit0), err_words.data_ptr(), int(err_bit0), conv.data_ptr(),
-            llr.data_ptr() if llr is not None else None, iters.data_ptr() if iters is not None else None,
-            ctypes.c_void_p(stream)))
+            self._h, B, syn_words.data_ptr(), int(syn_bit0), err_words.data_ptr(), int(err_bit0), tensor_ptr(conv, torch.uint8, B),
+            tensor_ptr(llr, torch.float64, (B, self.n), optional=True), tensor_ptr(iters, torch.int32, B, optional=True),
+            stream_ptr(stream, conv)))
 
     # -- reference interface (methods; free functions below) ----------------
     def decode_(self, syndrome):

@@ -8,20 +8,15 @@ from __future__ import annotations
 
 import ctypes
 from types import SimpleNamespace
-from typing import Optional, Tuple
+from typing import Optional
 
 import numpy as np
 
-from . import _capi
-from .decoder import AbstractDecoder, _pattern_of, syndrome_bytes
-
-
-def llr_of_probs(probs) -> np.ndarray:
-    """log(P(0) / P(1)) of error probabilities strictly inside (0, 1), as float32."""
-    p = np.asarray(probs, dtype=np.float64)
-    if p.size and not np.all((p > 0.0) & (p < 1.0)):   # (False for NaN as well)
-        raise ValueError("probabilities must lie strictly inside (0, 1)")
-    return np.log((1.0 - p) / p).astype(np.float32)
+from . import _capi, _host
+from ._host import (Handle, _pattern_of, as_int, channel_prior, csc_arrays, device_option, host_batch, host_ptr,
+                    llr_of_probs, one_prior_given, refuse_zero_alpha_clip, stream_ptr, tensor_ptr)
+from ._host import current_device as _current_device  # noqa: F401  (importable from here as before)
+from .decoder import AbstractDecoder
 
 
 class MinSumScratchSpace:
@@ -32,7 +27,7 @@ class MinSumScratchSpace:
         self.log_probabs = np.zeros(n, dtype=np.float64)
 
 
-class MinSumDecoder(AbstractDecoder):
+class MinSumDecoder(AbstractDecoder, Handle):
     """`MinSumDecoder(H, per, max_iters)` with a uniform prior, or one of `channel_probs=` (error probability per bit) /
     `channel_llr=` (log(P(0) / P(1)) per bit, finite) instead of `per`: exactly one of the three.  alpha in (0, 1]
     scales every check-to-bit message, clip > 0 clamps the bit-to-check values.  kernel_variant: 0 = by size, 1 = on-chip,
@@ -41,6 +36,9 @@ class MinSumDecoder(AbstractDecoder):
     of include/ldpc_mi355x.h; `.layers` tells the number of layers); anything else is a ValueError."""
 
     SCHEDULES = {"flooding": 0, "layered": 1}
+    _destroy = "ldpc_minsum_destroy"
+    _scratch_keeps = ("err", "log_probabs")
+    decode_, batchdecode_ = _host.decode_, _host.batchdecode_
 
     def __init__(self, H, per: Optional[float] = None, max_iters: int = 50, *, channel_llr=None, channel_probs=None,
                  alpha: float = 0.75, clip: float = 1e6, device: Optional[int] = None, kernel_variant: int = 0,
@@ -48,48 +46,27 @@ class MinSumDecoder(AbstractDecoder):
         if not isinstance(schedule, str) or schedule not in self.SCHEDULES:
             raise ValueError(f'schedule must be "flooding" or "layered", got {schedule!r}')
         self.schedule = schedule
-        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
-            raise TypeError("max_iters must be an Int")
-        if (per is not None) + (channel_llr is not None) + (channel_probs is not None) != 1:
-            raise TypeError("give exactly one of per, channel_probs and channel_llr")
+        as_int(max_iters, "max_iters")
+        one_prior_given(per, channel_probs, channel_llr)
         M = _pattern_of(H)
         self.s, self.n = int(M.shape[0]), int(M.shape[1])
         self.sparse_H = M
-        self.per = None
-        if per is not None:
-            if isinstance(per, bool) or not isinstance(per, (float, np.floating)):
-                raise TypeError("per must be a Float64")
-            self.per = float(per)
-            llr = llr_of_probs(np.full(self.n, self.per))
-        elif channel_probs is not None:
-            llr = llr_of_probs(channel_probs)
-        else:
-            llr = np.array(channel_llr, dtype=np.float32)
-        if llr.shape != (self.n,):
-            raise ValueError(f"one prior per bit: expected {self.n} entries, got shape {llr.shape}")
-        self.channel_llr = np.ascontiguousarray(llr, dtype=np.float32)
+        self.channel_llr = channel_prior(self.n, per, channel_probs, channel_llr)
+        self.per = None if per is None else float(per)
         self.max_iters, self.alpha, self.clip = int(max_iters), float(alpha), float(clip)
-        if np.float32(self.alpha) == 0.0 or np.float32(self.clip) == 0.0:
-            # a zero in ldpc_minsum_options selects the default there; here a default is spelled by leaving the keyword
-            # out, so a zero gets the status the library gives every other value outside the range
-            raise _capi.LdpcError(1, "alpha must lie in (0, 1] and clip must be finite and > 0 (got a zero)")
+        refuse_zero_alpha_clip(self.alpha, self.clip)
         self.scratch = MinSumScratchSpace(self.n)
         self.conditional_llr = None   # (llr_if0, llr_if1) once set_conditional_priors has been called
-        if device is None:
-            device = _current_device()   # the current device NOW is the handle's for good (what info() answers)
-        self.device = device
-        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        self.device = _current_device() if device is None else device   # (what info() answers)
+        colptr, rowval = csc_arrays(M)
         opts = _capi.MinSumOptions()
-        opts.device = -1 if device is None else int(device)
+        opts.device = device_option(self.device)
         opts.alpha, opts.clip = self.alpha, self.clip
         opts.kernel_variant = int(kernel_variant)
         opts.schedule = self.SCHEDULES[schedule]
-        self._h = ctypes.c_void_p()
-        self._L = _capi.lib_for(None)
-        _capi.check(self._L.ldpc_minsum_create(self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
-                                               self.channel_llr.ctypes.data, self.max_iters, ctypes.byref(opts),
-                                               ctypes.byref(self._h)), self._L)
+        L = _capi.lib_for(None)
+        self._create(L, L.ldpc_minsum_create, self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
+                     self.channel_llr.ctypes.data, self.max_iters, ctypes.byref(opts))
 
     @property
     def kernel(self) -> int:
@@ -114,29 +91,11 @@ class MinSumDecoder(AbstractDecoder):
                                priors_kernel=int(self._L.ldpc_minsum_priors_kernel(self._h)),
                                priors_tile_syndromes=int(self._L.ldpc_minsum_priors_tile_syndromes(self._h)))
 
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ldpc_minsum_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def decode_batch_host(self, syn_bs, want_llr: bool = False):
         """syn [B][s] uint8 -> (errors [B][n] u8, converged [B] u8, llr [B][n] f64 | None, iters [B] i32)."""
-        syn = np.ascontiguousarray(syn_bs, dtype=np.uint8)
-        if syn.ndim != 2 or syn.shape[1] != self.s:
-            raise AssertionError("syndrome length does not match the number of checks")
-        B = int(syn.shape[0])
-        err = np.empty((B, self.n), dtype=np.uint8)
-        conv = np.empty(B, dtype=np.uint8)
-        llr = np.empty((B, self.n), dtype=np.float64) if want_llr else None
-        its = np.empty(B, dtype=np.int32)
+        syn, B, err, conv, llr, its = host_batch(syn_bs, self.s, self.n, want_llr)
         _capi.check(self._L.ldpc_minsum_decode_batch(self._h, B, syn.ctypes.data, err.ctypes.data, conv.ctypes.data,
-                                                     llr.ctypes.data if want_llr else None, its.ctypes.data), self._L)
+                                                     host_ptr(llr), its.ctypes.data), self._L)
         return err, conv, llr, its
 
     def decode_batch_device(self, syn, err, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
@@ -146,55 +105,32 @@ class MinSumDecoder(AbstractDecoder):
         import torch
 
         B = int(syn.shape[0])
-        for x in (syn, err, conv):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
-        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
-        if llr is not None:
-            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
-        if iters is not None:
-            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
-        if stream is None:
-            stream = torch.cuda.current_stream(syn.device).cuda_stream
         _capi.check(self._L.ldpc_minsum_decode_batch_device(
-            self._h, B, syn.data_ptr(), err.data_ptr(), conv.data_ptr(), llr.data_ptr() if llr is not None else None,
-            iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)), self._L)
+            self._h, B, tensor_ptr(syn, torch.uint8, (B, self.s)), tensor_ptr(err, torch.uint8, (B, self.n)),
+            tensor_ptr(conv, torch.uint8, B), tensor_ptr(llr, torch.float64, (B, self.n), optional=True),
+            tensor_ptr(iters, torch.int32, B, optional=True), stream_ptr(stream, syn)), self._L)
 
     # -- per-syndrome priors (PER-SYNDROME PRIORS of include/ldpc_mi355x.h) ----------------------------------------------
-    def _host_outputs(self, syn_bs, want_llr):
-        syn = np.ascontiguousarray(syn_bs, dtype=np.uint8)
-        if syn.ndim != 2 or syn.shape[1] != self.s:
-            raise AssertionError("syndrome length does not match the number of checks")
-        B = int(syn.shape[0])
-        return (syn, B, np.empty((B, self.n), dtype=np.uint8), np.empty(B, dtype=np.uint8),
-                np.empty((B, self.n), dtype=np.float64) if want_llr else None, np.empty(B, dtype=np.int32))
-
     def _device_args(self, syn, extra, extra_dtype, err, conv, llr, iters, stream):
+        """The arguments of a device entry that takes a [B][n] input `extra` next to the syndromes, after its checks."""
         import torch
 
         B = int(syn.shape[0])
-        for x in (syn, err, conv):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
-        assert extra.is_cuda and extra.dtype == extra_dtype and extra.is_contiguous() and tuple(extra.shape) == (B, self.n)
-        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
-        if llr is not None:
-            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, self.n)
-        if iters is not None:
-            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
-        if stream is None:
-            stream = torch.cuda.current_stream(syn.device).cuda_stream
-        return (self._h, B, syn.data_ptr(), extra.data_ptr(), err.data_ptr(), conv.data_ptr(),
-                llr.data_ptr() if llr is not None else None, iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream))
+        return (self._h, B, tensor_ptr(syn, torch.uint8, (B, self.s)), tensor_ptr(extra, extra_dtype, (B, self.n)),
+                tensor_ptr(err, torch.uint8, (B, self.n)), tensor_ptr(conv, torch.uint8, B),
+                tensor_ptr(llr, torch.float64, (B, self.n), optional=True), tensor_ptr(iters, torch.int32, B, optional=True),
+                stream_ptr(stream, syn))
 
     def decode_batch_priors_host(self, syn_bs, priors, want_llr: bool = False):
         """syn [B][s] uint8, priors [B][n] float32 (one prior LLR per syndrome and bit, in place of `.channel_llr`) ->
         (errors, converged, llr | None, iters) as `decode_batch_host`.  A row with a non-finite prior is not decoded:
         zeros, converged 0, iters 0, llr 0."""
-        syn, B, err, conv, llr, its = self._host_outputs(syn_bs, want_llr)
+        syn, B, err, conv, llr, its = host_batch(syn_bs, self.s, self.n, want_llr)
         pri = np.ascontiguousarray(priors, dtype=np.float32)
         if pri.shape != (B, self.n):
             raise ValueError(f"one prior per syndrome and bit: expected shape {(B, self.n)}, got {pri.shape}")
         _capi.check(self._L.ldpc_minsum_decode_batch_priors(self._h, B, syn.ctypes.data, pri.ctypes.data, err.ctypes.data, conv.ctypes.data,
-                                                            llr.ctypes.data if want_llr else None, its.ctypes.data), self._L)
+                                                            host_ptr(llr), its.ctypes.data), self._L)
         return err, conv, llr, its
 
     def decode_batch_priors_device(self, syn, priors, err, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
@@ -225,12 +161,12 @@ class MinSumDecoder(AbstractDecoder):
     def decode_batch_given_host(self, syn_bs, given, want_llr: bool = False):
         """syn [B][s] uint8, given [B][n] uint8: the prior of bit j of row i is llr_if1[j] where given[i][j] & 1, else
         llr_if0[j] (`set_conditional_priors`) -> as `decode_batch_host`."""
-        syn, B, err, conv, llr, its = self._host_outputs(syn_bs, want_llr)
+        syn, B, err, conv, llr, its = host_batch(syn_bs, self.s, self.n, want_llr)
         giv = np.ascontiguousarray(given, dtype=np.uint8)
         if giv.shape != (B, self.n):
             raise ValueError(f"one given bit per syndrome and bit: expected shape {(B, self.n)}, got {giv.shape}")
         _capi.check(self._L.ldpc_minsum_decode_batch_given(self._h, B, syn.ctypes.data, giv.ctypes.data, err.ctypes.data, conv.ctypes.data,
-                                                           llr.ctypes.data if want_llr else None, its.ctypes.data), self._L)
+                                                           host_ptr(llr), its.ctypes.data), self._L)
         return err, conv, llr, its
 
     def decode_batch_given_device(self, syn, given, err, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
@@ -239,39 +175,3 @@ class MinSumDecoder(AbstractDecoder):
 
         _capi.check(self._L.ldpc_minsum_decode_batch_given_device(*self._device_args(syn, given, torch.uint8, err, conv, llr, iters, stream)),
                     self._L)
-
-    def decode_(self, syndrome) -> Tuple[np.ndarray, bool]:
-        """One syndrome: (scratch.err, converged); scratch.log_probabs holds its LLRs."""
-        syn = syndrome_bytes(np.asarray(syndrome).reshape(-1))
-        if syn.size != self.s:
-            raise IndexError(f"syndrome has length {syn.size}, decoder has {self.s} checks")
-        err, conv, llr, _ = self.decode_batch_host(syn.reshape(1, -1), want_llr=True)
-        self.scratch.err[:] = err[0]
-        self.scratch.log_probabs[:] = llr[0]
-        return self.scratch.err, bool(conv[0])
-
-    def batchdecode_(self, syndromes, errors, success=None):
-        """syndromes s x B, errors n x B (overwritten), success [B]: one device call."""
-        syndromes = np.asarray(syndromes)
-        B = syndromes.shape[1]
-        if success is None:
-            success = np.empty(B, dtype=np.bool_)
-        assert syndromes.shape[1] == errors.shape[1]
-        assert syndromes.shape[1] == len(success)
-        err, conv, llr, _ = self.decode_batch_host(np.ascontiguousarray(syndrome_bytes(syndromes).T), want_llr=True)
-        errors[:, :] = err.T
-        success[:] = conv.astype(np.bool_)
-        if B > 0:
-            self.scratch.err[:] = err[-1]
-            self.scratch.log_probabs[:] = llr[-1]
-        return errors, success
-
-
-def _current_device() -> Optional[int]:
-    """torch's current GPU, or None without one (ldpc_minsum_create then answers LDPC_ERR_NO_DEVICE itself)."""
-    try:
-        import torch
-
-        return int(torch.cuda.current_device()) if torch.cuda.is_available() else None
-    except Exception:
-        return None

@@ -12,38 +12,27 @@ returns another, equally valid estimate than the host form.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import numpy as np
 
 from . import _capi
-from .decoder import AbstractDecoder, BeliefPropagationDecoder, _pattern_of, syndrome_bytes
+from ._host import Handle, _pattern_of, csc_arrays, device_option, stream_ptr, syndrome_bytes, tensor_ptr
+from .decoder import AbstractDecoder, BeliefPropagationDecoder
 
 
-class OSDPostProcessor:
+class OSDPostProcessor(Handle):
     """Owns the `ldpc_osd` handle: bit-packed H and the OSD order.  Needs no GPU."""
+
+    _destroy = "ldpc_osd_destroy"
 
     def __init__(self, H, osd_order: int = 0):
         M = _pattern_of(H)
         self.s, self.n = int(M.shape[0]), int(M.shape[1])
         self.osd_order = int(osd_order)
-        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
-        self._h = ctypes.c_void_p()
-        _capi.check(_capi.lib().ldpc_osd_create(self.s, self.n, int(rowval.size), colptr.ctypes.data,
-                                                rowval.ctypes.data, self.osd_order, ctypes.byref(self._h)))
-
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _capi.lib().ldpc_osd_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        colptr, rowval = csc_arrays(M)
+        L = _capi.lib()
+        self._create(L, L.ldpc_osd_create, self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, self.osd_order)
 
     def postprocess(self, syn_bs, bp_err_bn, llr_bn, nthreads: int = 0) -> np.ndarray:
         """syn [B][s] u8 (0/1), bp_err [B][n] u8, llr [B][n] f64 -> errors [B][n] u8."""
@@ -53,22 +42,22 @@ class OSDPostProcessor:
         B = syn.shape[0]
         assert syn.shape == (B, self.s) and e.shape == (B, self.n) and L.shape == (B, self.n)
         out = np.empty((B, self.n), dtype=np.uint8)
-        _capi.check(_capi.lib().ldpc_osd_postprocess_batch(self._h, B, syn.ctypes.data, e.ctypes.data,
-                                                           L.ctypes.data, out.ctypes.data, int(nthreads)))
+        _capi.check(self._L.ldpc_osd_postprocess_batch(self._h, B, syn.ctypes.data, e.ctypes.data,
+                                                       L.ctypes.data, out.ctypes.data, int(nthreads)), self._L)
         return out
 
     # -- the opt-in device form ------------------------------------------------
     def prepare_device(self, device=None, kernel_variant: int = 0) -> int:
         """Upload the packed rows to `device` (None: the current one) and pick the kernel tier (0: by size; 1..3
         force it).  Once per post-processor.  Returns the tier (`.kernel`)."""
-        _capi.check(_capi.lib().ldpc_osd_device_prepare(self._h, -1 if device is None else int(device), int(kernel_variant)))
+        _capi.check(self._L.ldpc_osd_device_prepare(self._h, device_option(device), int(kernel_variant)), self._L)
         return self.kernel
 
     @property
     def kernel(self) -> int:
         """Tier of the device form (ldpc_osd_device_kernel): 1 one wave per syndrome, 2 one workgroup per syndrome
         (state in LDS), 3 unlimited (state in a global workspace); 0 = not prepared."""
-        return int(_capi.lib().ldpc_osd_device_kernel(self._h)) if self._h else 0
+        return int(self._L.ldpc_osd_device_kernel(self._h)) if self._h else 0
 
     def postprocess_device(self, syn, bp_err, llr, out=None, stream=None):
         """torch tensors on the prepared device: syn [B][s] u8, bp_err [B][n] u8, llr [B][n] f64, all contiguous
@@ -79,15 +68,9 @@ class OSDPostProcessor:
         B = int(syn.shape[0])
         if out is None:
             out = torch.empty((B, self.n), dtype=torch.uint8, device=bp_err.device)
-        for x in (syn, bp_err, out):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
-        assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous()
-        assert tuple(syn.shape) == (B, self.s) and tuple(bp_err.shape) == (B, self.n)
-        assert tuple(llr.shape) == (B, self.n) and tuple(out.shape) == (B, self.n)
-        if stream is None:
-            stream = torch.cuda.current_stream(bp_err.device).cuda_stream
-        _capi.check(_capi.lib().ldpc_osd_postprocess_batch_device(self._h, B, syn.data_ptr(), bp_err.data_ptr(),
-                                                                  llr.data_ptr(), out.data_ptr(), ctypes.c_void_p(stream)))
+        _capi.check(self._L.ldpc_osd_postprocess_batch_device(
+            self._h, B, tensor_ptr(syn, torch.uint8, (B, self.s)), tensor_ptr(bp_err, torch.uint8, (B, self.n)),
+            tensor_ptr(llr, torch.float64, (B, self.n)), tensor_ptr(out, torch.uint8, (B, self.n)), stream_ptr(stream, bp_err)), self._L)
         return out
 
 

@@ -13,9 +13,9 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
+from ._host import (Handle, _pattern_of, as_int, css_pattern, current_device, device_option, host_ptr, refuse_zero_alpha_clip,
+                    stream_ptr, tensor_ptr)
 from .css_trials import pauli_rates
-from .decoder import _pattern_of
-from .minsum import _current_device
 
 
 def pauli_priors(probs) -> np.ndarray:
@@ -30,18 +30,18 @@ def pauli_priors(probs) -> np.ndarray:
     return np.ascontiguousarray(np.log(rest[None, :] / q.T).astype(np.float32))
 
 
-class PauliMinSumDecoder:
+class PauliMinSumDecoder(Handle):
     """`PauliMinSumDecoder(Hx, Hz, p, max_iters)`: `p` as `pauli_rates` takes it (a float: depolarizing noise of total rate
     p; a triple (px, py, pz)), the same for every qubit -- or `p=None` and `pauli_probs=` an (n, 3) array of per-qubit
     (px, py, pz): exactly one of the two.  alpha in (0, 1] scales every check-to-qubit message, clip > 0 clamps the
     qubit-to-check values.  kernel_variant: 0 = by size, 1 = on-chip, 2 = unlimited (`.kernel` tells which tier the handle
     takes).  check: assert Hx * Hz' = 0 over GF(2), as `CSSTrials` does (the library does not).  Flooding schedule."""
 
+    _destroy = "ldpc_pauli_minsum_destroy"
+
     def __init__(self, Hx, Hz, p=None, max_iters: int = 50, alpha: float = 0.75, clip: float = 1e6, pauli_probs=None,
                  kernel_variant: int = 0, device: Optional[int] = None, check: bool = True):
-        self._h = None
-        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)):
-            raise TypeError("max_iters must be an Int")
+        as_int(max_iters, "max_iters")
         if (p is None) == (pauli_probs is None):
             raise TypeError("give exactly one of p and pauli_probs")
         Mx, Mz = _pattern_of(Hx), _pattern_of(Hz)
@@ -60,31 +60,16 @@ class PauliMinSumDecoder:
             raise ValueError(f"one (px, py, pz) per qubit: expected {self.n} rows, got {priors.shape[1]}")
         self.prior_x, self.prior_y, self.prior_z = (np.ascontiguousarray(priors[k]) for k in range(3))
         self.max_iters, self.alpha, self.clip = int(max_iters), float(alpha), float(clip)
-        if np.float32(self.alpha) == 0.0 or np.float32(self.clip) == 0.0:
-            # a zero in ldpc_pauli_minsum_options selects the default there; here a default is spelled by leaving the
-            # keyword out, so a zero gets the status the library gives every other value outside the range
-            raise _capi.LdpcError(1, "alpha must lie in (0, 1] and clip must be finite and > 0 (got a zero)")
-        if device is None:
-            device = _current_device()   # the current device NOW is the handle's for good (what info() answers)
-        self.device = device
-        keep, pats = [], []
-        for M in (Mx, Mz):
-            colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-            rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
-            keep += [colptr, rowval]
-            pat = _capi.CSSPattern()
-            pat.rows, pat.nnz, pat.colptr, pat.rowval = int(M.shape[0]), int(rowval.size), colptr.ctypes.data, rowval.ctypes.data
-            pats.append(pat)
+        refuse_zero_alpha_clip(self.alpha, self.clip)
+        self.device = current_device() if device is None else device   # (what info() answers)
+        pat_x, pat_z = css_pattern(Mx), css_pattern(Mz)
         opts = _capi.PauliMinSumOptions()
-        opts.device = -1 if device is None else int(device)
+        opts.device = device_option(self.device)
         opts.alpha, opts.clip = self.alpha, self.clip
         opts.kernel_variant = int(kernel_variant)
-        h = ctypes.c_void_p()
-        self._L = _capi.lib_for(None)
-        _capi.check(self._L.ldpc_pauli_minsum_create(self.n, ctypes.byref(pats[0]), ctypes.byref(pats[1]), self.prior_x.ctypes.data,
-                                                     self.prior_y.ctypes.data, self.prior_z.ctypes.data, self.max_iters,
-                                                     ctypes.byref(opts), ctypes.byref(h)), self._L)
-        self._h = h
+        L = _capi.lib_for(None)
+        self._create(L, L.ldpc_pauli_minsum_create, self.n, ctypes.byref(pat_x), ctypes.byref(pat_z), self.prior_x.ctypes.data,
+                     self.prior_y.ctypes.data, self.prior_z.ctypes.data, self.max_iters, ctypes.byref(opts))
 
     @property
     def kernel(self) -> int:
@@ -104,17 +89,6 @@ class PauliMinSumDecoder:
     def info(self):
         return SimpleNamespace(device=self.device, kernel=self.kernel, tile_syndromes=self.tile_syndromes, last_grid=self.last_grid)
 
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ldpc_pauli_minsum_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def decode_batch_host(self, sx, sz, want_llr: bool = False):
         """sx [B][rows_x] (= Hx ez), sz [B][rows_z] (= Hz ex) uint8 -> (gx [B][n] u8, gz [B][n] u8, converged [B] u8,
         llr [B][3][n] f64 | None: the planes GX, GY, GZ, iters [B] i32)."""
@@ -127,8 +101,7 @@ class PauliMinSumDecoder:
         llr = np.empty((B, 3, self.n), dtype=np.float64) if want_llr else None
         its = np.empty(B, dtype=np.int32)
         _capi.check(self._L.ldpc_pauli_minsum_decode_batch(self._h, B, sx.ctypes.data, sz.ctypes.data, gx.ctypes.data, gz.ctypes.data,
-                                                           conv.ctypes.data, llr.ctypes.data if want_llr else None, its.ctypes.data),
-                    self._L)
+                                                           conv.ctypes.data, host_ptr(llr), its.ctypes.data), self._L)
         return gx, gz, conv, llr, its
 
     def decode_batch_device(self, sx, sz, gx, gz, conv, llr=None, iters=None, stream: Optional[int] = None) -> None:
@@ -138,17 +111,8 @@ class PauliMinSumDecoder:
         import torch
 
         B = int(sx.shape[0])
-        for x in (sx, sz, gx, gz, conv):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
-        assert tuple(sx.shape) == (B, self.rows_x) and tuple(sz.shape) == (B, self.rows_z)
-        assert tuple(gx.shape) == (B, self.n) and tuple(gz.shape) == (B, self.n) and conv.numel() == B
-        if llr is not None:
-            assert llr.is_cuda and llr.dtype == torch.float64 and llr.is_contiguous() and tuple(llr.shape) == (B, 3, self.n)
-        if iters is not None:
-            assert iters.is_cuda and iters.dtype == torch.int32 and iters.is_contiguous() and iters.numel() == B
-        if stream is None:
-            stream = torch.cuda.current_stream(sx.device).cuda_stream
+        u8 = torch.uint8
         _capi.check(self._L.ldpc_pauli_minsum_decode_batch_device(
-            self._h, B, sx.data_ptr(), sz.data_ptr(), gx.data_ptr(), gz.data_ptr(), conv.data_ptr(),
-            llr.data_ptr() if llr is not None else None, iters.data_ptr() if iters is not None else None, ctypes.c_void_p(stream)),
-            self._L)
+            self._h, B, tensor_ptr(sx, u8, (B, self.rows_x)), tensor_ptr(sz, u8, (B, self.rows_z)), tensor_ptr(gx, u8, (B, self.n)),
+            tensor_ptr(gz, u8, (B, self.n)), tensor_ptr(conv, u8, B), tensor_ptr(llr, torch.float64, (B, 3, self.n), optional=True),
+            tensor_ptr(iters, torch.int32, B, optional=True), stream_ptr(stream, sx)), self._L)

@@ -14,27 +14,22 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .decoder import _pattern_of
+from ._host import Handle, _pattern_of, csc_arrays, device_option, host_ptr, stream_ptr, tensor_ptr
+from ._host import current_device as _current_device   # (importable from here as before)
 
 _M64 = (1 << 64) - 1
 
 
-def _current_device() -> Optional[int]:
-    """torch's current GPU, or None without one (ldpc_trials_create then answers LDPC_ERR_NO_DEVICE itself)."""
-    import torch
-
-    return int(torch.cuda.current_device()) if torch.cuda.is_available() else None
-
-
-class Trials:
+class Trials(Handle):
     """Owns the Tanner graph of `H` and the optional `logicals` (nl x n) on a device.  kernel_variant: 0 = by size,
     1 = on-chip bit image, 2 = unlimited (`.kernel` tells which one the handle takes)."""
+
+    _destroy = "ldpc_trials_destroy"
 
     def __init__(self, H, logicals=None, device: Optional[int] = None, kernel_variant: int = 0):
         M = _pattern_of(H)
         self.s, self.n = int(M.shape[0]), int(M.shape[1])
-        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
+        colptr, rowval = csc_arrays(M)
         self.nl = 0
         lcolptr = lrowval = None
         if logicals is not None:
@@ -43,21 +38,17 @@ class Trials:
                 raise AssertionError("logicals must have as many columns as H")
             self.nl = int(Lm.shape[0])
             if self.nl:
-                lcolptr = np.ascontiguousarray(Lm.indptr, dtype=np.int64)
-                lrowval = np.ascontiguousarray(Lm.indices, dtype=np.int64)
+                lcolptr, lrowval = csc_arrays(Lm)
         if device is None:
             # the current device NOW is the handle's for good: what `_torch_device` answers later must not follow a
             # change of the current device between here and a `sample`
             device = _current_device()
         opts = _capi.TrialsOptions()
-        opts.device = -1 if device is None else int(device)
+        opts.device = device_option(device)
         opts.kernel_variant = int(kernel_variant)
-        self._h = ctypes.c_void_p()
-        self._L = _capi.lib_for(None)
-        _capi.check(self._L.ldpc_trials_create(
-            self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, self.nl,
-            int(lrowval.size) if lrowval is not None else 0, lcolptr.ctypes.data if lcolptr is not None else None,
-            lrowval.ctypes.data if lrowval is not None else None, ctypes.byref(opts), ctypes.byref(self._h)), self._L)
+        L = _capi.lib_for(None)
+        self._create(L, L.ldpc_trials_create, self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, self.nl,
+                     int(lrowval.size) if lrowval is not None else 0, host_ptr(lcolptr), host_ptr(lrowval), ctypes.byref(opts))
         self.device = device
         self.rates = None   # the array handed to set_rates, or None
 
@@ -66,17 +57,6 @@ class Trials:
         """1 = on-chip bit image, 2 = unlimited (ldpc_trials_kernel)."""
         return int(self._L.ldpc_trials_kernel(self._h))
 
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ldpc_trials_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _torch_device(self):
         import torch
 
@@ -84,7 +64,8 @@ class Trials:
 
     # -- device forms (torch tensors, asynchronous on `stream`: a hipStream_t as int, default torch's current stream) --
     def _sample_out(self, B: int, out, stream):
-        """The (errors, syndromes) tensors of a sample and its stream."""
+        """The (errors, syndromes) tensors of a sample, and the last three arguments of its call: their addresses and the
+        stream."""
         import torch
 
         if out is None:
@@ -93,43 +74,33 @@ class Trials:
             syn = torch.empty((B, self.s), dtype=torch.uint8, device=dev)
         else:
             err, syn = out
-        for x, cols in ((err, self.n), (syn, self.s)):
-            if x is not None:
-                assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, cols)
-        if stream is None:
-            stream = torch.cuda.current_stream(err.device).cuda_stream
-        return err, syn, stream
+        return err, syn, (tensor_ptr(err, torch.uint8, (B, self.n)), tensor_ptr(syn, torch.uint8, (B, self.s), optional=True),
+                          stream_ptr(stream, err))
 
     def sample(self, batch: int, per: float, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
         """-> (errors [batch][n] u8, syndromes [batch][s] u8).  `out` = (errors, syndromes) to write into; a
         syndromes of None there skips them (errors only)."""
         B = int(batch)
-        err, syn, stream = self._sample_out(B, out, stream)
-        _capi.check(self._L.ldpc_trials_sample_device(self._h, B, int(column0), float(per), int(seed) & _M64, err.data_ptr(),
-                                                      syn.data_ptr() if syn is not None else None, ctypes.c_void_p(stream)),
-                    self._L)
+        err, syn, args = self._sample_out(B, out, stream)
+        _capi.check(self._L.ldpc_trials_sample_device(self._h, B, int(column0), float(per), int(seed) & _M64, *args), self._L)
         return err, syn
 
     def set_rates(self, rates) -> None:
         """One rate per bit (array-like of n floats in [0, 1]) for `sample_rates`; None clears them.  Synchronous, and
         ordered after every earlier call on the handle."""
-        if rates is None:
-            _capi.check(self._L.ldpc_trials_set_rates(self._h, self.n, None), self._L)
-            self.rates = None
-            return
-        r = np.ascontiguousarray(rates, dtype=np.float64)
-        if r.shape != (self.n,):
-            raise ValueError(f"one rate per bit: expected {self.n} entries, got shape {r.shape}")
-        _capi.check(self._L.ldpc_trials_set_rates(self._h, self.n, r.ctypes.data), self._L)
+        r = None
+        if rates is not None:
+            r = np.ascontiguousarray(rates, dtype=np.float64)
+            if r.shape != (self.n,):
+                raise ValueError(f"one rate per bit: expected {self.n} entries, got shape {r.shape}")
+        _capi.check(self._L.ldpc_trials_set_rates(self._h, self.n, host_ptr(r)), self._L)
         self.rates = r
 
     def sample_rates(self, batch: int, seed: int = 0, column0: int = 0, out=None, stream: Optional[int] = None):
         """`sample` with bit j drawn at rates[j] (`set_rates`); equal to `sample` in every element where all rates are equal."""
         B = int(batch)
-        err, syn, stream = self._sample_out(B, out, stream)
-        _capi.check(self._L.ldpc_trials_sample_rates_device(self._h, B, int(column0), int(seed) & _M64, err.data_ptr(),
-                                                            syn.data_ptr() if syn is not None else None, ctypes.c_void_p(stream)),
-                    self._L)
+        err, syn, args = self._sample_out(B, out, stream)
+        _capi.check(self._L.ldpc_trials_sample_rates_device(self._h, B, int(column0), int(seed) & _M64, *args), self._L)
         return err, syn
 
     def syndromes(self, errors, out=None, stream: Optional[int] = None):
@@ -138,12 +109,8 @@ class Trials:
 
         B = int(errors.shape[0])
         syn = torch.empty((B, self.s), dtype=torch.uint8, device=errors.device) if out is None else out
-        for x, cols in ((errors, self.n), (syn, self.s)):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, cols)
-        if stream is None:
-            stream = torch.cuda.current_stream(errors.device).cuda_stream
-        _capi.check(self._L.ldpc_trials_syndromes_device(self._h, B, errors.data_ptr(), syn.data_ptr(), ctypes.c_void_p(stream)),
-                    self._L)
+        _capi.check(self._L.ldpc_trials_syndromes_device(self._h, B, tensor_ptr(errors, torch.uint8, (B, self.n)),
+                                                         tensor_ptr(syn, torch.uint8, (B, self.s)), stream_ptr(stream, errors)), self._L)
         return syn
 
     def score(self, guesses, errors, flags=None, counts=None, stream: Optional[int] = None, want_flags: bool = True):
@@ -152,20 +119,13 @@ class Trials:
         import torch
 
         B = int(errors.shape[0])
-        for x in (guesses, errors):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, self.n)
+        g, e = tensor_ptr(guesses, torch.uint8, (B, self.n)), tensor_ptr(errors, torch.uint8, (B, self.n))
         if flags is None and want_flags:
             flags = torch.empty(B, dtype=torch.uint8, device=errors.device)
-        if flags is not None:
-            assert flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() == B
         if counts is None:
             counts = torch.zeros(4, dtype=torch.int64, device=errors.device)
-        assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 4
-        if stream is None:
-            stream = torch.cuda.current_stream(errors.device).cuda_stream
-        _capi.check(self._L.ldpc_trials_score_device(self._h, B, guesses.data_ptr(), errors.data_ptr(),
-                                                     flags.data_ptr() if flags is not None else None, counts.data_ptr(),
-                                                     ctypes.c_void_p(stream)), self._L)
+        _capi.check(self._L.ldpc_trials_score_device(self._h, B, g, e, tensor_ptr(flags, torch.uint8, B, optional=True),
+                                                     tensor_ptr(counts, torch.int64, 4), stream_ptr(stream, errors)), self._L)
         return flags, counts
 
     # -- host forms (numpy, synchronous) ---------------------------------------------------------------------------

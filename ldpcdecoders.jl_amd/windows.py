@@ -20,7 +20,9 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from .decoder import AbstractDecoder, _pattern_of, syndrome_bytes
+from ._host import Handle, _pattern_of, csc_arrays, device_option, stream_ptr, syndrome_bytes, tensor_ptr
+from ._host import current_device as _current_device
+from .decoder import AbstractDecoder
 from .dem import DetectorErrorModel
 
 
@@ -123,10 +125,12 @@ def _lists(seqs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
     return ptr, np.ascontiguousarray(idx, dtype=np.int64)
 
 
-class WindowStep:
+class WindowStep(Handle):
     """The window step of `H` (D x N) on a device: `det[k]`, `mech[k]`, `commit[k]` (positions in mech[k]) for every window.
     `gather` and `commit` take contiguous uint8 torch tensors on that device and are asynchronous on `stream` (a
     hipStream_t as int; default torch's current stream)."""
+
+    _destroy = "ldpc_windows_destroy"
 
     def __init__(self, H, det, mech, commit, device: Optional[int] = None):
         M = _pattern_of(H)
@@ -135,42 +139,19 @@ class WindowStep:
             raise ValueError("one det, mech and commit list per window")
         self.ndet = [int(len(x)) for x in det]
         self.nmech = [int(len(x)) for x in mech]
-        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64)
-        rowval = np.ascontiguousarray(M.indices, dtype=np.int64)
-        dp, di = _lists(det)
-        mp, mi = _lists(mech)
-        cp, ci = _lists(commit)
+        colptr, rowval = csc_arrays(M)
+        lists = [a for seqs in (det, mech, commit) for a in _lists(seqs)]   # (ptr, idx) of each, kept alive across the call
         if device is None:
             device = _current_device()   # the current device NOW is the handle's for good
         opts = _capi.WindowsOptions()
-        opts.device = -1 if device is None else int(device)
-        self._h = ctypes.c_void_p()
-        self._L = _capi.lib_for(None)
-        _capi.check(self._L.ldpc_windows_create(self.D, self.N, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, len(det),
-                                                dp.ctypes.data, di.ctypes.data, mp.ctypes.data, mi.ctypes.data, cp.ctypes.data,
-                                                ci.ctypes.data, ctypes.byref(opts), ctypes.byref(self._h)), self._L)
+        opts.device = device_option(device)
+        L = _capi.lib_for(None)
+        self._create(L, L.ldpc_windows_create, self.D, self.N, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, len(det),
+                     *(a.ctypes.data for a in lists), ctypes.byref(opts))
         self.device = device
 
     def __len__(self) -> int:
         return int(self._L.ldpc_windows_count(self._h))
-
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ldpc_windows_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _u8(x, shape) -> int:
-        import torch
-
-        assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == tuple(shape), (tuple(x.shape), shape)
-        return x.data_ptr()
 
     def gather(self, k: int, residual, out=None, stream: Optional[int] = None):
         """residual [B][D] -> window k's syndromes [B][|det_k|]."""
@@ -179,10 +160,9 @@ class WindowStep:
         k, B = int(k), int(residual.shape[0])
         if out is None:
             out = torch.empty((B, self.ndet[k]), dtype=torch.uint8, device=residual.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(residual.device).cuda_stream
-        _capi.check(self._L.ldpc_windows_gather_device(self._h, k, B, self._u8(residual, (B, self.D)), self._u8(out, (B, self.ndet[k])),
-                                                       ctypes.c_void_p(stream)), self._L)
+        _capi.check(self._L.ldpc_windows_gather_device(self._h, k, B, tensor_ptr(residual, torch.uint8, (B, self.D)),
+                                                       tensor_ptr(out, torch.uint8, (B, self.ndet[k])), stream_ptr(stream, residual)),
+                    self._L)
         return out
 
     def commit(self, k: int, win_guess, residual, guess, win_conv=None, conv=None, next_syndromes=None,
@@ -191,13 +171,12 @@ class WindowStep:
         syndromes [B][|det_{k+1}|] where given."""
         import torch
 
-        k, B = int(k), int(residual.shape[0])
-        if stream is None:
-            stream = torch.cuda.current_stream(residual.device).cuda_stream
+        k, B, u8 = int(k), int(residual.shape[0]), torch.uint8
         _capi.check(self._L.ldpc_windows_commit_device(
-            self._h, k, B, self._u8(win_guess, (B, self.nmech[k])), self._u8(win_conv, (B,)) if win_conv is not None else None,
-            self._u8(residual, (B, self.D)), self._u8(guess, (B, self.N)), self._u8(conv, (B,)) if conv is not None else None,
-            self._u8(next_syndromes, (B, self.ndet[k + 1])) if next_syndromes is not None else None, ctypes.c_void_p(stream)), self._L)
+            self._h, k, B, tensor_ptr(win_guess, u8, (B, self.nmech[k])), tensor_ptr(win_conv, u8, (B,), optional=True),
+            tensor_ptr(residual, u8, (B, self.D)), tensor_ptr(guess, u8, (B, self.N)), tensor_ptr(conv, u8, (B,), optional=True),
+            tensor_ptr(next_syndromes, u8, (B, self.ndet[k + 1])) if next_syndromes is not None else None,   # (no k + 1 after the last)
+            stream_ptr(stream, residual)), self._L)
 
 
 class SlidingWindowDecoder(AbstractDecoder):
@@ -286,9 +265,8 @@ class SlidingWindowDecoder(AbstractDecoder):
         import torch
 
         B = int(syn.shape[0])
-        for x in (syn, err, conv):
-            assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
-        assert tuple(syn.shape) == (B, self.s) and tuple(err.shape) == (B, self.n) and conv.numel() == B
+        for x, shape in ((syn, (B, self.s)), (err, (B, self.n)), (conv, B)):
+            tensor_ptr(x, torch.uint8, shape)
         if stream is not None and int(stream) != torch.cuda.current_stream(syn.device).cuda_stream:
             # the window decoders are driven on torch's current stream: make `stream` that one
             with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=syn.device)):
@@ -359,13 +337,3 @@ class SlidingWindowDecoder(AbstractDecoder):
         errors[:, :] = err.T
         success[:] = conv.astype(np.bool_)
         return errors, success
-
-
-def _current_device() -> Optional[int]:
-    """torch's current GPU, or None without one (ldpc_windows_create then answers LDPC_ERR_NO_DEVICE itself)."""
-    try:
-        import torch
-
-        return int(torch.cuda.current_device()) if torch.cuda.is_available() else None
-    except Exception:
-        return None
