@@ -11,6 +11,13 @@ CASES, SEEDS = 40, (20, 21)      # what tests/test_gpu_fuzz_models.py runs on th
 
 CASE = re.compile(r"^case (\d+): kind (\d) shape \((\d+), (\d+)\) nnz (\d+) B (\d+) checks<=32 (\d+) checks33-64 (\d+) checks>64 (\d+) "
                   r"empty_checks (\d+) empty_bits (\d+) max_bit_degree (\d+)$")
+# the lines of the legs that draw from the second generator; a leg of max_iters 0 decodes nothing and counts for no property
+LAYERED = re.compile(r"^   layered .* max_iters (\d+) .* layers (\d+) smallest_layer (\d+) checks<=32 (\d+) checks33-64 (\d+) "
+                     r"checks>64 (\d+) checks_empty (\d+)$")
+PRIORS = re.compile(r"^   priors (flooding|layered) (floats|given) .* max_iters (\d+) .* nonfinite_rows (\d+)$")
+PAULI = re.compile(r"^   pauli Hz \((\d+), (\d+)\) B (\d+) .* max_iters (\d+) .* uniform=(True|False) (sampled|arbitrary) syndromes "
+                   r"hx<=32 (\d+) hx33-64 (\d+) hx>64 (\d+) hx_empty (\d+) hz<=32 (\d+) hz33-64 (\d+) hz>64 (\d+) hz_empty (\d+)$")
+OLD_LEGS, NEW_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css"), ("layered", "priors", "pauli")
 
 
 def _tool(args, **env):
@@ -24,6 +31,27 @@ def coverage(listing):
     """The properties of the issue that the cases of a FUZZ_DRY listing have, as a set of names."""
     have = set()
     for line in listing.splitlines():
+        m = LAYERED.match(line)
+        if m and int(m.group(1)) > 0:
+            _, K, smallest, _, c64, cbig, _ = (int(x) for x in m.groups())
+            have |= {name for name, yes in (
+                ("layered: check of degree 33 ... 64", c64 > 0), ("layered: check of degree > 64", cbig > 0),
+                ("layered: a layer of one check", K > 0 and smallest == 1)) if yes}
+        m = PRIORS.match(line)
+        if m and int(m.group(3)) > 0:
+            have.add(f"priors: {m.group(1)} {m.group(2)}")
+            if int(m.group(4)) > 0:
+                have.add("priors: a non-finite row")
+        m = PAULI.match(line)
+        if m and int(m.group(4)) > 0:
+            B, uniform, syndromes = int(m.group(3)), m.group(5) == "True", m.group(6)
+            _, hx64, hxbig, hxe, _, hz64, hzbig, hze = (int(x) for x in m.groups()[6:])
+            have |= {name for name, yes in (
+                ("pauli: Hz check of degree 33 ... 64", hz64 > 0), ("pauli: Hz check of degree > 64", hzbig > 0),
+                ("pauli: Hx check of degree 33 ... 64", hx64 > 0), ("pauli: Hx check of degree > 64", hxbig > 0),
+                ("pauli: empty Hx check", hxe > 0), ("pauli: empty Hz check", hze > 0), ("pauli: batch 1", B == 1),
+                ("pauli: batch 65", B == 65), ("pauli: one triple for every qubit", uniform),
+                ("pauli: arbitrary syndromes", syndromes == "arbitrary")) if yes}
         m = CASE.match(line)
         if not m:
             continue
@@ -37,7 +65,13 @@ def coverage(listing):
 
 
 WANTED = {"check of degree <= 32", "check of degree 33 ... 64", "check of degree > 64", "empty check", "empty bit", "bit of degree > 64",
-          "n % 64 == 0", "n % 64 == 1", "n % 64 == 63", "n % 32 == 1", "batch 1", "batch 65"}
+          "n % 64 == 0", "n % 64 == 1", "n % 64 == 63", "n % 32 == 1", "batch 1", "batch 65",
+          "layered: check of degree 33 ... 64", "layered: check of degree > 64", "layered: a layer of one check",
+          "priors: flooding floats", "priors: flooding given", "priors: layered floats", "priors: layered given",
+          "priors: a non-finite row",
+          "pauli: Hz check of degree 33 ... 64", "pauli: Hz check of degree > 64", "pauli: Hx check of degree 33 ... 64",
+          "pauli: Hx check of degree > 64", "pauli: empty Hx check", "pauli: empty Hz check", "pauli: batch 1", "pauli: batch 65",
+          "pauli: one triple for every qubit", "pauli: arbitrary syndromes"}
 
 
 def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_the_boundary_shapes():
@@ -49,8 +83,11 @@ def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_th
         assert strip(first) == strip(again), f"seed {seed}: two dry runs list different cases"
         assert len([ln for ln in first.splitlines() if CASE.match(ln)]) == CASES
         # every leg of every case is listed: the draws do not depend on what ran
-        for leg in ("bitflip", "minsum", "relay", "osd", "trials", "css"):
+        for leg in OLD_LEGS + NEW_LEGS:
             assert len([ln for ln in first.splitlines() if ln.startswith(f"   {leg} ")]) == CASES, leg
+        # ... and every line of a new leg is one that coverage() can read
+        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI)):
+            assert all(pattern.match(ln) for ln in first.splitlines() if ln.startswith(f"   {leg} ")), leg
         have |= coverage(first)
     assert have == WANTED, f"the committed seeds never draw: {sorted(WANTED - have)}"
 
@@ -66,3 +103,4 @@ def test_a_window_of_cases_draws_what_the_whole_run_draws():
 def test_one_case_runs_through_the_models_to_the_end():
     out = _tool([3, SEEDS[0]], FUZZ_MODEL_ONLY="1", FUZZ_FROM="2", FUZZ_TO="2")
     assert "model seconds: bitflip" in out and "through the models only" in out.splitlines()[-1]
+    assert all(f"{leg} " in out.splitlines()[-2] for leg in OLD_LEGS + NEW_LEGS)

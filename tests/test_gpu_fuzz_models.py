@@ -12,7 +12,8 @@ from test_fuzz_models_cpu import CASES, SEEDS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TIERS = {"bitflip": {1, 2, 3}, "minsum": {1, 2}, "relay": {1, 2}, "osd": {1, 2, 3}, "trials": {1, 2}, "css": {1, 2}}
+TIERS = {"bitflip": {1, 2, 3}, "minsum": {1, 2}, "relay": {1, 2}, "osd": {1, 2, 3}, "trials": {1, 2}, "css": {1, 2},
+         "layered": {1, 2}, "priors": {1, 2}, "pauli": {1, 2}}
 _REPORTS = {}
 
 

@@ -7,7 +7,9 @@ never by calling the library for the sizes:
     S = the largest power of two <= 64 whose state fits 79 KiB (two workgroups a CU), else the largest that fits 159 KiB,
     else the unlimited tier with S = 64.
 
-tests/test_gpu_minsum_tiles.py runs every row of TABLE on the device and asserts the width read back from the handle.
+tests/test_gpu_minsum_tiles.py runs every row of TABLE on the device and asserts the width read back from the handle;
+tests/test_gpu_family_widths.py does the same for PAULI_TABLE and PRIORS_TABLE (the Pauli decoder and the entries with
+per-syndrome priors, whose states have other sizes: ldpc_debug_pauli_tile_plan, ldpc_debug_priors_tile_plan).
 At the end: the builder of the check records (ms_records, the same header) under the sanitizers."""
 import ctypes
 import os
@@ -126,6 +128,82 @@ def test_the_shapes_of_the_existing_gpu_tests_keep_their_tiers():
     rec = 0 + 4 + 5 + 5 + 70 + 22 * 4
     for relay in (False, True):
         assert plan(27, 150, rec, relay)[:3] == (OK, 1, 32) and plan(27, 150, rec, relay, 1)[:3] == (OK, 1, 32)
+
+
+# ---- the shapes of tests/test_gpu_family_widths.py --------------------------------------------------------------------
+# Pauli, Hx and Hz both (3,6)-regular over n qubits: s = n checks, rec_words = 4 n, 4 (2 n + 4 n) + n = 25 n bytes a syndrome.
+# n -> (tier, S)
+PAULI_TABLE = {
+    48: (1, 64),
+    96: (1, 32),
+    192: (1, 16),
+    384: (1, 8),
+    768: (1, 4),
+    1536: (1, 2),
+    3072: (1, 1),       # inside the 79 KiB budget
+    6144: (1, 1),       # inside the 159 KiB budget
+    6912: (2, 64),      # 172,800 bytes a syndrome: the unlimited tier by size
+}
+# The flooding entries with per-syndrome priors, (3,6)-regular H: 12.5 n bytes of plain state and 4 n of priors, 16.5 n a
+# syndrome.  `extra`: one more check row of degree 33 (a five-word record), which makes s odd, so that s S is no multiple of
+# 4 and the priors block starts behind padding bytes.  (n, extra) -> ((tier, S) of the priors entries, (tier, S) of the plain)
+PRIORS_TABLE = {
+    (72, 0): ((1, 64), (1, 64)),
+    (192, 0): ((1, 16), (1, 32)),
+    (384, 0): ((1, 8), (1, 16)),
+    (768, 0): ((1, 4), (1, 8)),
+    (1536, 0): ((1, 2), (1, 4)),
+    (1536, 1): ((1, 2), (1, 4)),      # s = 769: s S % 4 == 2
+    (3072, 0): ((1, 1), (1, 2)),
+    (3072, 1): ((1, 1), (1, 2)),      # s = 1537: s S % 4 == 1
+    (6144, 0): ((1, 1), (1, 1)),      # the priors entries inside the 159 KiB budget, the plain ones inside the 79 KiB one
+}
+
+
+def priors_state_bytes(s, n, rec_words, S):
+    """The plain blocks, the next word boundary, then P [n][S] f32 (minsum_kernels.hpp); rounded up to 256."""
+    return (((4 * (n + rec_words) + s) * S + 3) // 4 * 4 + 4 * n * S + 255) // 256 * 256
+
+
+def widest_fit(size_of):
+    """(tier, S) by the rule of the module docstring for a state of size_of(S) bytes."""
+    for budget in (KIB79, KIB159):
+        fits = [w for w in (64, 32, 16, 8, 4, 2, 1) if size_of(w) <= budget]
+        if fits:
+            return 1, fits[0]
+    return 2, 64
+
+
+def debug_plan(name, *args, experiments=False):
+    """(status, tier, S, state bytes) of one of the ldpc_debug_*_tile_plan functions."""
+    tier, S, nbytes = ctypes.c_int32(-7), ctypes.c_int32(-7), ctypes.c_int64(-7)
+    st = getattr(ldpc._capi.lib(experiments), name)(*args, ctypes.byref(tier), ctypes.byref(S), ctypes.byref(nbytes))
+    return st, tier.value, S.value, nbytes.value
+
+
+@pytest.mark.parametrize("experiments", [False, True])
+def test_the_shapes_of_the_family_width_tests_keep_their_rows(experiments):
+    """tests/test_gpu_family_widths.py asserts these widths on the handles; a planner change that moves a shape off its row
+    fails here first."""
+    for n, want in PAULI_TABLE.items():
+        size_of = lambda S: (25 * n * S + 255) // 256 * 256   # noqa: E731
+        assert 4 * (2 * n + 4 * n) + n == 25 * n and widest_fit(size_of) == want, n
+        assert debug_plan("ldpc_debug_pauli_tile_plan", n, n, 4 * n, 0, experiments=experiments) == (OK, *want, size_of(want[1])), n
+        on_chip = debug_plan("ldpc_debug_pauli_tile_plan", n, n, 4 * n, 1, experiments=experiments)
+        assert on_chip[:3] == (OK, *want) if want[0] == 1 else on_chip[0] == UNSUPPORTED, n
+    assert 25 * 3072 <= KIB79 < 25 * 6144 <= KIB159 < 25 * 6912
+    for (n, extra), (want_priors, want_plain) in PRIORS_TABLE.items():
+        s, rec = n // 2 + extra, 2 * n + 5 * extra
+        assert widest_fit(lambda S: priors_state_bytes(s, n, rec, S)) == want_priors, (n, extra)
+        assert widest_fit(lambda S: state_bytes(s, n, rec, S, False)) == want_plain, (n, extra)
+        S = want_priors[1]
+        assert debug_plan("ldpc_debug_priors_tile_plan", s, n, rec, 0, 0, experiments=experiments) == (OK, *want_priors, priors_state_bytes(s, n, rec, S))
+        assert debug_plan("ldpc_debug_tile_plan", s, n, rec, 0, 0, experiments=experiments)[:3] == (OK, *want_plain)
+        # a layered handle keeps no priors block: its priors plan is its plain plan
+        assert debug_plan("ldpc_debug_priors_tile_plan", s, n, rec, 1, 0, experiments=experiments)[:3] == (OK, *want_plain)
+        assert ((s * S) % 4 != 0) == bool(extra), (n, extra)
+    assert (769 * 2) % 4 == 2 and 1537 % 4 == 1 and 3072 % 4 == 0
+    assert priors_state_bytes(3072, 6144, 12288, 1) > KIB79 >= state_bytes(3072, 6144, 12288, 1, False)
 
 
 @pytest.mark.parametrize("relay", [False, True], ids=["minsum", "relay"])

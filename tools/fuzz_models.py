@@ -1,16 +1,25 @@
 #!/usr/bin/env python3
 """Randomised model-parity fuzz (GPU box) of the kernels that tools/fuzz_parity.py does not reach: the bit-flip decoder,
-min-sum, relay min-sum, the device OSD step, and the one-matrix and CSS trial steps.  Random Tanner graphs (irregular with
-empty and heavy nodes and sizes around the word boundaries, or small Gallager codes), ragged batches, every
-`kernel_variant` that create accepts, every result compared in every element with the numpy models of tests/ (min-sum
-and relay: the LLR bit patterns too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
+min-sum (flooding and layered schedule, shared and per-syndrome priors), relay min-sum, the joint X/Z (Pauli) min-sum, the
+device OSD step, and the one-matrix and CSS trial steps.  Random Tanner graphs (irregular with empty and heavy nodes and
+sizes around the word boundaries, or small Gallager codes), ragged batches, every `kernel_variant` that create accepts,
+every result compared in every element with the numpy models of tests/ (the min-sum family and relay: the LLR bit patterns
+too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
 
 FUZZ_DRY=1: draw the cases and print them without touching the GPU or a model (no draw depends on a result, so this lists
 what a run with the same seed decodes); FUZZ_FROM / FUZZ_TO: only run the cases with these indices (the others are drawn
 and skipped); FUZZ_VERBOSE=1: one line per leg BEFORE it runs; FUZZ_MODEL_ONLY=1: no GPU, the models alone, with their
 seconds.  A leg is skipped only when create answers UNSUPPORTED for an on-chip tier; every component decodes every case on
 its unlimited tier.  The leg in hand is kept in fuzz_models_current.txt and, on a mismatch (exit status 1), the inputs in
-fuzz_models_failure.npz, both in the directory FUZZ_OUT (default: fuzz_out/ in the repository root, which git ignores)."""
+fuzz_models_failure.npz, both in the directory FUZZ_OUT (default: fuzz_out/ in the repository root, which git ignores).
+
+The legs `layered`, `priors` and `pauli` draw from a generator of their own (seeded [seed, 1]): the six older legs decode for
+a seed what they decoded before those three existed.
+
+Model seconds of 40 cases on one CPU core (the `model seconds` line of FUZZ_MODEL_ONLY=1), the six older legs together against
+the three of the second generator:
+  seed 20: bitflip 0.35, minsum 1.60, relay 3.40, osd 0.62, trials 0.04, css 0.05 (6.1 s); layered 0.99, priors 1.27, pauli 1.61 (3.9 s)
+  seed 21: bitflip 0.18, minsum 1.08, relay 2.79, osd 0.36, trials 0.04, css 0.04 (4.5 s); layered 0.79, priors 0.81, pauli 1.00 (2.6 s)"""
 import os
 import sys
 import time
@@ -25,9 +34,12 @@ import ldpcdecoders_jl_amd as ldpc  # noqa: E402
 import css_trials_model as cm  # noqa: E402
 import dem_model as dm  # noqa: E402
 import trials_model as tm  # noqa: E402
+import priors_model as pm  # noqa: E402
 from bitflip_model import BitFlipModel  # noqa: E402
+from layered_model import LayeredMinSumModel, layers_of  # noqa: E402
 from minsum_model import MinSumModel, llr_of_probs  # noqa: E402
 from osd_model import osd_model_postprocess  # noqa: E402
+from pauli_model import PauliMinSumModel, pauli_priors  # noqa: E402
 from relay_model import RelayModel  # noqa: E402
 
 DRY = os.environ.get("FUZZ_DRY") == "1"
@@ -39,7 +51,8 @@ OUT = os.environ.get("FUZZ_OUT") or os.path.join(ROOT, "fuzz_out")
 UNSUPPORTED = 5
 # tiers a component can take here; the last one is its unlimited tier.  (Bit-flip tier 4, the 64-bit votes, needs
 # max_iters * max bit degree >= 2^31 and is held by test_unlimited_tier_with_64_bit_votes.)
-TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2)}
+TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2),
+         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2)}
 BOUNDARY = (31, 32, 33, 63, 64, 65, 127, 128, 129)
 
 if GPU:
@@ -54,6 +67,7 @@ if GPU:
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
+rng2 = np.random.default_rng([seed, 1])      # the layered, priors and pauli legs: never `rng`, whose stream the older legs own
 t0 = time.time()
 ran = {c: set() for c in TIERS}          # tiers that decoded
 legs_run = {c: 0 for c in TIERS}
@@ -102,9 +116,10 @@ def timed_model(component, f):
     return out
 
 
-def on_every_tier(component, variants, create, run, text):
+def on_every_tier(component, variants, create, run, text, tier_of=lambda h: int(h.kernel)):
     """create(variant) -> handle (LdpcError UNSUPPORTED for an on-chip tier: the leg is skipped); run(handle, tier)
-    compares; the unlimited tier must run."""
+    compares; the unlimited tier must run.  tier_of(handle): the tier that the entries under test take; 0 = they are
+    unsupported on this handle, which for an on-chip variant is a skipped leg as well."""
     unlimited = TIERS[component][-1]
     for variant in variants:
         note(component, f"kernel_variant {variant} {text}")
@@ -115,7 +130,11 @@ def on_every_tier(component, variants, create, run, text):
                 skipped[component] += 1
                 continue
             raise
-        tier = int(h.kernel)
+        tier = tier_of(h)
+        if tier == 0 and variant != unlimited:
+            h.close()
+            skipped[component] += 1
+            continue
         if tier != variant:
             fail(component, f"kernel_variant {variant} gave tier {tier} {text}")
         run(h, variant)
@@ -179,19 +198,21 @@ def draw_graph():
     return kind, H
 
 
-def draw_syndromes(H, B):
+def draw_syndromes(H, B, g=None):
     """Syndromes of random errors, or arbitrary ones."""
+    g = g or rng
     s, n = H.shape
-    if rng.random() < 0.6:
-        return ldpc.codes.syndromes_of(H, (rng.random((B, n)) < rng.uniform(0.01, 0.2)).astype(np.uint8))
-    return rng.integers(0, 2, (B, s)).astype(np.uint8)
+    if g.random() < 0.6:
+        return ldpc.codes.syndromes_of(H, (g.random((B, n)) < g.uniform(0.01, 0.2)).astype(np.uint8))
+    return g.integers(0, 2, (B, s)).astype(np.uint8)
 
 
-def draw_priors(n):
-    """Per-bit prior LLRs with a few negative, +-0 and subnormal ones."""
-    prior = llr_of_probs(rng.uniform(0.005, 0.45, n))
+def draw_priors(shape, g=None):
+    """Prior LLRs ([n], or [B][n] for a prior per syndrome) with a few negative, +-0 and subnormal ones."""
+    g = g or rng
+    prior = llr_of_probs(g.uniform(0.005, 0.45, shape))
     for value in (None, 0.0, -0.0, 1e-40, -1e-41):
-        hit = rng.random(n) < 0.04
+        hit = g.random(shape) < 0.04
         prior[hit] = -prior[hit] if value is None else np.float32(value)
     return prior
 
@@ -515,6 +536,202 @@ def leg_css(B, run):
     on_every_tier("css", (1, 2), lambda v: ldpc.CSSTrials(Hx, Hz, logicals, kernel_variant=v), go, text)
 
 
+# ---- the legs of the second generator ----------------------------------------------------------------------------------
+def draw_rule(g):
+    """alpha, clip, max_iters of a leg of the min-sum family (the models loop over the edges in Python: 10 iterations)."""
+    return float(g.choice([0.5, 0.75, 1.0])), float(g.choice([4.0, 20.0, 1e6])), int(g.choice([0, 1, 3, 10]))
+
+
+def degrees_text(H, name):
+    """The record forms among the checks of H (csc) and its empty checks, for a dry line."""
+    deg = np.diff(sp.csr_matrix(H).indptr)
+    return (f"{name}<=32 {int(((deg > 0) & (deg <= 32)).sum())} {name}33-64 {int(((deg > 32) & (deg <= 64)).sum())} "
+            f"{name}>64 {int((deg > 64).sum())} {name}_empty {int((deg == 0).sum())}")
+
+
+def device_outputs(B, n, planes, want_llr, want_iters):
+    """(err-like [B][n] u8, conv, llr | None, iters | None) on the device, pre-filled with values no decode writes."""
+    shape = (B, n) if planes == 1 else (B, planes, n)
+    return (torch.full((B, n), 7, dtype=torch.uint8, device="cuda"), torch.full((B,), 7, dtype=torch.uint8, device="cuda"),
+            torch.full(shape, 7.0, dtype=torch.float64, device="cuda") if want_llr else None,
+            torch.full((B,), -7, dtype=torch.int32, device="cuda") if want_iters else None)
+
+
+def host_of(x):
+    return None if x is None else x.cpu().numpy()
+
+
+def leg_layered(H, B, run):
+    g = rng2
+    s, n = H.shape
+    alpha, clip, max_iters = draw_rule(g)
+    prior = draw_priors(n, g)
+    device_entry = bool(g.random() < 0.5)
+    syn = draw_syndromes(H, B, g)
+    text = f"alpha {alpha} clip {clip} max_iters {max_iters} {'device' if device_entry else 'host'} entry"
+    if DRY or VERBOSE:
+        layer_of, K = layers_of(H)
+        sizes = np.bincount(layer_of[layer_of >= 0], minlength=K)
+        print(f"   layered {text} layers {K} smallest_layer {int(sizes.min()) if K else 0} {degrees_text(H, 'checks')}", flush=True)
+    if not run:
+        return
+    model = LayeredMinSumModel(H, prior, max_iters, alpha=alpha, clip=clip)
+    merr, mconv, mits, mL = timed_model("layered", lambda: model.decode(syn))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if int(dec.layers) != model.K:
+            fail("layered", f"{dec.layers} layers, the model has {model.K}, kernel_variant {variant} {text}", colptr=H.indptr,
+                 rowval=H.indices, shape=H.shape)
+        if device_entry:
+            err, conv, llr, its = device_outputs(B, n, 1, True, True)
+            dec.decode_batch_device(dev(syn), err, conv, llr, its)
+            torch.cuda.synchronize()
+            err, conv, llr, its = (x.cpu().numpy() for x in (err, conv, llr, its))
+        else:
+            err, conv, llr, its = dec.decode_batch_host(syn, want_llr=True)
+        if not (same(err, merr) and same(conv, mconv) and same(its, mits) and same_bits(llr, mL)):
+            fail("layered", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, prior=prior,
+                 err=err, conv=conv, its=its, llr=llr, merr=merr, mconv=mconv, mits=mits, mL=mL)
+
+    on_every_tier("layered", (1, 2), lambda v: ldpc.MinSumDecoder(H, None, max_iters, channel_llr=prior, alpha=alpha, clip=clip,
+                                                                  kernel_variant=v, schedule="layered"), go, text)
+
+
+def leg_priors(H, B, run):
+    """The entries with a prior per syndrome and bit: both schedules, the priors as floats or selected by given bits."""
+    g = rng2
+    s, n = H.shape
+    schedule = ("flooding", "layered")[int(g.integers(0, 2))]
+    source = ("floats", "given")[int(g.integers(0, 2))]
+    alpha, clip, max_iters = draw_rule(g)
+    shared = draw_priors(n, g)                 # the handle's channel_llr: these entries never read it
+    nonfinite = 0
+    if source == "floats":
+        pri = draw_priors((B, n), g)
+        if g.random() < 0.3:                   # a NaN, a +inf or a -inf in a few rows: such a row is not decoded
+            rows = g.choice(B, size=min(B, int(g.integers(1, 4))), replace=False)
+            pri[rows, g.integers(0, n, size=rows.size)] = g.choice(np.array([np.nan, np.inf, -np.inf], dtype=np.float32), size=rows.size)
+            nonfinite = int(rows.size)
+        t0 = t1 = given = None
+    else:
+        t0, t1 = draw_priors(n, g), draw_priors(n, g)
+        given = g.integers(0, 256, size=(B, n), dtype=np.uint8)
+        pri = pm.select_priors(given, t0, t1)
+    device_entry, want_llr, want_iters = (bool(g.random() < 0.5) for _ in range(3))
+    syn = draw_syndromes(H, B, g)
+    text = (f"{schedule} {source} alpha {alpha} clip {clip} max_iters {max_iters} {'device' if device_entry else 'host'} entry "
+            f"llr={want_llr} iters={want_iters} nonfinite_rows {nonfinite}")
+    if DRY or VERBOSE:
+        print(f"   priors {text}", flush=True)
+    if not run:
+        return
+    merr, mconv, mits, mL = timed_model("priors", lambda: pm.model_of(schedule, H, max_iters, alpha, clip).decode(syn, pri))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if source == "given":
+            dec.set_conditional_priors(t0, t1)
+        extra = pri if source == "floats" else given
+        if device_entry:
+            err, conv, llr, its = device_outputs(B, n, 1, want_llr, want_iters)
+            entry = dec.decode_batch_priors_device if source == "floats" else dec.decode_batch_given_device
+            entry(dev(syn), dev(extra), err, conv, llr, its)
+            torch.cuda.synchronize()
+            err, conv, llr, its = (host_of(x) for x in (err, conv, llr, its))
+        else:
+            entry = dec.decode_batch_priors_host if source == "floats" else dec.decode_batch_given_host
+            err, conv, llr, its = entry(syn, extra, want_llr=want_llr)
+            if (llr is None) != (not want_llr):
+                fail("priors", f"the host entry returns LLRs it was not asked for, or none, kernel_variant {variant} {text}")
+        ok = same(err, merr) and same(conv, mconv) and (its is None or same(its, mits)) and (llr is None or same_bits(llr, mL))
+        if not ok:
+            fail("priors", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, pri=pri,
+                 given=given, t0=t0, t1=t1, err=err, conv=conv, its=its, llr=llr, merr=merr, mconv=mconv, mits=mits, mL=mL)
+
+    on_every_tier("priors", (1, 2), lambda v: ldpc.MinSumDecoder(H, None, max_iters, channel_llr=shared, alpha=alpha, clip=clip,
+                                                                 kernel_variant=v, schedule=schedule), go, text,
+                  tier_of=lambda h: int(h.info().priors_kernel))
+
+
+def draw_pauli_probs(n, g):
+    """(probs [n][3], uniform): per-qubit (px, py, pz); a few qubits where one Pauli is likelier than I (a negative prior), a
+    few with pW == 1 - px - py - pz exactly (a prior of +0: 0.25 against 0.125 and 0.375, all exact in binary); in a quarter
+    of the cases one triple (a, b, a) for every qubit, so that GX == GZ wherever TX == TZ."""
+    if g.random() < 0.25:
+        a, b = g.uniform(0.005, 0.1, size=2)
+        return np.tile(np.array([a, b, a]), (n, 1)), True
+    probs = g.uniform(0.002, 0.1, size=(n, 3))
+    likely = np.nonzero(g.random(n) < 0.06)[0]
+    probs[likely] = 0.1
+    probs[likely, g.integers(0, 3, size=likely.size)] = g.uniform(0.4, 0.7, size=likely.size)
+    zero = np.nonzero(g.random(n) < 0.06)[0]
+    for j, w in zip(zero, g.integers(0, 3, size=zero.size)):
+        probs[j] = np.roll([0.25, 0.125, 0.375], w)
+    return probs, False
+
+
+def leg_pauli(H, B, run):
+    """Hx = the case's H, Hz a second drawn matrix over the same qubits; the sides need not commute (check=False)."""
+    g = rng2
+    rx, n = H.shape
+    rz = int(g.integers(1, 41))
+    A = (g.random((rz, n)) < g.uniform(0.02, 0.25)).astype(np.uint8)
+    empty, heavy = int(g.integers(0, rz)), int(g.integers(0, rz))
+    if heavy == empty:
+        heavy = (heavy + 1) % rz
+    if g.random() < 0.35:
+        A[empty, :] = 0
+    if g.random() < 0.5 and n >= 33:          # a row of 33 ... 80 ones
+        A[heavy, g.choice(n, size=min(n, int(g.integers(33, 81))), replace=False)] = 1
+    Hz = sp.csc_matrix(A)
+    Hz.sort_indices()
+    alpha, clip, max_iters = draw_rule(g)
+    probs, uniform = draw_pauli_probs(n, g)
+    device_entry, want_llr, want_iters = (bool(g.random() < 0.5) for _ in range(3))
+    sampled = bool(g.random() < 0.6)
+    if sampled:                               # the syndromes of sampled Pauli errors: sx = Hx ez, sz = Hz ex
+        rate = g.uniform(0.01, 0.15)
+        ex, ez = ((g.random((B, n)) < rate).astype(np.uint8) for _ in range(2))
+        sx, sz = ldpc.codes.syndromes_of(H, ez), ldpc.codes.syndromes_of(Hz, ex)
+    else:
+        sx, sz = g.integers(0, 2, (B, rx)).astype(np.uint8), g.integers(0, 2, (B, rz)).astype(np.uint8)
+    text = (f"Hz ({rz}, {n}) B {B} alpha {alpha} clip {clip} max_iters {max_iters} {'device' if device_entry else 'host'} entry "
+            f"llr={want_llr} iters={want_iters} uniform={uniform} {'sampled' if sampled else 'arbitrary'} syndromes")
+    if DRY or VERBOSE:
+        print(f"   pauli {text} {degrees_text(H, 'hx')} {degrees_text(Hz, 'hz')}", flush=True)
+    if not run:
+        return
+    tables = pauli_priors(probs)
+    mgx, mgz, mconv, mits, mG = timed_model(
+        "pauli", lambda: PauliMinSumModel(H, Hz, tables, max_iters, alpha=alpha, clip=clip).decode(sx, sz))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        for name, got, want in zip("xyz", (dec.prior_x, dec.prior_y, dec.prior_z), tables):
+            if not (got.dtype == np.float32 and np.array_equal(got.view(np.int32), want.view(np.int32))):
+                fail("pauli", f"prior_{name} differs from the model's table {text}", probs=probs, got=got, want=want)
+        if device_entry:
+            gx, conv, llr, its = device_outputs(B, n, 3, want_llr, want_iters)
+            gz = torch.full((B, n), 7, dtype=torch.uint8, device="cuda")
+            dec.decode_batch_device(dev(sx), dev(sz), gx, gz, conv, llr, its)
+            torch.cuda.synchronize()
+            gx, gz, conv, llr, its = (host_of(x) for x in (gx, gz, conv, llr, its))
+        else:
+            gx, gz, conv, llr, its = dec.decode_batch_host(sx, sz, want_llr=want_llr)
+        ok = (same(gx, mgx) and same(gz, mgz) and same(conv, mconv) and (its is None or same(its, mits))
+              and (llr is None or same_bits(llr, mG)))
+        if not ok:
+            fail("pauli", f"kernel_variant {variant} {text}", hx_colptr=H.indptr, hx_rowval=H.indices, hx_shape=H.shape, hz=A, probs=probs,
+                 sx=sx, sz=sz, gx=gx, gz=gz, conv=conv, its=its, llr=llr, mgx=mgx, mgz=mgz, mconv=mconv, mits=mits, mG=mG)
+
+    on_every_tier("pauli", (1, 2), lambda v: ldpc.PauliMinSumDecoder(H, Hz, None, max_iters, pauli_probs=probs, alpha=alpha, clip=clip,
+                                                                     kernel_variant=v, check=False), go, text)
+
+
 # ---- the cases ---------------------------------------------------------------------------------------------------------
 last_note = t0
 for case in range(ncases):
@@ -532,6 +749,9 @@ for case in range(ncases):
     leg_osd(H, B, run)
     leg_trials(H, B, run)
     leg_css(B, run)
+    leg_layered(H, B, run)
+    leg_priors(H, B, run)
+    leg_pauli(H, B, run)
     if time.time() - last_note > 60:   # a silent GPU job looks hung to the runner
         last_note = time.time()
         print(f"... {case + 1} cases, {time.time() - t0:.0f} s", flush=True)
