@@ -4,7 +4,8 @@
  * host-side planning the team kernel relies on (ldpcdecoders.jl_amd/csrc/team_plan.cpp: team_plan_pure(),
  * team_rows_tables(), team_irr_tables()) and the tier / tile-width choice of the min-sum and relay decoders
  * (csrc/tile_plan.hpp) and the layers of the layered min-sum schedule (csrc/layer_plan.hpp).  Pure host code; no device
- * is needed or touched.
+ * is needed or touched.  Likewise the kernel, tile width and register buckets of the BP-OTS decoder (csrc/bpots_plan.hpp), and
+ * how a BP-OTS handle launched its last batch (host fields of the handle).
  */
 #ifndef LDPC_MI355X_DEBUG_H
 #define LDPC_MI355X_DEBUG_H
@@ -91,6 +92,30 @@ ldpc_status ldpc_debug_pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, 
    No reference counterpart. */
 ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t *layer_of,
                                   int32_t *K);
+
+/* The kernel ldpc_bpots_create chooses for a graph of s checks, n bits and nnz edges whose largest check has max_cdeg
+   edges and whose largest bit has max_bdeg -- csrc/bpots_plan.hpp ots_plan(), the function create calls.  A workgroup of
+   the LDS-resident kernel that decodes S syndromes at a time keeps
+       8 S nnz + 12 S n + 24 n + 32 s + 2112 + 24 * 512 + 2 (s + n + 2 + 2 nnz) + 32
+   bytes in dynamic LDS.  Kernel 2 (LDS-resident) with the largest S = 1 ... 64 for which that plus 8192 fits 76 KiB; else
+   with S = 1 where that fits 156 KiB (the large budget is only ever taken with S = 1).  Never for s, n or nnz >= 65535, a
+   check of more than 32 or a bit of more than 16 edges (`wide`), or force_node != 0 (what LDPC_BPOTS_FORCE_NODE sets in
+   the experiments build).  Else kernel 3 (node-parallel; LDS: round16(s + 3 n) + 4 s + 28 * 1024 + 64 bytes), unless the
+   graph is wide, force_node >= 2 or that plus 1024 is past 156 KiB: kernel 5 (unlimited, no dynamic LDS).  Out (each may be
+   NULL): the kernel as ldpc_bpots_kernel reports it; log2 S (-1 outside kernel 2); the dynamic LDS bytes of the choice;
+   the budget it fits in KiB (76 or 156; 0 outside kernel 2); the register buckets of the instantiation, dc = 8 or 32 and
+   dv = 4 or 16 (0 for kernel 5).  A negative argument: LDPC_ERR_INVALID_ARGUMENT; s, n or nnz >= 2^28: LDPC_ERR_UNSUPPORTED,
+   as create answers.  No reference counterpart. */
+ldpc_status ldpc_debug_bpots_plan(int64_t s, int64_t n, int64_t nnz, int32_t max_cdeg, int32_t max_bdeg, int32_t force_node,
+                                  int32_t *kernel, int32_t *logS, int64_t *lds_bytes, int32_t *budget_kib, int32_t *dc, int32_t *dv);
+
+/* How the most recent decode of a BP-OTS handle was launched; reads host fields of the handle only.  Out (each may be
+   NULL): path 0 = nothing launched (no decode yet, or max_iters == 0), 1 = the latency path of the host entry (one
+   workgroup per group, results through a host-mapped image), 2 = workgroups that take groups from a queue; groups = tiles
+   of S syndromes (kernel 2) or syndromes (kernels 3, 5) of the batch; the workgroups launched; chunk = groups a workgroup
+   takes from the queue at a time; per_cu = workgroups a CU holds as the occupancy query answered (kernel 2; else 0). */
+ldpc_status ldpc_debug_bpots_last_launch(const ldpc_bpots_decoder *dec, int32_t *path, int64_t *groups, int32_t *grid,
+                                         int32_t *chunk, int32_t *per_cu);
 
 /* Two builds of the library in one process (the product and the -DLDPC_EXPERIMENTS build: the Python host of the tests)
    must not run team grids on one device at the same time -- every member of a team has to be resident.  Each build

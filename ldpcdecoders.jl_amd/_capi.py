@@ -234,6 +234,8 @@ DEBUG_API = {
     "ldpc_debug_layer_plan": (i32, [i64, i64, vp, vp, vp, P(i32)]),
     "ldpc_debug_priors_tile_plan": (i32, [i64, i64, i64, i32, i32, P(i32), P(i32), P(i64)]),
     "ldpc_debug_pauli_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
+    "ldpc_debug_bpots_plan": (i32, [i64, i64, i64, i32, i32, i32, P(i32), P(i32), P(i64), P(i32), P(i32), P(i32)]),
+    "ldpc_debug_bpots_last_launch": (i32, [vp, P(i32), P(i64), P(i32), P(i32), P(i32)]),
 }
 EXPORTED_SYMBOLS = tuple(API)
 DEBUG_SYMBOLS = tuple(DEBUG_API)

@@ -2,9 +2,37 @@
 ldpc_bpots_* entry points; decode!/batchdecode! as in :225-340 and abstract_decoder.jl:31-48."""
 from __future__ import annotations
 
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+
 from . import _capi, _host
 from ._host import Handle, _pattern_of, csc_arrays, device_option, host_batch, stream_ptr, tensor_ptr
 from .decoder import AbstractDecoder
+
+
+BPOTSPlan = namedtuple("BPOTSPlan", "kernel S lds_bytes budget_kib DC DV")
+BPOTSLaunch = namedtuple("BPOTSLaunch", "path groups grid chunk per_cu")
+
+
+def bpots_plan(s, n, nnz, max_cdeg, max_bdeg, force_node=0, experiments=False) -> BPOTSPlan:
+    """What ldpc_bpots_create would choose for such a graph (ldpc_debug_bpots_plan; no device needed): the kernel (2, 3, 5),
+    S syndromes per workgroup (0 outside the LDS kernel), its dynamic LDS bytes, the budget in KiB (76, 156; 0 outside the
+    LDS kernel) and the register buckets DC, DV (0 for kernel 5)."""
+    L = _capi.lib(experiments)
+    k, logS, b, dc, dv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    nbytes = ctypes.c_int64()
+    _capi.check(L.ldpc_debug_bpots_plan(int(s), int(n), int(nnz), int(max_cdeg), int(max_bdeg), int(force_node), ctypes.byref(k),
+                                        ctypes.byref(logS), ctypes.byref(nbytes), ctypes.byref(b), ctypes.byref(dc), ctypes.byref(dv)), L)
+    return BPOTSPlan(k.value, 1 << logS.value if logS.value >= 0 else 0, nbytes.value, b.value, dc.value, dv.value)
+
+
+def bpots_plan_of(H, force_node=0, experiments=False) -> BPOTSPlan:
+    """bpots_plan of a parity-check matrix (anything BPOTSDecoder takes)."""
+    M = _pattern_of(H)
+    cdeg, bdeg = np.diff(M.tocsr().indptr), np.diff(M.tocsc().indptr)
+    return bpots_plan(M.shape[0], M.shape[1], M.nnz, int(cdeg.max(initial=0)), int(bdeg.max(initial=0)), force_node, experiments)
 
 
 class BPOTSDecoder(AbstractDecoder, Handle):
@@ -31,6 +59,14 @@ class BPOTSDecoder(AbstractDecoder, Handle):
     def kernel(self) -> int:
         """2 = LDS-resident kernel, 3 = node-parallel kernel with the messages in a global slot (ldpc_bpots_kernel)."""
         return int(self._L.ldpc_bpots_kernel(self._h))
+
+    def last_launch(self) -> BPOTSLaunch:
+        """How the most recent decode was launched (ldpc_debug_bpots_last_launch): path 0 none / 1 latency / 2 queue,
+        groups, workgroups, groups per queue ticket, workgroups per CU by the occupancy query (LDS kernel only)."""
+        path, grid, chunk, per_cu, groups = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        _capi.check(self._L.ldpc_debug_bpots_last_launch(self._h, ctypes.byref(path), ctypes.byref(groups), ctypes.byref(grid),
+                                                         ctypes.byref(chunk), ctypes.byref(per_cu)), self._L)
+        return BPOTSLaunch(path.value, groups.value, grid.value, chunk.value, per_cu.value)
 
     def decode_batch_host(self, syn_bs):
         """syn [B][s] uint8 -> (errors [B][n] u8 = best_decisions, converged [B] u8, iters [B] i32)."""

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bpots_plan.hpp"
 #include "portable_math.h"
 #include "latency_mode.hpp"
 
@@ -40,20 +41,7 @@ struct OtsParams {
     unsigned int done_ticket;
 };
 
-constexpr int kOtsThreads = 512;
-
-__host__ __device__ inline size_t ots_lds_bytes(int s, int n, int nnz, int S)
-{
-    size_t b = (size_t)nnz * S * 8;                 // messages (in place: cv <-> vc)
-    b += (size_t)n * S * 8;                         // llrs
-    b += (size_t)n * S * 4;                         // oscillation counters
-    b += 3 * (size_t)n * 8;                         // decision / prior / best masks
-    b += 4 * (size_t)s * 8;                         // sign, target, never, parity masks
-    b += 8 * 64 * 4 + 64;                           // per-syndrome words
-    b += (size_t)kOtsThreads * 24;                  // arg-min partials (one double key + three ints per thread)
-    b += 2 * ((size_t)s + 1 + (size_t)n + 1 + 2 * (size_t)nnz) + 32;   // graph (uint16)
-    return b;
-}
+// kOtsThreads, kOtsNodeThreads and the LDS sizes ots_lds_bytes() / ots_node_lds_bytes(): bpots_plan.hpp
 
 template <int DC, int DV>
 __global__ void __launch_bounds__(kOtsThreads)
@@ -337,12 +325,6 @@ struct OtsNodeParams {
     long long slot_doubles;
 };
 
-constexpr int kOtsNodeThreads = 1024;
-
-__host__ __device__ inline size_t ots_node_lds_bytes(int s, int n)
-{
-    return (((size_t)s + 3 * (size_t)n + 15) & ~(size_t)15) + 4 * (size_t)s + (size_t)kOtsNodeThreads * 28 + 64;
-}
 __host__ __device__ inline size_t ots_node_slot_doubles(int n, int nnz)
 {
     return (((size_t)nnz + (size_t)n + ((size_t)n + 1) / 2) + 63) & ~(size_t)63;

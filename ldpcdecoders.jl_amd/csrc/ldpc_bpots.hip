@@ -1,11 +1,14 @@
 // ldpc_bpots.hip -- host side of the BP-OTS decoder: the ldpc_bpots_* entry points
 // of include/ldpc_mi355x.h.  Replaces BPOTSDecoder / decode! / batchdecode! of
-// src/decoders/bpots_decoder.jl:39-115, 225-340.  Device code: bpots_kernels.hpp.
-// Two kernels: LDS-resident (S syndromes per workgroup; every code of the reference's BP-OTS tests) and, for graphs
+// src/decoders/bpots_decoder.jl:39-115, 225-340.  Device code: bpots_kernels.hpp; the choice of kernel, tile width and
+// launch path: bpots_plan.hpp (HIP-free; ldpc_debug_bpots_plan hands it to the CPU tests).
+// Three kernels: LDS-resident (S syndromes per workgroup; every code of the reference's BP-OTS tests); for graphs
 // whose messages do not fit a CU's LDS, node-parallel with the messages in a global slot (one workgroup per
-// syndrome).  Beyond s + 3n + 4s bytes of LDS (n ~ 30,000 for a rate-1/2 code), check degree 32 or bit degree 16:
-// LDPC_ERR_UNSUPPORTED.  No CPU path.
+// syndrome); and beyond s + 3n + 4s bytes of LDS (n ~ 23,600 for a rate-1/2 code), check degree 32 or bit degree 16, the
+// unlimited kernel with everything in the global slot and nodes of any degree.  Only a graph of 2^28 or more checks, bits or
+// edges answers LDPC_ERR_UNSUPPORTED.  No CPU path.
 #include "../../include/ldpc_mi355x.h"
+#include "../../include/ldpc_mi355x_debug.h"
 #include "bpots_kernels.hpp"
 #include "host_env.hpp"
 
@@ -25,7 +28,7 @@ using ldpc_detail::set_error;
 struct ldpc_bpots_decoder {
     int64_t s = 0, n = 0, nnz = 0, max_iters = 0, T = 9;
     double per = 0.0, C = 2.0;
-    int device = 0, num_cus = 0, logS = 0, max_cdeg = 0, max_bdeg = 0;
+    int device = 0, num_cus = 0, logS = 0, max_cdeg = 0, max_bdeg = 0, DC = 0, DV = 0;   // DC, DV: the plan's register buckets
     int *row_ptr = nullptr, *csc_row = nullptr, *col_ptr = nullptr, *csc2csr = nullptr;
     unsigned int *queue = nullptr;
     void *stage = nullptr;      // device staging for the host-pointer entry
@@ -42,6 +45,7 @@ struct ldpc_bpots_decoder {
                                 // register buckets): bpots_big_kernel, everything in the global slot, any degree
     double *node_ws = nullptr;  // [grid][slot] of the node kernel
     size_t node_ws_cap = 0;
+    OtsLaunch last;             // how the most recent decode was launched (ldpc_debug_bpots_last_launch)
     ~ldpc_bpots_decoder()
     {
         if (ldpc_detail::device_stalled(device)) return;   // (host_wait.hpp: nothing a stalled device may still use is freed)
@@ -54,18 +58,19 @@ struct ldpc_bpots_decoder {
 
 typedef void (*ots_kernel_t)(OtsParams, const int *, const int *, const int *, const int *);
 
-static ots_kernel_t pick_ots(int dc, int dv)
+// by the register buckets of the plan (bpots_plan.hpp: DC 8 or 32, DV 4 or 16)
+static ots_kernel_t pick_ots(int DC, int DV)
 {
-    if (dc <= 8) return dv <= 4 ? bpots_lds_kernel<8, 4> : bpots_lds_kernel<8, 16>;
-    return dv <= 4 ? bpots_lds_kernel<32, 4> : bpots_lds_kernel<32, 16>;
+    if (DC == 8) return DV == 4 ? bpots_lds_kernel<8, 4> : bpots_lds_kernel<8, 16>;
+    return DV == 4 ? bpots_lds_kernel<32, 4> : bpots_lds_kernel<32, 16>;
 }
 
 typedef void (*ots_node_kernel_t)(OtsNodeParams, const int *, const int *, const int *, const int *);
 
-static ots_node_kernel_t pick_ots_node(int dc, int dv)
+static ots_node_kernel_t pick_ots_node(int DC, int DV)
 {
-    if (dc <= 8) return dv <= 4 ? bpots_node_kernel<8, 4> : bpots_node_kernel<8, 16>;
-    return dv <= 4 ? bpots_node_kernel<32, 4> : bpots_node_kernel<32, 16>;
+    if (DC == 8) return DV == 4 ? bpots_node_kernel<8, 4> : bpots_node_kernel<8, 16>;
+    return DV == 4 ? bpots_node_kernel<32, 4> : bpots_node_kernel<32, 16>;
 }
 
 extern "C" {
@@ -90,27 +95,16 @@ ldpc_status ldpc_bpots_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
     d->device = device; d->num_cus = prop.multiProcessorCount;
     const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
     d->max_cdeg = g.max_cdeg; d->max_bdeg = g.max_bdeg;
-    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28)) {
+    // tests (experiments build, read at create): LDPC_BPOTS_FORCE_NODE = 1 sends small graphs through the node kernel, 2 through the unlimited one
+    const int force_node = exp_env("LDPC_BPOTS_FORCE_NODE") ? std::max(1, std::atoi(exp_env("LDPC_BPOTS_FORCE_NODE"))) : 0;
+    OtsPlan plan;   // bpots_plan.hpp: the kernel, the tile width and the buckets, from the sizes and largest degrees
+    if (!ots_plan(s, n, nnz, d->max_cdeg, d->max_bdeg, force_node, &plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "BP-OTS kernels: graph too large for 32-bit edge indexing");
     }
-    d->logS = -1;
-    // tests (experiments build, read at create): LDPC_BPOTS_FORCE_NODE = 1 sends small graphs through the node kernel, 2 through the unlimited one
-    const int force_node = exp_env("LDPC_BPOTS_FORCE_NODE") ? std::max(1, std::atoi(exp_env("LDPC_BPOTS_FORCE_NODE"))) : 0;
-    const bool wide = d->max_cdeg > 32 || d->max_bdeg > 16;   // beyond the register buckets of the two fast kernels
-    if (!force_node && !wide && nnz < 65535 && s < 65535 && n < 65535)   // (uint16 graph copies in LDS)
-        for (int l = 0; l <= 6; ++l) {
-            const size_t b = ots_lds_bytes((int)s, (int)n, (int)nnz, 1 << l) + 8192;
-            if (b <= (size_t)76 * 1024 || (d->logS < 0 && b <= (size_t)156 * 1024)) d->logS = l;
-            else if (b > (size_t)156 * 1024) break;
-        }
-    if (d->logS < 0) {
-        // beyond the LDS kernel: one workgroup per syndrome, messages in a global slot, bytes / parities in LDS
-        d->node_mode = true;
-        // ... and when even the bytes and parities of one syndrome do not fit the LDS, or nodes are wider than the register
-        // buckets: everything in the global slot, any degree (the reference's BPOTSDecoder has no limit either)
-        d->big_mode = wide || force_node >= 2 || ots_node_lds_bytes((int)s, (int)n) + 1024 > (size_t)156 * 1024;
-    }
+    d->logS = plan.logS; d->DC = plan.DC; d->DV = plan.DV;
+    d->node_mode = plan.kernel != 2;   // bpots_node_kernel: one workgroup per syndrome, messages in a global slot
+    d->big_mode = plan.kernel == 5;    // bpots_big_kernel: everything in the global slot, any degree
     using ldpc_detail::upload;
     if (!upload(&d->row_ptr, g.row_ptr) || !upload(&d->csc_row, g.csc_row) || !upload(&d->col_ptr, g.col_ptr) ||
         !upload(&d->csc2csr, g.csc2csr) ||
@@ -152,6 +146,7 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
     hipStream_t stream = (hipStream_t)stream_v;
     LDPC_HIP_TRY(hipSetDevice(d->device));
     if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
+    d->last = OtsLaunch();
     if (d->max_iters == 0) {   // the loop at :239 never runs: best_decisions = 0, converged = false
         if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
         LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
@@ -160,7 +155,7 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
     }
     if (d->node_mode) {
         if (batch > (1ll << 30)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-        ots_node_kernel_t nk = d->big_mode ? (ots_node_kernel_t)bpots_big_kernel : pick_ots_node(d->max_cdeg, d->max_bdeg);
+        ots_node_kernel_t nk = d->big_mode ? (ots_node_kernel_t)bpots_big_kernel : pick_ots_node(d->DC, d->DV);
         const size_t nlds = d->big_mode ? 0 : ots_node_lds_bytes((int)d->s, (int)d->n);
         if (!d->kernel_ready) {
             if (nlds) LDPC_HIP_TRY(hipFuncSetAttribute((const void *)nk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nlds));
@@ -182,9 +177,10 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
         hipLaunchKernelGGL(nk, dim3((unsigned)grid), dim3(kOtsNodeThreads), nlds, stream, np, (const int *)d->row_ptr,
                            (const int *)d->csc_row, (const int *)d->col_ptr, (const int *)d->csc2csr);
         LDPC_HIP_TRY(hipGetLastError());
+        d->last.path = 2; d->last.groups = batch; d->last.grid = grid; d->last.chunk = 1;
         return LDPC_OK;
     }
-    const int64_t ngroups = (batch + (1ll << d->logS) - 1) >> d->logS;
+    const int64_t ngroups = ots_groups(batch, d->logS);
     if (ngroups > (1ll << 30)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
     OtsParams p;
     p.s = (int)d->s; p.n = (int)d->n; p.nnz = (int)d->nnz; p.max_iters = (int)d->max_iters; p.T = (int)d->T;
@@ -193,7 +189,7 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
     p.C = d->C;
     p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.iters = d_iters; p.queue = d->queue;
     const size_t lds = ots_lds_bytes((int)d->s, (int)d->n, (int)d->nnz, 1 << d->logS);
-    ots_kernel_t k = pick_ots(d->max_cdeg, d->max_bdeg);
+    ots_kernel_t k = pick_ots(d->DC, d->DV);
     if (!d->kernel_ready) {
         LDPC_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         d->per_cu = ldpc_detail::blocks_per_cu((const void *)k, kOtsThreads, lds);
@@ -206,18 +202,49 @@ static ldpc_status bpots_decode_impl(ldpc_bpots_decoder *d, int64_t batch, const
         hipLaunchKernelGGL(k, dim3((unsigned)ngroups), dim3(kOtsThreads), lds, stream, p, (const int *)d->row_ptr,
                            (const int *)d->csc_row, (const int *)d->col_ptr, (const int *)d->csc2csr);
         LDPC_HIP_TRY(hipGetLastError());
+        d->last.path = 1; d->last.groups = ngroups; d->last.grid = (int)ngroups; d->last.chunk = 1; d->last.per_cu = d->per_cu;
         return LDPC_OK;
     }
-    const int grid = (int)std::min<int64_t>(ngroups, (int64_t)d->per_cu * d->num_cus);
-    p.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, ngroups / ((int64_t)grid * 16)));
+    int grid = 0;
+    ots_queue_launch(ngroups, d->per_cu, d->num_cus, &grid, &p.chunk);
     LDPC_HIP_TRY(hipMemsetAsync(d->queue, 0, 64, stream));
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kOtsThreads), lds, stream, p, (const int *)d->row_ptr,
                        (const int *)d->csc_row, (const int *)d->col_ptr, (const int *)d->csc2csr);
     LDPC_HIP_TRY(hipGetLastError());
+    d->last.path = 2; d->last.groups = ngroups; d->last.grid = grid; d->last.chunk = p.chunk; d->last.per_cu = d->per_cu;
     return LDPC_OK;
 }
 
 extern "C" {
+
+ldpc_status ldpc_debug_bpots_plan(int64_t s, int64_t n, int64_t nnz, int32_t max_cdeg, int32_t max_bdeg, int32_t force_node,
+                                  int32_t *kernel, int32_t *logS, int64_t *lds_bytes, int32_t *budget_kib, int32_t *dc, int32_t *dv)
+{
+    if (s < 0 || n < 0 || nnz < 0 || max_cdeg < 0 || max_bdeg < 0 || force_node < 0)
+        return set_error(LDPC_ERR_INVALID_ARGUMENT, "ldpc_debug_bpots_plan: negative size, degree or force_node");
+    OtsPlan plan;
+    if (!ots_plan(s, n, nnz, max_cdeg, max_bdeg, force_node, &plan))
+        return set_error(LDPC_ERR_UNSUPPORTED, "BP-OTS kernels: graph too large for 32-bit edge indexing");
+    if (kernel) *kernel = plan.kernel;
+    if (logS) *logS = plan.logS;
+    if (lds_bytes) *lds_bytes = (int64_t)plan.lds_bytes;
+    if (budget_kib) *budget_kib = plan.budget_kib;
+    if (dc) *dc = plan.DC;
+    if (dv) *dv = plan.DV;
+    return LDPC_OK;
+}
+
+ldpc_status ldpc_debug_bpots_last_launch(const ldpc_bpots_decoder *d, int32_t *path, int64_t *groups, int32_t *grid, int32_t *chunk,
+                                         int32_t *per_cu)
+{
+    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
+    if (path) *path = d->last.path;
+    if (groups) *groups = d->last.groups;
+    if (grid) *grid = d->last.grid;
+    if (chunk) *chunk = d->last.chunk;
+    if (per_cu) *per_cu = d->last.per_cu;
+    return LDPC_OK;
+}
 
 ldpc_status ldpc_bpots_decode_batch_device(ldpc_bpots_decoder *d, int64_t batch, const uint8_t *d_syn, uint8_t *d_err,
                                            uint8_t *d_conv, int32_t *d_iters, void *stream_v)
@@ -238,11 +265,10 @@ ldpc_status ldpc_bpots_decode_batch(ldpc_bpots_decoder *d, int64_t batch, const 
     image.take(B * s);
     const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4), total = image.at;
     static const bool lat_off = exp_env("LDPC_NO_LATENCY_PATH") != nullptr;
-    const int64_t lat_groups = d->node_mode ? batch : (batch + (1ll << d->logS) - 1) >> d->logS;
-    if (!d->node_mode && !lat_off && total <= ((size_t)256 << 10) && d->max_iters > 0 && lat_groups <= 2 * (int64_t)d->num_cus) {
+    if (!d->node_mode && !lat_off && d->max_iters > 0 && ots_latency_ok(total, ots_groups(batch, d->logS), d->num_cus)) {
         const size_t hdr = 256;
         if (!d->lat_pin) {
-            const size_t cap = hdr + ((size_t)256 << 10);
+            const size_t cap = hdr + kOtsLatencyImage;
             LDPC_HIP_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
             std::memset(d->lat_pin, 0, hdr);
             LDPC_HIP_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));

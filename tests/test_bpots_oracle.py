@@ -155,3 +155,28 @@ def test_independent_libm_oracle_and_the_band_two_correct_libms_live_in():
     S = ldpc.codes.syndromes_of(HX, ldpc.codes.random_errors(72, 1500, 0.04, seed=3))
     d, oa, ob = _band(HX, 0.04, 50, 9, 2.0, S)
     assert d <= 0.01 and oa >= 0.99 and ob >= 0.99
+
+
+def test_c_oracle_equals_python_restatement_at_the_parameter_edges():
+    """tests/test_gpu_bpots_paths.py holds the GPU against the C oracle at per in {1e-6, 0.75 (prior exactly 0), 0.9, 1
+    (negative prior)} x T in {1, max_iters + 5} x C in {0, 2}.  Here the oracle itself is held against its second witness
+    on the same graphs, parameters and syndromes, every one of them (all-zero, ordinary, entries of 2 and 3), and on a graph
+    without edges."""
+    import bpots_cases as bc
+
+    for name, (H, syn) in bc.param_graphs().items():
+        assert (syn == 2).any() and (name == "bb72" or (syn == 3).any()) and not syn[0].any()
+        if name == "irregular":
+            assert not H[4].any() and not H[:, 7].any()       # an empty check, an empty bit
+        for per, T, C in bc.param_cases():
+            pool = bc.param_pool(name, per, T, C)
+            for b in range(len(syn)):          # every syndrome the GPU test decodes
+                py = DensePyBPOTS(H.tolist(), per, bc.PARAM_ITERS, T, C)
+                perr, pconv = py.decode(syn[b].tolist())
+                assert perr == pool.err[b].tolist() and pconv == bool(pool.conv[b]) and py.iters == pool.its[b], (name, per, T, C, b)
+    H = np.zeros((3, 5), dtype=np.uint8)
+    for row in ([0, 0, 0], [1, 0, 0], [0, 2, 0]):
+        err, conv, its = _oracle(H, 0.05, 7, 2, 2.0).batchdecode(np.array([row], dtype=np.uint8))
+        py = DensePyBPOTS(H.tolist(), 0.05, 7, 2, 2.0)
+        perr, pconv = py.decode(row)
+        assert perr == err[0].tolist() == [0] * 5 and pconv == bool(conv[0]) == (not any(row)) and py.iters == its[0] == (7 if any(row) else 1)

@@ -17,7 +17,10 @@ LAYERED = re.compile(r"^   layered .* max_iters (\d+) .* layers (\d+) smallest_l
 PRIORS = re.compile(r"^   priors (flooding|layered) (floats|given) .* max_iters (\d+) .* nonfinite_rows (\d+)$")
 PAULI = re.compile(r"^   pauli Hz \((\d+), (\d+)\) B (\d+) .* max_iters (\d+) .* uniform=(True|False) (sampled|arbitrary) syndromes "
                    r"hx<=32 (\d+) hx33-64 (\d+) hx>64 (\d+) hx_empty (\d+) hz<=32 (\d+) hz33-64 (\d+) hz>64 (\d+) hz_empty (\d+)$")
-OLD_LEGS, NEW_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css"), ("layered", "priors", "pauli")
+# the leg of the third generator: the three BP-OTS kernels; S, DC, DV as ldpc_debug_bpots_plan answers for the unforced handle
+BPOTS = re.compile(r"^   bpots per (\S+) T (\d+) C (\S+) max_iters (\d+) batch (\d+) (device|host) entry iters=(True|False) "
+                   r"edges (\d+) kernel ([235]) S (\d+) DC (\d+) DV (\d+)$")
+OLD_LEGS, NEW_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css"), ("layered", "priors", "pauli", "bpots")
 
 
 def _tool(args, **env):
@@ -52,6 +55,14 @@ def coverage(listing):
                 ("pauli: empty Hx check", hxe > 0), ("pauli: empty Hz check", hze > 0), ("pauli: batch 1", B == 1),
                 ("pauli: batch 65", B == 65), ("pauli: one triple for every qubit", uniform),
                 ("pauli: arbitrary syndromes", syndromes == "arbitrary")) if yes}
+        m = BPOTS.match(line)
+        if m and int(m.group(4)) > 0:
+            per, T, kernel, S, DC, DV = float(m.group(1)), int(m.group(2)), int(m.group(9)), int(m.group(10)), int(m.group(11)), int(m.group(12))
+            assert int(m.group(5)) <= 65 and (kernel == 2) == (S > 0) and (kernel == 5) == (DC == 0) == (DV == 0)
+            have |= {name for name, yes in (
+                (f"bpots: S = {S}", kernel == 2), (f"bpots: DC {DC}", kernel == 2), (f"bpots: DV {DV}", kernel == 2),
+                ("bpots: T = 1", T == 1), ("bpots: per = 0.75", per == 0.75), ("bpots: a wide graph", kernel == 5),
+                ("bpots: a graph without edges", int(m.group(8)) == 0)) if yes}
         m = CASE.match(line)
         if not m:
             continue
@@ -71,7 +82,12 @@ WANTED = {"check of degree <= 32", "check of degree 33 ... 64", "check of degree
           "priors: a non-finite row",
           "pauli: Hz check of degree 33 ... 64", "pauli: Hz check of degree > 64", "pauli: Hx check of degree 33 ... 64",
           "pauli: Hx check of degree > 64", "pauli: empty Hx check", "pauli: empty Hz check", "pauli: batch 1", "pauli: batch 65",
-          "pauli: one triple for every qubit", "pauli: arbitrary syndromes"}
+          "pauli: one triple for every qubit", "pauli: arbitrary syndromes",
+          # BP-OTS: each register bucket, the bias step in every iteration, a prior of exactly 0, a graph that takes kernel 5 only
+          "bpots: DC 8", "bpots: DC 32", "bpots: DV 4", "bpots: DV 16", "bpots: T = 1", "bpots: per = 0.75", "bpots: a wide graph"}
+# A graph without edges is NOT among them: the graphs are the cases' own, drawn from the first generator, whose stream the
+# older legs own; the smallest graph of the committed seeds has 7 edges.  tests/test_gpu_bpots_paths.py
+# (test_a_graph_without_edges) pins that shape instead.
 
 
 def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_the_boundary_shapes():
@@ -86,10 +102,13 @@ def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_th
         for leg in OLD_LEGS + NEW_LEGS:
             assert len([ln for ln in first.splitlines() if ln.startswith(f"   {leg} ")]) == CASES, leg
         # ... and every line of a new leg is one that coverage() can read
-        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI)):
+        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS)):
             assert all(pattern.match(ln) for ln in first.splitlines() if ln.startswith(f"   {leg} ")), leg
         have |= coverage(first)
-    assert have == WANTED, f"the committed seeds never draw: {sorted(WANTED - have)}"
+    widths = {name for name in have if name.startswith("bpots: S = ")}
+    assert len(widths) >= 3, f"the committed seeds reach only the BP-OTS tile widths {sorted(widths)}"
+    assert "bpots: a graph without edges" not in have       # (see WANTED: if a seed ever draws one, say so there)
+    assert have - widths == WANTED, f"the committed seeds never draw: {sorted(WANTED - have)}"
 
 
 def test_a_window_of_cases_draws_what_the_whole_run_draws():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised model-parity fuzz (GPU box) of the kernels that tools/fuzz_parity.py does not reach: the bit-flip decoder,
 min-sum (flooding and layered schedule, shared and per-syndrome priors), relay min-sum, the joint X/Z (Pauli) min-sum, the
-device OSD step, and the one-matrix and CSS trial steps.  Random Tanner graphs (irregular with empty and heavy nodes and
+device OSD step, the one-matrix and CSS trial steps, and the three BP-OTS kernels at parameters fuzz_parity.py leaves out.  Random Tanner graphs (irregular with empty and heavy nodes and
 sizes around the word boundaries, or small Gallager codes), ragged batches, every `kernel_variant` that create accepts,
 every result compared in every element with the numpy models of tests/ (the min-sum family and relay: the LLR bit patterns
 too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
@@ -14,12 +14,16 @@ its unlimited tier.  The leg in hand is kept in fuzz_models_current.txt and, on 
 fuzz_models_failure.npz, both in the directory FUZZ_OUT (default: fuzz_out/ in the repository root, which git ignores).
 
 The legs `layered`, `priors` and `pauli` draw from a generator of their own (seeded [seed, 1]): the six older legs decode for
-a seed what they decoded before those three existed.
+a seed what they decoded before those three existed.  The leg `bpots` draws from a third (seeded [seed, 2]) for the same
+reason.  BP-OTS has no kernel_variant: its tiers are the kernels 2 (LDS-resident), 3 (node-parallel) and 5 (unlimited), reached
+through LDPC_BPOTS_FORCE_NODE unset, 1 and 2 (experiments build); a graph with a check of more than 32 or a bit of more than
+16 edges runs as kernel 5 only and the other two count as skipped.  Its model is the C oracle (oracle/bpots_oracle.c), its
+batch is capped at 65.
 
-Model seconds of 40 cases on one CPU core (the `model seconds` line of FUZZ_MODEL_ONLY=1), the six older legs together against
-the three of the second generator:
-  seed 20: bitflip 0.35, minsum 1.60, relay 3.40, osd 0.62, trials 0.04, css 0.05 (6.1 s); layered 0.99, priors 1.27, pauli 1.61 (3.9 s)
-  seed 21: bitflip 0.18, minsum 1.08, relay 2.79, osd 0.36, trials 0.04, css 0.04 (4.5 s); layered 0.79, priors 0.81, pauli 1.00 (2.6 s)"""
+Model seconds of 40 cases on one CPU core (the `model seconds` line of FUZZ_MODEL_ONLY=1, all ten legs in one run): the six older
+legs, the three of the second generator, and the BP-OTS oracle (C, not numpy):
+  seed 20: bitflip 0.43, minsum 2.64, relay 5.82, osd 0.84, trials 0.06, css 0.08 (9.9 s); layered 1.68, priors 2.05, pauli 2.59 (6.3 s); bpots 2.04
+  seed 21: bitflip 0.34, minsum 1.92, relay 4.96, osd 0.69, trials 0.06, css 0.08 (8.1 s); layered 1.56, priors 1.60, pauli 1.84 (5.0 s); bpots 1.42"""
 import os
 import sys
 import time
@@ -41,6 +45,7 @@ from minsum_model import MinSumModel, llr_of_probs  # noqa: E402
 from osd_model import osd_model_postprocess  # noqa: E402
 from pauli_model import PauliMinSumModel, pauli_priors  # noqa: E402
 from relay_model import RelayModel  # noqa: E402
+from oracle import BPOTSOracle  # noqa: E402
 
 DRY = os.environ.get("FUZZ_DRY") == "1"
 FROM, TO = int(os.environ.get("FUZZ_FROM", "0")), int(os.environ.get("FUZZ_TO", str(1 << 60)))
@@ -52,7 +57,7 @@ UNSUPPORTED = 5
 # tiers a component can take here; the last one is its unlimited tier.  (Bit-flip tier 4, the 64-bit votes, needs
 # max_iters * max bit degree >= 2^31 and is held by test_unlimited_tier_with_64_bit_votes.)
 TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2),
-         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2)}
+         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2), "bpots": (2, 3, 5)}
 BOUNDARY = (31, 32, 33, 63, 64, 65, 127, 128, 129)
 
 if GPU:
@@ -68,6 +73,7 @@ ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
 rng2 = np.random.default_rng([seed, 1])      # the layered, priors and pauli legs: never `rng`, whose stream the older legs own
+rng3 = np.random.default_rng([seed, 2])      # the bpots leg
 t0 = time.time()
 ran = {c: set() for c in TIERS}          # tiers that decoded
 legs_run = {c: 0 for c in TIERS}
@@ -732,6 +738,68 @@ def leg_pauli(H, B, run):
                                                                      kernel_variant=v, check=False), go, text)
 
 
+# ---- the leg of the third generator ------------------------------------------------------------------------------------
+BPOTS_BATCH_CAP = 65      # (the oracle costs about 0.28 us per edge, iteration and syndrome)
+
+
+def leg_bpots(H, B, run):
+    """The three BP-OTS kernels on the case's graph (graphs without edges included) against the C oracle: errors, flags and
+    iteration counts in every element."""
+    g = rng3
+    s, n = H.shape
+    per = float(g.choice([1e-6, 0.01, 0.05, 0.2, 0.75, 0.9]))
+    T, C = int(g.choice([1, 2, 3, 9])), float(g.choice([0.0, 1.0, 2.0, 3.0]))
+    max_iters = int(g.choice([0, 1, 3, 10]))
+    device_entry, want_iters = bool(g.random() < 0.5), bool(g.random() < 0.5)
+    Bo = min(B, BPOTS_BATCH_CAP)
+    syn = draw_syndromes(H, Bo, g)
+    if g.random() < 0.25:
+        hit = g.random(syn.shape) < 0.05
+        syn[hit] = g.integers(2, 4, size=int(hit.sum()))
+    plans = [ldpc.bpots.bpots_plan_of(H, force_node=f) for f in (0, 1, 2)]      # host code: no device needed
+    text = (f"per {per} T {T} C {C} max_iters {max_iters} batch {Bo} {'device' if device_entry else 'host'} entry iters={want_iters} "
+            f"edges {H.nnz} kernel {plans[0].kernel} S {plans[0].S} DC {plans[0].DC} DV {plans[0].DV}")
+    if DRY or VERBOSE:
+        print(f"   bpots {text}", flush=True)
+    if not run:
+        return
+    werr, wconv, wits = timed_model("bpots", lambda: BPOTSOracle((H.indptr, H.indices), H.shape, per, max_iters, T, C).batchdecode(syn))
+    if not GPU:
+        return
+    done = set()
+    for force, plan in enumerate(plans):
+        if plan.kernel in done:          # a wide graph: LDPC_BPOTS_FORCE_NODE changes nothing
+            skipped["bpots"] += 1
+            continue
+        note("bpots", f"LDPC_BPOTS_FORCE_NODE {force} {text}")
+        if force:
+            os.environ["LDPC_BPOTS_FORCE_NODE"] = str(force)
+        try:
+            dec = ldpc.BPOTSDecoder(H, per, max_iters, T=T, C=C)
+        finally:
+            os.environ.pop("LDPC_BPOTS_FORCE_NODE", None)
+        if dec.kernel != plan.kernel:
+            fail("bpots", f"LDPC_BPOTS_FORCE_NODE {force} gave kernel {dec.kernel}, the plan says {plan.kernel} {text}")
+        if device_entry:
+            err, conv, _, its = device_outputs(Bo, n, 1, False, want_iters)
+            dec.decode_batch_device(dev(syn), err, conv, its)
+            torch.cuda.synchronize()
+            err, conv, its = (host_of(x) for x in (err, conv, its))
+        else:
+            err, conv, its = dec.decode_batch_host(syn)
+        launch = dec.last_launch()
+        dec.close()
+        if not (same(err, werr) and same(conv, wconv) and (its is None or same(its, wits))):
+            fail("bpots", f"kernel {plan.kernel} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, err=err, conv=conv,
+                 its=its, werr=werr, wconv=wconv, wits=wits)
+        if (launch.path == 0) != (max_iters == 0):
+            fail("bpots", f"kernel {plan.kernel}: launch path {launch.path} {text}")
+        done.add(plan.kernel)
+        if launch.path != 0:             # max_iters == 0 launches no kernel: compared, but no tier has run
+            ran["bpots"].add(plan.kernel)
+            legs_run["bpots"] += 1
+
+
 # ---- the cases ---------------------------------------------------------------------------------------------------------
 last_note = t0
 for case in range(ncases):
@@ -752,6 +820,7 @@ for case in range(ncases):
     leg_layered(H, B, run)
     leg_priors(H, B, run)
     leg_pauli(H, B, run)
+    leg_bpots(H, B, run)
     if time.time() - last_note > 60:   # a silent GPU job looks hung to the runner
         last_note = time.time()
         print(f"... {case + 1} cases, {time.time() - t0:.0f} s", flush=True)
