@@ -995,6 +995,82 @@ ldpc_status ldpc_relay_decode_batch_device(ldpc_relay_decoder *dec, int64_t batc
                                            int32_t *d_solutions, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Guided-decimation min-sum decoder (belief propagation with guided decimation, BPGD): normalised min-sum in ROUNDS of
+ * round_iters iterations; a round that ends without a solution hard-fixes ("decimates", "pins") the most reliable
+ * undecided bit, keeps every message and goes on.  For the degenerate, short-cycle graphs of quantum LDPC codes, where
+ * plain min-sum stalls: no elimination, no table of random strengths, one parameter (max_decimations).  Like
+ * ldpc_minsum_* it has no division and no transcendental function, so THE RULE below has one legal outcome in IEEE
+ * binary32 and a numpy model equals the device in every bit.
+ *
+ * Inputs.  H, channel_llr[n], alpha, clip: as ldpc_minsum_create takes them.  round_iters T >= 0; max_decimations Dmax
+ * with 0 <= Dmax <= n; T * (Dmax + 1) at most INT32_MAX; pin = 2.0f * clip must be finite.  A syndrome entry that is not
+ * 0 counts as 1.
+ *
+ * THE RULE.  All arithmetic is binary32, every operation rounded once (no fused multiply-add), subnormals kept.
+ * State per syndrome: L[j], initially channel_llr[j]; the check-to-bit messages c[i][j], initially +0; the set D of
+ * decimated bits, initially empty; a pending bit j*, initially none, with its sign; iters = 0.
+ * For t = 1, 2, ...:
+ *   1. Check sweep: step 1 of the min-sum rule above on L, unchanged.  A pinned bit enters like any other: because
+ *      |c| <= alpha * clip <= clip its b_k is exactly +-clip, which is never < m1, so it gives its sign to par and nothing
+ *      to the minima.
+ *   2. Bit sweep.  The pending bit, if there is one:  L[j*] = negative ? -pin : +pin, and nothing is pending any more.
+ *      For every other j not in D:  L[j] = channel_llr[j] + c[i_0][j] + c[i_1][j] + ... from the left, checks ascending
+ *      (the min-sum rule).  For every other j in D, L[j] is not written.  Then err[j] = (L[j] <= 0) and iters = t.
+ *   3. Test.  If H * err == syndrome (an empty check is matched only by a 0 entry): converged = 1, the syndrome stops.
+ *   4. End of a round, only when t is a multiple of T and the test failed.  If |D| == Dmax (which covers |D| == n):
+ *      converged = 0, the syndrome stops.  Otherwise j* = the j not in D with the largest |L[j]|, the lowest j on a tie
+ *      (the maximum over (magnitude, -index), so any reduction order is legal); negative = (L[j*] <= 0); j* enters D and
+ *      is pending.  The messages are kept.  A bit of degree 0 may be chosen like any other.
+ * The order is part of the rule: check sweep t + 1 still reads L[j*] as bit sweep t left it, and the pin stands in L
+ * from bit sweep t + 1 on.  (A kernel whose stop test of iteration t rides on check sweep t + 1 therefore decimates
+ * between that check sweep and the bit sweep after it, and needs no sweep of its own for the test.)  A syndrome never
+ * stops with a bit pending: iteration t + 1 always follows a decimation.
+ *
+ * Outputs.  errors [batch][n] uint8 = (L <= 0); converged [batch] uint8; llr [batch][n] DOUBLE (may be NULL): L widened
+ * exactly, so a pinned bit reads +-pin; iters [batch] int32 (may be NULL); decimated [batch] int32 (may be NULL): |D|
+ * when the syndrome stopped.  round_iters = 0: zeros everywhere (converged = 0, llr = 0, iters = 0, decimated = 0), as
+ * max_iters = 0 of min-sum.  batch = 0: LDPC_OK, nothing touched.
+ *
+ * Consequence.  With max_decimations = 0 every output equals ldpc_minsum_* (flooding) with max_iters = round_iters in
+ * every bit, and decimated = 0.
+ *
+ * ldpc_decim_kernel: 1 = on-chip (L, the check records, D and the syndromes of the S <= 64 syndromes a workgroup holds
+ * live in LDS for the whole decode; needs (4 (n + record words + ceil(n / 32)) + s) bytes <= 159 KiB for one syndrome,
+ * records as in ldpc_minsum_kernel); 2 = unlimited (tiles of 64 syndromes in a workspace the handle owns, sized by the
+ * resident workgroups; any H with nnz < 2^28); 0 for NULL.  options->kernel_variant 0 = by size, 1 / 2 force a tier (1
+ * where the state does not fit: LDPC_ERR_UNSUPPORTED).  A tile ends with its last syndrome, after at most
+ * T * (Dmax + 1) iterations.
+ *
+ * ldpc_decim_tile_syndromes, ldpc_decim_last_grid: as ldpc_minsum_tile_syndromes and ldpc_minsum_last_grid -- the S of
+ * the handle, and the workgroups of its most recent kernel launch (0 before any launch); 0 for NULL.
+ *
+ * ldpc_decim_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for a NULL or non-finite
+ * channel_llr, a negative round_iters, max_decimations outside 0 .. n, round_iters * (max_decimations + 1) beyond
+ * INT32_MAX, a clip whose double is not finite, alpha or clip outside their min-sum ranges, a kernel_variant outside
+ * 0..2 and a pattern ldpc_bp_create rejects; without a device LDPC_ERR_NO_DEVICE; s, n or nnz of 2^28 or more:
+ * LDPC_ERR_UNSUPPORTED.  The decode entries behave as those of ldpc_minsum_*: ldpc_decim_decode_batch takes HOST buffers
+ * and is synchronous (its wait is bounded by ldpc_set_wait_limit_ms); ldpc_decim_decode_batch_device takes DEVICE
+ * pointers and is asynchronous on `stream`; calls on one handle run in call order whatever streams they are given.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_decim_decoder ldpc_decim_decoder;
+
+/* Optional; pass NULL to ldpc_decim_create for defaults.  A zeroed struct means defaults too, except `device` (0 is
+ * device 0; -1 = the current one): alpha = 0 / clip = 0 select 0.75 / 1.0e6f. */
+typedef struct ldpc_decim_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    float alpha;             /* normalisation factor in (0, 1]; 0 = default 0.75 */
+    float clip;              /* clamp of the bit-to-check values, finite, > 0, 2 * clip finite; 0 = default 1.0e6f */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_decim_kernel */
+    int32_t reserved[12];
+} ldpc_decim_options;
+
+/* The seven ldpc_decim_* functions are declared in ldpc_mi355x_decim.h, which this header includes here: this file and
+ * ldpc_mi355x_debug.h keep the functions they declared before the section was added. */
+#include "ldpc_mi355x_decim.h"
+
+/* ------------------------------------------------------------------------
  * Sliding-window decoding: the step between two windows.  A model H (D detectors x N mechanisms, zero-based CSC) too
  * long to decode in one piece is decoded window by window: window k sees the detectors det_k and the mechanisms mech_k,
  * any decoder of this library decodes its syndromes against H[det_k, mech_k], the first mechanisms of its guess --

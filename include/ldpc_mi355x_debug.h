@@ -84,6 +84,12 @@ ldpc_status ldpc_debug_priors_tile_plan(int64_t s, int64_t n, int64_t rec_words,
 ldpc_status ldpc_debug_pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, int32_t kernel_variant, int32_t *tier,
                                        int32_t *tile_syndromes, int64_t *state_bytes);
 
+/* The plan of a guided-decimation min-sum handle -- csrc/tile_plan.hpp decim_tile_plan(), the function
+   ldpc_decim_create calls.  A tile of S syndromes has a state of  S (4 (n + rec_words + ceil(n / 32)) + s)  bytes (L, the
+   check records, a bit per decimated bit, the syndromes), rounded up to 256, and the policy of ldpc_debug_tile_plan runs
+   over that size.  Out and statuses as there.  No reference counterpart. */
+#include "ldpc_mi355x_decim_debug.h"   /* (declares it: this header keeps the hooks it declared before) */
+
 /* The layers ldpc_minsum_create gives a handle of the layered schedule (options->schedule = 1; THE LAYERED RULE of
    include/ldpc_mi355x.h) -- csrc/layer_plan.hpp layer_plan_build(), the function create calls, followed by the same
    verification (no two checks of a layer share a bit, every non-empty check in exactly one layer).  H as the zero-based

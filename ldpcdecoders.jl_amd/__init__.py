@@ -28,6 +28,7 @@ from .bpots import BPOTSDecoder  # noqa: F401,E402
 from .bitflip import BitFlipDecoder, BitFlipScratchSpace  # noqa: F401,E402
 from .minsum import MinSumDecoder, MinSumScratchSpace  # noqa: F401,E402
 from .relay import RelayMinSumDecoder  # noqa: F401,E402
+from .decim import DecimatedMinSumDecoder  # noqa: F401,E402
 from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 from .css_trials import CSSTrialResult, CSSTrials, conditional_probs, run_css_joint_trials, run_css_trials  # noqa: F401,E402
 from .pauli import PauliMinSumDecoder  # noqa: F401,E402
@@ -39,7 +40,7 @@ __all__ = [
     "decode_", "batchdecode_", "reset_", "AbstractDecoder", "BeliefPropagationDecoder",
     "BeliefPropagationScratchSpace", "parity_check_matrix", "save_pcm", "load_pcm",
     "LdpcError", "build", "codes", "syndrome_bytes", "BitMatrix",
-    "MinSumDecoder", "MinSumScratchSpace", "RelayMinSumDecoder",
+    "MinSumDecoder", "MinSumScratchSpace", "RelayMinSumDecoder", "DecimatedMinSumDecoder",
     "Trials", "TrialResult", "run_trials",
     "CSSTrials", "CSSTrialResult", "run_css_trials", "run_css_joint_trials", "conditional_probs", "PauliMinSumDecoder",
     "DetectorErrorModel", "phenomenological", "run_dem_trials",

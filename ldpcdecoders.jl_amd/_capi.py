@@ -94,6 +94,14 @@ class RelayOptions(ctypes.Structure):
     ]
 
 
+class DecimOptions(ctypes.Structure):
+    """ldpc_decim_options: alpha = 0 / clip = 0 select the defaults (0.75, 1e6)."""
+    _fields_ = [
+        ("device", ctypes.c_int32), ("alpha", ctypes.c_float), ("clip", ctypes.c_float),
+        ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 12),
+    ]
+
+
 class PauliMinSumOptions(ctypes.Structure):
     """ldpc_pauli_minsum_options: alpha = 0 / clip = 0 select the defaults (0.75, 1e6)."""
     _fields_ = [
@@ -237,8 +245,25 @@ DEBUG_API = {
     "ldpc_debug_bpots_plan": (i32, [i64, i64, i64, i32, i32, i32, P(i32), P(i32), P(i64), P(i32), P(i32), P(i32)]),
     "ldpc_debug_bpots_last_launch": (i32, [vp, P(i32), P(i64), P(i32), P(i32), P(i32)]),
 }
+# The guided-decimation min-sum decoder: include/ldpc_mi355x_decim.h (a part of ldpc_mi355x.h) and its test hook,
+# include/ldpc_mi355x_decim_debug.h (a part of ldpc_mi355x_debug.h).  The two tables above stay what the two headers
+# themselves declare; these follow the same conventions and are bound with them.
+DECIM_API = {
+    "ldpc_decim_create": (i32, [i64, i64, i64, vp, vp, vp, i64, i64, P(DecimOptions), P(vp)]),
+    "ldpc_decim_destroy": (i32, [vp]),
+    "ldpc_decim_kernel": (i32, [vp]),
+    "ldpc_decim_tile_syndromes": (i32, [vp]),
+    "ldpc_decim_last_grid": (i32, [vp]),
+    "ldpc_decim_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_decim_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+}
+DECIM_DEBUG_API = {
+    "ldpc_debug_decim_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
+}
 EXPORTED_SYMBOLS = tuple(API)
 DEBUG_SYMBOLS = tuple(DEBUG_API)
+DECIM_SYMBOLS = tuple(DECIM_API)
+DECIM_DEBUG_SYMBOLS = tuple(DECIM_DEBUG_API)
 
 
 def build(force: bool = False) -> str:
@@ -276,7 +301,7 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
                            "or `make -C ldpcdecoders.jl_amd/csrc`. There is no CPU fallback.")
     _one_hip_runtime()
     L = ctypes.CDLL(path)
-    for group in (API, DEBUG_API):
+    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -1,5 +1,5 @@
 // tile_host.hpp -- the host scaffolding that the decoders of the min-sum family share (ldpc_minsum.hip, ldpc_relay.hip,
-// ldpc_pauli.hip) on top of host_common.hpp: a syndrome in a lane, tiles of S <= 64 syndromes on a persistent grid, the
+// ldpc_pauli.hip, ldpc_decim.hip) on top of host_common.hpp: a syndrome in a lane, tiles of S <= 64 syndromes on a persistent grid, the
 // state of a tile in LDS (tier 1) or in a workspace slot (tier 2; the plan: tile_plan.hpp).  Here, once each: the constants
 // of the design, the validation of the common options, the part of a handle that every launch needs (TileHost), the
 // geometry of a launch (tile_geometry, the one place the grid rule lives), the host-pointer form of an entry

@@ -1,5 +1,6 @@
-// tile_plan.hpp -- what the host of every decoder of the min-sum family (ldpc_minsum.hip, ldpc_relay.hip, ldpc_pauli.hip;
-// device code: minsum_kernels.hpp, layered_kernels.hpp, relay_kernels.hpp, pauli_kernels.hpp) derives from a graph's sizes
+// tile_plan.hpp -- what the host of every decoder of the min-sum family (ldpc_minsum.hip, ldpc_relay.hip, ldpc_pauli.hip,
+// ldpc_decim.hip; device code: minsum_kernels.hpp, layered_kernels.hpp, relay_kernels.hpp, pauli_kernels.hpp,
+// decim_kernels.hpp) derives from a graph's sizes
 // alone: the sizes of a tile's state, the tier and the tile width chosen from them (the policy: plan_tiles(), the one
 // place it is stated) and the check records of a Tanner graph (ms_records(), the one place they are laid out).  Pure host
 // code over the standard library -- no HIP, no decoder handle, no environment -- so that it builds with a plain C++
@@ -93,6 +94,20 @@ inline size_t pauli_state_bytes(long long s, long long n, long long rec_words, i
 inline bool pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, int variant, TilePlan *out)
 {
     return plan_tiles([=](int S) { return pauli_state_bytes(s, n, rec_words, S); }, variant, out);
+}
+
+// ---- the guided-decimation min-sum decoder ------------------------------------------------------------------------------------
+// bytes of a decimation tile's state: S lanes of (n + rec_words + ceil(n / 32)) words -- L (the pins live in it), the check
+// records and the set D of decimated bits, a bit each -- and s syndrome bytes, rounded up to 256
+inline size_t decim_state_bytes(long long s, long long n, long long rec_words, int S)
+{
+    return (((size_t)(n + rec_words + ((n + 31) >> 5)) * 4 + (size_t)s) * (size_t)S + 255) & ~(size_t)255;
+}
+
+// Its plan.
+inline bool decim_tile_plan(int64_t s, int64_t n, int64_t rec_words, int variant, TilePlan *out)
+{
+    return plan_tiles([=](int S) { return decim_state_bytes(s, n, rec_words, S); }, variant, out);
 }
 
 // ---- the check records of a graph ------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised model-parity fuzz (GPU box) of the kernels that tools/fuzz_parity.py does not reach: the bit-flip decoder,
 min-sum (flooding and layered schedule, shared and per-syndrome priors), relay min-sum, the joint X/Z (Pauli) min-sum, the
-device OSD step, the one-matrix and CSS trial steps, and the three BP-OTS kernels at parameters fuzz_parity.py leaves out.  Random Tanner graphs (irregular with empty and heavy nodes and
+device OSD step, the one-matrix and CSS trial steps, the three BP-OTS kernels at parameters fuzz_parity.py leaves out, and the
+guided-decimation min-sum (leg `decim`: 2 ... 4 model seconds for the 40 cases of seeds 20 and 21).  Random Tanner graphs (irregular with empty and heavy nodes and
 sizes around the word boundaries, or small Gallager codes), ragged batches, every `kernel_variant` that create accepts,
 every result compared in every element with the numpy models of tests/ (the min-sum family and relay: the LLR bit patterns
 too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
@@ -15,7 +16,7 @@ fuzz_models_failure.npz, both in the directory FUZZ_OUT (default: fuzz_out/ in t
 
 The legs `layered`, `priors` and `pauli` draw from a generator of their own (seeded [seed, 1]): the six older legs decode for
 a seed what they decoded before those three existed.  The leg `bpots` draws from a third (seeded [seed, 2]) for the same
-reason.  BP-OTS has no kernel_variant: its tiers are the kernels 2 (LDS-resident), 3 (node-parallel) and 5 (unlimited), reached
+reason, and the leg `decim` (guided-decimation min-sum) from a fourth (seeded [seed, 3]).  BP-OTS has no kernel_variant: its tiers are the kernels 2 (LDS-resident), 3 (node-parallel) and 5 (unlimited), reached
 through LDPC_BPOTS_FORCE_NODE unset, 1 and 2 (experiments build); a graph with a check of more than 32 or a bit of more than
 16 edges runs as kernel 5 only and the other two count as skipped.  Its model is the C oracle (oracle/bpots_oracle.c), its
 batch is capped at 65.
@@ -41,6 +42,7 @@ import trials_model as tm  # noqa: E402
 import priors_model as pm  # noqa: E402
 from bitflip_model import BitFlipModel  # noqa: E402
 from layered_model import LayeredMinSumModel, layers_of  # noqa: E402
+from decim_model import DecimModel  # noqa: E402
 from minsum_model import MinSumModel, llr_of_probs  # noqa: E402
 from osd_model import osd_model_postprocess  # noqa: E402
 from pauli_model import PauliMinSumModel, pauli_priors  # noqa: E402
@@ -57,7 +59,7 @@ UNSUPPORTED = 5
 # tiers a component can take here; the last one is its unlimited tier.  (Bit-flip tier 4, the 64-bit votes, needs
 # max_iters * max bit degree >= 2^31 and is held by test_unlimited_tier_with_64_bit_votes.)
 TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2),
-         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2), "bpots": (2, 3, 5)}
+         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2), "bpots": (2, 3, 5), "decim": (1, 2)}
 BOUNDARY = (31, 32, 33, 63, 64, 65, 127, 128, 129)
 
 if GPU:
@@ -74,6 +76,7 @@ seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
 rng2 = np.random.default_rng([seed, 1])      # the layered, priors and pauli legs: never `rng`, whose stream the older legs own
 rng3 = np.random.default_rng([seed, 2])      # the bpots leg
+rng4 = np.random.default_rng([seed, 3])      # the decim leg
 t0 = time.time()
 ran = {c: set() for c in TIERS}          # tiers that decoded
 legs_run = {c: 0 for c in TIERS}
@@ -800,6 +803,55 @@ def leg_bpots(H, B, run):
             legs_run["bpots"] += 1
 
 
+# ---- the leg of the fourth generator -----------------------------------------------------------------------------------
+def leg_decim(H, B, run):
+    """Guided-decimation min-sum on the case's graph against the numpy model: errors, flags, iteration and decimation counts
+    and the LLR bit patterns.  Rounds of 0 ... 4 iterations and few decimations, or -- on a graph of at most 48 bits -- rounds
+    of one iteration and every bit free to be pinned (the |D| == n exit), so that a leg stays within about 50 iterations."""
+    g = rng4
+    s, n = H.shape
+    every_bit = g.random() < 0.3
+    T, Dmax = int(g.choice([0, 1, 2, 4])), min(n, int(g.choice([0, 1, 3, 8])))
+    if every_bit and n <= 48:
+        T, Dmax = 1, n
+    alpha, clip = float(g.choice([0.5, 0.75, 1.0])), float(g.choice([4.0, 20.0, 1e6]))
+    prior = draw_priors(n, g)
+    device_entry, want_decimated = bool(g.random() < 0.5), bool(g.random() < 0.5)
+    Bd = min(B, 65)
+    syn = draw_syndromes(H, Bd, g)
+    text = (f"round_iters {T} max_decimations {Dmax} alpha {alpha} clip {clip} batch {Bd} {'device' if device_entry else 'host'} entry "
+            f"decimated={want_decimated}")
+    if DRY or VERBOSE:
+        print(f"   decim {text}", flush=True)
+    if not run:
+        return
+    merr, mconv, mits, mdec, mL = timed_model("decim", lambda: DecimModel(H, prior, T, Dmax, alpha=alpha, clip=clip).decode(syn))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if device_entry:
+            err, conv = torch.full((Bd, n), 7, dtype=torch.uint8, device="cuda"), torch.full((Bd,), 7, dtype=torch.uint8, device="cuda")
+            llr = torch.full((Bd, n), 7.0, dtype=torch.float64, device="cuda")
+            its = torch.full((Bd,), -7, dtype=torch.int32, device="cuda")
+            nd = torch.full((Bd,), -7, dtype=torch.int32, device="cuda") if want_decimated else None
+            dec.decode_batch_device(dev(syn), err, conv, llr, its, nd)
+            torch.cuda.synchronize()
+            err, conv, llr, its = (x.cpu().numpy() for x in (err, conv, llr, its))
+            nd = nd.cpu().numpy() if want_decimated else None
+        else:
+            out = dec.decode_batch_host(syn, want_llr=True, want_decimated=want_decimated)
+            err, conv, llr, its = out[:4]
+            nd = out[4] if want_decimated else None
+        ok = same(err, merr) and same(conv, mconv) and same(its, mits) and same_bits(llr, mL) and (nd is None or same(nd, mdec))
+        if not ok:
+            fail("decim", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, prior=prior,
+                 err=err, conv=conv, its=its, llr=llr, nd=nd, merr=merr, mconv=mconv, mits=mits, mdec=mdec, mL=mL)
+
+    on_every_tier("decim", (1, 2), lambda v: ldpc.DecimatedMinSumDecoder(H, None, T, channel_llr=prior, max_decimations=Dmax, alpha=alpha,
+                                                                         clip=clip, kernel_variant=v), go, text)
+
+
 # ---- the cases ---------------------------------------------------------------------------------------------------------
 last_note = t0
 for case in range(ncases):
@@ -821,6 +873,7 @@ for case in range(ncases):
     leg_priors(H, B, run)
     leg_pauli(H, B, run)
     leg_bpots(H, B, run)
+    leg_decim(H, B, run)
     if time.time() - last_note > 60:   # a silent GPU job looks hung to the runner
         last_note = time.time()
         print(f"... {case + 1} cases, {time.time() - t0:.0f} s", flush=True)
