@@ -8,6 +8,10 @@ is one float32 operation, and a column that has stopped is frozen -- never writt
                  test: H err == syndrome -> converged, stop
                  t % T == 0 and not matched: |D| == Dmax -> stop; else j* = argmax |L| outside D (lowest index on a tie),
                  negative = L[j*] <= 0, j* joins D and is pending: check sweep t + 1 still reads L[j*] as it is
+
+Two additions serve the tests of the tie rule alone: `tie="highest"` restates the rule with the HIGHEST index on a tie (what a
+kernel that breaks ties wrongly would compute; the default "lowest" is the rule), and `last_ties` counts, over the last
+decode, the decimations in which at least two bits outside D shared the largest |L| -- the decimations where the two differ.
 """
 import numpy as np
 
@@ -17,8 +21,11 @@ F = np.float32
 
 
 class DecimModel(MinSumModel):
-    def __init__(self, H, channel_llr, round_iters: int, max_decimations: int, alpha: float = 0.75, clip: float = 1e6):
+    def __init__(self, H, channel_llr, round_iters: int, max_decimations: int, alpha: float = 0.75, clip: float = 1e6,
+                 tie: str = "lowest"):
         super().__init__(H, channel_llr, round_iters, alpha, clip)
+        assert tie in ("lowest", "highest")
+        self.tie, self.last_ties = tie, 0
         self.round_iters, self.max_dec = int(round_iters), int(max_decimations)
         assert self.round_iters >= 0 and 0 <= self.max_dec <= self.n
         self.pin = F(2.0) * self.clip
@@ -28,6 +35,7 @@ class DecimModel(MinSumModel):
         """syn [B][s] -> (err [B][n] u8, conv [B] u8, iters [B] i32, decimated [B] i32, L [B][n] f32)."""
         y = (np.asarray(syn_bs).reshape(-1, self.s) != 0)
         B, n, T = y.shape[0], self.n, self.round_iters
+        self.last_ties = 0
         if T == 0:
             return (np.zeros((B, n), np.uint8), np.zeros(B, np.uint8), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, n), F))
         alpha, clip = self.alpha, self.clip
@@ -88,6 +96,9 @@ class DecimModel(MinSumModel):
                 if active.any():
                     mag = np.where(D, F(-1.0), np.abs(L))     # outside D only; argmax takes the lowest index on a tie
                     jstar = np.argmax(mag, axis=1)
+                    if self.tie == "highest":
+                        jstar = n - 1 - np.argmax(mag[:, ::-1], axis=1)
+                    self.last_ties += int(((mag == mag.max(axis=1, keepdims=True)).sum(axis=1) >= 2)[active].sum())
                     rows_a = rows_b[active]
                     assert not D[rows_a, jstar[active]].any()
                     negative[active] = L[rows_a, jstar[active]] <= 0

@@ -363,3 +363,73 @@ def test_decim_plan_under_sanitizers(tmp_path):
                            os.path.join(ROOT, "tests", "native", "decim_plan_sanitize.cpp")])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("OK ") and "decimation plans" in out.stdout, out.stdout + out.stderr
+
+
+# ---- the table of tests/test_gpu_decim_widths.py ------------------------------------------------------------------------------
+# (3,6)-regular graphs of parity_check_csc(n, 6, 3): s = n / 2, rec_words = 2 n, so a lane takes
+# 4 (n + 2 n + ceil(n / 32)) + n / 2 = 12.625 n bytes (n a multiple of 32).  n -> (tier, S, the budget S was found under)
+DECIM_TABLE = {
+    96: (1, 64, KIB79),
+    192: (1, 32, KIB79),
+    384: (1, 16, KIB79),
+    768: (1, 8, KIB79),
+    1536: (1, 4, KIB79),
+    3072: (1, 2, KIB79),
+    6144: (1, 1, KIB79),
+    6432: (1, 2, KIB159),     # 81204 bytes a lane miss 79 KiB; two lanes, 162408 -> 162560, fit 159 KiB: S = 2, not 1
+    12288: (1, 1, KIB159),    # 155136 bytes: one workgroup a CU
+    13824: (2, 64, 0),        # 174528 bytes a lane: the unlimited tier by size
+}
+
+
+@pytest.mark.parametrize("experiments", [False, True])
+@pytest.mark.parametrize("n", sorted(DECIM_TABLE))
+def test_the_table_of_the_width_tests(n, experiments):
+    tier, S, budget = DECIM_TABLE[n]
+    s, rec = n // 2, 2 * n
+    assert n % 32 == 0 and 4 * (n + rec + n // 32) + s == 12.625 * n                # the per-lane formula ...
+    assert state_bytes(s, n, rec, 1) == -(-int(12.625 * n) // 256) * 256             # ... and the 256-byte rounding of a tile
+    assert plan_of(s, n, rec, 0) == (tier, S, state_bytes(s, n, rec, S))           # the row follows from the restated rule
+    assert lib_plan(s, n, rec, 0, experiments) == (tier, S, state_bytes(s, n, rec, S))
+    if tier == 1:
+        assert lib_plan(s, n, rec, 1, experiments) == (tier, S, state_bytes(s, n, rec, S))
+        assert state_bytes(s, n, rec, S) <= budget and (S == 64 or state_bytes(s, n, rec, 2 * S) > budget)
+        assert (budget == KIB79) == (state_bytes(s, n, rec, 1) <= KIB79)          # 159 KiB is tried only where 79 KiB holds nothing
+    else:
+        assert state_bytes(s, n, rec, 1) > KIB159 and lib_plan(s, n, rec, 1, experiments) == UNSUPPORTED
+        assert "on-chip" in ldpc._capi.lib(experiments).ldpc_last_error().decode()
+    assert lib_plan(s, n, rec, 2, experiments) == (2, 64, state_bytes(s, n, rec, 64))
+    if n == 6432:      # the window: one lane lies in (79 KiB, 159 KiB / 2]
+        assert (int(12.625 * n), state_bytes(s, n, rec, 2)) == (81204, 162560) and KIB79 < 81204 <= KIB159 // 2
+    if n == 12288:
+        assert state_bytes(s, n, rec, 1) == 155136
+    if n == 13824:
+        assert int(12.625 * n) == 174528
+
+
+# ---- the model's additions for the tests of the tie rule ----------------------------------------------------------------------
+
+def test_model_tie_argument_and_tie_count(bb72):
+    """The hand case: at its one decimation both |L| are 0, a tie; "highest" pins bit 1 where the rule pins bit 0, with the
+    mirrored outcome.  On BB-72 with the uniform prior ties occur and change LLRs; with distinct priors on a graph without
+    symmetry no tie occurs and the two coincide.  The default is the rule, and `last_ties` is reset by every decode."""
+    H = np.array([[1, 1]], dtype=np.uint8)
+    syn = np.array([[1]], dtype=np.uint8)
+    low, high = DecimModel(H, [1.0, 1.0], 2, 2, alpha=1.0), DecimModel(H, [1.0, 1.0], 2, 2, alpha=1.0, tie="highest")
+    assert _same(low.decode(syn), DecimModel(H, [1.0, 1.0], 2, 2, alpha=1.0, tie="lowest").decode(syn))
+    assert high.decode(syn)[4].tolist() == [[1000001.0, -2000000.0]] and low.decode(syn)[4].tolist() == [[-2000000.0, 1000001.0]]
+    assert (low.last_ties, high.last_ties) == (1, 1)
+    assert low.decode(np.array([[0]], dtype=np.uint8))[1][0] == 1 and low.last_ties == 0          # reset; no decimation, no tie
+    with pytest.raises(AssertionError):
+        DecimModel(H, [1.0, 1.0], 2, 2, tie="first")
+    syn = ldpc.codes.syndromes_of(bb72, ldpc.codes.random_errors(72, 60, 0.06, seed=3))
+    prior = llr_of_probs(np.full(72, 0.06))
+    low, high = DecimModel(bb72, prior, 3, 6), DecimModel(bb72, prior, 3, 6, tie="highest")
+    a, b = low.decode(syn), high.decode(syn)
+    assert 0 < low.last_ties <= int(a[3].sum()) and (a[4].view(np.int32) != b[4].view(np.int32)).any()
+    assert _same(DecimModel(bb72, prior, 0, 6, tie="highest").decode(syn), DecimModel(bb72, prior, 0, 6).decode(syn))
+    rng = np.random.default_rng(2)
+    distinct = llr_of_probs(rng.uniform(0.01, 0.2, 72))
+    low, high = DecimModel(bb72, distinct, 3, 6), DecimModel(bb72, distinct, 3, 6, tie="highest")
+    a, b = low.decode(syn), high.decode(syn)
+    assert a[3].sum() > 0 and (low.last_ties > 0 or _same(a, b))                       # no tie: the two rules are one

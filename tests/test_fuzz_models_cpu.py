@@ -20,7 +20,11 @@ PAULI = re.compile(r"^   pauli Hz \((\d+), (\d+)\) B (\d+) .* max_iters (\d+) .*
 # the leg of the third generator: the three BP-OTS kernels; S, DC, DV as ldpc_debug_bpots_plan answers for the unforced handle
 BPOTS = re.compile(r"^   bpots per (\S+) T (\d+) C (\S+) max_iters (\d+) batch (\d+) (device|host) entry iters=(True|False) "
                    r"edges (\d+) kernel ([235]) S (\d+) DC (\d+) DV (\d+)$")
-OLD_LEGS, NEW_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css"), ("layered", "priors", "pauli", "bpots")
+# the leg of the fourth generator: guided-decimation min-sum; n and the on-chip S of the unforced plan (0: nothing fits) as
+# ldpc_debug_decim_tile_plan answers.  A leg of round_iters 0 launches no kernel: it counts for that property alone
+DECIM = re.compile(r"^   decim round_iters (\d+) max_decimations (\d+) alpha (\S+) clip (\S+) batch (\d+) (device|host) entry "
+                   r"decimated=(True|False) n (\d+) S (\d+)$")
+OLD_LEGS, NEW_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css"), ("layered", "priors", "pauli", "bpots", "decim")
 
 
 def _tool(args, **env):
@@ -63,6 +67,16 @@ def coverage(listing):
                 (f"bpots: S = {S}", kernel == 2), (f"bpots: DC {DC}", kernel == 2), (f"bpots: DV {DV}", kernel == 2),
                 ("bpots: T = 1", T == 1), ("bpots: per = 0.75", per == 0.75), ("bpots: a wide graph", kernel == 5),
                 ("bpots: a graph without edges", int(m.group(8)) == 0)) if yes}
+        m = DECIM.match(line)
+        if m:
+            T, Dmax, B, n, S = (int(m.group(k)) for k in (1, 2, 5, 8, 9))
+            clip, entry, counts = float(m.group(4)), m.group(6), m.group(7) == "True"
+            assert 1 <= B <= 65 and 0 <= Dmax <= n and S in (0, 1, 2, 4, 8, 16, 32, 64)
+            have |= {name for name, yes in (
+                ("decim: round_iters 0", T == 0), ("decim: max_decimations 0", T > 0 and Dmax == 0),
+                ("decim: every bit free", T == 1 and Dmax == n > 0), (f"decim: {entry} entry", T > 0),
+                ("decim: decimated=False", T > 0 and not counts), (f"decim: clip {clip:g}", T > 0),
+                (f"decim: S = {S}", T > 0 and S > 0)) if yes}
         m = CASE.match(line)
         if not m:
             continue
@@ -84,7 +98,11 @@ WANTED = {"check of degree <= 32", "check of degree 33 ... 64", "check of degree
           "pauli: Hx check of degree > 64", "pauli: empty Hx check", "pauli: empty Hz check", "pauli: batch 1", "pauli: batch 65",
           "pauli: one triple for every qubit", "pauli: arbitrary syndromes",
           # BP-OTS: each register bucket, the bias step in every iteration, a prior of exactly 0, a graph that takes kernel 5 only
-          "bpots: DC 8", "bpots: DC 32", "bpots: DV 4", "bpots: DV 16", "bpots: T = 1", "bpots: per = 0.75", "bpots: a wide graph"}
+          "bpots: DC 8", "bpots: DC 32", "bpots: DV 4", "bpots: DV 16", "bpots: T = 1", "bpots: per = 0.75", "bpots: a wide graph",
+          # decimation: no launch, no decimation (plain min-sum), the |D| == n exit, both entries, the optional output left
+          # out, the clamp at each of the three clips the leg draws
+          "decim: round_iters 0", "decim: max_decimations 0", "decim: every bit free", "decim: device entry", "decim: host entry",
+          "decim: decimated=False", "decim: clip 4", "decim: clip 20", "decim: clip 1e+06"}
 # A graph without edges is NOT among them: the graphs are the cases' own, drawn from the first generator, whose stream the
 # older legs own; the smallest graph of the committed seeds has 7 edges.  tests/test_gpu_bpots_paths.py
 # (test_a_graph_without_edges) pins that shape instead.
@@ -102,13 +120,15 @@ def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_th
         for leg in OLD_LEGS + NEW_LEGS:
             assert len([ln for ln in first.splitlines() if ln.startswith(f"   {leg} ")]) == CASES, leg
         # ... and every line of a new leg is one that coverage() can read
-        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS)):
+        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS, DECIM)):
             assert all(pattern.match(ln) for ln in first.splitlines() if ln.startswith(f"   {leg} ")), leg
         have |= coverage(first)
     widths = {name for name in have if name.startswith("bpots: S = ")}
     assert len(widths) >= 3, f"the committed seeds reach only the BP-OTS tile widths {sorted(widths)}"
     assert "bpots: a graph without edges" not in have       # (see WANTED: if a seed ever draws one, say so there)
-    assert have - widths == WANTED, f"the committed seeds never draw: {sorted(WANTED - have)}"
+    decim_widths = {name for name in have if name.startswith("decim: S = ")}
+    assert len(decim_widths) >= 3, f"the committed seeds reach only the decimation tile widths {sorted(decim_widths)}"
+    assert have - widths - decim_widths == WANTED, f"the committed seeds never draw: {sorted(WANTED - have)}"
 
 
 def test_a_window_of_cases_draws_what_the_whole_run_draws():

@@ -1,7 +1,8 @@
 """A short run of tools/fuzz_models.py: random Tanner graphs (irregular with empty and heavy nodes and sizes at the word
 boundaries, small Gallager codes), ragged batches, every kernel_variant that create accepts, the bit-flip, min-sum, relay,
 device OSD, trials and CSS trials kernels compared in every element with their numpy models, the three BP-OTS kernels
-(tiers 2, 3, 5: LDS-resident, node-parallel, unlimited) with the C oracle."""
+(tiers 2, 3, 5: LDS-resident, node-parallel, unlimited) with the C oracle, the guided-decimation min-sum kernels (tiers 1
+and 2) with their numpy model."""
 import os
 import re
 import subprocess
@@ -14,7 +15,7 @@ from test_fuzz_models_cpu import CASES, SEEDS
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TIERS = {"bitflip": {1, 2, 3}, "minsum": {1, 2}, "relay": {1, 2}, "osd": {1, 2, 3}, "trials": {1, 2}, "css": {1, 2},
-         "layered": {1, 2}, "priors": {1, 2}, "pauli": {1, 2}, "bpots": {2, 3, 5}}
+         "layered": {1, 2}, "priors": {1, 2}, "pauli": {1, 2}, "bpots": {2, 3, 5}, "decim": {1, 2}}
 _REPORTS = {}
 
 

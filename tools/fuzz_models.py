@@ -16,7 +16,8 @@ fuzz_models_failure.npz, both in the directory FUZZ_OUT (default: fuzz_out/ in t
 
 The legs `layered`, `priors` and `pauli` draw from a generator of their own (seeded [seed, 1]): the six older legs decode for
 a seed what they decoded before those three existed.  The leg `bpots` draws from a third (seeded [seed, 2]) for the same
-reason, and the leg `decim` (guided-decimation min-sum) from a fourth (seeded [seed, 3]).  BP-OTS has no kernel_variant: its tiers are the kernels 2 (LDS-resident), 3 (node-parallel) and 5 (unlimited), reached
+reason, and the leg `decim` (guided-decimation min-sum) from a fourth (seeded [seed, 3]); its line ends with `n` and the
+on-chip tile width of the unforced plan (`S 0`: nothing fits on chip), which draw nothing.  BP-OTS has no kernel_variant: its tiers are the kernels 2 (LDS-resident), 3 (node-parallel) and 5 (unlimited), reached
 through LDPC_BPOTS_FORCE_NODE unset, 1 and 2 (experiments build); a graph with a check of more than 32 or a bit of more than
 16 edges runs as kernel 5 only and the other two count as skipped.  Its model is the C oracle (oracle/bpots_oracle.c), its
 batch is capped at 65.
@@ -804,6 +805,20 @@ def leg_bpots(H, B, run):
 
 
 # ---- the leg of the fourth generator -----------------------------------------------------------------------------------
+def decim_on_chip_width(H):
+    """The tile width of the unforced plan (ldpc_debug_decim_tile_plan: host code, no device needed) where it is the on-chip
+    tier, 0 where not even one syndrome fits.  Draws nothing."""
+    import ctypes
+
+    s, n = H.shape
+    deg = np.diff(sp.csr_matrix(H).indptr)
+    rec_words = int(np.where(deg == 0, 0, np.where(deg <= 32, 4, np.where(deg <= 64, 5, deg))).sum())
+    tier, S = ctypes.c_int32(0), ctypes.c_int32(0)
+    L = ldpc._capi.lib()
+    ldpc._capi.check(L.ldpc_debug_decim_tile_plan(s, n, rec_words, 0, ctypes.byref(tier), ctypes.byref(S), None), L)
+    return S.value if tier.value == 1 else 0
+
+
 def leg_decim(H, B, run):
     """Guided-decimation min-sum on the case's graph against the numpy model: errors, flags, iteration and decimation counts
     and the LLR bit patterns.  Rounds of 0 ... 4 iterations and few decimations, or -- on a graph of at most 48 bits -- rounds
@@ -820,7 +835,7 @@ def leg_decim(H, B, run):
     Bd = min(B, 65)
     syn = draw_syndromes(H, Bd, g)
     text = (f"round_iters {T} max_decimations {Dmax} alpha {alpha} clip {clip} batch {Bd} {'device' if device_entry else 'host'} entry "
-            f"decimated={want_decimated}")
+            f"decimated={want_decimated} n {n} S {decim_on_chip_width(H)}")
     if DRY or VERBOSE:
         print(f"   decim {text}", flush=True)
     if not run:
