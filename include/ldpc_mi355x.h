@@ -386,6 +386,44 @@ ldpc_status ldpc_osd_postprocess_batch_device(ldpc_osd *osd, int64_t batch, cons
                                               const uint8_t *d_bp_errors, const double *d_llr, uint8_t *d_errors,
                                               void *stream);
 
+/* THE STANDARD RULE, a second rule on the same handle: opt-in, DEVICE FORM ONLY (csrc/osd_search_kernels.hpp).  The rule
+ * above is the reference's and stays the default: its key max(exp(llr), 1 - exp(llr)) puts the bits BP is most certain
+ * of first.  OSD as published (Panteleev-Kalachev 2021; Roffe et al. 2020) eliminates the columns most likely to be in
+ * error first, searches by the combination sweep and weighs a correction by the priors.  Everything below is integer
+ * arithmetic or an exact comparison of doubles, so a numpy model equals the device in every element.
+ *
+ * Per handle: H (s x n); method 1 = exhaustive, 2 = combination sweep; order = lambda >= 0 (at most 16 for method 1,
+ * at most 64 for method 2); one weight q[j] (int64) per bit: all 1 (the Hamming weight; channel_llr = NULL), or from
+ * channel_llr[n] by the relay decoder's formula, q[j] = (int64) rint(clamp(channel_llr[j], -2^24, 2^24) * 2^16) (ties to
+ * even).  Entries must be finite and may be negative.  n <= 2^22, so that a cost fits int64.
+ * Per syndrome: syn[s] (an entry that is not 0 counts as 1), bp_err[n] (0 / 1), llr[n] double.
+ *   1. If H bp_err == syn the output is bp_err unchanged, at every order.
+ *   2. The columns are ordered by ascending llr, the most likely in error first: -0.0 equals +0.0, ties go by ascending
+ *      column index, a NaN comes last (after +inf), NaNs among themselves by index.
+ *   3. The pivot columns are the greedy independent set in that order, r of them; the non-pivot columns, in that order,
+ *      are t_0 ... t_{K-1}, K = n - r.
+ *   4. For a set F of non-pivot columns, e(F) is 1 on F, 0 on every other non-pivot column, and has the unique pivot
+ *      bits with H e = syn.  The BP hard decisions are not used beyond step 1.  For a syndrome outside the column space
+ *      of H the output is not specified.
+ *   5. The candidates, with w = min(lambda, K), in a fixed enumeration.  Exhaustive: index x in [0, 2^w), F = {t_k : bit k
+ *      of x}.  Combination sweep: index 0, F empty (OSD-0); index 1 + k, F = {t_k}, for EVERY k < K; then F = {t_a, t_b}
+ *      for a < b < w, a ascending then b ascending, from index 1 + K on.
+ *   6. cost(F) = sum over j of e(F)[j] * q[j] in int64.  The output is the e(F) with the smallest (cost, index).
+ *
+ * ldpc_osd_set_search(osd, method, order, n, channel_llr_or_NULL): before ldpc_osd_device_prepare; replaces the order
+ * given to ldpc_osd_create.  method 0 restores the reference rule (order up to 40, no weights).  LDPC_ERR_INVALID_ARGUMENT
+ * for a NULL handle, a method outside 0..2, an order that is negative or beyond its method's bound, an n that is not the
+ * handle's, a channel_llr entry that is not finite, weights next to method 0, and a handle that is already prepared;
+ * LDPC_ERR_UNSUPPORTED for n > 2^22 with method 1 or 2.  A call that fails changes nothing.
+ * ldpc_osd_search_method: the method of the handle (0 for NULL).  ldpc_osd_search_weight(osd, j): q[j] as the handle holds
+ * it (1 without weights; 0 for NULL or j outside [0, n)).
+ * On such a handle ldpc_osd_device_prepare picks the tier by the state of THIS rule's kernel (tier 1: s <= 128, n <= 512
+ * as above; tier 2: s * 8 * (n/64 + 1 made odd) + 16 n + 12 s + 16 (ceil(n/64) + 1) + 520 (ceil(s/64) + 1) bytes, each
+ * part rounded up to 16, <= 159 KiB; tier 3 beyond), and ldpc_osd_postprocess_batch_device keeps its signature and its promises (in place, call
+ * order).  The HOST form of this rule is out of scope: ldpc_osd_postprocess_batch on such a handle answers
+ * LDPC_ERR_UNSUPPORTED and names the device entry. */
+#include "ldpc_mi355x_osd_search.h"
+
 /* ------------------------------------------------------------------------
  * BP-OTS decoder: LLR-domain tanh/atanh BP with oscillation-driven prior biasing.
  * Graphs whose messages fit one CU's LDS (every code of the reference's BP-OTS tests) take an LDS-resident

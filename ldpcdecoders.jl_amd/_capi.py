@@ -260,10 +260,17 @@ DECIM_API = {
 DECIM_DEBUG_API = {
     "ldpc_debug_decim_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
 }
+# The standard rule of the OSD step: include/ldpc_mi355x_osd_search.h (a part of ldpc_mi355x.h), bound the same way.
+OSD_SEARCH_API = {
+    "ldpc_osd_set_search": (i32, [vp, i32, i64, i64, vp]),
+    "ldpc_osd_search_method": (i32, [vp]),
+    "ldpc_osd_search_weight": (i64, [vp, i64]),
+}
 EXPORTED_SYMBOLS = tuple(API)
 DEBUG_SYMBOLS = tuple(DEBUG_API)
 DECIM_SYMBOLS = tuple(DECIM_API)
 DECIM_DEBUG_SYMBOLS = tuple(DECIM_DEBUG_API)
+OSD_SEARCH_SYMBOLS = tuple(OSD_SEARCH_API)
 
 
 def build(force: bool = False) -> str:
@@ -301,7 +308,7 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
                            "or `make -C ldpcdecoders.jl_amd/csrc`. There is no CPU fallback.")
     _one_hip_runtime()
     L = ctypes.CDLL(path)
-    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API):
+    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API, OSD_SEARCH_API):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -6,10 +6,13 @@
 //   1  on-chip, one wave per syndrome            s <= 128, n <= 512 (<= 17 KiB of LDS: nine workgroups a CU and more)
 //   2  on-chip, one 16-wave workgroup per syndrome   state up to 159 KiB of LDS
 //   3  unlimited: the state in a global workspace, one slot per workgroup of a persistent grid, slots capped at 1 GiB
+// A handle on the standard rule (ldpc_osd_set_search, method 1 or 2) runs osd_search_kernel (osd_search_kernels.hpp) in the
+// same three tiers, bounded by ITS state (osd_search_state_bytes: 16 n + 12 s bytes + 65 row bitsets beside the rows).
 // No CPU path behind these entries.
 #include "../../include/ldpc_mi355x.h"
 #include "osd_handle.hpp"
 #include "osd_kernels.hpp"
+#include "osd_search_kernels.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -32,6 +35,7 @@ struct OsdDevice {
     int device = 0, num_cus = 0, tier = 0, per_cu = 1, threads = 64;
     size_t state = 0, lds = 0;
     osd_u64 *rows = nullptr;
+    long long *q = nullptr;        // standard rule with weights: [n]
     unsigned char *ws = nullptr;   // tier 3: [grid][state]
     int64_t ws_grid = 0;
     ldpc_detail::CallOrder calls;   // calls on a handle run in call order whatever streams they are given (tier 3: they share the workspace)
@@ -48,6 +52,18 @@ osd_kernel_t osd_kernel_of(int tier)
     }
 }
 
+static_assert(kOsdSearchExhaustiveCap <= 16 && kOsdSearchSweepCap <= kOsdSearchCols, "the search kernel holds 64 column bitsets and counts 2^16 subsets");
+typedef void (*osd_search_kernel_t)(OsdSearchParams);
+
+osd_search_kernel_t osd_search_kernel_of(int tier)
+{
+    switch (tier) {
+    case 1: return osd_search_kernel<1, false>;
+    case 2: return osd_search_kernel<kOsdGroupWaves, false>;
+    default: return osd_search_kernel<kOsdGroupWaves, true>;
+    }
+}
+
 void osd_device_free(void *v)
 {
     OsdDevice *dv = (OsdDevice *)v;
@@ -56,6 +72,7 @@ void osd_device_free(void *v)
     if (!ldpc_detail::device_stalled(dv->device) &&
         ldpc_detail::device_idle_for_release(dv->device, "ldpc_osd_destroy (device synchronise)")) {
         if (dv->rows) (void)hipFree(dv->rows);
+        if (dv->q) (void)hipFree(dv->q);
         if (dv->ws) (void)hipFree(dv->ws);
         dv->calls.destroy();
     }
@@ -73,11 +90,12 @@ ldpc_status ldpc_osd_device_prepare(ldpc_osd *d, int32_t device, int32_t kernel_
     if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "osd handle is NULL");
     if (kernel_variant < 0 || kernel_variant > 3) return set_error(LDPC_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1, 2 or 3");
     if (d->dev) return set_error(LDPC_ERR_INVALID_ARGUMENT, "osd handle is already prepared for a device");
-    if (d->order > kOsdMaxOrder)
+    const bool search = d->method != 0;   // (ldpc_osd_set_search has bounded its order and n)
+    if (!search && d->order > kOsdMaxOrder)
         return set_error(LDPC_ERR_UNSUPPORTED, "device OSD runs osd_order <= 16 (2^16 candidates per syndrome); use the host entry beyond");
     if (d->m >= ((int64_t)1 << 24) || d->n >= ((int64_t)1 << 24))
         return set_error(LDPC_ERR_UNSUPPORTED, "device OSD: graph too large for 32-bit row indexing");
-    const size_t state = osd_state_bytes(d->m, d->n);
+    const size_t state = search ? osd_search_state_bytes(d->m, d->n) : osd_state_bytes(d->m, d->n);
     const bool fits1 = d->m <= kOsdWaveRows && d->n <= kOsdWaveCols, fits2 = state <= kOsdGroupLds;
     if ((kernel_variant == 1 && !fits1) || (kernel_variant == 2 && !fits2))
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant: the state of a syndrome does not fit that on-chip tier");
@@ -102,10 +120,15 @@ ldpc_status ldpc_osd_device_prepare(ldpc_osd *d, int32_t device, int32_t kernel_
     if (!d->rows.empty() && hipMemcpy(dv->rows, d->rows.data(), d->rows.size() * sizeof(osd_u64), hipMemcpyHostToDevice) != hipSuccess)
         return fail(LDPC_ERR_HIP, "upload of the packed rows failed");
     if (dv->calls.create() != hipSuccess) return fail(LDPC_ERR_HIP, "hipEventCreate failed");
-    osd_kernel_t k = osd_kernel_of(dv->tier);
-    if (dv->lds && hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv->lds) != hipSuccess)
+    if (search && !d->q.empty()) {
+        if (hipMalloc((void **)&dv->q, d->q.size() * sizeof(long long)) != hipSuccess) return fail(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the weights failed");
+        if (hipMemcpy(dv->q, d->q.data(), d->q.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(LDPC_ERR_HIP, "upload of the weights failed");
+    }
+    const void *k = search ? (const void *)osd_search_kernel_of(dv->tier) : (const void *)osd_kernel_of(dv->tier);
+    if (dv->lds && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv->lds) != hipSuccess)
         return fail(LDPC_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    const int per_cu = dv->per_cu = ldpc_detail::blocks_per_cu((const void *)k, dv->threads, dv->lds);
+    const int per_cu = dv->per_cu = ldpc_detail::blocks_per_cu(k, dv->threads, dv->lds);
     if (dv->tier == 3) {
         dv->ws_grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)per_cu * dv->num_cus, (int64_t)(kOsdWorkspaceCap / state)));
         if (hipMalloc((void **)&dv->ws, (size_t)dv->ws_grid * state) != hipSuccess)
@@ -136,6 +159,16 @@ ldpc_status ldpc_osd_postprocess_batch_device(ldpc_osd *d, int64_t batch, const 
     if (ent != LDPC_OK) return ent;
     int64_t grid = std::min<int64_t>(batch, (int64_t)dv->per_cu * dv->num_cus);
     if (dv->tier == 3) grid = std::min<int64_t>(grid, dv->ws_grid);
+    if (d->method != 0) {
+        OsdSearchParams p{};
+        p.m = (int)d->m; p.n = (int)d->n; p.nw = (int)d->nw; p.st = (int)osd_stride(d->nw); p.mw = (int)((d->m + 63) >> 6);
+        p.method = (int)d->method; p.order = (int)d->order; p.batch = batch;
+        p.syn = d_syndromes; p.bp = d_bp_errors; p.llr = d_llr; p.out = d_errors;
+        p.rows = dv->rows; p.q = dv->q; p.ws = dv->ws; p.slot_bytes = (long long)dv->state;
+        hipLaunchKernelGGL(osd_search_kernel_of(dv->tier), dim3((unsigned)grid), dim3((unsigned)dv->threads), dv->lds, stream, p);
+        LDPC_HIP_TRY(hipGetLastError());
+        return dv->calls.leave(stream);
+    }
     OsdParams p{};
     p.m = (int)d->m; p.n = (int)d->n; p.nw = (int)d->nw; p.st = (int)osd_stride(d->nw); p.mw = (int)((d->m + 63) >> 6);
     p.order = (int)d->order; p.batch = batch;

@@ -232,11 +232,47 @@ ldpc_status ldpc_osd_destroy(ldpc_osd *d)
     return LDPC_OK;
 }
 
+int32_t ldpc_osd_search_method(const ldpc_osd *d) { return d ? d->method : 0; }
+
+ldpc_status ldpc_osd_set_search(ldpc_osd *d, int32_t method, int64_t order, int64_t n, const double *channel_llr)
+{
+    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "osd handle is NULL");
+    if (d->dev) return set_error(LDPC_ERR_INVALID_ARGUMENT, "ldpc_osd_set_search comes before ldpc_osd_device_prepare: the handle is already prepared");
+    if (method < 0 || method > 2) return set_error(LDPC_ERR_INVALID_ARGUMENT, "method must be 0 (reference rule), 1 (exhaustive) or 2 (combination sweep)");
+    const int64_t cap = method == 0 ? 40 : method == 1 ? kOsdSearchExhaustiveCap : kOsdSearchSweepCap;
+    if (order < 0 || order > cap)
+        return set_error(LDPC_ERR_INVALID_ARGUMENT, "order must be in [0, 40] for method 0, [0, 16] for method 1, [0, 64] for method 2");
+    if (n != d->n) return set_error(LDPC_ERR_INVALID_ARGUMENT, "n is not the number of columns of the handle");
+    if (method == 0 && channel_llr) return set_error(LDPC_ERR_INVALID_ARGUMENT, "the reference rule (method 0) takes no weights");
+    if (method != 0 && n > kOsdSearchMaxBits) return set_error(LDPC_ERR_UNSUPPORTED, "standard rule: n > 2^22 (a cost must fit int64)");
+    std::vector<int64_t> q;
+    if (channel_llr) {
+        q.resize((size_t)n);
+        for (int64_t j = 0; j < n; ++j) {
+            if (!std::isfinite(channel_llr[j])) return set_error(LDPC_ERR_INVALID_ARGUMENT, "channel_llr entries must be finite");
+            // the relay decoder's weight: q = rint(clamp(llr, -2^24, 2^24) * 2^16)
+            q[(size_t)j] = (int64_t)std::rint(std::min(std::max(channel_llr[j], -16777216.0), 16777216.0) * 65536.0);
+        }
+    }
+    d->method = method;
+    d->order = order;
+    d->q.swap(q);
+    return LDPC_OK;
+}
+
+int64_t ldpc_osd_search_weight(const ldpc_osd *d, int64_t j)
+{
+    if (!d || j < 0 || j >= d->n) return 0;
+    return d->q.empty() ? 1 : d->q[(size_t)j];
+}
+
 ldpc_status ldpc_osd_postprocess_batch(const ldpc_osd *d, int64_t batch, const uint8_t *syndromes,
                                        const uint8_t *bp_errors, const double *llr, uint8_t *errors,
                                        int32_t nthreads)
 {
     if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "osd handle is NULL");
+    if (d->method != 0)
+        return set_error(LDPC_ERR_UNSUPPORTED, "the standard rule (ldpc_osd_set_search, method 1 or 2) has a device form only: use ldpc_osd_postprocess_batch_device");
     if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
     if (batch == 0) return LDPC_OK;
     if ((d->m > 0 && !syndromes) || (d->n > 0 && (!bp_errors || !llr || !errors)))

@@ -289,6 +289,23 @@ function osd_postprocess_device!(d::MI355XBeliefPropagationOSDDecoder, batch::In
     return nothing
 end
 
+# The standard rule of the ordered-statistics step (include/ldpc_mi355x.h "THE STANDARD RULE"; device form only): call
+# before osd_device_prepare!.  method 0 = the reference rule, 1 = exhaustive, 2 = combination sweep; channel_llr = nothing
+# weighs by count.
+function osd_set_search!(d::MI355XBeliefPropagationOSDDecoder, method::Integer, order::Integer,
+                         channel_llr::Union{Nothing,Vector{Float64}}=nothing)
+    n = size(d.H, 2)
+    check(ccall((:ldpc_osd_set_search, libldpc), Cint, (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}),
+                d.osd_handle, method, order, n, channel_llr === nothing ? Ptr{Float64}(C_NULL) : pointer(channel_llr)))
+    return nothing
+end
+
+osd_search_method(d::MI355XBeliefPropagationOSDDecoder) =
+    Int(ccall((:ldpc_osd_search_method, libldpc), Int32, (Ptr{Cvoid},), d.osd_handle))
+
+osd_search_weight(d::MI355XBeliefPropagationOSDDecoder, j::Integer) =
+    ccall((:ldpc_osd_search_weight, libldpc), Int64, (Ptr{Cvoid}, Int64), d.osd_handle, j)
+
 # ---------------------------------------------------------------------------------------------
 # BP-OTS (src/decoders/bpots_decoder.jl:39-115, 225-340) over ldpc_bpots_* (LDS-resident kernel for small graphs,
 # node-parallel kernel with the messages in global memory up to n ~ 30,000; beyond that LDPCMI355XError(5, ...)).

@@ -9,6 +9,10 @@ Opt-in (`osd="device"`): the same step as HIP kernels (`ldpc_osd_postprocess_bat
 that should not leave the GPU.  Its reliability key is the stated one (include/ldpc_mi355x.h: pm_exp, ties by
 column index); on the rare syndrome where libm's exp orders two nearly tied columns the other way round, it
 returns another, equally valid estimate than the host form.
+
+A second rule, opt-in and device form only (`method=` / `osd_method=`; include/ldpc_mi355x.h "THE STANDARD RULE"): the
+columns most likely in error are eliminated first, the search is exhaustive or the combination sweep, and the cost of a
+correction is an integer weight per bit (all ones, or from channel LLRs).  The reference's rule stays the default.
 """
 from __future__ import annotations
 
@@ -21,18 +25,38 @@ from ._host import Handle, _pattern_of, csc_arrays, device_option, stream_ptr, s
 from .decoder import AbstractDecoder, BeliefPropagationDecoder
 
 
+OSD_METHODS = {"reference": 0, "exhaustive": 1, "combination_sweep": 2}
+
+
 class OSDPostProcessor(Handle):
-    """Owns the `ldpc_osd` handle: bit-packed H and the OSD order.  Needs no GPU."""
+    """Owns the `ldpc_osd` handle: bit-packed H and the OSD order.  Needs no GPU.
+    method: "reference" (the reference's rule: host and device form), or "exhaustive" / "combination_sweep" (the
+    standard rule, ldpc_osd_set_search: device form only).  weights: an array of n channel LLRs for the standard rule's
+    cost (None: the Hamming weight)."""
 
     _destroy = "ldpc_osd_destroy"
 
-    def __init__(self, H, osd_order: int = 0):
+    def __init__(self, H, osd_order: int = 0, method: str = "reference", weights=None):
+        if method not in OSD_METHODS:
+            raise ValueError('method must be "reference", "exhaustive" or "combination_sweep"')
         M = _pattern_of(H)
         self.s, self.n = int(M.shape[0]), int(M.shape[1])
         self.osd_order = int(osd_order)
+        self.method = method
+        if weights is not None:
+            if method == "reference":
+                raise ValueError("the reference rule weighs by count: weights= needs another method")
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.shape != (self.n,):
+                raise ValueError(f"weights must hold one channel LLR per bit ({self.n}), got shape {weights.shape}")
         colptr, rowval = csc_arrays(M)
         L = _capi.lib()
-        self._create(L, L.ldpc_osd_create, self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data, self.osd_order)
+        # (ldpc_osd_create bounds the reference rule's order; ldpc_osd_set_search sets and bounds the standard rule's)
+        self._create(L, L.ldpc_osd_create, self.s, self.n, int(rowval.size), colptr.ctypes.data, rowval.ctypes.data,
+                     self.osd_order if method == "reference" else 0)
+        if method != "reference":
+            _capi.check(L.ldpc_osd_set_search(self._h, OSD_METHODS[method], self.osd_order, self.n,
+                                              None if weights is None else weights.ctypes.data), L)
 
     def postprocess(self, syn_bs, bp_err_bn, llr_bn, nthreads: int = 0) -> np.ndarray:
         """syn [B][s] u8 (0/1), bp_err [B][n] u8, llr [B][n] f64 -> errors [B][n] u8."""
@@ -80,14 +104,25 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
     decoder's GPU (`OSDPostProcessor.postprocess_device`), so that `batchdecode_device` never leaves the device."""
 
     def __init__(self, H, per: float = None, max_iters: int = None, *, osd_order: int = 0, osd: str = "host",
-                 bp_decoder=None, **bp_kwargs):
+                 bp_decoder=None, osd_method: str = "reference", osd_weights="hamming", **bp_kwargs):
         """bp_decoder: a decoder object to use as `self.bp_decoder` instead of constructing a BeliefPropagationDecoder --
         anything with `decode_batch_host(syn, want_llr=True)`, `decode_batch_device(syn, err, conv, llr, iters)`,
         `.s`, `.n`, `.sparse_H`, `.scratch` and `info().device`, such as a MinSumDecoder.  Its pattern must equal H's
         (ValueError otherwise); `per` and `max_iters` are then IGNORED (the object carries its own priors and iteration
-        count) and no other decoder keyword may be given."""
+        count) and no other decoder keyword may be given.
+        osd_method: "reference" (default), "exhaustive" or "combination_sweep" -- the standard rule, osd="device" only.
+        osd_weights, for the standard rule: "hamming" (all ones), "priors" (log((1 - per) / per), or the `channel_llr`
+        of the bp_decoder= object) or an array of n channel LLRs."""
         if osd not in ("host", "device"):
             raise ValueError('osd must be "host" or "device"')
+        if osd_method not in OSD_METHODS:
+            raise ValueError('osd_method must be "reference", "exhaustive" or "combination_sweep"')
+        if osd_method != "reference" and osd != "device":
+            raise ValueError('osd_method="%s" has a device form only: pass osd="device"' % osd_method)
+        if isinstance(osd_weights, str) and osd_weights not in ("hamming", "priors"):
+            raise ValueError('osd_weights must be "hamming", "priors" or an array of channel LLRs')
+        if osd_method == "reference" and not (isinstance(osd_weights, str) and osd_weights == "hamming"):
+            raise ValueError("the reference rule weighs by count: osd_weights needs another osd_method")
         if bp_decoder is not None:
             if bp_kwargs:
                 raise TypeError("decoder keywords (%s) have no meaning next to bp_decoder=" % ", ".join(sorted(bp_kwargs)))
@@ -103,7 +138,19 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
             self.bp_decoder = BeliefPropagationDecoder(H, per, max_iters, **bp_kwargs)   # :27
         self.H = H                                                                    # :21
         self.osd_order = int(osd_order)                                               # :23
-        self._osd = OSDPostProcessor(H, osd_order)
+        self.osd_method = osd_method
+        if isinstance(osd_weights, str) and osd_weights == "hamming":
+            weights = None
+        elif isinstance(osd_weights, str):   # "priors"
+            if bp_decoder is not None:
+                if getattr(bp_decoder, "channel_llr", None) is None:
+                    raise ValueError('osd_weights="priors": the bp_decoder= object has no channel_llr')
+                weights = np.asarray(bp_decoder.channel_llr, dtype=np.float64)
+            else:
+                weights = np.full(int(_pattern_of(H).shape[1]), np.log((1.0 - per) / per), dtype=np.float64)
+        else:
+            weights = osd_weights
+        self._osd = OSDPostProcessor(H, osd_order, method=osd_method, weights=weights)
         self.osd = osd
         if osd == "device":
             self._osd.prepare_device(self.bp_decoder.info().device)
@@ -161,7 +208,8 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
         GPU.  BP runs on the device; only the syndromes that still need OSD travel to the host:
         with osd_order = 0 a converged syndrome is returned unchanged by the reference's shortcut
         (belief_propagation_osd.jl:66-74: zero residual), so its OSD call is skipped; with
-        osd_order > 0 every syndrome is post-processed, like the reference.
+        osd_order > 0 every syndrome is post-processed, like the reference.  The standard rule (osd_method=) has the
+        shortcut at every order, so only the unconverged syndromes are sent at every order.
         Returns (errors [B][n] uint8 tensor, converged [B] uint8 tensor, number sent to OSD).
         With osd="device" nothing of the payload leaves the GPU: the same two passes for osd_order = 0, the OSD
         kernel on the compacted unconverged rows and an index scatter; for osd_order > 0 one BP pass with LLRs and
@@ -216,12 +264,13 @@ class BeliefPropagationOSDDecoder(AbstractDecoder):
         dev = syn.device
         err = torch.empty((B, bp.n), dtype=torch.uint8, device=dev)
         conv = torch.empty(B, dtype=torch.uint8, device=dev)
-        if self.osd_order > 0:
+        if self.osd_order > 0 and self.osd_method == "reference":
             llr = torch.empty((B, bp.n), dtype=torch.float64, device=dev)
             bp.decode_batch_device(syn, err, conv, llr, None)
             if B:
                 self._osd.postprocess_device(syn, err, llr, out=err)
             return err, conv, B
+        # order 0, and the standard rule at every order (its step 1 returns a converged estimate unchanged)
         if getattr(self, "_osd_frac", 0.0) <= 0.2:
             # two passes, as on the host path: no 8n-byte LLR row for the syndromes BP converges on
             bp.decode_batch_device(syn, err, conv, None, None)
