@@ -1109,6 +1109,103 @@ typedef struct ldpc_decim_options {
 #include "ldpc_mi355x_decim.h"
 
 /* ------------------------------------------------------------------------
+ * Pauli relay min-sum decoder: the joint X/Z (Pauli) min-sum of ldpc_pauli_minsum_* run with the per-qubit MEMORY and the
+ * chain of LEGS of ldpc_relay_*, returning the Pauli solution of lowest prior weight among the first `stop_after` it finds.
+ * One decoder over both check matrices of a CSS code (three beliefs a qubit, so the correlation a Y error puts between
+ * the two sides is used) that also gets out of the stalls of plain min-sum on degenerate graphs.  Not a decoder of the
+ * reference.  Like its two parents it has no division and no transcendental function, so THE RULE below has one legal
+ * outcome in IEEE binary32 and a numpy model equals the device in every bit, LLRs included.  Flooding schedule only.
+ *
+ * Inputs.  n, hx (rx >= 1 rows), hz (rz >= 1 rows), prior_x[n], prior_y[n], prior_z[n]: as ldpc_pauli_minsum_create takes
+ * them.  legs >= 1; gammas[legs][n] binary32, the memory strengths, each finite with -1 < gamma < 1: one strength per qubit
+ * and leg, shared by its three beliefs; leg_iters[legs] int32, each >= 0, their sum at most INT32_MAX; stop_after >= 1
+ * (default 1); alpha, clip: as ldpc_minsum_create takes them.  The checks are numbered Hx rows first (0 .. rx - 1), then Hz
+ * rows (rx .. rx + rz - 1).  Syndromes sx [batch][rx] (= Hx ez) and sz [batch][rz] (= Hz ex); an entry that is not 0 counts
+ * as 1.  The library draws no random number and calls no log: the caller supplies priors and gammas.
+ *
+ * THE RULE.  All arithmetic is binary32, every operation rounded once (no fused multiply-add), subnormals kept.
+ * min(x, y) below means  x < y ? x : y  with the operands in the order given.
+ * Derived once per handle, for W = X, Y, Z:
+ *   g0W[r][j] = (1.0f - gammas[r][j]) * prior_W[j]                       (one subtraction, one multiplication)
+ *   qW[j]     = (int64) rint(clamp((double) prior_W[j], -2^24, 2^24) * 2^16)        (the product is exact in double)
+ * n > 2^22 answers LDPC_ERR_UNSUPPORTED, so a weight (a sum of one q per qubit) always fits int64.
+ * State per syndrome: the posteriors MX[j], MY[j], MZ[j], initially prior_x[j], prior_y[j], prior_z[j]; the totals TX[j],
+ * TZ[j]; the check-to-qubit messages c[i][j]; found = 0, iters = 0; best, a Pauli pattern, and its weight best_w.
+ * For leg r = 0 .. legs - 1 (a leg with leg_iters[r] = 0 is skipped):
+ *   Leg start.  Every c <- +0;  every TX[j], TZ[j] <- +0.
+ *   Derived wherever read, with the M that stands at that moment:
+ *     LambdaW[j] = g0W[r][j] + gammas[r][j] * MW[j]   (multiply, then add)   for W = X, Y, Z;
+ *     GX[j] = LambdaX[j] + TX[j];   GZ[j] = LambdaZ[j] + TZ[j];   GY[j] = (LambdaY[j] + TX[j]) + TZ[j].
+ *   For t = 1 .. leg_iters[r]:
+ *     1. Check sweep: step 1 of THE RULE of ldpc_pauli_minsum_* on these G, verbatim -- u_k and w_k by the kind of row,
+ *        b_k = min(max((u_k - c[i][j_k]) - w_k, -clip), clip), the ascending scan for m1, m2, a, par from the check's own
+ *        syndrome entry, the new message alpha * (k == a ? m2 : m1) with its sign bit set iff par XOR neg_k (-0 included);
+ *        all b_k of a check are formed from the old state; a check with no qubits sends nothing.
+ *     2. Bit sweep, for every j.  The new TX[j] = ((+0 + c[i_0][j]) + c[i_1][j]) + ... over the Hz checks of j in ascending
+ *        order, the new TZ[j] the same sum over the Hx checks of j.  With LambdaW from the OLD M:
+ *          MX[j] = LambdaX[j] + TX[j];   MZ[j] = LambdaZ[j] + TZ[j];   MY[j] = (LambdaY[j] + TX[j]) + TZ[j].
+ *        (The next check sweep forms its G with LambdaW from this NEW M and the same TX, TZ.)  Decision on (MX, MY, MZ)
+ *        exactly as ldpc_pauli_minsum_* decides on (GX, GY, GZ):  best = X, g = MX;  if MZ < g { best = Z, g = MZ };
+ *        if MY < g { best = Y, g = MY };  E = (g <= 0) ? best : I;  ex[j] = (E is X or Y);  ez[j] = (E is Z or Y).
+ *        iters += 1.
+ *     3. Test.  If Hz ex == sz and Hx ez == sx (an empty check is matched only by a 0 entry):  w = the sum over j of
+ *        qX[j] where E is X, qY[j] where it is Y, qZ[j] where it is Z, 0 where it is I, in int64 (exact, so any summation
+ *        order is legal);  if found == 0 or w < best_w: best = (ex, ez), best_w = w (a tie keeps the earlier solution);
+ *        found += 1;  if found == stop_after the syndrome stops, otherwise the leg ends and the next leg starts from
+ *        this M.
+ *   A leg that uses up leg_iters[r] without a solution ends, and the next starts from its M.
+ * After the last leg the syndrome stops.
+ *
+ * Outputs.  gx [batch][n] uint8 and gz [batch][n] uint8: the X part and the Z part of best if found > 0, else the decision
+ * on (MX, MY, MZ) as they stand; converged [batch] uint8 = (found > 0); iters [batch] int32 (may be NULL): the total over
+ * all legs; solutions [batch] int32 (may be NULL) = found; llr [batch][3][n] DOUBLE (may be NULL): the planes MX, MY, MZ as
+ * they stand when the syndrome stops, widened exactly -- with found > 1 that is the M of the LAST solution (or of the last
+ * iteration), not necessarily the M of `best`.  Every leg of 0 iterations: zeros everywhere (converged = 0, llr = 0,
+ * iters = 0, solutions = 0).  batch = 0: LDPC_OK, nothing touched.
+ *
+ * Consequence.  With legs = 1, gammas all 0, stop_after = 1 and no prior equal to -0, every output equals
+ * ldpc_pauli_minsum_* with max_iters = leg_iters[0] in every bit, the LLR planes included:  (1 - 0) * p = p,
+ * p + (+-0) = p, so LambdaW = prior_W and M is the G of that rule after every bit sweep.
+ *
+ * ldpc_pauli_relay_kernel: 1 = on-chip (the state of the S <= 64 syndromes a workgroup holds lives in LDS for the whole
+ * decode: the three G the check sweep reads, MX, MY, MZ, the check records of both sides, a bit plane each for the X part
+ * and the Z part of best, the syndromes; needs (4 (6 n + record words + 2 ceil(n / 32)) + rx + rz) bytes <= 159 KiB for
+ * one syndrome, records as in ldpc_minsum_kernel); 2 = unlimited (tiles of 64 syndromes in a workspace the handle owns,
+ * sized by the resident workgroups); 0 for NULL.  options->kernel_variant 0 = by size, 1 / 2 force a tier (1 where the
+ * state does not fit: LDPC_ERR_UNSUPPORTED).  ldpc_pauli_relay_tile_syndromes and ldpc_pauli_relay_last_grid: as
+ * ldpc_minsum_tile_syndromes and ldpc_minsum_last_grid, by the same policy over that state.  A tile ends with its last
+ * syndrome.
+ *
+ * ldpc_pauli_relay_create answers LDPC_ERR_INVALID_ARGUMENT -- before any device work -- for everything
+ * ldpc_pauli_minsum_create and ldpc_relay_create refuse: a NULL or non-finite prior, a NULL gammas or leg_iters, a gamma
+ * that is not finite or outside (-1, 1), legs < 1, a negative leg_iters entry, a leg_iters sum beyond INT32_MAX,
+ * stop_after < 0 (0 = default 1), alpha outside (0, 1], clip not in (0, inf), a kernel_variant outside 0..2, a NULL pattern
+ * or one ldpc_bp_create rejects on either side, and rx < 1 or rz < 1; without a device LDPC_ERR_NO_DEVICE.  The library
+ * does not check that Hx and Hz commute.  The decode entries reject a NULL handle, a negative batch and a NULL required
+ * pointer the same way.  ldpc_pauli_relay_decode_batch takes HOST buffers and is synchronous (its wait is bounded by
+ * ldpc_set_wait_limit_ms); ldpc_pauli_relay_decode_batch_device takes DEVICE pointers and is asynchronous on `stream`;
+ * calls on one handle run in call order whatever streams they are given.
+ *
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+typedef struct ldpc_pauli_relay_decoder ldpc_pauli_relay_decoder;
+
+/* Optional; pass NULL to ldpc_pauli_relay_create for defaults.  A zeroed struct means defaults too, except `device` (0 is
+ * device 0; -1 = the current one): alpha = 0 / clip = 0 / stop_after = 0 select 0.75 / 1.0e6f / 1. */
+typedef struct ldpc_pauli_relay_options {
+    int32_t device;          /* HIP device ordinal; -1 = current device */
+    float alpha;             /* normalisation factor in (0, 1]; 0 = default 0.75 */
+    float clip;              /* clamp of the qubit-to-check values, finite, > 0; 0 = default 1.0e6f */
+    int32_t kernel_variant;  /* 0 = auto; 1, 2 force that tier of ldpc_pauli_relay_kernel */
+    int32_t stop_after;      /* solutions to collect before a syndrome stops; 0 = default 1 */
+    int32_t reserved[11];
+} ldpc_pauli_relay_options;
+
+/* The seven ldpc_pauli_relay_* functions are declared in ldpc_mi355x_pauli_relay.h, which this header includes here: this
+ * file and ldpc_mi355x_debug.h keep the functions they declared before the section was added. */
+#include "ldpc_mi355x_pauli_relay.h"
+
+/* ------------------------------------------------------------------------
  * Sliding-window decoding: the step between two windows.  A model H (D detectors x N mechanisms, zero-based CSC) too
  * long to decode in one piece is decoded window by window: window k sees the detectors det_k and the mechanisms mech_k,
  * any decoder of this library decodes its syndromes against H[det_k, mech_k], the first mechanisms of its guess --

@@ -90,6 +90,14 @@ ldpc_status ldpc_debug_pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, 
    over that size.  Out and statuses as there.  No reference counterpart. */
 #include "ldpc_mi355x_decim_debug.h"   /* (declares it: this header keeps the hooks it declared before) */
 
+/* The plan of a Pauli relay min-sum handle -- csrc/tile_plan.hpp pauli_relay_tile_plan(), the function
+   ldpc_pauli_relay_create calls; s = rx + rz and rec_words count the checks of both sides.  A tile of S syndromes has a
+   state of  S (4 (6 n + rec_words + 2 ceil(n / 32)) + s)  bytes (the three beliefs the check sweep reads, the three
+   posteriors, the check records, a bit plane each for the X part and the Z part of the lightest solution, the syndromes),
+   rounded up to 256, and the policy of ldpc_debug_tile_plan runs over that size.  Out and statuses as there.  No reference
+   counterpart. */
+#include "ldpc_mi355x_pauli_relay_debug.h"   /* (declares ldpc_debug_pauli_relay_tile_plan) */
+
 /* The layers ldpc_minsum_create gives a handle of the layered schedule (options->schedule = 1; THE LAYERED RULE of
    include/ldpc_mi355x.h) -- csrc/layer_plan.hpp layer_plan_build(), the function create calls, followed by the same
    verification (no two checks of a layer share a bit, every non-empty check in exactly one layer).  H as the zero-based

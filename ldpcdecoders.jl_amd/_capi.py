@@ -110,6 +110,14 @@ class PauliMinSumOptions(ctypes.Structure):
     ]
 
 
+class PauliRelayOptions(ctypes.Structure):
+    """ldpc_pauli_relay_options: alpha = 0 / clip = 0 / stop_after = 0 select the defaults (0.75, 1e6, 1)."""
+    _fields_ = [
+        ("device", ctypes.c_int32), ("alpha", ctypes.c_float), ("clip", ctypes.c_float),
+        ("kernel_variant", ctypes.c_int32), ("stop_after", ctypes.c_int32), ("reserved", ctypes.c_int32 * 11),
+    ]
+
+
 class TrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
@@ -266,11 +274,27 @@ OSD_SEARCH_API = {
     "ldpc_osd_search_method": (i32, [vp]),
     "ldpc_osd_search_weight": (i64, [vp, i64]),
 }
+# The Pauli relay min-sum decoder: include/ldpc_mi355x_pauli_relay.h (a part of ldpc_mi355x.h) and its test hook,
+# include/ldpc_mi355x_pauli_relay_debug.h (a part of ldpc_mi355x_debug.h), bound the same way.
+PAULI_RELAY_API = {
+    "ldpc_pauli_relay_create": (i32, [i64, P(CSSPattern), P(CSSPattern), vp, vp, vp, i64, vp, vp, P(PauliRelayOptions), P(vp)]),
+    "ldpc_pauli_relay_destroy": (i32, [vp]),
+    "ldpc_pauli_relay_kernel": (i32, [vp]),
+    "ldpc_pauli_relay_tile_syndromes": (i32, [vp]),
+    "ldpc_pauli_relay_last_grid": (i32, [vp]),
+    "ldpc_pauli_relay_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ldpc_pauli_relay_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+PAULI_RELAY_DEBUG_API = {
+    "ldpc_debug_pauli_relay_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
+}
 EXPORTED_SYMBOLS = tuple(API)
 DEBUG_SYMBOLS = tuple(DEBUG_API)
 DECIM_SYMBOLS = tuple(DECIM_API)
 DECIM_DEBUG_SYMBOLS = tuple(DECIM_DEBUG_API)
 OSD_SEARCH_SYMBOLS = tuple(OSD_SEARCH_API)
+PAULI_RELAY_SYMBOLS = tuple(PAULI_RELAY_API)
+PAULI_RELAY_DEBUG_SYMBOLS = tuple(PAULI_RELAY_DEBUG_API)
 
 
 def build(force: bool = False) -> str:
@@ -308,7 +332,7 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
                            "or `make -C ldpcdecoders.jl_amd/csrc`. There is no CPU fallback.")
     _one_hip_runtime()
     L = ctypes.CDLL(path)
-    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API, OSD_SEARCH_API):
+    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API, OSD_SEARCH_API, PAULI_RELAY_API, PAULI_RELAY_DEBUG_API):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
