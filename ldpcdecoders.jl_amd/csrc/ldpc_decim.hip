@@ -1,8 +1,10 @@
 // ldpc_decim.hip -- host side of the guided-decimation min-sum decoder (min-sum in rounds; a round that does not converge
 // hard-fixes the most reliable undecided bit and the next one goes on from the same messages): the ldpc_decim_* entry
 // points of include/ldpc_mi355x.h (the rule is stated there).  Device code: decim_kernels.hpp.  The tiers
-// (ldpc_decim_kernel) and the tile width: tile_plan.hpp, over the decimation state; the launch geometry and the rest of
-// what the min-sum family shares on the host: tile_host.hpp.  No CPU path.
+// (ldpc_decim_kernel) and the tile width: tile_plan.hpp, over the decimation state.  Shared with the rest of the min-sum
+// family (tile_host.hpp): the graph of a handle, the check of an entry's arguments, the launch (tile_run) and its geometry,
+// the staging of the host-pointer entry, the end of a create.  Here: the order of the create's checks and DecimParams.
+// No CPU path.
 #include "../../include/ldpc_mi355x.h"
 #include "../../include/ldpc_mi355x_debug.h"
 #include "decim_kernels.hpp"
@@ -16,7 +18,6 @@
 
 using namespace ldpc;
 
-#include "host_env.hpp"      // exp_env: LDPC_MS_GRID_MAX, experiments build only
 #include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
 #include "tile_host.hpp"
 using ldpc_detail::set_error;
@@ -25,17 +26,21 @@ struct ldpc_decim_decoder {
     int64_t s = 0, n = 0, nnz = 0;
     int round_iters = 0, max_dec = 0;
     float alpha = 0.0f, clip = 0.0f, pin = 0.0f;
-    int rec_words = 0;
     TilePlan plan;
-    int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *edge_rec = nullptr, *edge_pos = nullptr;
     float *prior = nullptr;
-    ldpc_detail::TileHost tile;   // (grid_max: LDPC_MS_GRID_MAX of the experiments build)
+    ldpc_detail::TileHost tile;   // the graph and what a launch needs (grid_max: LDPC_MS_GRID_MAX of the experiments build)
     ldpc_detail::TileKernel kernel;
-    ~ldpc_decim_decoder() { tile.release({row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, prior}); }
+    ~ldpc_decim_decoder() { tile.release({prior}); }
 };
 
 typedef void (*decim_kernel_t)(DecimParams);
 static decim_kernel_t decim_kernel_of(int tier) { return tier == 1 ? decim_kernel<ldpc_detail::kTileLdsWaves, false> : decim_kernel<ldpc_detail::kTileGlobalWaves, true>; }
+
+// what every entry checks before any device work; batch == 0 is the caller's to answer
+static ldpc_status decim_check_batch(const ldpc_decim_decoder *d, int64_t batch, const void *syn, const void *err, const void *conv)
+{
+    return ldpc_detail::tile_check_batch(d, batch, {{syn, &ldpc_decim_decoder::s}, {err, &ldpc_decim_decoder::n}, {conv, nullptr}});
+}
 
 extern "C" {
 
@@ -64,34 +69,20 @@ ldpc_status ldpc_decim_create(int64_t s, int64_t n, int64_t nnz, const int64_t *
     hipDeviceProp_t prop;
     if ((st = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (this library has no CPU fallback)")) != LDPC_OK)
         return st;
-    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
-        return set_error(LDPC_ERR_UNSUPPORTED, "decimation kernels: graph too large for 32-bit edge indexing");
+    if ((st = ldpc_detail::tile_index_limits("decimation", s, n, nnz, true)) != LDPC_OK) return st;
 
     ldpc_decim_decoder *d = new (std::nothrow) ldpc_decim_decoder();
     if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     d->s = s; d->n = n; d->nnz = nnz; d->alpha = alpha; d->clip = clip; d->pin = pin;
     d->round_iters = (int)round_iters; d->max_dec = (int)max_decimations;
     d->tile.device = device; d->tile.num_cus = prop.multiProcessorCount;
-    // CSR (checks -> bits, ascending) next to the caller's CSC; a record per check; per CSC edge its record and position
-    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
-    const MsRecords rec = ms_records(s, nnz, g.row_ptr.data(), g.csc_row.data(), g.csc2csr.data());   // words <= 4 s + nnz < 2^31
-    d->rec_words = (int)rec.words;
-    if (!decim_tile_plan(s, n, rec.words, variant, &d->plan)) {
+    d->tile.graph.build(s, n, nnz, colptr, rowval);
+    if (!decim_tile_plan(s, n, d->tile.graph.rec.words, variant, &d->plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
-    if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->tile.grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
-    using ldpc_detail::upload;
-    bool ok = upload(&d->row_ptr, g.row_ptr) && upload(&d->csr_col, g.csr_col) && upload(&d->rec_off, rec.rec_off) &&
-              upload(&d->col_ptr, g.col_ptr) && upload(&d->edge_rec, rec.edge_rec) && upload(&d->edge_pos, rec.edge_pos) &&
-              upload(&d->prior, std::vector<float>(channel_llr, channel_llr + n)) && d->tile.calls.create() == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete d;
-        return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the Tanner graph failed");
-    }
-    *out = d;
-    return LDPC_OK;
+    ldpc_detail::tile_grid_max_env(&d->tile);
+    return ldpc_detail::tile_create_finish(d, out, [&] { return ldpc_detail::upload(&d->prior, std::vector<float>(channel_llr, channel_llr + n)); });
 }
 
 // (include/ldpc_mi355x_debug.h) the choice create makes, without a device
@@ -114,54 +105,28 @@ ldpc_status ldpc_decim_destroy(ldpc_decim_decoder *d) { return ldpc_detail::tile
 ldpc_status ldpc_decim_decode_batch_device(ldpc_decim_decoder *d, int64_t batch, const uint8_t *d_syn, uint8_t *d_err,
                                            uint8_t *d_conv, double *d_llr, int32_t *d_iters, int32_t *d_decimated, void *stream_v)
 {
-    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    if (batch == 0) return LDPC_OK;
-    if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
-    if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-    hipStream_t stream = (hipStream_t)stream_v;
-    LDPC_HIP_TRY(hipSetDevice(d->tile.device));
-    if (ldpc_detail::device_stalled(d->tile.device)) return ldpc_detail::stalled_error(d->tile.device);
-    ldpc_status st = d->tile.calls.enter(stream);
-    if (st != LDPC_OK) return st;
-    if (d->round_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
-        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
-        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_llr && d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * d->n * sizeof(double), stream));
-        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
-        if (d_decimated) LDPC_HIP_TRY(hipMemsetAsync(d_decimated, 0, (size_t)batch * sizeof(int32_t), stream));
-    } else {
-        const decim_kernel_t k = decim_kernel_of(d->plan.tier);
-        const int threads = ldpc_detail::tile_threads(d->plan.tier);
-        int64_t grid;
-        size_t lds;
-        st = ldpc_detail::tile_geometry(&d->tile, &d->kernel, (const void *)k, threads, d->plan, batch,
-                                        "decimation workspace regrow (device synchronise before the free)", &grid, &lds);
-        if (st != LDPC_OK) return st;
-        DecimParams p{};
-        p.s = (int)d->s; p.n = (int)d->n; p.round_iters = d->round_iters; p.max_dec = d->max_dec;
-        p.total_iters = d->round_iters * (d->max_dec + 1);   // (create: fits int32)
-        p.S = d->plan.S; p.shift = d->plan.shift;
-        p.batch = batch; p.alpha = d->alpha; p.clip = d->clip; p.pin = d->pin;
-        p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters; p.decimated = d_decimated;
-        p.prior = d->prior;
-        p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
-        p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
-        p.ws = d->tile.ws; p.slot_bytes = (long long)d->plan.state_bytes;
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
-        LDPC_HIP_TRY(hipGetLastError());
-        d->tile.last_grid = (int)grid;
-    }
-    return d->tile.calls.leave(stream);
+    const ldpc_status st = decim_check_batch(d, batch, d_syn, d_err, d_conv);
+    if (st != LDPC_OK || batch == 0) return st;
+    const size_t B = (size_t)batch, n = (size_t)d->n;
+    if (d->round_iters == 0)   // no iteration runs
+        return ldpc_detail::tile_zero(&d->tile, (hipStream_t)stream_v,
+                                      {{d_err, B * n}, {d_conv, B}, {d_llr, B * n * sizeof(double)}, {d_iters, B * 4}, {d_decimated, B * 4}});
+    return ldpc_detail::tile_run(&d->tile, &d->kernel, decim_kernel_of(d->plan.tier), d->plan, batch, (hipStream_t)stream_v,
+                                 "decimation workspace regrow (device synchronise before the free)", [&](DecimParams &p) {
+                                     d->tile.fill(p, d->plan, batch);
+                                     p.s = (int)d->s; p.n = (int)d->n; p.round_iters = d->round_iters; p.max_dec = d->max_dec;
+                                     p.total_iters = d->round_iters * (d->max_dec + 1);   // (create: fits int32)
+                                     p.alpha = d->alpha; p.clip = d->clip; p.pin = d->pin;
+                                     p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters; p.decimated = d_decimated;
+                                     p.prior = d->prior;
+                                 });
 }
 
 ldpc_status ldpc_decim_decode_batch(ldpc_decim_decoder *d, int64_t batch, const uint8_t *syn, uint8_t *err, uint8_t *conv,
                                     double *llr, int32_t *iters, int32_t *decimated)
 {
-    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    if (batch == 0) return LDPC_OK;
-    if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
+    const ldpc_status st = decim_check_batch(d, batch, syn, err, conv);
+    if (st != LDPC_OK || batch == 0) return st;
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
     ldpc_detail::StageRegion r[] = {{syn, nullptr, B * s},   {nullptr, err, B * n},       {nullptr, conv, B},
                                     {nullptr, iters, B * 4}, {nullptr, decimated, B * 4}, {nullptr, llr, llr ? B * n * sizeof(double) : 0}};

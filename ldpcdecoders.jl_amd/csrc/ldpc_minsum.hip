@@ -1,8 +1,10 @@
 // ldpc_minsum.hip -- host side of the normalised min-sum decoder with per-bit channel LLRs: the ldpc_minsum_* entry
 // points of include/ldpc_mi355x.h (the rule is stated there).  Device code: minsum_kernels.hpp (the flooding schedule) and
 // layered_kernels.hpp (the layered one, over the layers of layer_plan.hpp).  The tiers (ldpc_minsum_kernel) and the tile
-// width of both schedules: tile_plan.hpp; the launch geometry, the staging of the host-pointer entries and the rest of
-// what the min-sum family shares on the host: tile_host.hpp.  The entries with per-syndrome priors (decode_batch_priors /
+// width of both schedules: tile_plan.hpp.  Shared with the rest of the min-sum family (tile_host.hpp): the graph of a
+// handle, the check of an entry's arguments, the launch (tile_run) and its geometry, the staging of the host-pointer
+// entries, the end of a create.  Here: the order of the create's checks, the choice among the six kernels and their three
+// Params structs (ms_launch), the layers.  The entries with per-syndrome priors (decode_batch_priors /
 // decode_batch_given) run the same kernel templates with another prior source and, in the flooding schedule, a larger
 // state (the staged priors): a handle holds a second plan for them (priors_tile_plan), computed at create.  No CPU path.
 #include "../../include/ldpc_mi355x.h"
@@ -20,7 +22,6 @@
 
 using namespace ldpc;
 
-#include "host_env.hpp"      // exp_env: LDPC_MS_GRID_MAX, experiments build only
 #include "host_common.hpp"   // set_error, LDPC_HIP_TRY, the create-time scaffolding and (host_wait.hpp) the bounded waits
 #include "tile_host.hpp"
 using ldpc_detail::set_error;
@@ -30,17 +31,15 @@ using ldpc_detail::kTileGlobalWaves;
 struct ldpc_minsum_decoder {
     int64_t s = 0, n = 0, nnz = 0, max_iters = 0;
     float alpha = 0.0f, clip = 0.0f;
-    int rec_words = 0;
     TilePlan plan;              // of the plain entries
     TilePlan pplan;             // of the priors / given entries; tier 0: kernel_variant 1 and their state does not fit
     int schedule = 0, layers = 0;   // 1 = layered: K layers, layer_ptr [K + 1] and layer_checks on the device
     int *layer_ptr = nullptr, *layer_checks = nullptr;
-    int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *edge_rec = nullptr, *edge_pos = nullptr;
     float *prior = nullptr;
     float *cond = nullptr;      // [2][n]: llr_if0, llr_if1, once ldpc_minsum_set_conditional_priors has been called
-    ldpc_detail::TileHost tile;            // (grid_max: LDPC_MS_GRID_MAX of the experiments build)
+    ldpc_detail::TileHost tile;            // the graph and what a launch needs (grid_max: LDPC_MS_GRID_MAX of the experiments build)
     ldpc_detail::TileKernel kernels[3];    // per prior source (kMsPrior*): each is a kernel function of its own
-    ~ldpc_minsum_decoder() { tile.release({row_ptr, csr_col, rec_off, col_ptr, edge_rec, edge_pos, layer_ptr, layer_checks, prior, cond}); }
+    ~ldpc_minsum_decoder() { tile.release({layer_ptr, layer_checks, prior, cond}); }
 };
 
 typedef void (*ms_kernel_t)(MsParams);
@@ -67,66 +66,35 @@ template <int SRC> static layered_priors_kernel_t layered_priors_kernel_of(int t
 static ldpc_status ms_launch(ldpc_minsum_decoder *d, int src_kind, const MsPriorSource &src, int64_t batch, const uint8_t *d_syn,
                              uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters, hipStream_t stream)
 {
-    LDPC_HIP_TRY(hipSetDevice(d->tile.device));
-    if (ldpc_detail::device_stalled(d->tile.device)) return ldpc_detail::stalled_error(d->tile.device);
-    ldpc_status st = d->tile.calls.enter(stream);
-    if (st != LDPC_OK) return st;
-    if (d->max_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
-        if (d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * d->n, stream));
-        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_llr && d->n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * d->n * sizeof(double), stream));
-        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
-    } else {
-        const bool staged = src_kind != kMsPriorTable, layered = d->schedule == 1;
-        const TilePlan &plan = staged ? d->pplan : d->plan;
-        const int tier = plan.tier, threads = ldpc_detail::tile_threads(tier);
-        const void *k;
-        if (src_kind == kMsPriorFloats)
-            k = layered ? (const void *)layered_priors_kernel_of<kMsPriorFloats>(tier) : (const void *)ms_priors_kernel_of<kMsPriorFloats>(tier);
-        else if (src_kind == kMsPriorGiven)
-            k = layered ? (const void *)layered_priors_kernel_of<kMsPriorGiven>(tier) : (const void *)ms_priors_kernel_of<kMsPriorGiven>(tier);
-        else
-            k = layered ? (const void *)layered_kernel_of(tier) : (const void *)ms_kernel_of(tier);
-        int64_t grid;
-        size_t lds;
-        st = ldpc_detail::tile_geometry(&d->tile, &d->kernels[src_kind], k, threads, plan, batch,
-                                        "min-sum workspace regrow (device synchronise before the free)", &grid, &lds);
-        if (st != LDPC_OK) return st;
-        MsParams p{};
-        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = plan.S; p.shift = plan.shift;
-        p.batch = batch; p.alpha = d->alpha; p.clip = d->clip;
-        p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
-        p.prior = d->prior; p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off;
-        p.col_ptr = d->col_ptr; p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
-        p.ws = d->tile.ws; p.slot_bytes = (long long)plan.state_bytes;
-        const dim3 g((unsigned)grid), b((unsigned)threads);
-        if (layered) {
-            LayeredPriorsParams lp{};
-            lp.ms = p; lp.K = d->layers; lp.layer_ptr = d->layer_ptr; lp.layer_checks = d->layer_checks; lp.src = src;
-            if (src_kind == kMsPriorFloats) hipLaunchKernelGGL(layered_priors_kernel_of<kMsPriorFloats>(tier), g, b, lds, stream, lp);
-            else if (src_kind == kMsPriorGiven) hipLaunchKernelGGL(layered_priors_kernel_of<kMsPriorGiven>(tier), g, b, lds, stream, lp);
-            else hipLaunchKernelGGL(layered_kernel_of(tier), g, b, lds, stream, (const LayeredParams &)lp);
-        } else {
-            MsPriorsParams pp{};
-            (MsParams &)pp = p; pp.src = src;
-            if (src_kind == kMsPriorFloats) hipLaunchKernelGGL(ms_priors_kernel_of<kMsPriorFloats>(tier), g, b, lds, stream, pp);
-            else if (src_kind == kMsPriorGiven) hipLaunchKernelGGL(ms_priors_kernel_of<kMsPriorGiven>(tier), g, b, lds, stream, pp);
-            else hipLaunchKernelGGL(ms_kernel_of(tier), g, b, lds, stream, p);
-        }
-        LDPC_HIP_TRY(hipGetLastError());
-        d->tile.last_grid = (int)grid;
-    }
-    return d->tile.calls.leave(stream);
+    const size_t B = (size_t)batch, n = (size_t)d->n;
+    if (d->max_iters == 0)   // no iteration runs
+        return ldpc_detail::tile_zero(&d->tile, stream, {{d_err, B * n}, {d_conv, B}, {d_llr, B * n * sizeof(double)}, {d_iters, B * 4}});
+    const bool staged = src_kind != kMsPriorTable, layered = d->schedule == 1;
+    const TilePlan &plan = staged ? d->pplan : d->plan;
+    const int tier = plan.tier;
+    const auto run = [&](auto kernel, auto fill) {
+        return ldpc_detail::tile_run(&d->tile, &d->kernels[src_kind], kernel, plan, batch, stream,
+                                     "min-sum workspace regrow (device synchronise before the free)", fill);
+    };
+    const auto table = [&](MsParams &p) {
+        d->tile.fill(p, plan, batch);
+        p.s = (int)d->s; p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.alpha = d->alpha; p.clip = d->clip;
+        p.syn = d_syn; p.err = d_err; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters; p.prior = d->prior;
+    };
+    const auto sourced = [&](MsPriorsParams &pp) { table(pp); pp.src = src; };
+    const auto layers = [&](LayeredParams &lp) { table(lp.ms); lp.K = d->layers; lp.layer_ptr = d->layer_ptr; lp.layer_checks = d->layer_checks; };
+    const auto layers_sourced = [&](LayeredPriorsParams &lp) { layers(lp); lp.src = src; };
+    if (src_kind == kMsPriorFloats)
+        return layered ? run(layered_priors_kernel_of<kMsPriorFloats>(tier), layers_sourced) : run(ms_priors_kernel_of<kMsPriorFloats>(tier), sourced);
+    if (src_kind == kMsPriorGiven)
+        return layered ? run(layered_priors_kernel_of<kMsPriorGiven>(tier), layers_sourced) : run(ms_priors_kernel_of<kMsPriorGiven>(tier), sourced);
+    return layered ? run(layered_kernel_of(tier), layers) : run(ms_kernel_of(tier), table);
 }
 
-// what every device entry checks before any device work; batch == 0 is the caller's to answer
+// what every entry checks before any device work; batch == 0 is the caller's to answer
 static ldpc_status ms_check_batch(const ldpc_minsum_decoder *d, int64_t batch, const void *syn, const void *err, const void *conv)
 {
-    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    if (batch == 0) return LDPC_OK;
-    if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
-    return LDPC_OK;
+    return ldpc_detail::tile_check_batch(d, batch, {{syn, &ldpc_minsum_decoder::s}, {err, &ldpc_minsum_decoder::n}, {conv, nullptr}});
 }
 
 // ... and the priors / given entries on top: their own pointer, the tables of the given form, the second plan
@@ -137,7 +105,6 @@ static ldpc_status ms_check_priors(const ldpc_minsum_decoder *d, int64_t batch, 
     if (st != LDPC_OK) return st;
     if (given && !d->cond) return set_error(LDPC_ERR_INVALID_ARGUMENT, "no conditional priors are set (ldpc_minsum_set_conditional_priors)");
     if (batch > 0 && d->n > 0 && !per_syndrome) return set_error(LDPC_ERR_INVALID_ARGUMENT, given ? "given pointer is NULL" : "priors pointer is NULL");
-    if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
     if (d->pplan.tier == 0)
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome with its priors does not fit the on-chip tier");
     return LDPC_OK;
@@ -181,22 +148,20 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
     hipDeviceProp_t prop;
     if ((st = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (this library has no CPU fallback)")) != LDPC_OK)
         return st;
-    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
-        return set_error(LDPC_ERR_UNSUPPORTED, "min-sum kernels: graph too large for 32-bit edge indexing");
+    if ((st = ldpc_detail::tile_index_limits("min-sum", s, n, nnz, true)) != LDPC_OK) return st;
 
     ldpc_minsum_decoder *d = new (std::nothrow) ldpc_minsum_decoder();
     if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     d->s = s; d->n = n; d->nnz = nnz; d->max_iters = max_iters; d->alpha = alpha; d->clip = clip;
     d->tile.device = device; d->tile.num_cus = prop.multiProcessorCount; d->schedule = schedule;
-    // CSR (checks -> bits, ascending) next to the caller's CSC; a record per check; per CSC edge its record and position
-    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
-    const MsRecords rec = ms_records(s, nnz, g.row_ptr.data(), g.csc_row.data(), g.csc2csr.data());   // words <= 4 s + nnz < 2^31
-    d->rec_words = (int)rec.words;
-    if (!tile_plan(s, n, rec.words, false, variant, &d->plan)) {
+    d->tile.graph.build(s, n, nnz, colptr, rowval);
+    const ldpc_detail::TannerGraph &g = d->tile.graph.host;
+    const int64_t words = d->tile.graph.rec.words;
+    if (!tile_plan(s, n, words, false, variant, &d->plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
     }
-    if (!priors_tile_plan(s, n, rec.words, schedule == 1, variant, &d->pplan)) d->pplan = TilePlan();   // (tier 0: those entries answer UNSUPPORTED)
+    if (!priors_tile_plan(s, n, words, schedule == 1, variant, &d->pplan)) d->pplan = TilePlan();   // (tier 0: those entries answer UNSUPPORTED)
     LayerPlan layers;   // the layered schedule: first-fit layers (layer_plan.hpp), verified before they reach the device
     if (schedule == 1) {
         std::string why;
@@ -211,19 +176,12 @@ ldpc_status ldpc_minsum_create(int64_t s, int64_t n, int64_t nnz, const int64_t 
         }
         d->layers = layers.K;
     }
-    if (const char *e = exp_env("LDPC_MS_GRID_MAX")) d->tile.grid_max = std::max(1, std::atoi(e));   // (experiments build: tests cap the grid)
+    ldpc_detail::tile_grid_max_env(&d->tile);
     using ldpc_detail::upload;
-    bool ok = upload(&d->row_ptr, g.row_ptr) && upload(&d->csr_col, g.csr_col) && upload(&d->rec_off, rec.rec_off) &&
-              upload(&d->col_ptr, g.col_ptr) && upload(&d->edge_rec, rec.edge_rec) && upload(&d->edge_pos, rec.edge_pos) &&
-              (schedule == 0 || (upload(&d->layer_ptr, layers.layer_ptr) && upload(&d->layer_checks, layers.layer_checks))) &&
-              upload(&d->prior, std::vector<float>(channel_llr, channel_llr + n)) && d->tile.calls.create() == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete d;
-        return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the Tanner graph failed");
-    }
-    *out = d;
-    return LDPC_OK;
+    return ldpc_detail::tile_create_finish(d, out, [&] {
+        return (schedule == 0 || (upload(&d->layer_ptr, layers.layer_ptr) && upload(&d->layer_checks, layers.layer_checks))) &&
+               upload(&d->prior, std::vector<float>(channel_llr, channel_llr + n));
+    });
 }
 
 // (include/ldpc_mi355x_debug.h) the choice both create routines make, without a device
@@ -257,8 +215,7 @@ ldpc_status ldpc_debug_layer_plan(int64_t s, int64_t n, const int64_t *colptr, c
     const int64_t nnz = n > 0 ? colptr[n] : 0;
     ldpc_status st = ldpc_detail::check_csc_args(s, n, nnz, colptr, rowval, 0);
     if (st != LDPC_OK || (st = ldpc_detail::check_csc_pattern(s, n, nnz, colptr, rowval)) != LDPC_OK) return st;
-    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
-        return set_error(LDPC_ERR_UNSUPPORTED, "min-sum kernels: graph too large for 32-bit edge indexing");
+    if ((st = ldpc_detail::tile_index_limits("min-sum", s, n, nnz, true)) != LDPC_OK) return st;
     const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr, rowval);
     LayerPlan plan;
     std::string why;
@@ -286,7 +243,6 @@ ldpc_status ldpc_minsum_decode_batch_device(ldpc_minsum_decoder *d, int64_t batc
 {
     const ldpc_status st = ms_check_batch(d, batch, d_syn, d_err, d_conv);
     if (st != LDPC_OK || batch == 0) return st;
-    if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
     return ms_launch(d, kMsPriorTable, MsPriorSource{}, batch, d_syn, d_err, d_conv, d_llr, d_iters, (hipStream_t)stream_v);
 }
 

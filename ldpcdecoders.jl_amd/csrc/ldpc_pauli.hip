@@ -1,9 +1,10 @@
 // ldpc_pauli.hip -- host side of the joint X/Z (Pauli) min-sum decoder of CSS codes: the ldpc_pauli_minsum_* entry points
 // of include/ldpc_mi355x.h (the rule is stated there).  Device code: pauli_kernels.hpp.  The checks of both sides are one
 // Tanner graph here -- Hx rows first, then Hz rows -- so the create-time scaffolding of the binary decoders serves as it
-// is.  The tiers (ldpc_pauli_minsum_kernel) and the tile width: pauli_tile_plan() of tile_plan.hpp; the launch geometry and
-// the rest of what the min-sum family shares on the host: tile_host.hpp.  This unit reads no environment variable.  No CPU
-// path.
+// is.  The tiers (ldpc_pauli_minsum_kernel) and the tile width: pauli_tile_plan() of tile_plan.hpp.  Shared with the rest
+// of the min-sum family (tile_host.hpp): the graph of a handle (with col_mid), the check of an entry's arguments, the launch
+// (tile_run) and its geometry, the staging of the host-pointer entry, the end of a create.  Here: the two sides made one
+// graph, the order of the create's checks and PauliParams.  This unit reads no environment variable.  No CPU path.
 #include "../../include/ldpc_mi355x.h"
 #include "../../include/ldpc_mi355x_debug.h"
 #include "pauli_kernels.hpp"
@@ -23,14 +24,11 @@ using ldpc_detail::set_error;
 struct ldpc_pauli_minsum_decoder {
     int64_t rx = 0, rz = 0, n = 0, max_iters = 0;
     float alpha = 0.0f, clip = 0.0f;
-    int rec_words = 0;
     TilePlan plan;
-    int *row_ptr = nullptr, *csr_col = nullptr, *rec_off = nullptr, *col_ptr = nullptr, *col_mid = nullptr, *edge_rec = nullptr,
-        *edge_pos = nullptr;
     float *priors = nullptr;       // [3][n]: prior_x, prior_y, prior_z
-    ldpc_detail::TileHost tile;    // (grid_max stays 0: no cap)
+    ldpc_detail::TileHost tile;    // the graph (with col_mid) and what a launch needs (grid_max stays 0: no cap)
     ldpc_detail::TileKernel kernel;
-    ~ldpc_pauli_minsum_decoder() { tile.release({row_ptr, csr_col, rec_off, col_ptr, col_mid, edge_rec, edge_pos, priors}); }
+    ~ldpc_pauli_minsum_decoder() { tile.release({priors}); }
 };
 
 typedef void (*pauli_kernel_t)(PauliParams);
@@ -55,12 +53,8 @@ static ldpc_status pauli_check_side(const char *name, const ldpc_css_pattern *m,
 static ldpc_status pauli_check_batch(const ldpc_pauli_minsum_decoder *d, int64_t batch, const void *sx, const void *sz, const void *gx,
                                      const void *gz, const void *conv)
 {
-    if (!d) return set_error(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return set_error(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    if (batch == 0) return LDPC_OK;
-    if (!sx || !sz || (d->n > 0 && (!gx || !gz)) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
-    if (batch > ((int64_t)1 << 40)) return set_error(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-    return LDPC_OK;
+    typedef ldpc_pauli_minsum_decoder D;
+    return ldpc_detail::tile_check_batch(d, batch, {{sx, nullptr}, {sz, nullptr}, {gx, &D::n}, {gz, &D::n}, {conv, nullptr}});
 }
 
 extern "C" {
@@ -90,8 +84,7 @@ ldpc_status ldpc_pauli_minsum_create(int64_t n, const ldpc_css_pattern *hx, cons
     if ((st = ldpc_detail::select_device(device, &device, &prop, "no HIP device available (this library has no CPU fallback)")) != LDPC_OK)
         return st;
     const int64_t rx = hx->rows, rz = hz->rows, s = rx + rz, nnz = hx->nnz + hz->nnz;
-    if (nnz >= ((int64_t)1 << 28) || s >= ((int64_t)1 << 28) || n >= ((int64_t)1 << 28))
-        return set_error(LDPC_ERR_UNSUPPORTED, "Pauli min-sum kernels: graph too large for 32-bit edge indexing");
+    if ((st = ldpc_detail::tile_index_limits("Pauli min-sum", s, n, nnz, true)) != LDPC_OK) return st;
 
     // one graph: the Hx rows, then the Hz rows; a qubit's edges are its Hx checks, then its Hz checks, each ascending
     std::vector<int64_t> colptr((size_t)n + 1, 0), rowval((size_t)std::max<int64_t>(nnz, 1), 0);
@@ -109,14 +102,12 @@ ldpc_status ldpc_pauli_minsum_create(int64_t n, const ldpc_css_pattern *hx, cons
     if (!d) return set_error(LDPC_ERR_OUT_OF_MEMORY, "host allocation failed");
     d->rx = rx; d->rz = rz; d->n = n; d->max_iters = max_iters; d->alpha = alpha; d->clip = clip;
     d->tile.device = device; d->tile.num_cus = prop.multiProcessorCount;
-    const ldpc_detail::TannerGraph g = ldpc_detail::tanner_graph(s, n, nnz, colptr.data(), rowval.data());
-    const MsRecords rec = ms_records(s, nnz, g.row_ptr.data(), g.csc_row.data(), g.csc2csr.data());
-    const int64_t words = rec.words;
+    d->tile.graph.build(s, n, nnz, colptr.data(), rowval.data(), std::move(col_mid));
+    const int64_t words = d->tile.graph.rec.words;
     if (2 * n + words >= ((int64_t)1 << 31)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "Pauli min-sum kernels: the state of one syndrome is too large for 32-bit word indexing");
     }
-    d->rec_words = (int)words;
     if (!pauli_tile_plan(s, n, words, variant, &d->plan)) {
         delete d;
         return set_error(LDPC_ERR_UNSUPPORTED, "kernel_variant 1: the state of one syndrome does not fit the on-chip tier");
@@ -124,17 +115,7 @@ ldpc_status ldpc_pauli_minsum_create(int64_t n, const ldpc_css_pattern *hx, cons
     std::vector<float> priors((size_t)std::max<int64_t>(3 * n, 1), 0.0f);
     for (int k = 0; k < 3; ++k)
         for (int64_t j = 0; j < n; ++j) priors[(size_t)(k * n + j)] = tables[k][j];
-    using ldpc_detail::upload;
-    bool ok = upload(&d->row_ptr, g.row_ptr) && upload(&d->csr_col, g.csr_col) && upload(&d->rec_off, rec.rec_off) &&
-              upload(&d->col_ptr, g.col_ptr) && upload(&d->col_mid, col_mid) && upload(&d->edge_rec, rec.edge_rec) &&
-              upload(&d->edge_pos, rec.edge_pos) && upload(&d->priors, priors) && d->tile.calls.create() == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete d;
-        return set_error(LDPC_ERR_OUT_OF_MEMORY, "device allocation of the Tanner graph failed");
-    }
-    *out = d;
-    return LDPC_OK;
+    return ldpc_detail::tile_create_finish(d, out, [&] { return ldpc_detail::upload(&d->priors, priors); });
 }
 
 // (include/ldpc_mi355x_debug.h) the choice create makes, without a device
@@ -161,41 +142,20 @@ ldpc_status ldpc_pauli_minsum_decode_batch_device(ldpc_pauli_minsum_decoder *d, 
                                                   uint8_t *d_gx, uint8_t *d_gz, uint8_t *d_conv, double *d_llr, int32_t *d_iters,
                                                   void *stream_v)
 {
-    ldpc_status st = pauli_check_batch(d, batch, d_sx, d_sz, d_gx, d_gz, d_conv);
+    const ldpc_status st = pauli_check_batch(d, batch, d_sx, d_sz, d_gx, d_gz, d_conv);
     if (st != LDPC_OK || batch == 0) return st;
-    hipStream_t stream = (hipStream_t)stream_v;
-    LDPC_HIP_TRY(hipSetDevice(d->tile.device));
-    if (ldpc_detail::device_stalled(d->tile.device)) return ldpc_detail::stalled_error(d->tile.device);
-    if ((st = d->tile.calls.enter(stream)) != LDPC_OK) return st;
-    if (d->max_iters == 0) {   // no iteration runs: zeros, converged = 0, llr = 0
-        if (d->n > 0) {
-            LDPC_HIP_TRY(hipMemsetAsync(d_gx, 0, (size_t)batch * d->n, stream));
-            LDPC_HIP_TRY(hipMemsetAsync(d_gz, 0, (size_t)batch * d->n, stream));
-            if (d_llr) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * 3 * d->n * sizeof(double), stream));
-        }
-        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
-    } else {
-        const pauli_kernel_t k = pauli_kernel_of(d->plan.tier);
-        const int threads = ldpc_detail::tile_threads(d->plan.tier);
-        int64_t grid;
-        size_t lds;
-        st = ldpc_detail::tile_geometry(&d->tile, &d->kernel, (const void *)k, threads, d->plan, batch,
-                                        "Pauli min-sum workspace regrow (device synchronise before the free)", &grid, &lds);
-        if (st != LDPC_OK) return st;
-        PauliParams p{};
-        p.rx = (int)d->rx; p.s = (int)(d->rx + d->rz); p.n = (int)d->n; p.max_iters = (int)d->max_iters; p.S = d->plan.S; p.shift = d->plan.shift;
-        p.batch = batch; p.alpha = d->alpha; p.clip = d->clip;
-        p.sx = d_sx; p.sz = d_sz; p.gx = d_gx; p.gz = d_gz; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
-        p.prior_x = d->priors; p.prior_y = d->priors + d->n; p.prior_z = d->priors + 2 * d->n;
-        p.row_ptr = d->row_ptr; p.csr_col = d->csr_col; p.rec_off = d->rec_off; p.col_ptr = d->col_ptr; p.col_mid = d->col_mid;
-        p.edge_rec = d->edge_rec; p.edge_pos = d->edge_pos; p.rec_words = d->rec_words;
-        p.ws = d->tile.ws; p.slot_bytes = (long long)d->plan.state_bytes;
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, p);
-        LDPC_HIP_TRY(hipGetLastError());
-        d->tile.last_grid = (int)grid;
-    }
-    return d->tile.calls.leave(stream);
+    const size_t B = (size_t)batch, n = (size_t)d->n;
+    if (d->max_iters == 0)   // no iteration runs
+        return ldpc_detail::tile_zero(&d->tile, (hipStream_t)stream_v,
+                                      {{d_gx, B * n}, {d_gz, B * n}, {d_llr, B * 3 * n * sizeof(double)}, {d_conv, B}, {d_iters, B * 4}});
+    return ldpc_detail::tile_run(&d->tile, &d->kernel, pauli_kernel_of(d->plan.tier), d->plan, batch, (hipStream_t)stream_v,
+                                 "Pauli min-sum workspace regrow (device synchronise before the free)", [&](PauliParams &p) {
+                                     d->tile.fill(p, d->plan, batch);
+                                     p.rx = (int)d->rx; p.s = (int)(d->rx + d->rz); p.n = (int)d->n; p.max_iters = (int)d->max_iters;
+                                     p.alpha = d->alpha; p.clip = d->clip;
+                                     p.sx = d_sx; p.sz = d_sz; p.gx = d_gx; p.gz = d_gz; p.conv = d_conv; p.llr = d_llr; p.iters = d_iters;
+                                     p.prior_x = d->priors; p.prior_y = d->priors + d->n; p.prior_z = d->priors + 2 * d->n;
+                                 });
 }
 
 ldpc_status ldpc_pauli_minsum_decode_batch(ldpc_pauli_minsum_decoder *d, int64_t batch, const uint8_t *sx, const uint8_t *sz, uint8_t *gx,
