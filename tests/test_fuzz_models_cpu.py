@@ -1,5 +1,6 @@
 """tools/fuzz_models.py without a GPU: the draws of the committed seeds are reproducible, together they contain the shapes
 the tool is there for, and the models run a case to the end."""
+import hashlib
 import os
 import re
 import subprocess
@@ -24,7 +25,20 @@ BPOTS = re.compile(r"^   bpots per (\S+) T (\d+) C (\S+) max_iters (\d+) batch (
 # ldpc_debug_decim_tile_plan answers.  A leg of round_iters 0 launches no kernel: it counts for that property alone
 DECIM = re.compile(r"^   decim round_iters (\d+) max_decimations (\d+) alpha (\S+) clip (\S+) batch (\d+) (device|host) entry "
                    r"decimated=(True|False) n (\d+) S (\d+)$")
-OLD_LEGS, NEW_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css"), ("layered", "priors", "pauli", "bpots", "decim")
+# the leg of the fifth generator: the Pauli relay; a leg whose every count is 0 decodes nothing and counts for no property
+PAULI_RELAY = re.compile(r"^   pauli_relay Hz \((\d+), (\d+)\) B (\d+) leg_iters \[([\d, ]+)\] stop_after (\d) negative_gammas (\d+) "
+                         r"alpha (\S+) clip (\S+) (device|host) entry llr=(True|False) iters=(True|False) solutions=(True|False) "
+                         r"uniform=(True|False) (sampled|arbitrary) syndromes "
+                         r"hx<=32 (\d+) hx33-64 (\d+) hx>64 (\d+) hx_empty (\d+) hz<=32 (\d+) hz33-64 (\d+) hz>64 (\d+) hz_empty (\d+)$")
+# the leg of the sixth generator: the OSD step by the standard rule
+OSD_SEARCH = re.compile(r"^   osd_search (combination_sweep|exhaustive) order (\d+) weights (none|floats|zero|clamped) batch (\d+) "
+                        r"reproducing_rows (\d+) nan=(True|False) (in place|out of place)$")
+OLD_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css")
+NEW_LEGS = ("layered", "priors", "pauli", "bpots", "decim", "pauli_relay", "osd_search")
+# SHA-256 of a FUZZ_DRY listing of 40 cases without its last line (which carries seconds) and without the lines of the legs
+# `pauli_relay` and `osd_search`, computed from the tool as it stood before those two legs: the eleven older legs draw for a
+# committed seed exactly what they drew then
+OLDER_LEGS_SHA256 = {20: "79f335c86efda4e16c389aba6c77ae75d485c8f8923acf8f58472b46312e0478", 21: "d0798cff3517aa9a274a5c4bf55af307230cd8ec1dd12ff22a5c4b1b13e2b099"}
 
 
 def _tool(args, **env):
@@ -77,6 +91,26 @@ def coverage(listing):
                 ("decim: every bit free", T == 1 and Dmax == n > 0), (f"decim: {entry} entry", T > 0),
                 ("decim: decimated=False", T > 0 and not counts), (f"decim: clip {clip:g}", T > 0),
                 (f"decim: S = {S}", T > 0 and S > 0)) if yes}
+        m = PAULI_RELAY.match(line)
+        if m and any(int(x) > 0 for x in m.group(4).split(",")):
+            B, legs, stop_after, negative = int(m.group(3)), [int(x) for x in m.group(4).split(",")], int(m.group(5)), int(m.group(6))
+            assert 1 <= B <= 65 and 1 <= len(legs) <= 4 and max(legs) <= 6 and 1 <= stop_after <= 3
+            _, hx64, hxbig, hxe, _, hz64, hzbig, hze = (int(x) for x in m.groups()[14:])
+            have |= {name for name, yes in (
+                ("pauli_relay: Hx check of degree 33 ... 64", hx64 > 0), ("pauli_relay: Hx check of degree > 64", hxbig > 0),
+                ("pauli_relay: Hz check of degree 33 ... 64", hz64 > 0), ("pauli_relay: Hz check of degree > 64", hzbig > 0),
+                ("pauli_relay: empty Hx check", hxe > 0), ("pauli_relay: empty Hz check", hze > 0), ("pauli_relay: batch 1", B == 1),
+                ("pauli_relay: batch 65", B == 65), ("pauli_relay: a skipped leg", 0 in legs),
+                ("pauli_relay: stop_after above 1", stop_after > 1), ("pauli_relay: a negative gamma", negative > 0),
+                (f"pauli_relay: {m.group(9)} entry", True), ("pauli_relay: solutions=False", m.group(12) == "False")) if yes}
+        m = OSD_SEARCH.match(line)
+        if m:
+            method, order, kind, B, own = m.group(1), int(m.group(2)), m.group(3), int(m.group(4)), int(m.group(5))
+            assert 1 <= B <= 65 and own <= B and order in ((0, 1, 2, 10, 64) if method == "combination_sweep" else (0, 1, 3, 8))
+            have |= {name for name, yes in (
+                (f"osd_search: {method}", True), ("osd_search: order 0", order == 0), ("osd_search: order 64", order == 64),
+                (f"osd_search: weights {kind}", True), ("osd_search: a row that reproduces its syndrome", own > 0),
+                ("osd_search: a NaN LLR", m.group(6) == "True"), ("osd_search: in place", m.group(7) == "in place")) if yes}
         m = CASE.match(line)
         if not m:
             continue
@@ -102,7 +136,19 @@ WANTED = {"check of degree <= 32", "check of degree 33 ... 64", "check of degree
           # decimation: no launch, no decimation (plain min-sum), the |D| == n exit, both entries, the optional output left
           # out, the clamp at each of the three clips the leg draws
           "decim: round_iters 0", "decim: max_decimations 0", "decim: every bit free", "decim: device entry", "decim: host entry",
-          "decim: decimated=False", "decim: clip 4", "decim: clip 20", "decim: clip 1e+06"}
+          "decim: decimated=False", "decim: clip 4", "decim: clip 20", "decim: clip 1e+06",
+          # Pauli relay, among the legs that run at least one iteration: five-word and per-edge records on each side, an empty
+          # check on each side, a one-column and a ragged batch, a leg of 0 iterations next to one that runs, a second and a
+          # third solution wanted, a leg that forgets (gamma < 0), both entries, the optional output left out
+          "pauli_relay: Hx check of degree 33 ... 64", "pauli_relay: Hx check of degree > 64", "pauli_relay: Hz check of degree 33 ... 64",
+          "pauli_relay: Hz check of degree > 64", "pauli_relay: empty Hx check", "pauli_relay: empty Hz check", "pauli_relay: batch 1",
+          "pauli_relay: batch 65", "pauli_relay: a skipped leg", "pauli_relay: stop_after above 1", "pauli_relay: a negative gamma",
+          "pauli_relay: device entry", "pauli_relay: host entry", "pauli_relay: solutions=False",
+          # the standard rule of the OSD step: both methods, no free position (order 0) and more than there are (order 64), each
+          # kind of cost, step 1 (bp_err already reproduces the syndrome), the NaN-last order, in place
+          "osd_search: combination_sweep", "osd_search: exhaustive", "osd_search: order 0", "osd_search: order 64",
+          "osd_search: weights none", "osd_search: weights floats", "osd_search: weights zero", "osd_search: weights clamped",
+          "osd_search: a row that reproduces its syndrome", "osd_search: a NaN LLR", "osd_search: in place"}
 # A graph without edges is NOT among them: the graphs are the cases' own, drawn from the first generator, whose stream the
 # older legs own; the smallest graph of the committed seeds has 7 edges.  tests/test_gpu_bpots_paths.py
 # (test_a_graph_without_edges) pins that shape instead.
@@ -120,8 +166,11 @@ def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_th
         for leg in OLD_LEGS + NEW_LEGS:
             assert len([ln for ln in first.splitlines() if ln.startswith(f"   {leg} ")]) == CASES, leg
         # ... and every line of a new leg is one that coverage() can read
-        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS, DECIM)):
+        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS, DECIM, PAULI_RELAY, OSD_SEARCH)):
             assert all(pattern.match(ln) for ln in first.splitlines() if ln.startswith(f"   {leg} ")), leg
+        # ... and the eleven older legs draw what they drew before the legs pauli_relay and osd_search existed
+        older = [ln for ln in first.splitlines()[:-1] if not ln.startswith(("   pauli_relay ", "   osd_search "))]
+        assert hashlib.sha256(("\n".join(older) + "\n").encode()).hexdigest() == OLDER_LEGS_SHA256[seed], f"seed {seed}: an older leg draws otherwise"
         have |= coverage(first)
     widths = {name for name in have if name.startswith("bpots: S = ")}
     assert len(widths) >= 3, f"the committed seeds reach only the BP-OTS tile widths {sorted(widths)}"

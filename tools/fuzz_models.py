@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Randomised model-parity fuzz (GPU box) of the kernels that tools/fuzz_parity.py does not reach: the bit-flip decoder,
 min-sum (flooding and layered schedule, shared and per-syndrome priors), relay min-sum, the joint X/Z (Pauli) min-sum, the
-device OSD step, the one-matrix and CSS trial steps, the three BP-OTS kernels at parameters fuzz_parity.py leaves out, and the
-guided-decimation min-sum (leg `decim`: 2 ... 4 model seconds for the 40 cases of seeds 20 and 21).  Random Tanner graphs (irregular with empty and heavy nodes and
+device OSD step, the one-matrix and CSS trial steps, the three BP-OTS kernels at parameters fuzz_parity.py leaves out, the Pauli relay min-sum, the OSD step by the
+standard rule, and the guided-decimation min-sum (leg `decim`: 2 ... 4 model seconds for the 40 cases of seeds 20 and 21).  Random Tanner graphs (irregular with empty and heavy nodes and
 sizes around the word boundaries, or small Gallager codes), ragged batches, every `kernel_variant` that create accepts,
 every result compared in every element with the numpy models of tests/ (the min-sum family and relay: the LLR bit patterns
 too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
@@ -25,7 +25,16 @@ batch is capped at 65.
 Model seconds of 40 cases on one CPU core (the `model seconds` line of FUZZ_MODEL_ONLY=1, all ten legs in one run): the six older
 legs, the three of the second generator, and the BP-OTS oracle (C, not numpy):
   seed 20: bitflip 0.43, minsum 2.64, relay 5.82, osd 0.84, trials 0.06, css 0.08 (9.9 s); layered 1.68, priors 2.05, pauli 2.59 (6.3 s); bpots 2.04
-  seed 21: bitflip 0.34, minsum 1.92, relay 4.96, osd 0.69, trials 0.06, css 0.08 (8.1 s); layered 1.56, priors 1.60, pauli 1.84 (5.0 s); bpots 1.42"""
+  seed 21: bitflip 0.34, minsum 1.92, relay 4.96, osd 0.69, trials 0.06, css 0.08 (8.1 s); layered 1.56, priors 1.60, pauli 1.84 (5.0 s); bpots 1.42
+
+The legs `pauli_relay` (the Pauli relay min-sum: Hx the case's graph, Hz a second drawn matrix, a count of its own for every
+leg) and `osd_search` (the OSD step by the standard rule: combination sweep or exhaustive search, Hamming cost or weights)
+draw from a fifth and a sixth generator (seeded [seed, 4] and [seed, 5]): the eleven older legs draw what they drew.  The
+batch of `osd_search` is capped at 65, so that its model costs no more than the relay leg's for the same seed.  Model
+seconds of these two legs for 40 cases, all thirteen legs in one run on one core of a faster machine than the figures
+above come from, with the relay leg of the same run beside them:
+  seed 20: pauli_relay 3.59, osd_search 0.92 (relay 2.67)
+  seed 21: pauli_relay 3.04, osd_search 1.01 (relay 2.26)"""
 import os
 import sys
 import time
@@ -46,7 +55,9 @@ from layered_model import LayeredMinSumModel, layers_of  # noqa: E402
 from decim_model import DecimModel  # noqa: E402
 from minsum_model import MinSumModel, llr_of_probs  # noqa: E402
 from osd_model import osd_model_postprocess  # noqa: E402
+from osd_search_model import METHODS as OSD_SEARCH_METHODS, osd_search_model, weights_of as osd_search_weights_of  # noqa: E402
 from pauli_model import PauliMinSumModel, pauli_priors  # noqa: E402
+from pauli_relay_model import PauliRelayModel  # noqa: E402
 from relay_model import RelayModel  # noqa: E402
 from oracle import BPOTSOracle  # noqa: E402
 
@@ -60,7 +71,8 @@ UNSUPPORTED = 5
 # tiers a component can take here; the last one is its unlimited tier.  (Bit-flip tier 4, the 64-bit votes, needs
 # max_iters * max bit degree >= 2^31 and is held by test_unlimited_tier_with_64_bit_votes.)
 TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2),
-         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2), "bpots": (2, 3, 5), "decim": (1, 2)}
+         "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2), "bpots": (2, 3, 5), "decim": (1, 2), "pauli_relay": (1, 2),
+         "osd_search": (1, 2, 3)}
 BOUNDARY = (31, 32, 33, 63, 64, 65, 127, 128, 129)
 
 if GPU:
@@ -78,6 +90,8 @@ rng = np.random.default_rng(seed)
 rng2 = np.random.default_rng([seed, 1])      # the layered, priors and pauli legs: never `rng`, whose stream the older legs own
 rng3 = np.random.default_rng([seed, 2])      # the bpots leg
 rng4 = np.random.default_rng([seed, 3])      # the decim leg
+rng5 = np.random.default_rng([seed, 4])      # the pauli_relay leg
+rng6 = np.random.default_rng([seed, 5])      # the osd_search leg
 t0 = time.time()
 ran = {c: set() for c in TIERS}          # tiers that decoded
 legs_run = {c: 0 for c in TIERS}
@@ -683,10 +697,9 @@ def draw_pauli_probs(n, g):
     return probs, False
 
 
-def leg_pauli(H, B, run):
-    """Hx = the case's H, Hz a second drawn matrix over the same qubits; the sides need not commute (check=False)."""
-    g = rng2
-    rx, n = H.shape
+def draw_hz(n, g):
+    """(A dense, Hz csc): a second matrix of 1 ... 40 rows over the n qubits of the case's graph, with an empty row and a row
+    of 33 ... 80 ones now and then."""
     rz = int(g.integers(1, 41))
     A = (g.random((rz, n)) < g.uniform(0.02, 0.25)).astype(np.uint8)
     empty, heavy = int(g.integers(0, rz)), int(g.integers(0, rz))
@@ -698,6 +711,15 @@ def leg_pauli(H, B, run):
         A[heavy, g.choice(n, size=min(n, int(g.integers(33, 81))), replace=False)] = 1
     Hz = sp.csc_matrix(A)
     Hz.sort_indices()
+    return A, Hz
+
+
+def leg_pauli(H, B, run):
+    """Hx = the case's H, Hz a second drawn matrix over the same qubits; the sides need not commute (check=False)."""
+    g = rng2
+    rx, n = H.shape
+    A, Hz = draw_hz(n, g)
+    rz = Hz.shape[0]
     alpha, clip, max_iters = draw_rule(g)
     probs, uniform = draw_pauli_probs(n, g)
     device_entry, want_llr, want_iters = (bool(g.random() < 0.5) for _ in range(3))
@@ -867,6 +889,172 @@ def leg_decim(H, B, run):
                                                                          clip=clip, kernel_variant=v), go, text)
 
 
+# ---- the leg of the fifth generator ------------------------------------------------------------------------------------
+class PauliRelayPerLeg(ldpc.PauliRelayMinSumDecoder):
+    """A PauliRelayMinSumDecoder with an iteration count of its own for every leg (ldpc_pauli_relay_create takes one per
+    leg, the class's constructor gives leg 0 one count and all later legs another); the sides need not commute.  The decode
+    methods are the class's."""
+
+    def __init__(self, Hx, Hz, priors, gammas, leg_iters, stop_after, alpha, clip, kernel_variant):
+        import ctypes
+
+        from ldpcdecoders_jl_amd._host import _pattern_of, css_pattern
+
+        Mx, Mz = _pattern_of(Hx), _pattern_of(Hz)
+        self.sparse_Hx, self.sparse_Hz = Mx, Mz
+        self.n, self.rows_x, self.rows_z, self.device = int(Mx.shape[1]), int(Mx.shape[0]), int(Mz.shape[0]), 0
+        self.prior_x, self.prior_y, self.prior_z = (np.ascontiguousarray(priors[k], dtype=np.float32) for k in range(3))
+        self.gammas = np.ascontiguousarray(gammas, dtype=np.float32)
+        self.leg_iters = np.ascontiguousarray(leg_iters, dtype=np.int32)
+        self.legs = int(self.leg_iters.size)
+        assert self.gammas.shape == (self.legs, self.n)
+        pat_x, pat_z = css_pattern(Mx), css_pattern(Mz)
+        opts = ldpc._capi.PauliRelayOptions()
+        opts.device, opts.alpha, opts.clip = 0, float(alpha), float(clip)
+        opts.kernel_variant, opts.stop_after = int(kernel_variant), int(stop_after)
+        L = ldpc._capi.lib_for(None)
+        self._create(L, L.ldpc_pauli_relay_create, self.n, ctypes.byref(pat_x), ctypes.byref(pat_z), self.prior_x.ctypes.data,
+                     self.prior_y.ctypes.data, self.prior_z.ctypes.data, self.legs, self.gammas.ctypes.data, self.leg_iters.ctypes.data,
+                     ctypes.byref(opts))
+
+
+def leg_pauli_relay(H, B, run):
+    """The Pauli relay on Hx = the case's H and a second drawn Hz (the recipe of the pauli leg): 1 ... 4 legs of 0 ... 6
+    iterations each (a leg of 0 is skipped wherever it stands), gammas in (-0.3, 0.9) per qubit and leg, stop_after 1 ... 3;
+    with one triple for every qubit the weights tie, and a tie keeps the earlier solution."""
+    g = rng5
+    rx, n = H.shape
+    A, Hz = draw_hz(n, g)
+    rz = Hz.shape[0]
+    legs = int(g.integers(1, 5))
+    leg_iters = [int(x) for x in g.integers(0, 7, size=legs)]
+    gammas = g.uniform(-0.3, 0.9, size=(legs, n)).astype(np.float32)
+    stop_after = int(g.integers(1, 4))
+    alpha, clip, _ = draw_rule(g)
+    probs, uniform = draw_pauli_probs(n, g)
+    device_entry, want_llr, want_iters, want_sol = (bool(g.random() < 0.5) for _ in range(4))
+    Bp = min(B, 65)
+    sampled = bool(g.random() < 0.6)
+    if sampled:                               # the syndromes of sampled Pauli errors: sx = Hx ez, sz = Hz ex
+        rate = g.uniform(0.01, 0.15)
+        ex, ez = ((g.random((Bp, n)) < rate).astype(np.uint8) for _ in range(2))
+        sx, sz = ldpc.codes.syndromes_of(H, ez), ldpc.codes.syndromes_of(Hz, ex)
+    else:
+        sx, sz = g.integers(0, 2, (Bp, rx)).astype(np.uint8), g.integers(0, 2, (Bp, rz)).astype(np.uint8)
+    running = [k for k in range(legs) if leg_iters[k] > 0]
+    text = (f"Hz ({rz}, {n}) B {Bp} leg_iters {leg_iters} stop_after {stop_after} negative_gammas {int((gammas[running] < 0).sum())} "
+            f"alpha {alpha} clip {clip} {'device' if device_entry else 'host'} entry llr={want_llr} iters={want_iters} "
+            f"solutions={want_sol} uniform={uniform} {'sampled' if sampled else 'arbitrary'} syndromes")
+    if DRY or VERBOSE:
+        print(f"   pauli_relay {text} {degrees_text(H, 'hx')} {degrees_text(Hz, 'hz')}", flush=True)
+    if not run:
+        return
+    tables = pauli_priors(probs)
+    mgx, mgz, mconv, mits, msol, mM = timed_model(
+        "pauli_relay", lambda: PauliRelayModel(H, Hz, tables, gammas, leg_iters, alpha=alpha, clip=clip, stop_after=stop_after).decode(sx, sz))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        if device_entry:
+            gx, conv, llr, its = device_outputs(Bp, n, 3, want_llr, want_iters)
+            gz = torch.full((Bp, n), 7, dtype=torch.uint8, device="cuda")
+            sol = torch.full((Bp,), -7, dtype=torch.int32, device="cuda") if want_sol else None
+            dec.decode_batch_device(dev(sx), dev(sz), gx, gz, conv, llr, its, sol)
+            torch.cuda.synchronize()
+            gx, gz, conv, llr, its, sol = (host_of(x) for x in (gx, gz, conv, llr, its, sol))
+        else:
+            out = dec.decode_batch_host(sx, sz, want_llr=want_llr, want_solutions=want_sol)
+            gx, gz, conv, llr, its = out[:5]
+            sol = out[5] if want_sol else None
+            if (llr is None) != (not want_llr) or len(out) != (6 if want_sol else 5):
+                fail("pauli_relay", f"the host entry returns outputs it was not asked for, or none, kernel_variant {variant} {text}")
+        ok = (same(gx, mgx) and same(gz, mgz) and same(conv, mconv) and (its is None or same(its, mits))
+              and (sol is None or same(sol, msol)) and (llr is None or same_bits(llr, mM)))
+        if not ok:
+            fail("pauli_relay", f"kernel_variant {variant} {text}", hx_colptr=H.indptr, hx_rowval=H.indices, hx_shape=H.shape, hz=A,
+                 probs=probs, gammas=gammas, leg_iters=leg_iters, sx=sx, sz=sz, gx=gx, gz=gz, conv=conv, its=its, sol=sol, llr=llr,
+                 mgx=mgx, mgz=mgz, mconv=mconv, mits=mits, msol=msol, mM=mM)
+
+    on_every_tier("pauli_relay", (1, 2), lambda v: PauliRelayPerLeg(H, Hz, tables, gammas, leg_iters, stop_after, alpha, clip, v), go, text)
+
+
+# ---- the leg of the sixth generator ------------------------------------------------------------------------------------
+OSD_SEARCH_BATCH_CAP = 65      # (the model is one dense elimination and up to 2080 candidates per syndrome)
+
+
+def leg_osd_search(H, B, run):
+    """The OSD step by the standard rule (ldpc_osd_set_search) on the case's graph against osd_search_model, per syndrome
+    and in every element: both methods, the orders at their edges (0; 64 is clamped to K by the sweep), Hamming cost or
+    weights -- drawn floats with negative entries, all zero (every candidate costs 0: the first wins), or values that clamp
+    to +-2^40 --, a share of rows whose bp_err already reproduces the syndrome (step 1: the output is bp_err), LLRs with
+    ties, +-0.0, +-inf and NaN.  Every syndrome is H e: none lies outside the column space."""
+    g = rng6
+    s, n = H.shape
+    if g.random() < 0.6:
+        method, order = "combination_sweep", int(g.choice([0, 1, 2, 10, 64]))
+    else:
+        method, order = "exhaustive", int(g.choice([0, 1, 3, 8]))
+    kind = ("none", "floats", "zero", "clamped")[int(g.integers(0, 4))]
+    weights = {"none": None, "floats": g.normal(1.0, 2.0, n), "zero": np.zeros(n),
+               "clamped": g.choice([1e9, 2.0 ** 24, 1.0, 2.0 ** -16, -2.0 ** 24, -1e9], size=n)}[kind]
+    inplace = bool(g.random() < 0.5)
+    Bo = min(B, OSD_SEARCH_BATCH_CAP)
+    E = (g.random((Bo, n)) < 0.1).astype(np.uint8)
+    syn = ldpc.codes.syndromes_of(H, E)
+    bp_err = (g.random((Bo, n)) < 0.1).astype(np.uint8)
+    own = g.random(Bo) < 0.25                 # step 1: an estimate that reproduces the syndrome is returned unchanged
+    bp_err[own] = E[own]
+    reproducing = int((ldpc.codes.syndromes_of(H, bp_err) == syn).all(axis=1).sum())
+    llr = g.normal(1.0, 3.0, (Bo, n))
+    llr[g.random((Bo, n)) < 0.3] = llr[0, 0]        # ties
+    llr[g.random((Bo, n)) < 0.05] = 0.0
+    llr[g.random((Bo, n)) < 0.05] = -0.0
+    if g.random() < 0.4:
+        llr[g.random((Bo, n)) < 0.05] = np.nan
+        llr[g.random((Bo, n)) < 0.03] = -np.inf
+        llr[g.random((Bo, n)) < 0.03] = np.inf
+    text = (f"{method} order {order} weights {kind} batch {Bo} reproducing_rows {reproducing} nan={bool(np.isnan(llr).any())} "
+            f"{'in place' if inplace else 'out of place'}")
+    if DRY or VERBOSE:
+        print(f"   osd_search {text}", flush=True)
+    if not run:
+        return
+    Hd = np.asarray(H.todense()).astype(np.uint8)
+    q = None if weights is None else osd_search_weights_of(weights)
+    want = timed_model("osd_search", lambda: np.stack([osd_search_model(Hd, syn[b], bp_err[b], llr[b], OSD_SEARCH_METHODS[method], order, q)
+                                                       for b in range(Bo)]).astype(np.uint8))
+    if not same(ldpc.codes.syndromes_of(H, want), syn):
+        fail("osd_search", f"a model output does not reproduce its syndrome {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape,
+             syn=syn, bp_err=bp_err, llr=llr, want=want)
+    if not GPU:
+        return
+
+    class Post:
+        def __init__(self, variant):
+            self.post = ldpc.OSDPostProcessor(H, order, method=method, weights=weights)
+            try:
+                self.post.prepare_device(0, variant)
+            except ldpc.LdpcError:
+                self.post.close()
+                raise
+            self.kernel = self.post.kernel
+
+        def close(self):
+            self.post.close()
+
+    def go(h, variant):
+        d_err = dev(bp_err)
+        out = h.post.postprocess_device(dev(syn), d_err, dev(llr), out=d_err if inplace else None)
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        if not same(got, want) or not (inplace or same(d_err.cpu().numpy(), bp_err)):
+            fail("osd_search", f"kernel_variant {variant} {text}", colptr=H.indptr, rowval=H.indices, shape=H.shape, syn=syn, bp_err=bp_err,
+                 llr=llr, weights=weights, got=got, want=want)
+
+    on_every_tier("osd_search", (1, 2, 3), Post, go, text)
+
+
 # ---- the cases ---------------------------------------------------------------------------------------------------------
 last_note = t0
 for case in range(ncases):
@@ -889,6 +1077,8 @@ for case in range(ncases):
     leg_pauli(H, B, run)
     leg_bpots(H, B, run)
     leg_decim(H, B, run)
+    leg_pauli_relay(H, B, run)
+    leg_osd_search(H, B, run)
     if time.time() - last_note > 60:   # a silent GPU job looks hung to the runner
         last_note = time.time()
         print(f"... {case + 1} cases, {time.time() - t0:.0f} s", flush=True)
