@@ -74,14 +74,7 @@ __global__ __launch_bounds__(TW * 64) void decim_kernel(DecimParams p)
         // ---- state of iteration 0: L = channel_llr, every message +0, D empty; the syndromes, a wave per column
         for (int j = q; j < n; j += Q) L[((size_t)j << sh) + l] = prior[j];
         for (int w = q; w < p.rec_words + dw; w += Q) R[((size_t)w << sh) + l] = 0u;   // (D follows the records)
-        for (int c = wave; c < S; c += TW) {
-            if (c < valid) {
-                const uint8_t *src = p.syn + (col0 + c) * s;
-                for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = src[i] != 0;
-            } else {   // a lane past the batch reads nothing and never becomes active
-                for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = 0;
-            }
-        }
+        ms_stage_syndromes<TW>(Y, s, S, sh, valid, wave, lane, [&](int c, int i) { return p.syn[(col0 + c) * s + i]; });
         if (t < 64) { sh_bad[t] = 0; sh_key[t] = 0ull; }
         bool active = l < valid;
         int my_iters = 0, my_dec = 0, my_conv = 0;
@@ -101,72 +94,11 @@ __global__ __launch_bounds__(TW * 64) void decim_kernel(DecimParams p)
                         bad |= (int)y;
                         continue;
                     }
-                    unsigned *rec = R + ((size_t)rec_off[i] << sh) + l;
-                    float m1 = clip, m2 = clip;
-                    unsigned a = kMsNone, par = y;
-                    if (deg <= 64) {
-                        const float o1 = __uint_as_float(rec[0]), o2 = __uint_as_float(rec[(size_t)1 << sh]);
-                        const unsigned oa = rec[(size_t)2 << sh];
-                        unsigned sg = rec[(size_t)3 << sh], neg_lo = 0, neg_hi = 0;
-                        const int d0 = deg < 32 ? deg : 32;
-                        for (int k = 0; k < d0; ++k) {
-                            const float Lj = L[((size_t)csr_col[ra + k] << sh) + l];
-                            hard ^= (unsigned)(Lj <= 0.0f);
-                            const float cm = (unsigned)k == oa ? o2 : o1;
-                            const float c = (sg >> k) & 1u ? -cm : cm;
-                            const float b = ms_clamp(Lj - c, clip);   // (a pinned bit: exactly +-clip, never below m1)
-                            const unsigned ng = b < 0.0f;
-                            const float mag = fabsf(b);
-                            neg_lo |= ng << k;
-                            par ^= ng;
-                            if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
-                            else if (mag < m2) m2 = mag;
-                        }
-                        if (deg > 32) {
-                            sg = rec[(size_t)4 << sh];
-                            for (int k = 32; k < deg; ++k) {
-                                const float Lj = L[((size_t)csr_col[ra + k] << sh) + l];
-                                hard ^= (unsigned)(Lj <= 0.0f);
-                                const float cm = (unsigned)k == oa ? o2 : o1;
-                                const float c = (sg >> (k - 32)) & 1u ? -cm : cm;
-                                const float b = ms_clamp(Lj - c, clip);
-                                const unsigned ng = b < 0.0f;
-                                const float mag = fabsf(b);
-                                neg_hi |= ng << (k - 32);
-                                par ^= ng;
-                                if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
-                                else if (mag < m2) m2 = mag;
-                            }
-                        }
-                        if (!test_only) {
-                            const unsigned flip = par ? 0xffffffffu : 0u;   // negative iff par XOR neg_k
-                            rec[0] = __float_as_uint(alpha * m1);
-                            rec[(size_t)1 << sh] = __float_as_uint(alpha * m2);
-                            rec[(size_t)2 << sh] = a;
-                            rec[(size_t)3 << sh] = (neg_lo ^ flip) & (d0 == 32 ? 0xffffffffu : (1u << d0) - 1u);
-                            if (deg > 32) rec[(size_t)4 << sh] = (neg_hi ^ flip) & (deg == 64 ? 0xffffffffu : (1u << (deg - 32)) - 1u);
-                        }
-                    } else {
-                        // per-edge record: the minima first, then every edge's b once more for its sign
-                        for (int k = 0; k < deg; ++k) {
-                            const float Lj = L[((size_t)csr_col[ra + k] << sh) + l];
-                            hard ^= (unsigned)(Lj <= 0.0f);
-                            const float b = ms_clamp(Lj - __uint_as_float(rec[(size_t)k << sh]), clip);
-                            const float mag = fabsf(b);
-                            par ^= (unsigned)(b < 0.0f);
-                            if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
-                            else if (mag < m2) m2 = mag;
-                        }
-                        if (!test_only) {
-                            const float n1 = alpha * m1, n2 = alpha * m2;
-                            for (int k = 0; k < deg; ++k) {
-                                const float Lj = L[((size_t)csr_col[ra + k] << sh) + l];
-                                const float b = ms_clamp(Lj - __uint_as_float(rec[(size_t)k << sh]), clip);
-                                const float cm = (unsigned)k == a ? n2 : n1;
-                                rec[(size_t)k << sh] = __float_as_uint((par ^ (unsigned)(b < 0.0f)) ? -cm : cm);
-                            }
-                        }
-                    }
+                    ms_check_update(R + ((size_t)rec_off[i] << sh) + l, deg, sh, alpha, clip, y, false, !test_only, [&](int k, float c, bool test) {
+                        const float Lj = L[((size_t)csr_col[ra + k] << sh) + l];
+                        if (test) hard ^= (unsigned)(Lj <= 0.0f);
+                        return ms_clamp(Lj - c, clip);   // (a pinned bit: exactly +-clip, never below m1)
+                    });
                     bad |= (int)(hard ^ y);
                 }
                 if (bad) sh_bad[l] = 1;
@@ -230,15 +162,7 @@ __global__ __launch_bounds__(TW * 64) void decim_kernel(DecimParams p)
         }
 
         // ---- results, a wave per column: err = (L <= 0), llr = L widened
-        for (int c = wave; c < valid; c += TW) {
-            uint8_t *eo = p.err + (col0 + c) * n;
-            double *lo = p.llr ? p.llr + (col0 + c) * n : nullptr;
-            for (int j = lane; j < n; j += 64) {
-                const float v = L[((size_t)j << sh) + c];
-                eo[j] = v <= 0.0f;
-                if (lo) lo[j] = (double)v;
-            }
-        }
+        ms_write_results<TW>(L, n, sh, valid, wave, lane, p.err + col0 * n, p.llr ? p.llr + col0 * n : nullptr);
         if (q == 0 && l < valid) {
             p.conv[col0 + l] = (uint8_t)my_conv;
             if (p.iters) p.iters[col0 + l] = my_iters;

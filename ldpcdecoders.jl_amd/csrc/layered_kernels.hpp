@@ -100,6 +100,8 @@ __global__ __launch_bounds__(TW * 64) void layered_minsum_kernel(typename Layere
                     for (int qi = layer_ptr[ly] + q; qi < qe; qi += Q) {
                         const int i = layer_checks[qi];
                         const int ra = row_ptr[i], deg = row_ptr[i + 1] - ra;   // >= 1: an empty check is in no layer
+                        // (a writer of the record forms of its own, next to ms_check_update of minsum_kernels.hpp: the write-back needs
+                        // the old and the new record in registers at once, and the per-edge form fuses its store with L = b + c)
                         unsigned *rec = R + ((size_t)rec_off[i] << sh) + l;
                         float m1 = clip, m2 = clip;
                         unsigned a = kMsNone, par = Y[((size_t)i << sh) + l];

@@ -108,6 +108,97 @@ __device__ inline float ms_message(const unsigned *rec, int k, int sh)
     return (sg >> (k & 31)) & 1u ? -cm : cm;
 }
 
+// The update of one check's record in the thread's lane (rec: the record's first word there): the minima and the parity
+// (from the syndrome entry y) of the check's b_k, then, if `write`, the new record -- the writer of the record forms in
+// decim_kernel and pauli_relay_kernel.  minsum_kernel below, relay_kernel and pauli_minsum_kernel keep the same text inline:
+// with this function each had a probe row beyond the parent's spread (profiles/check_update_refactor_probe.txt), and
+// layered_minsum_kernel needs the old and the new record at once.  A fix to a record form is made here and in those four.
+// `fresh`: the old record reads as all-zero words.  edge(k, c, test) is the kernel's part: the clamped b_k of the check's
+// k-th bit against its old message c; where `test` it also folds the bit's hard decision into the caller's stop test (the
+// per-edge form forms every b_k twice and tests once).  A strict < in the minima: a tie keeps the earlier position.
+template <class Edge>
+__device__ inline void ms_check_update(unsigned *rec, int deg, int sh, float alpha, float clip, unsigned y, bool fresh, bool write, Edge edge)
+{
+    float m1 = clip, m2 = clip;
+    unsigned a = kMsNone, par = y;
+    auto least = [&](int k, float mag) {
+        if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
+        else if (mag < m2) m2 = mag;
+    };
+    if (deg <= 64) {
+        const float o1 = fresh ? 0.0f : __uint_as_float(rec[0]), o2 = fresh ? 0.0f : __uint_as_float(rec[(size_t)1 << sh]);
+        const unsigned oa = rec[(size_t)2 << sh];
+        // the edges k0 .. k1 - 1 against their old sign word sg; their new sign bits before the parity is known
+        auto word = [&](int k0, int k1, unsigned sg) -> unsigned {
+            unsigned neg = 0;
+            for (int k = k0; k < k1; ++k) {
+                const float cm = (unsigned)k == oa ? o2 : o1;
+                const float b = edge(k, (sg >> (k - k0)) & 1u ? -cm : cm, true);
+                const unsigned ng = b < 0.0f;
+                neg |= ng << (k - k0);
+                par ^= ng;
+                least(k, fabsf(b));
+            }
+            return neg;
+        };
+        const int d0 = deg < 32 ? deg : 32;
+        const unsigned neg_lo = word(0, d0, fresh ? 0u : rec[(size_t)3 << sh]);
+        const unsigned neg_hi = deg > 32 ? word(32, deg, fresh ? 0u : rec[(size_t)4 << sh]) : 0u;
+        if (write) {
+            const unsigned flip = par ? 0xffffffffu : 0u;   // negative iff par XOR neg_k
+            rec[0] = __float_as_uint(alpha * m1);
+            rec[(size_t)1 << sh] = __float_as_uint(alpha * m2);
+            rec[(size_t)2 << sh] = a;
+            rec[(size_t)3 << sh] = (neg_lo ^ flip) & (d0 == 32 ? 0xffffffffu : (1u << d0) - 1u);
+            if (deg > 32) rec[(size_t)4 << sh] = (neg_hi ^ flip) & (deg == 64 ? 0xffffffffu : (1u << (deg - 32)) - 1u);
+        }
+    } else {
+        // per-edge record: the minima first, then every edge's b once more for its sign
+        for (int k = 0; k < deg; ++k) {
+            const float b = edge(k, fresh ? 0.0f : __uint_as_float(rec[(size_t)k << sh]), true);
+            par ^= (unsigned)(b < 0.0f);
+            least(k, fabsf(b));
+        }
+        if (write) {
+            const float n1 = alpha * m1, n2 = alpha * m2;
+            for (int k = 0; k < deg; ++k) {
+                const float b = edge(k, fresh ? 0.0f : __uint_as_float(rec[(size_t)k << sh]), false);
+                const float cm = (unsigned)k == a ? n2 : n1;
+                rec[(size_t)k << sh] = __float_as_uint((par ^ (unsigned)(b < 0.0f)) ? -cm : cm);
+            }
+        }
+    }
+}
+
+// The syndromes of a tile into Y [s][S], a wave per column with its lanes along the checks: entry(c, i) is entry i of the
+// tile's column c.  A lane past the batch reads nothing, gets zeros and never becomes active.
+template <int TW, class Entry>
+__device__ inline void ms_stage_syndromes(unsigned char *Y, int s, int S, int sh, int valid, int wave, int lane, Entry entry)
+{
+    for (int c = wave; c < S; c += TW) {
+        if (c < valid)
+            for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = entry(c, i) != 0;
+        else
+            for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = 0;
+    }
+}
+
+// The plain results of a tile, a wave per column: err = (L <= 0), llr = L widened (err, llr: at the tile's first column,
+// llr may be null).
+template <int TW>
+__device__ inline void ms_write_results(const float *L, int n, int sh, int valid, int wave, int lane, uint8_t *err, double *llr)
+{
+    for (int c = wave; c < valid; c += TW) {
+        uint8_t *eo = err + (long long)c * n;
+        double *lo = llr ? llr + (long long)c * n : nullptr;
+        for (int j = lane; j < n; j += 64) {
+            const float v = L[((size_t)j << sh) + c];
+            eo[j] = v <= 0.0f;
+            if (lo) lo[j] = (double)v;
+        }
+    }
+}
+
 template <int TW, bool GLOBAL, int SRC = kMsPriorTable>
 __global__ __launch_bounds__(TW * 64) void minsum_kernel(typename MsParamsOf<SRC>::type kp)
 {

@@ -30,7 +30,7 @@
 //   * the weight of a solution is summed in int64 per lane over the threads that share it, through an LDS word per lane.
 // A lane that has stopped is frozen: its M and best are not written again.  The tile ends with its last lane.
 #pragma once
-#include "pauli_kernels.hpp"   // pauli_decide; minsum_kernels.hpp: ms_clamp, ms_message, kMsNone
+#include "pauli_kernels.hpp"   // pauli_decide; minsum_kernels.hpp: ms_clamp, ms_message, ms_check_update
 
 namespace ldpc {
 
@@ -52,6 +52,90 @@ struct PauliRelayParams {
     unsigned char *ws;                // GLOBAL: [grid][slot_bytes]
     long long slot_bytes;
 };
+
+// ---- the legs of a lane, as named steps (relay_kernel of relay_kernels.hpp spells the same steps inline: with these
+// functions it measured about 1 % slower, profiles/check_update_refactor_probe.txt).  Every thread of a lane keeps an equal copy.
+struct RelayLeg {
+    bool fresh = true, pending = false, last = false;   // fresh: the leg starts with the next check sweep; pending: a bit sweep awaits its test
+    int leg = 0, t_in = 0, my_iters = 0, my_found = 0;   // t_in: iterations of the leg that have run
+    long long best_w = 0;
+};
+
+// A solution (`sol`: the lane's test found one): its weight, summed per lane over the threads that share it through sh_w;
+// the lighter one is kept in best, PLANES bit planes of bw words.  decision(j): bit p of it goes into plane p;
+// weight_of(j, E): the weight of decision E at j.  Every thread of the workgroup calls this: one barrier where no lane has
+// a solution, three where one has.
+template <int PLANES, class Decision, class WeightOf>
+__device__ inline void relay_keep_lighter(RelayLeg &g, bool sol, unsigned long long *sh_w, unsigned *best, int n, int sh, int l, int q, int Q, int t,
+                                          Decision decision, WeightOf weight_of)
+{
+    const int bw = (n + 31) >> 5;
+    if (!__syncthreads_or(sol)) return;
+    if (sol) {
+        long long part = 0;
+        for (int w = q; w < bw; w += Q) {
+            const int je = (w << 5) + 32 < n ? (w << 5) + 32 : n;
+            for (int j = w << 5; j < je; ++j) part += weight_of(j, decision(j));
+        }
+        if (part) atomicAdd(&sh_w[l], (unsigned long long)part);
+    }
+    __syncthreads();
+    if (sol) {
+        const long long w_now = (long long)sh_w[l];
+        if (g.my_found == 0 || w_now < g.best_w) {   // a tie keeps the earlier solution
+            g.best_w = w_now;
+            for (int w = q; w < bw; w += Q) {
+                const int je = (w << 5) + 32 < n ? (w << 5) + 32 : n;
+                unsigned bits[PLANES] = {};
+                for (int j = w << 5; j < je; ++j) {
+                    const unsigned E = decision(j);
+#pragma unroll
+                    for (int pl = 0; pl < PLANES; ++pl) bits[pl] |= ((E >> pl) & 1u) << (j & 31);
+                }
+#pragma unroll
+                for (int pl = 0; pl < PLANES; ++pl) best[((size_t)(pl * bw + w) << sh) + l] = bits[pl];
+            }
+        }
+        g.my_found += 1;
+    }
+    __syncthreads();
+    if (t < 64) sh_w[t] = 0ull;
+}
+
+// What the test means for a lane whose bit sweep awaited it: stop (false goes into `active`), go on, or start the next leg
+// from this M in the middle of the old one -- then true is returned, and the lane spends the round's bit sweep on that start.
+// A lane that stops leaves in sh_have whether the write-out takes best.
+__device__ inline bool relay_after_test(RelayLeg &g, bool &active, bool sol, int legs, int stop_after, unsigned char *sh_have, int l, int q)
+{
+    const bool was_fresh = g.fresh;
+    bool restart = false;
+    g.fresh = false;
+    if (active && g.pending) {
+        bool stop = g.last;   // the last leg has used up its iterations
+        if (sol) {
+            if (g.my_found == stop_after) stop = true;
+            else if (was_fresh) {}   // the leg ended with this iteration anyway: the next one has started
+            else if (g.leg + 1 < legs) { g.leg += 1; g.t_in = 0; g.fresh = true; restart = true; }
+            else stop = true;
+        }
+        if (stop) {
+            active = false;
+            if (q == 0) sh_have[l] = g.my_found > 0;
+        }
+        g.pending = false;
+    }
+    return restart;
+}
+
+// A bit sweep has run: the iteration counts; `next`: it wrote the next leg's start, `ends`: the leg ended with it.
+__device__ inline void relay_after_sweep(RelayLeg &g, bool ends, bool next)
+{
+    g.t_in += 1;
+    g.my_iters += 1;
+    g.pending = true;
+    if (next) { g.leg += 1; g.t_in = 0; g.fresh = true; }
+    else if (ends) g.last = true;
+}
 
 template <int TW, bool GLOBAL>
 __global__ __launch_bounds__(TW * 64) void pauli_relay_kernel(PauliRelayParams p)
@@ -101,18 +185,11 @@ __global__ __launch_bounds__(TW * 64) void pauli_relay_kernel(PauliRelayParams p
             G[plane + at] = ((tab[(size_t)2 * n + j] + g * my) + 0.0f) + 0.0f;
             G[2 * plane + at] = (tab[(size_t)3 * n + j] + g * mz) + 0.0f;
         }
-        for (int c = wave; c < S; c += TW) {
-            if (c < valid) {
-                const uint8_t *ax = p.sx + (col0 + c) * rx, *az = p.sz + (col0 + c) * rz;
-                for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = (i < rx ? ax[i] : az[i - rx]) != 0;
-            } else {   // a lane past the batch reads nothing and never becomes active
-                for (int i = lane; i < s; i += 64) Y[((size_t)i << sh) + c] = 0;
-            }
-        }
+        ms_stage_syndromes<TW>(Y, s, S, sh, valid, wave, lane,
+                               [&](int c, int i) { return i < rx ? p.sx[(col0 + c) * rx + i] : p.sz[(col0 + c) * rz + (i - rx)]; });
         if (t < 64) { sh_bad[t] = 0; sh_have[t] = 0; sh_w[t] = 0ull; }
-        bool active = l < valid, fresh = true, pending = false, last = false;
-        int leg = 0, t_in = 0, my_iters = 0, my_found = 0;
-        long long best_w = 0;
+        bool active = l < valid;
+        RelayLeg lg;
         __syncthreads();
 
         for (;;) {
@@ -128,140 +205,34 @@ __global__ __launch_bounds__(TW * 64) void pauli_relay_kernel(PauliRelayParams p
                     }
                     const bool zrow = i >= rx;   // an Hz row: it sees the X parts
                     unsigned hard = 0;
-                    // b_k of the check's k-th qubit against its old message c
-                    auto edge = [&](int k, float c) -> float {
+                    // b_k of the check's k-th qubit (on G) against its old message c; where tested, the part of the qubit's
+                    // decision (on M) that the check sees goes into `hard`
+                    ms_check_update(R + ((size_t)rec_off[i] << sh) + l, deg, sh, alpha, clip, y, lg.fresh, true, [&](int k, float c, bool test) {
                         const size_t at = ((size_t)csr_col[ra + k] << sh) + l;
+                        if (test) {
+                            const unsigned E = decide_at(at);
+                            hard ^= zrow ? (E & 1u) : (E >> 1);
+                        }
                         const float gx = G[at], gy = G[plane + at], gz = G[2 * plane + at];
                         const float own = zrow ? gx : gz, other = zrow ? gz : gx;
                         const float u = gy < own ? gy : own;            // min(GY, own)
                         const float w = other < 0.0f ? other : 0.0f;
                         return ms_clamp((u - c) - w, clip);
-                    };
-                    // the part of the k-th qubit's decision (on M) that the check sees
-                    auto seen = [&](int k) -> unsigned {
-                        const unsigned E = decide_at(((size_t)csr_col[ra + k] << sh) + l);
-                        return zrow ? (E & 1u) : (E >> 1);
-                    };
-                    unsigned *rec = R + ((size_t)rec_off[i] << sh) + l;
-                    float m1 = clip, m2 = clip;
-                    unsigned a = kMsNone, par = y;
-                    if (deg <= 64) {
-                        const float o1 = fresh ? 0.0f : __uint_as_float(rec[0]);
-                        const float o2 = fresh ? 0.0f : __uint_as_float(rec[(size_t)1 << sh]);
-                        const unsigned oa = rec[(size_t)2 << sh];
-                        unsigned sg = fresh ? 0u : rec[(size_t)3 << sh], neg_lo = 0, neg_hi = 0;
-                        const int d0 = deg < 32 ? deg : 32;
-                        for (int k = 0; k < d0; ++k) {
-                            hard ^= seen(k);
-                            const float cm = (unsigned)k == oa ? o2 : o1;
-                            const float b = edge(k, (sg >> k) & 1u ? -cm : cm);
-                            const unsigned ng = b < 0.0f;
-                            const float mag = fabsf(b);
-                            neg_lo |= ng << k;
-                            par ^= ng;
-                            if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
-                            else if (mag < m2) m2 = mag;
-                        }
-                        if (deg > 32) {
-                            sg = fresh ? 0u : rec[(size_t)4 << sh];
-                            for (int k = 32; k < deg; ++k) {
-                                hard ^= seen(k);
-                                const float cm = (unsigned)k == oa ? o2 : o1;
-                                const float b = edge(k, (sg >> (k - 32)) & 1u ? -cm : cm);
-                                const unsigned ng = b < 0.0f;
-                                const float mag = fabsf(b);
-                                neg_hi |= ng << (k - 32);
-                                par ^= ng;
-                                if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
-                                else if (mag < m2) m2 = mag;
-                            }
-                        }
-                        const unsigned flip = par ? 0xffffffffu : 0u;   // negative iff par XOR neg_k
-                        rec[0] = __float_as_uint(alpha * m1);
-                        rec[(size_t)1 << sh] = __float_as_uint(alpha * m2);
-                        rec[(size_t)2 << sh] = a;
-                        rec[(size_t)3 << sh] = (neg_lo ^ flip) & (d0 == 32 ? 0xffffffffu : (1u << d0) - 1u);
-                        if (deg > 32) rec[(size_t)4 << sh] = (neg_hi ^ flip) & (deg == 64 ? 0xffffffffu : (1u << (deg - 32)) - 1u);
-                    } else {
-                        // per-edge record: the minima first, then every edge's b once more for its sign
-                        for (int k = 0; k < deg; ++k) {
-                            hard ^= seen(k);
-                            const float b = edge(k, fresh ? 0.0f : __uint_as_float(rec[(size_t)k << sh]));
-                            const float mag = fabsf(b);
-                            par ^= (unsigned)(b < 0.0f);
-                            if (mag < m1) { m2 = m1; m1 = mag; a = (unsigned)k; }
-                            else if (mag < m2) m2 = mag;
-                        }
-                        const float n1 = alpha * m1, n2 = alpha * m2;
-                        for (int k = 0; k < deg; ++k) {
-                            const float b = edge(k, fresh ? 0.0f : __uint_as_float(rec[(size_t)k << sh]));
-                            const float cm = (unsigned)k == a ? n2 : n1;
-                            rec[(size_t)k << sh] = __float_as_uint((par ^ (unsigned)(b < 0.0f)) ? -cm : cm);
-                        }
-                    }
+                    });
                     bad |= (int)(hard ^ y);
                 }
                 if (bad) sh_bad[l] = 1;
             }
             __syncthreads();
-            const bool was_fresh = fresh;
-            const bool sol = active && pending && !sh_bad[l];   // the M of the bit sweep before reproduces both syndromes
-            fresh = false;
-            // ---- a solution: its weight, summed per lane over the threads that share it; the lighter one is kept
-            if (__syncthreads_or(sol)) {
-                if (sol) {
-                    long long part = 0;
-                    for (int w = q; w < bw; w += Q) {
-                        const int je = (w << 5) + 32 < n ? (w << 5) + 32 : n;
-                        for (int j = w << 5; j < je; ++j) {
-                            const unsigned E = decide_at(((size_t)j << sh) + l);   // 1 = X, 3 = Y, 2 = Z
-                            if (E) part += weight[(size_t)(E == 1u ? 0 : E == 3u ? 1 : 2) * n + j];
-                        }
-                    }
-                    if (part) atomicAdd(&sh_w[l], (unsigned long long)part);
-                }
-                __syncthreads();
-                if (sol) {
-                    const long long w_now = (long long)sh_w[l];
-                    if (my_found == 0 || w_now < best_w) {   // a tie keeps the earlier solution
-                        best_w = w_now;
-                        for (int w = q; w < bw; w += Q) {
-                            const int je = (w << 5) + 32 < n ? (w << 5) + 32 : n;
-                            unsigned bx = 0, bz = 0;
-                            for (int j = w << 5; j < je; ++j) {
-                                const unsigned E = decide_at(((size_t)j << sh) + l);
-                                bx |= (E & 1u) << (j & 31);
-                                bz |= (E >> 1) << (j & 31);
-                            }
-                            Bst[((size_t)w << sh) + l] = bx;
-                            Bst[((size_t)(bw + w) << sh) + l] = bz;
-                        }
-                    }
-                    my_found += 1;
-                }
-                __syncthreads();
-                if (t < 64) sh_w[t] = 0ull;
-            }
+            const bool sol = active && lg.pending && !sh_bad[l];   // the M of the bit sweep before reproduces both syndromes
+            relay_keep_lighter<2>(lg, sol, sh_w, Bst, n, sh, l, q, Q, t,
+                                  [&](int j) -> unsigned { return decide_at(((size_t)j << sh) + l); },   // 1 = X, 3 = Y, 2 = Z
+                                  [&](int j, unsigned E) -> long long { return E ? weight[(size_t)(E == 1u ? 0 : E == 3u ? 1 : 2) * n + j] : 0; });
             if (t < 64) sh_bad[t] = 0;
-            // ---- what the test means for the lane: stop, go on, or start the next leg from this M
-            bool restart = false;
-            if (active && pending) {
-                bool stop = last;   // the last leg has used up its iterations
-                if (sol) {
-                    if (my_found == p.stop_after) stop = true;
-                    else if (was_fresh) {}   // the leg ended with this iteration anyway: the next one has started
-                    else if (leg + 1 < p.legs) { leg += 1; t_in = 0; fresh = true; restart = true; }
-                    else stop = true;
-                }
-                if (stop) {
-                    active = false;
-                    if (q == 0) sh_have[l] = my_found > 0;
-                }
-                pending = false;
-            }
+            const bool restart = relay_after_test(lg, active, sol, p.legs, p.stop_after, sh_have, l, q);
             if (!__syncthreads_or(active)) break;
             if (active) {
-                const float *__restrict__ row = tab + (size_t)leg * 4 * (size_t)n;   // gamma, g0X, g0Y, g0Z of the lane's leg
+                const float *__restrict__ row = tab + (size_t)lg.leg * 4 * (size_t)n;   // gamma, g0X, g0Y, g0Z of the lane's leg
                 if (restart) {
                     // ---- leg start in the middle of the old leg: G = Lambda + (+0) totals; the next round sweeps it (`fresh`)
                     for (int j = q; j < n; j += Q) {
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(TW * 64) void pauli_relay_kernel(PauliRelayParams p
                     // ---- bit sweep: TZ over the qubit's Hx checks, TX over its Hz checks, each from +0 in ascending order;
                     // M = Lambda(old M) + T; G = Lambda(new M) + T, or, where the leg ends with this iteration, the next
                     // leg's start G = Lambda'(new M) + (+0)
-                    const bool ends = t_in + 1 == leg_iters[leg], next = ends && leg + 1 < p.legs;
+                    const bool ends = lg.t_in + 1 == leg_iters[lg.leg], next = ends && lg.leg + 1 < p.legs;
                     const float *__restrict__ row2 = row + (size_t)4 * n;
                     for (int j = q; j < n; j += Q) {
                         const size_t at = ((size_t)j << sh) + l;
@@ -301,11 +272,7 @@ __global__ __launch_bounds__(TW * 64) void pauli_relay_kernel(PauliRelayParams p
                             G[2 * plane + at] = (hz + g * mz) + tz;
                         }
                     }
-                    t_in += 1;
-                    my_iters += 1;
-                    pending = true;
-                    if (next) { leg += 1; t_in = 0; fresh = true; }
-                    else if (ends) last = true;
+                    relay_after_sweep(lg, ends, next);
                 }
             }
             __syncthreads();
@@ -332,9 +299,9 @@ __global__ __launch_bounds__(TW * 64) void pauli_relay_kernel(PauliRelayParams p
             }
         }
         if (q == 0 && l < valid) {
-            p.conv[col0 + l] = (uint8_t)(my_found > 0);
-            if (p.iters) p.iters[col0 + l] = my_iters;
-            if (p.solutions) p.solutions[col0 + l] = my_found;
+            p.conv[col0 + l] = (uint8_t)(lg.my_found > 0);
+            if (p.iters) p.iters[col0 + l] = lg.my_iters;
+            if (p.solutions) p.solutions[col0 + l] = lg.my_found;
         }
         __syncthreads();
     }

@@ -35,9 +35,10 @@ class PauliRelayModel(PauliMinSumModel):
         self.q = tuple(weights_of(p) for p in (self.px, self.py, self.pz))                       # qX, qY, qZ
         self.stop_after = int(stop_after)
 
-    def decode(self, sx_b, sz_b):
+    def decode(self, sx_b, sz_b, trace=None):
         """sx [B][rx], sz [B][rz] -> (gx [B][n] u8, gz [B][n] u8, conv [B] u8, iters [B] i32, solutions [B] i32,
-        M [B][3][n] f32: the planes MX, MY, MZ)."""
+        M [B][3][n] f32: the planes MX, MY, MZ).
+        trace: a list that receives (leg [B], iterations done in it [B], hit [B]) after every iteration."""
         yx = np.asarray(sx_b).reshape(-1, self.rx) != 0
         yz = np.asarray(sz_b).reshape(-1, self.rz) != 0
         assert yx.shape[0] == yz.shape[0]
@@ -126,6 +127,8 @@ class PauliRelayModel(PauliMinSumModel):
             best_x[better], best_z[better] = ex[better], ez[better]
             best_w[better] = w[better]
             found[hit] += 1
+            if trace is not None:
+                trace.append((leg.copy(), t.copy(), hit.copy()))
             stop = hit & (found == self.stop_after)
             leg_end = active & ~stop & (hit | (t == self.leg_iters[leg]))
             at[leg_end] += 1

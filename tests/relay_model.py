@@ -44,9 +44,10 @@ class RelayModel:
                 out[:, j] = out[:, j] + c[i][:, self.pos[(int(i), j)]]
         return out
 
-    def decode(self, syn_bs, trace=None):
+    def decode(self, syn_bs, trace=None, steps=None):
         """syn [B][s] -> (err [B][n] u8, conv [B] u8, iters [B] i32, solutions [B] i32, M [B][n] f32).
-        trace: a list that receives (iteration, leg [B], M, X, weight [B], hit [B]) after every iteration."""
+        trace: a list that receives (iteration, leg [B], M, X, weight [B], hit [B]) after every iteration;
+        steps: one that receives (leg [B], iterations done in it [B], hit [B]), the form of PauliRelayModel's trace."""
         y = (np.asarray(syn_bs).reshape(-1, self.s) != 0)
         B, n = y.shape[0], self.n
         run = [r for r in range(self.legs) if self.leg_iters[r] > 0]   # a leg of 0 iterations is skipped
@@ -114,6 +115,8 @@ class RelayModel:
             found[hit] += 1
             if trace is not None:
                 trace.append((step, leg.copy(), M.copy(), X.copy(), w.copy(), hit.copy()))
+            if steps is not None:
+                steps.append((leg.copy(), t.copy(), hit.copy()))
             stop = hit & (found == self.stop_after)
             leg_end = active & ~stop & (hit | (t == self.leg_iters[leg]))
             at[leg_end] += 1
