@@ -1,7 +1,7 @@
 // host_common.hpp -- the host-side scaffolding that the C entry points of every decoder share (BP, the multi-GPU
 // wrapper, BP-OTS, bit-flip, OSD on the device): the error text, the one "try a HIP call" macro, validation of the
-// caller's CSC pattern, device selection, the Tanner graph in both orders, device-buffer growth, the staging layout,
-// the latency path's flag spin and a few small helpers.  None of it has numerics or decides a kernel launch.
+// caller's CSC pattern, device selection, the Tanner graph in both orders, device-buffer growth, the staging layout
+// (host_pipe_plan.hpp), the latency path's mapped image and flag spin and a few small helpers.  None of it has numerics or decides a kernel launch.
 // Implemented in host_common.hip, except what is defined inline here.  The bounded waits: host_wait.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ldpc_mi355x.h"
+#include "host_pipe_plan.hpp"
 #include "host_wait.hpp"
 
 namespace ldpc_detail {
@@ -77,17 +78,7 @@ ldpc_status grow_device_buffer(void **p, size_t *cap, size_t bytes, int device, 
 // host_common.hip: workgroups of `kernel` a CU holds at once (1 if the runtime cannot tell)
 int blocks_per_cu(const void *kernel, int threads, size_t lds);
 
-// Carves a staging image into regions that each start on a 256-byte boundary: take() hands out the offset of the next
-// region, `at` is the size of what has been taken so far.
-struct Carve {
-    size_t at = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
+// (Carve, the staging layout: host_pipe_plan.hpp)
 
 // "Calls on a handle run in call order whatever streams they are given" (they share a workspace): a call enters by
 // making its stream wait for the one before, if that ran on another stream, and leaves by recording itself.
@@ -134,5 +125,35 @@ inline ldpc_status wait_flag(volatile unsigned int *flag, unsigned int ticket, h
         __builtin_ia32_pause();
     }
 }
+
+// The latency paths' image: host memory mapped into the device, [flag header 256 B][staging image].  The kernel reads and
+// writes the image in place and its last workgroup stores the call's ticket into the first word of the header, which
+// wait_flag() spins on.  Tickets skip 0, the value of a fresh header.
+struct LatencyImage {
+    static constexpr size_t kHeader = 256;
+    void *host = nullptr, *dev = nullptr;
+    size_t cap = 0;
+    unsigned ticket = 0;
+    ldpc_status ensure(size_t image_bytes)   // room for an image of that many bytes behind the header
+    {
+        if (cap >= kHeader + image_bytes) return LDPC_OK;
+        release();
+        LDPC_HIP_TRY(hipHostMalloc(&host, kHeader + image_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(host, 0, kHeader);
+        LDPC_HIP_TRY(hipHostGetDevicePointer(&dev, host, 0));
+        cap = kHeader + image_bytes;
+        return LDPC_OK;
+    }
+    void release()
+    {
+        if (host) (void)hipHostFree(host);
+        host = dev = nullptr; cap = 0;
+    }
+    char *image() const { return (char *)host + kHeader; }
+    char *image_dev() const { return (char *)dev + kHeader; }
+    volatile unsigned int *flag() const { return (volatile unsigned int *)host; }
+    unsigned int *flag_dev() const { return (unsigned int *)dev; }
+    unsigned next_ticket() { if (++ticket == 0) ticket = 1; return ticket; }
+};
 
 }  // namespace ldpc_detail

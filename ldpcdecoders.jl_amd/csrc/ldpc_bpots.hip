@@ -35,9 +35,7 @@ struct ldpc_bpots_decoder {
     size_t stage_cap = 0;
     // latency path of the host-pointer entry (DESIGN.md "Latency path"): host-mapped I/O image with a flag word
     unsigned int *done_ctr = nullptr;
-    void *lat_pin = nullptr, *lat_pin_dev = nullptr;
-    size_t lat_pin_cap = 0;
-    unsigned lat_ticket = 0;
+    ldpc_detail::LatencyImage lat;
     bool kernel_ready = false;  // dynamic-LDS limit set, occupancy known
     int per_cu = 1;
     bool node_mode = false;     // the graph is beyond the LDS kernel: bpots_node_kernel, messages in a global slot
@@ -52,7 +50,7 @@ struct ldpc_bpots_decoder {
         void *all[] = {row_ptr, csc_row, col_ptr, csc2csr, queue, stage, done_ctr, node_ws};
         for (void *q : all)
             if (q) (void)hipFree(q);
-        if (lat_pin) (void)hipHostFree(lat_pin);
+        lat.release();
     }
 };
 
@@ -261,28 +259,19 @@ ldpc_status ldpc_bpots_decode_batch(ldpc_bpots_decoder *d, int64_t batch, const 
     if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv) return set_error(LDPC_ERR_INVALID_ARGUMENT, "NULL batch pointer");
     LDPC_HIP_TRY(hipSetDevice(d->device));
     const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations]
-    image.take(B * s);
-    const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * 4), total = image.at;
+    const ldpc_detail::StageLayout L = ldpc_detail::stage_layout(B, B * s, B * n, false, n);   // [syndromes][errors][converged][iterations]
+    const size_t o_err = L.o_err, o_conv = L.o_conv, o_it = L.o_it, total = L.total;
     static const bool lat_off = exp_env("LDPC_NO_LATENCY_PATH") != nullptr;
     if (!d->node_mode && !lat_off && d->max_iters > 0 && ots_latency_ok(total, ots_groups(batch, d->logS), d->num_cus)) {
-        const size_t hdr = 256;
-        if (!d->lat_pin) {
-            const size_t cap = hdr + kOtsLatencyImage;
-            LDPC_HIP_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset(d->lat_pin, 0, hdr);
-            LDPC_HIP_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));
-            d->lat_pin_cap = cap;
-        }
-        char *hp = (char *)d->lat_pin + hdr, *dp = (char *)d->lat_pin_dev + hdr;
-        volatile unsigned int *flag = (volatile unsigned int *)d->lat_pin;
-        if (++d->lat_ticket == 0) d->lat_ticket = 1;
-        const OtsLatencyCtl lc{(unsigned int *)d->lat_pin_dev, d->lat_ticket};
+        const ldpc_status ist = d->lat.ensure(kOtsLatencyImage);
+        if (ist != LDPC_OK) return ist;
+        char *hp = d->lat.image(), *dp = d->lat.image_dev();
+        const OtsLatencyCtl lc{d->lat.flag_dev(), d->lat.next_ticket()};
         std::memcpy(hp, syn, B * s);
         ldpc_status lst = bpots_decode_impl(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
                                             (int32_t *)(dp + o_it), nullptr, &lc);
         if (lst != LDPC_OK) return lst;
-        if ((lst = ldpc_detail::wait_flag(flag, lc.ticket, nullptr, d->device, "BP-OTS latency path (flag of the last workgroup)")) != LDPC_OK) return lst;
+        if ((lst = ldpc_detail::wait_flag(d->lat.flag(), lc.ticket, nullptr, d->device, "BP-OTS latency path (flag of the last workgroup)")) != LDPC_OK) return lst;
         std::memcpy(err, hp + o_err, B * n);
         std::memcpy(conv, hp + o_conv, B);
         if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));

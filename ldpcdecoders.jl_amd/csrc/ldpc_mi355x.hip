@@ -385,10 +385,7 @@ struct ldpc_bp_decoder {
     // latency mode of the host-pointer entry (tiny batches, a plain decode!): the kernel reads and writes a
     // host-mapped staging image and raises a flag in it; no copies, no events, no stream synchronisation
     DevBuf done_ctr;          // one device word, zero between launches
-    void *lat_pin = nullptr;  // [flag 256 B][syndromes][errors][converged][iters][llr], hipHostMallocMapped
-    void *lat_pin_dev = nullptr;
-    size_t lat_pin_cap = 0;
-    unsigned lat_ticket = 0;
+    ldpc_detail::LatencyImage lat;   // [flag 256 B][syndromes][errors][converged][iters][llr], host memory mapped into the device
     // kernels whose dynamic-LDS limit is set / whose occupancy is known (both are ~us runtime calls)
     std::vector<std::pair<const void *, int>> kernel_info;
     ldpc_status prepare_kernel(const void *fn, int threads, size_t lds, int *per_cu);
@@ -413,10 +410,12 @@ struct ldpc_bp_decoder {
     DevBuf st_all;            // device image of a small host batch
     void *pin = nullptr;      // pinned host image for small batches
     size_t pin_cap = 0;
-    // host-buffer pipeline for large batches: 3 pinned + 3 device chunk images, copy / compute / copy streams
+    // host-buffer pipeline for large batches: 3 pinned + 3 device chunk images, copy / compute / copy streams.  ONE ring
+    // for the byte and the bit-packed entry: both are synchronous and drain it before they return, so a call never finds
+    // a slot in use.  Every slot has a capacity of its own: a call does not touch the slots beyond its chunk count.
     static constexpr int kPipe = 3;
     void *pipe_pin[kPipe] = {};
-    size_t pipe_pin_cap = 0;
+    size_t pipe_pin_cap[kPipe] = {};
     DevBuf pipe_dev[kPipe];
     hipStream_t pipe_stream[3] = {};          // H2D, compute, D2H
     hipEvent_t pipe_ev[kPipe][3] = {};        // per slot: H2D done, compute done, D2H done
@@ -435,13 +434,11 @@ struct ldpc_bp_decoder {
     hipStream_t last_stream = nullptr;
     hipEvent_t last_ev = nullptr;  // one of ev[][] / bits_ev[][] (not owned): completion of the most recent enqueued call
     // bit-packed entries (ldpc_bp_decode_batch_bits[_device]; bit_io_kernels.hpp): byte staging of the caller's bit
-    // strings, the events that bracket conversion + decode + conversion of a call (total_ms of that call), and the
-    // pinned word images of the host pipeline (the device images are pipe_dev / st_all, the streams pipe_stream)
+    // strings, and the events that bracket conversion + decode + conversion of a call (total_ms of that call).  The host
+    // entry stages its word images where the byte entry stages bytes: pin / st_all, the pipeline's ring above.
     DevBuf bits_syn, bits_err;
     hipEvent_t bits_ev[kRing][2] = {};
     bool bits_timed[kRing] = {};
-    void *bits_pin[kPipe] = {};
-    size_t bits_pin_cap[kPipe] = {};
     int inject_fault = 0;          // tests (experiments build, LDPC_TEAM_INJECT_FAULT at create): 1 = team kernels raise the fault word at once, 2 = a member misses the roll call
     unsigned rollcall_ticks = 2000000u;   // 20 ms of the 100 MHz clock: how long the members of a team wait for each other at launch (team_rollcall)
 
@@ -460,11 +457,9 @@ struct ldpc_bp_decoder {
         for (DevBuf &b : pipe_dev) b.release(idle);
         if (stalled) return;   // pinned memory the device may still write, streams it may still run: left alone
         if (pin) (void)hipHostFree(pin);
-        if (lat_pin) (void)hipHostFree(lat_pin);
+        lat.release();
         if (team_fault) (void)hipHostFree(team_fault);
         for (void *&q : pipe_pin)
-            if (q) (void)hipHostFree(q);
-        for (void *&q : bits_pin)
             if (q) (void)hipHostFree(q);
         for (auto &pair : bits_ev)
             for (hipEvent_t &e : pair)
@@ -497,6 +492,7 @@ namespace {
 void parallel_memcpy(void *dst, const void *src, size_t bytes)
 {
     if (bytes == 0) return;
+    if (bytes < ((size_t)8 << 20)) { std::memcpy(dst, src, bytes); return; }   // (under 4 MiB a thread: one thread, and no question to the system)
     unsigned hw = std::thread::hardware_concurrency();
     size_t nt = std::min<size_t>(std::max<unsigned>(hw / 2, 1), 8);
     nt = std::min(nt, bytes / ((size_t)4 << 20));
@@ -946,7 +942,7 @@ static hipError_t launch_team_grid(ldpc_bp_decoder *d, team_kernel_t tk, int gri
     return e;
 }
 
-// Latency mode (see ldpc_bp_decoder::lat_pin): the word the last workgroup raises, and its value.
+// Latency mode (see ldpc_bp_decoder::lat): the word the last workgroup raises, and its value.
 struct LatencyCtl {
     unsigned int *flag;
     unsigned int ticket;
@@ -1323,6 +1319,50 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         return LDPC_OK;
     }
 
+    const int *a_row = (const int *)d->row_ptr.p, *a_eb = (const int *)d->edge_bit.p, *a_col = (const int *)d->col_ptr.p,
+              *a_c2r = (const int *)d->csc2csr.p;
+    // The launch of a single-kernel path.  Latency mode: the launch and nothing else -- no memset, no events.  Otherwise
+    // between two events, the control slot zeroed first unless the call before left it clean, as this kernel leaves the next.
+    auto single_kernel = [&](auto fn, int64_t grid, int threads, size_t lds, const auto &params) -> ldpc_status {
+        if (!lat) {
+            if (!d->ctrl_clean[slot]) LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
+            d->ctrl_clean[slot] = false;
+            LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
+        }
+        hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, params, a_row, a_eb, a_col, a_c2r);
+        LDPC_HIP_TRY(hipGetLastError());
+        if (lat) return LDPC_OK;
+        LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
+        d->ctrl_clean[nslot] = true; d->timed[nslot] = false;
+        d->timed[slot] = true; d->two_events[slot] = true;
+        d->last_ev = ev[2];
+        return LDPC_OK;
+    };
+    // Set-up of a node-parallel launch (bp_node_kernels.hpp), for a fresh batch and for the stragglers of a packed level:
+    // where the messages live, the instantiation, its LDS and message slots, and the NodeParams fields that do not depend
+    // on who launches.  threads_global: the thread count with the messages in the global slots (in LDS, in part or whole:
+    // one 16-wave workgroup per CU); grid_of(per_cu, msg_mode): the caller's grid.
+    struct NodeLaunch { int msg_mode, threads, grid; size_t lds; node_kernel_t fn; };
+    auto node_launch_setup = [&](int threads_global, auto &&grid_of, NodeLaunch &nl, NodeParams &np) -> ldpc_status {
+        nl.msg_mode = d->node_msg_lds ? 1 : (d->node_split_check > 0 ? 2 : 0);
+        nl.threads = nl.msg_mode ? 1024 : threads_global;
+        nl.lds = node_lds_bytes((int)s, (int)n) +
+                 (nl.msg_mode == 1 ? (size_t)d->nnz : nl.msg_mode == 2 ? (size_t)d->node_split_edge : 0) * sizeof(double);
+        nl.fn = pick_node_kernel(d->max_cdeg, d->max_bdeg, d_llr != nullptr, nl.threads, nl.msg_mode);
+        int per_cu = 0;
+        ldpc_status nst = d->prepare_kernel((const void *)nl.fn, nl.threads, nl.lds, &per_cu);
+        if (nst != LDPC_OK) return nst;
+        nl.grid = grid_of(per_cu, nl.msg_mode);
+        const size_t stride = (std::max<size_t>((size_t)d->nnz, 1) + 63) & ~(size_t)63;   // 512-byte aligned slots
+        if ((nst = d->node_msg.ensure(nl.msg_mode == 1 ? 64 : (size_t)nl.grid * stride * sizeof(double))) != LDPC_OK) return nst;
+        np.s = (int)s; np.n = (int)n; np.nnz = (int)d->nnz; np.max_iters = (int)d->max_iters; np.r = d->per / (1 - d->per);
+        np.syn = d_syn; np.err = d_err; np.conv = d_conv; np.iters = d_iters; np.llr = d_llr; np.llr_exact = d->llr_exact ? 1 : 0;
+        np.msg = (double *)d->node_msg.p; np.slot_stride = (long long)stride;
+        np.sum_iters = (u64 *)(ctrl + 8);
+        np.split_check = d->node_split_check; np.split_edge = d->node_split_edge;
+        return LDPC_OK;   // (queue, index / count / it0 / state and the done counters: the caller's; zero so far)
+    };
+
     const bool want_llr_early = d_llr != nullptr;
     if (takes_lds_kernel(d, want_llr_early)) {
         // ---- on-chip path: messages never leave the LDS (bp_lds_kernels.hpp)
@@ -1339,8 +1379,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         lp.queue = (unsigned int *)ctrl;
         lp.sum_iters = (u64 *)(ctrl + 8);
         lp.phase_ticks = (u64 *)(ctrl + 16);
-        lp.done_count = (unsigned int *)d->done_ctr.p; lp.done_flag = nullptr; lp.done_ticket = 0;
-        lp.next_ctrl = nullptr;
+        lp.done_count = (unsigned int *)d->done_ctr.p;
         const size_t lds = lds_bytes_needed((int)s, (int)n, (int)d->nnz, 1 << logS, want_llr_early);
         // 512 threads when two or more workgroups share a CU; when the LDS footprint admits only
         // one, give that one all 16 waves (measured +21 % on the (9,10)-regular n=1000 code)
@@ -1354,87 +1393,33 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         const int lgrid = (int)std::min<int64_t>(ngroups64, (int64_t)per_cu * d->num_cus);
         // dequeue in chunks: ~16 dequeues per workgroup keep the load balanced and the queue word quiet
         lp.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, ngroups64 / ((int64_t)lgrid * 16)));
-        if (lat) {   // one launch and nothing else: no queue, no statistics, no events
+        if (lat) {   // no queue (a workgroup per group), no statistics
             lp.queue = nullptr; lp.sum_iters = nullptr; lp.chunk = 1;
             lp.done_flag = lat->flag; lp.done_ticket = lat->ticket;
-            hipLaunchKernelGGL(lk, dim3((unsigned)ngroups64), dim3((unsigned)lthreads), lds, stream, lp,
-                               (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
-                               (const int *)d->csc2csr.p);
-            LDPC_HIP_TRY(hipGetLastError());
-            return LDPC_OK;
-        }
-        if (!d->ctrl_clean[slot]) LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
-        d->ctrl_clean[slot] = false;
-        lp.next_ctrl = (u64 *)next_ctrl;
-        LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
-        hipLaunchKernelGGL(lk, dim3((unsigned)lgrid), dim3((unsigned)lthreads), lds, stream, lp,
-                           (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
-                           (const int *)d->csc2csr.p);
-        LDPC_HIP_TRY(hipGetLastError());
-        LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
-        d->ctrl_clean[nslot] = true;
-        d->timed[nslot] = false;
-        d->timed[slot] = true;
-        d->two_events[slot] = true;
-        d->last_ev = ev[2];
-        return LDPC_OK;
+        } else lp.next_ctrl = (u64 *)next_ctrl;
+        return single_kernel(lk, lat ? ngroups64 : (int64_t)lgrid, lthreads, lds, lp);
     }
 
     if (takes_node_kernel(d, batch, want_llr_early)) {
         // ---- small batch on a large graph: one workgroup per syndrome, one thread per node (bp_node_kernels.hpp)
         if (batch > (1ll << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
         // all 16 waves of a CU on one syndrome while there are CUs to spare, else two 8-wave workgroups per CU
-        const bool mlds = d->node_msg_lds;   // messages in LDS: one 16-wave workgroup per CU
-        const int msg_mode = mlds ? 1 : (d->node_split_check > 0 ? 2 : 0);
-        const int nthreads = msg_mode ? 1024 : (d->wpt_fixed ? (d->wpt_fixed >= 12 ? 1024 : 512) : (batch <= d->num_cus ? 1024 : 512));
-        const size_t nlds = node_lds_bytes((int)s, (int)n) +
-                            (msg_mode == 1 ? (size_t)d->nnz : msg_mode == 2 ? (size_t)d->node_split_edge : 0) * sizeof(double);
-        node_kernel_t nk = pick_node_kernel(d->max_cdeg, d->max_bdeg, want_llr_early, nthreads, msg_mode);
-        int per_cu = 0;
-        ldpc_status pst = d->prepare_kernel((const void *)nk, nthreads, nlds, &per_cu);
+        NodeLaunch nl; NodeParams np{};
+        const ldpc_status pst = node_launch_setup(
+            d->wpt_fixed ? (d->wpt_fixed >= 12 ? 1024 : 512) : (batch <= d->num_cus ? 1024 : 512),
+            [&](int per_cu, int) { return lat ? (int)batch : (int)std::min<int64_t>(batch, (int64_t)std::min(per_cu, 2) * d->num_cus); }, nl, np);
         if (pst != LDPC_OK) return pst;
-        per_cu = std::min(per_cu, 2);
-        const int ngrid = lat ? (int)batch : (int)std::min<int64_t>(batch, (int64_t)per_cu * d->num_cus);
-        const size_t stride = (std::max<size_t>((size_t)d->nnz, 1) + 63) & ~(size_t)63;   // 512-byte aligned slots
-        ldpc_status nst = d->node_msg.ensure(mlds ? 64 : (size_t)ngrid * stride * sizeof(double));
-        if (nst != LDPC_OK) return nst;
         d->last_kernel = 3; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0;
-        NodeParams np{};
-        np.s = (int)s; np.n = (int)n; np.nnz = (int)d->nnz; np.max_iters = (int)d->max_iters;
-        np.batch = batch; np.r = d->per / (1 - d->per);
-        np.syn = d_syn; np.err = d_err; np.conv = d_conv; np.iters = d_iters; np.llr = d_llr; np.llr_exact = d->llr_exact ? 1 : 0;
-        np.msg = (double *)d->node_msg.p; np.slot_stride = (long long)stride;
+        np.batch = batch;
         np.queue = (unsigned int *)ctrl;
-        np.sum_iters = (u64 *)(ctrl + 8);
-        np.index = nullptr; np.count_dev = nullptr; np.count_max = 0;
-        np.split_check = d->node_split_check; np.split_edge = d->node_split_edge;
-        np.done_count = (unsigned int *)d->done_ctr.p; np.done_flag = nullptr; np.done_ticket = 0;
-        np.next_ctrl = nullptr;
-        if (lat) {
+        np.done_count = (unsigned int *)d->done_ctr.p;
+        if (lat) {   // no queue (a workgroup per syndrome), no statistics
             np.queue = nullptr; np.sum_iters = nullptr;
             np.done_flag = lat->flag; np.done_ticket = lat->ticket;
-            hipLaunchKernelGGL(nk, dim3((unsigned)ngrid), dim3((unsigned)nthreads), nlds, stream, np,
-                               (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
-                               (const int *)d->csc2csr.p);
-            LDPC_HIP_TRY(hipGetLastError());
-            return LDPC_OK;
-        }
-        if (!d->ctrl_clean[slot]) LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
-        d->ctrl_clean[slot] = false;
-        np.next_ctrl = (u64 *)next_ctrl;
-        LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
-        hipLaunchKernelGGL(nk, dim3((unsigned)ngrid), dim3((unsigned)nthreads), nlds, stream, np,
-                           (const int *)d->row_ptr.p, (const int *)d->edge_bit.p, (const int *)d->col_ptr.p,
-                           (const int *)d->csc2csr.p);
-        LDPC_HIP_TRY(hipGetLastError());
-        LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
-        d->ctrl_clean[nslot] = true;
-        d->timed[nslot] = false;
-        d->two_events[slot] = true;
-        d->timed[slot] = true;
-        d->last_ev = ev[2];
-        d->last_threads = nthreads; d->last_grid = ngrid;
-        return LDPC_OK;
+        } else np.next_ctrl = (u64 *)next_ctrl;
+        const ldpc_status lst = single_kernel(nl.fn, nl.grid, nl.threads, nl.lds, np);
+        if (lst == LDPC_OK && !lat) { d->last_threads = nl.threads; d->last_grid = nl.grid; }
+        return lst;
     }
 
     if (lat) return fail(LDPC_ERR_HIP, "internal: latency mode reached the tile kernel");
@@ -1577,15 +1562,35 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     LDPC_HIP_TRY(hipEventRecord(ev[0], stream));
     // four checks (bits) per lane in the pack / unpack kernels where the caller's arrays allow 4-byte accesses
     const bool syn_v4 = s % 4 == 0 && ((uintptr_t)d_syn & 3u) == 0, err_v4 = n % 4 == 0 && ((uintptr_t)d_err & 3u) == 0;
-    if (s > 0) {
-        dim3 g((unsigned)((s + (syn_v4 ? 255 : 63)) / (syn_v4 ? 256 : 64)), (unsigned)ntiles);
-        hipLaunchKernelGGL(syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, stream, d_syn, (long long)batch, (int)s,
-                           (u64 *)d->synmask.p, (u64 *)d->nevermask.p, (const int *)nullptr,
-                           (const unsigned int *)nullptr, 0u);
+    // Pack / unpack between the caller's arrays and the masks of `tiles` tiles: level 0 over the batch (list and count
+    // NULL), a packed level over the positions in its list (batch 0; beyond node_take syndromes only).
+    auto launch_pack = [&](DevBuf &syn_m, DevBuf &never_m, int tiles, long long batch_or_0, const int *list, const unsigned int *count,
+                           unsigned node_take) -> ldpc_status {
+        if (s <= 0) return LDPC_OK;
+        const dim3 g((unsigned)((s + (syn_v4 ? 255 : 63)) / (syn_v4 ? 256 : 64)), (unsigned)tiles);
+        hipLaunchKernelGGL(syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, stream, d_syn, batch_or_0, (int)s,
+                           (u64 *)syn_m.p, (u64 *)never_m.p, list, count, node_take);
         LDPC_HIP_TRY(hipGetLastError());
-    }
-    const int *a_row = (const int *)d->row_ptr.p, *a_eb = (const int *)d->edge_bit.p, *a_col = (const int *)d->col_ptr.p,
-              *a_c2r = (const int *)d->csc2csr.p;
+        return LDPC_OK;
+    };
+    auto launch_unpack_errors = [&](DevBuf &fin_m, int tiles, long long batch_or_0, const int *list, const unsigned int *count,
+                                    unsigned node_take) -> ldpc_status {
+        const dim3 g((unsigned)((n + (err_v4 ? 255 : 63)) / (err_v4 ? 256 : 64)), (unsigned)tiles);
+        hipLaunchKernelGGL(err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, g, dim3(64), 0, stream, (const u64 *)fin_m.p,
+                           batch_or_0, (int)n, d_err, list, count, node_take);
+        LDPC_HIP_TRY(hipGetLastError());
+        return LDPC_OK;
+    };
+    // (raw / exact / posmap: what a team's fresh pass left in llr_t, TeamParams::llr_raw; 0 / 0 / NULL for logarithms in bit order)
+    auto launch_unpack_llr = [&](DevBuf &llr_m, int tiles, long long batch_or_0, const int *list, const unsigned int *count,
+                                 unsigned node_take, int raw, int exact, const int *posmap) -> ldpc_status {
+        const dim3 g((unsigned)((n + 63) / 64), ((unsigned)tiles + 7u) & ~7u);   // (unpack_llr_kernel deals the tiles over the XCDs in eights)
+        hipLaunchKernelGGL(unpack_llr_kernel, g, dim3(256), 0, stream, (const double *)llr_m.p, batch_or_0, (int)n, d_llr, list, count,
+                           node_take, raw, exact, posmap);
+        LDPC_HIP_TRY(hipGetLastError());
+        return LDPC_OK;
+    };
+    if ((st = launch_pack(d->synmask, d->nevermask, ntiles, (long long)batch, nullptr, nullptr, 0u)) != LDPC_OK) return st;
     const unsigned ticket = (unsigned)(d->ncalls & 0x7fffffffu) ? (unsigned)(d->ncalls & 0x7fffffffu) : 0x7fffffffu;
     // per pass: the hot parameters travel by value (BPParams), the rest in a BPCold block in device memory
     BPCold cold[3] = {};
@@ -1784,13 +1789,8 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     for (int l = 1; l <= nlevels; ++l) {
         Level &L = lv[l];
         const u64 *l_syn = (const u64 *)d->lvl_syn[l - 1].p, *l_nev = (const u64 *)d->lvl_never[l - 1].p;
-        if (s > 0) {
-            dim3 g((unsigned)((s + (syn_v4 ? 255 : 63)) / (syn_v4 ? 256 : 64)), (unsigned)L.cap_tiles);
-            hipLaunchKernelGGL(syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, stream, d_syn, (long long)0, (int)s,
-                               (u64 *)d->lvl_syn[l - 1].p, (u64 *)d->lvl_never[l - 1].p, (const int *)d->lvl_list[l - 1].p,
-                               (const unsigned int *)L.count, L.node_take);
-            LDPC_HIP_TRY(hipGetLastError());
-        }
+        if ((st = launch_pack(d->lvl_syn[l - 1], d->lvl_never[l - 1], L.cap_tiles, 0, (const int *)d->lvl_list[l - 1].p, L.count, L.node_take)) != LDPC_OK)
+            return st;
         BPParams q = p;
         q.msg = (double *)d->lvl_state[l - 1].p;
         q.errmask = (u64 *)d->lvl_err[l - 1].p;
@@ -1822,62 +1822,29 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
     // ---- results out: level 0 first, then every level over the rows its lower levels gave up
     if (n > 0) {
-        dim3 g((unsigned)((n + 63) / 64), (unsigned)ntiles);
-        const dim3 ge((unsigned)((n + (err_v4 ? 255 : 63)) / (err_v4 ? 256 : 64)), (unsigned)ntiles);
-        hipLaunchKernelGGL(err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, ge, dim3(64), 0, stream, (const u64 *)d->finmask.p,
-                           (long long)batch, (int)n, d_err, (const int *)nullptr, (const unsigned int *)nullptr, 0u);
-        LDPC_HIP_TRY(hipGetLastError());
-        if (want_llr) {
-            const dim3 gl(g.x, (g.y + 7u) & ~7u);     // (unpack_llr_kernel deals the tiles over the XCDs in eights)
-            hipLaunchKernelGGL(unpack_llr_kernel, gl, dim3(256), 0, stream, (const double *)d->llr_t.p,
-                               (long long)batch, (int)n, d_llr, (const int *)nullptr, (const unsigned int *)nullptr, 0u, llr_raw_out, d->llr_exact ? 1 : 0, llr_posmap);
-            LDPC_HIP_TRY(hipGetLastError());
-        }
+        if ((st = launch_unpack_errors(d->finmask, ntiles, (long long)batch, nullptr, nullptr, 0u)) != LDPC_OK) return st;
+        if (want_llr && (st = launch_unpack_llr(d->llr_t, ntiles, (long long)batch, nullptr, nullptr, 0u, llr_raw_out, d->llr_exact ? 1 : 0, llr_posmap)) != LDPC_OK)
+            return st;
         for (int l = 1; l <= nlevels; ++l) {
-            dim3 g2((unsigned)((n + 63) / 64), (unsigned)lv[l].cap_tiles);
-            const dim3 ge2((unsigned)((n + (err_v4 ? 255 : 63)) / (err_v4 ? 256 : 64)), (unsigned)lv[l].cap_tiles);
-            hipLaunchKernelGGL(err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, ge2, dim3(64), 0, stream, (const u64 *)d->lvl_fin[l - 1].p,
-                               (long long)0, (int)n, d_err, (const int *)d->lvl_list[l - 1].p,
-                               (const unsigned int *)lv[l].count, lv[l].node_take);
-            LDPC_HIP_TRY(hipGetLastError());
-            if (want_llr) {
-                const dim3 gl2(g2.x, (g2.y + 7u) & ~7u);
-                hipLaunchKernelGGL(unpack_llr_kernel, gl2, dim3(256), 0, stream, (const double *)d->lvl_llr[l - 1].p,
-                                   (long long)0, (int)n, d_llr, (const int *)d->lvl_list[l - 1].p,
-                                   (const unsigned int *)lv[l].count, lv[l].node_take, 0, 0, (const int *)nullptr);
-                LDPC_HIP_TRY(hipGetLastError());
-            }
+            const int *list = (const int *)d->lvl_list[l - 1].p;
+            if ((st = launch_unpack_errors(d->lvl_fin[l - 1], lv[l].cap_tiles, 0, list, lv[l].count, lv[l].node_take)) != LDPC_OK) return st;
+            if (want_llr && (st = launch_unpack_llr(d->lvl_llr[l - 1], lv[l].cap_tiles, 0, list, lv[l].count, lv[l].node_take, 0, 0, nullptr)) != LDPC_OK)
+                return st;
         }
     }
     // ---- levels that hold only a few syndromes: the node-parallel kernel resumes each from its packed column
     for (int l = 1; l <= nlevels; ++l) {
         Level &L = lv[l];
         if (!L.node_take) continue;
-        const bool mlds = d->node_msg_lds;
-        const int msg_mode = mlds ? 1 : (d->node_split_check > 0 ? 2 : 0);
-        const int nthreads = msg_mode ? 1024 : 512;   // (global slots: 1024 x 1 per CU measured the same as 512 x 2)
-        const size_t nlds = node_lds_bytes((int)s, (int)n) +
-                            (msg_mode == 1 ? (size_t)d->nnz : msg_mode == 2 ? (size_t)d->node_split_edge : 0) * sizeof(double);
-        node_kernel_t nk = pick_node_kernel(d->max_cdeg, d->max_bdeg, want_llr, nthreads, msg_mode);
-        int per_cu_unused = 0;
-        if ((st = d->prepare_kernel((const void *)nk, nthreads, nlds, &per_cu_unused)) != LDPC_OK) return st;
-        const int ngrid = (int)std::min<int64_t>((int64_t)L.node_take, (int64_t)(msg_mode ? 1 : 2) * d->num_cus);
-        const size_t stride = (std::max<size_t>((size_t)d->nnz, 1) + 63) & ~(size_t)63;
-        if ((st = d->node_msg.ensure(mlds ? 64 : (size_t)ngrid * stride * sizeof(double))) != LDPC_OK) return st;
-        NodeParams np{};
-        np.s = (int)s; np.n = (int)n; np.nnz = (int)d->nnz; np.max_iters = (int)d->max_iters;
-        np.batch = 0; np.r = p.r;
-        np.syn = d_syn; np.err = d_err; np.conv = d_conv; np.iters = d_iters; np.llr = d_llr; np.llr_exact = d->llr_exact ? 1 : 0;
-        np.msg = (double *)d->node_msg.p; np.slot_stride = (long long)stride;
-        np.queue = L.node_queue;
-        np.sum_iters = (u64 *)(ctrl + 8);
+        NodeLaunch nl; NodeParams np{};
+        st = node_launch_setup(512 /* (global slots: 1024 x 1 per CU measured the same as 512 x 2) */,
+                               [&](int, int msg_mode) { return (int)std::min<int64_t>((int64_t)L.node_take, (int64_t)(msg_mode ? 1 : 2) * d->num_cus); }, nl, np);
+        if (st != LDPC_OK) return st;
+        np.batch = 0; np.queue = L.node_queue;
         np.index = (const int *)d->lvl_list[l - 1].p; np.count_dev = L.count; np.count_max = L.node_take;
-        np.it0 = (const int *)d->lvl_it[l - 1].p;
-        np.state = (const double *)d->lvl_state[l - 1].p;
+        np.it0 = (const int *)d->lvl_it[l - 1].p; np.state = (const double *)d->lvl_state[l - 1].p;
         np.state_stride = (long long)(slot_stride_bytes / sizeof(double));
-        np.done_count = nullptr; np.done_flag = nullptr; np.done_ticket = 0; np.next_ctrl = nullptr;
-        np.split_check = d->node_split_check; np.split_edge = d->node_split_edge;
-        hipLaunchKernelGGL(nk, dim3((unsigned)ngrid), dim3((unsigned)nthreads), nlds, stream, np, a_row, a_eb, a_col, a_c2r);
+        hipLaunchKernelGGL(nl.fn, dim3((unsigned)nl.grid), dim3((unsigned)nl.threads), nl.lds, stream, np, a_row, a_eb, a_col, a_c2r);
         LDPC_HIP_TRY(hipGetLastError());
     }
     LDPC_HIP_TRY(hipEventRecord(ev[3], stream));
@@ -1910,6 +1877,167 @@ ldpc_status ldpc_bp_decode_batch(ldpc_bp_decoder *d, int64_t batch, const uint8_
     return st;
 }
 
+}  // extern "C"
+
+// ---- host staging of the host-pointer entries: ldpc_bp_decode_batch (bytes) and ldpc_bp_decode_batch_bits (bit strings)
+// stage a batch the same way (arithmetic: host_pipe_plan.hpp).  A view of the caller's arrays says where they differ:
+//   layout(rows, llr) / bps(llr)  the staging image of `rows` syndromes / bytes per syndrome for the chunk rule
+//   fill(hp, b0, nb)              the input of columns [b0, b0 + nb) -> the head of the host image hp; returns the bytes to go H2D
+//   decode(d, b0, nb, dp, ...)    the entry's device form on the device image dp of those columns
+//   errors_out(img, b0, nb)       their hard decisions out of the error region of a host image
+// and carries the names the error texts use.  Converged flags, iteration counts and LLRs are the same for both.
+namespace {
+
+using ldpc_detail::StageLayout; using ldpc_detail::stage_layout; using ldpc_detail::word_image_bytes; using ldpc_detail::span_of;
+
+struct ByteView {
+    static constexpr const char *entry = "ldpc_bp_decode_batch", *pipe = "host pipeline";
+    const uint8_t *syn; uint8_t *err; size_t s, n;
+    StageLayout layout(size_t rows, bool llr) const { return stage_layout(rows, rows * s, rows * n, llr, n); }
+    size_t bps(bool llr) const { return s + n + 1 + sizeof(int32_t) + (llr ? n * sizeof(double) : 0); }
+    size_t fill(char *hp, size_t b0, size_t nb) const { parallel_memcpy(hp, syn + b0 * s, nb * s); return nb * s; }
+    ldpc_status decode(ldpc_bp_decoder *d, size_t, size_t nb, char *dp, const StageLayout &L, bool llr, hipStream_t stream) const
+    {
+        return ldpc_bp_decode_batch_device(d, (int64_t)nb, (const uint8_t *)dp, (uint8_t *)(dp + L.o_err), (uint8_t *)(dp + L.o_conv),
+                                           llr ? (double *)(dp + L.o_llr) : nullptr, (int32_t *)(dp + L.o_it), stream);
+    }
+    void errors_out(const char *img, size_t b0, size_t nb) const { parallel_memcpy(err + b0 * n, img, nb * n); }
+};
+
+// A chunk of columns starts at any bit: its image holds the words that cover it (span_of), the device entry gets the
+// offset into the first one, and the copy out merges the first / last word under a mask.
+struct BitsView {
+    static constexpr const char *entry = "ldpc_bp_decode_batch_bits", *pipe = "host pipeline of the bits entry";
+    const uint64_t *syn_w; int64_t syn_bit0; uint64_t *err_w; int64_t err_bit0; size_t s, n;
+    StageLayout layout(size_t rows, bool llr) const { return stage_layout(rows, word_image_bytes(rows * s), word_image_bytes(rows * n), llr, n); }
+    size_t bps(bool llr) const { return (s + n + 7) / 8 + 1 + sizeof(int32_t) + (llr ? n * sizeof(double) : 0); }   // bit layout
+    size_t fill(char *hp, size_t b0, size_t nb) const
+    {
+        const ldpc_detail::Span ss = span_of(syn_bit0, b0, nb, s);
+        if (ss.nwords) parallel_memcpy(hp, syn_w + ss.w0, ss.nwords * sizeof(uint64_t));
+        return ss.nwords * sizeof(uint64_t);
+    }
+    ldpc_status decode(ldpc_bp_decoder *d, size_t b0, size_t nb, char *dp, const StageLayout &L, bool llr, hipStream_t stream) const
+    {
+        return ldpc_bp_decode_batch_bits_device(d, (int64_t)nb, (const uint64_t *)dp, span_of(syn_bit0, b0, nb, s).off, (uint64_t *)(dp + L.o_err),
+                                                span_of(err_bit0, b0, nb, n).off, (uint8_t *)(dp + L.o_conv),
+                                                llr ? (double *)(dp + L.o_llr) : nullptr, (int32_t *)(dp + L.o_it), stream);
+    }
+    void errors_out(const char *img, size_t b0, size_t nb) const
+    {
+        const ldpc_detail::Span se = span_of(err_bit0, b0, nb, n);
+        ldpc_detail::merge_bit_range(err_w + se.w0, (const uint64_t *)img, se.off, nb * n, parallel_memcpy);
+    }
+};
+
+// pinned host memory of at least `bytes` (contents not kept)
+ldpc_status grow_pinned(void **p, size_t *cap, size_t bytes)
+{
+    if (*cap >= bytes) return LDPC_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    LDPC_HIP_TRY(hipHostMalloc(p, bytes, hipHostMallocDefault));
+    *cap = bytes;
+    return LDPC_OK;
+}
+
+// columns [b0, b0 + nb) out of the host image hp into the caller's arrays
+template <class View>
+void results_out(const View &v, const char *hp, const StageLayout &L, size_t b0, size_t nb, uint8_t *conv, double *llr, int32_t *iters)
+{
+    v.errors_out(hp + L.o_err, b0, nb);
+    std::memcpy(conv + b0, hp + L.o_conv, nb);
+    if (iters) std::memcpy(iters + b0, hp + L.o_it, nb * sizeof(int32_t));
+    if (llr) parallel_memcpy(llr + b0 * v.n, hp + L.o_llr, nb * v.n * sizeof(double));
+}
+
+// Small batches (decode! is batch = 1): one pinned staging image, ONE copy in and ONE copy out instead of five
+// pageable transfers -- the call is latency-bound, not bandwidth-bound.
+template <class View>
+ldpc_status host_round_trip(ldpc_bp_decoder *d, const View &v, size_t B, const StageLayout &L, uint8_t *conv, double *llr, int32_t *iters)
+{
+    ldpc_status st;
+    hipStream_t stream = nullptr;
+    if ((st = d->st_all.ensure(L.total)) != LDPC_OK || (st = grow_pinned(&d->pin, &d->pin_cap, L.total)) != LDPC_OK) return st;
+    char *hp = (char *)d->pin, *dp = (char *)d->st_all.p;
+    const size_t h2d = v.fill(hp, 0, B);
+    if (h2d) LDPC_HIP_TRY(hipMemcpyAsync(dp, hp, h2d, hipMemcpyHostToDevice, stream));
+    if ((st = v.decode(d, 0, B, dp, L, llr != nullptr, stream)) != LDPC_OK) return st;
+    LDPC_HIP_TRY(hipMemcpyAsync(hp + L.o_err, dp + L.o_err, L.total - L.o_err, hipMemcpyDeviceToHost, stream));
+    const std::string what = std::string(View::entry) + " (small batch: stream synchronise)";
+    if ((st = ldpc_detail::wait_stream(stream, d->device, what.c_str())) != LDPC_OK) return st;
+    results_out(v, hp, L, 0, B, conv, llr, iters);
+    return LDPC_OK;
+}
+
+// Large batches: chunks flow through a 3-slot pipeline -- host memcpy into pinned memory (a few
+// threads), H2D on a copy stream, decode on the compute stream, D2H on a second copy stream, host
+// memcpy out -- so that PCIe runs at pinned-memory speed in both directions while the GPU decodes.
+// (A single pageable hipMemcpy each way measured 11 GB/s and made the call 5-7x slower than the
+// HBM-resident entry for small codes.)
+template <class View>
+ldpc_status host_decode(ldpc_bp_decoder *d, const View &v, size_t B, uint8_t *conv, double *llr, int32_t *iters)
+{
+    const StageLayout whole = v.layout(B, llr != nullptr);
+    if (whole.total <= ((size_t)4 << 20)) return host_round_trip(d, v, B, whole, conv, llr, iters);
+    const bool lds_path = d->variant != 1 && d->lds_logS[llr ? 1 : 0] >= 0;
+    // (experiments build: the chunk size in MiB, or in syndromes outright -- tests: chunk borders inside words, ring growth)
+    const char *e_mb = exp_env("LDPC_PIPE_CHUNK_MB"), *e_syn = exp_env("LDPC_BITS_CHUNK_SYNDROMES");
+    const ldpc_detail::ChunkPlan cp = ldpc_detail::pipe_chunks(v.bps(llr != nullptr), lds_path ? 32768 : 65536 /* enough syndromes to fill the chip */, B,
+                                                               e_mb ? (size_t)std::max<long>(1, std::atol(e_mb)) : 24,
+                                                               e_syn ? (size_t)std::max<long>(1, std::atol(e_syn)) : 0);
+    const size_t cb = cp.cb, nchunks = cp.nchunks;
+    const StageLayout L = v.layout(cb, llr != nullptr);
+    ldpc_status st;
+    for (int q = 0; q < 3; ++q)
+        if (!d->pipe_stream[q]) LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
+    for (auto &row : d->pipe_ev)
+        for (hipEvent_t &e : row)
+            if (!e) LDPC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int R = (int)std::min<size_t>(ldpc_bp_decoder::kPipe, nchunks);
+    for (int q = 0; q < R; ++q)   // (every slot this call uses: each has a capacity of its own)
+        if ((st = grow_pinned(&d->pipe_pin[q], &d->pipe_pin_cap[q], L.total)) != LDPC_OK || (st = d->pipe_dev[q].ensure(L.total)) != LDPC_OK) return st;
+    hipStream_t s_in = d->pipe_stream[0], s_comp = d->pipe_stream[1], s_out = d->pipe_stream[2];
+    const std::string entry = View::entry, pipe = View::pipe;
+    auto drain = [&](size_t j) -> ldpc_status {
+        const int slot = (int)(j % (size_t)R);
+        const size_t b0 = j * cb, nb = std::min(cb, B - b0);
+        const ldpc_status wst = ldpc_detail::wait_event(d->pipe_ev[slot][2], d->device, (entry + " (host pipeline: results of a chunk)").c_str());
+        if (wst != LDPC_OK) return wst;
+        results_out(v, (const char *)d->pipe_pin[slot], L, b0, nb, conv, llr, iters);
+        return LDPC_OK;
+    };
+    ldpc_status pst = LDPC_OK;
+    for (size_t k = 0; k < nchunks && pst == LDPC_OK; ++k) {
+        const int slot = (int)(k % (size_t)R);
+        const size_t b0 = k * cb, nb = std::min(cb, B - b0);
+        if (k >= (size_t)R && (pst = drain(k - R)) != LDPC_OK) break;
+        char *hp = (char *)d->pipe_pin[slot], *dp = (char *)d->pipe_dev[slot].p;
+        const size_t h2d = v.fill(hp, b0, nb);
+        hipError_t e = hipSuccess;
+        if (h2d) e = hipMemcpyAsync(dp, hp, h2d, hipMemcpyHostToDevice, s_in);
+        if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][0], s_in);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s_comp, d->pipe_ev[slot][0], 0);
+        if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, pipe + " (H2D): " + hipGetErrorString(e)); break; }
+        if ((pst = v.decode(d, b0, nb, dp, L, llr != nullptr, s_comp)) != LDPC_OK) break;
+        e = hipEventRecord(d->pipe_ev[slot][1], s_comp);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s_out, d->pipe_ev[slot][1], 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(hp + L.o_err, dp + L.o_err, L.total - L.o_err, hipMemcpyDeviceToHost, s_out);
+        if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][2], s_out);
+        if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, pipe + " (D2H): " + hipGetErrorString(e)); break; }
+    }
+    if (pst == LDPC_OK)
+        for (size_t j = nchunks > (size_t)R ? nchunks - R : 0; j < nchunks && pst == LDPC_OK; ++j) pst = drain(j);
+    if (pst != LDPC_OK) {
+        const std::string keep = ldpc_detail::last_error();
+        (void)ldpc_detail::wait_device(d->device, (entry + " (host pipeline: drain after an error)").c_str());   // nothing of this call may still be in flight when we return
+        (void)fail(pst, keep);
+    }
+    return pst;
+}
+
+}  // namespace
+
 static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, const uint8_t *syn, uint8_t *err,
                                           uint8_t *conv, double *llr, int32_t *iters)
 {
@@ -1919,158 +2047,32 @@ static ldpc_status decode_batch_host_impl(ldpc_bp_decoder *d, int64_t batch, con
     if ((d->s > 0 && !syn) || (d->n > 0 && !err) || !conv)
         return fail(LDPC_ERR_INVALID_ARGUMENT, "syndromes/errors/converged pointer is NULL");
     LDPC_HIP_TRY(hipSetDevice(d->device));
-    const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    ldpc_status st;
-    hipStream_t stream = nullptr;
-    // Small batches (decode! is batch = 1): one pinned staging image, ONE copy in and ONE copy out
-    // instead of five pageable transfers -- the call is latency-bound, not bandwidth-bound.
-    {
-        ldpc_detail::Carve image;   // [syndromes][errors][converged][iterations][LLRs]
-        image.take(B * s);
-        const size_t o_err = image.take(B * n), o_conv = image.take(B), o_it = image.take(B * sizeof(int32_t)),
-                     o_llr = image.take(llr ? B * n * sizeof(double) : 0), total = image.at;
-        // Tiny batches on the two kernels that read their input once (a plain decode! above all): the
-        // kernel works on a host-mapped image directly and raises a flag in it when the last workgroup
-        // is through -- ONE runtime call (the launch) instead of nine, no copies, no stream synchronisation.
-        static const bool lat_off = exp_env("LDPC_NO_LATENCY_PATH") != nullptr;
-        const bool lds_k = takes_lds_kernel(d, llr != nullptr);
-        const int64_t lat_groups = lds_k ? ((batch + (1ll << d->lds_logS[llr ? 1 : 0]) - 1) >> d->lds_logS[llr ? 1 : 0]) : batch;
-        if (!lat_off && total <= ((size_t)256 << 10) && d->max_iters > 0 && lat_groups <= 2 * (int64_t)d->num_cus &&
-            (lds_k || takes_node_kernel(d, batch, llr != nullptr))) {
-            const size_t hdr = 256;
-            if (d->lat_pin_cap < hdr + total) {
-                if (d->lat_pin) (void)hipHostFree(d->lat_pin);
-                d->lat_pin = nullptr; d->lat_pin_cap = 0;
-                const size_t cap = hdr + ((size_t)256 << 10);
-                LDPC_HIP_TRY(hipHostMalloc(&d->lat_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
-                std::memset(d->lat_pin, 0, hdr);
-                LDPC_HIP_TRY(hipHostGetDevicePointer(&d->lat_pin_dev, d->lat_pin, 0));
-                d->lat_pin_cap = cap;
-            }
-            char *hp = (char *)d->lat_pin + hdr, *dp = (char *)d->lat_pin_dev + hdr;
-            volatile unsigned int *flag = (volatile unsigned int *)d->lat_pin;
-            if (++d->lat_ticket == 0) d->lat_ticket = 1;
-            const LatencyCtl lc{(unsigned int *)d->lat_pin_dev, d->lat_ticket};
-            std::memcpy(hp, syn, B * s);
-            st = decode_device_impl(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
-                                    llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it), stream, &lc);
-            if (st != LDPC_OK) return st;
-            if ((st = ldpc_detail::wait_flag(flag, lc.ticket, stream, d->device, "latency path (flag of the last workgroup)")) != LDPC_OK) return st;
-            std::memcpy(err, hp + o_err, B * n);
-            std::memcpy(conv, hp + o_conv, B);
-            if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));
-            if (llr) std::memcpy(llr, hp + o_llr, B * n * sizeof(double));
-            return LDPC_OK;
-        }
-        if (total <= ((size_t)4 << 20)) {
-            if ((st = d->st_all.ensure(total)) != LDPC_OK) return st;
-            if (d->pin_cap < total) {
-                if (d->pin) (void)hipHostFree(d->pin);
-                d->pin = nullptr; d->pin_cap = 0;
-                LDPC_HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
-                d->pin_cap = total;
-            }
-            char *hp = (char *)d->pin, *dp = (char *)d->st_all.p;
-            std::memcpy(hp, syn, B * s);
-            if (s > 0) LDPC_HIP_TRY(hipMemcpyAsync(dp, hp, B * s, hipMemcpyHostToDevice, stream));
-            st = ldpc_bp_decode_batch_device(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + o_err), (uint8_t *)(dp + o_conv),
-                                             llr ? (double *)(dp + o_llr) : nullptr, (int32_t *)(dp + o_it), stream);
-            if (st != LDPC_OK) return st;
-            LDPC_HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
-            if ((st = ldpc_detail::wait_stream(stream, d->device, "ldpc_bp_decode_batch (small batch: stream synchronise)")) != LDPC_OK) return st;
-            std::memcpy(err, hp + o_err, B * n);
-            std::memcpy(conv, hp + o_conv, B);
-            if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));
-            if (llr) std::memcpy(llr, hp + o_llr, B * n * sizeof(double));
-            return LDPC_OK;
-        }
+    const size_t B = (size_t)batch;
+    const ByteView v{syn, err, (size_t)d->s, (size_t)d->n};
+    const StageLayout L = v.layout(B, llr != nullptr);
+    // Tiny batches on the two kernels that read their input once (a plain decode! above all): the
+    // kernel works on a host-mapped image directly and raises a flag in it when the last workgroup
+    // is through -- ONE runtime call (the launch) instead of nine, no copies, no stream synchronisation.
+    static const bool lat_off = exp_env("LDPC_NO_LATENCY_PATH") != nullptr;
+    const bool lds_k = takes_lds_kernel(d, llr != nullptr);
+    const int64_t lat_groups = lds_k ? ((batch + (1ll << d->lds_logS[llr ? 1 : 0]) - 1) >> d->lds_logS[llr ? 1 : 0]) : batch;
+    if (!lat_off && L.total <= ((size_t)256 << 10) && d->max_iters > 0 && lat_groups <= 2 * (int64_t)d->num_cus &&
+        (lds_k || takes_node_kernel(d, batch, llr != nullptr))) {
+        hipStream_t stream = nullptr;
+        ldpc_status st;
+        if ((st = d->lat.ensure((size_t)256 << 10)) != LDPC_OK) return st;
+        char *hp = d->lat.image(), *dp = d->lat.image_dev();
+        const LatencyCtl lc{d->lat.flag_dev(), d->lat.next_ticket()};
+        std::memcpy(hp, syn, B * v.s);
+        st = decode_device_impl(d, batch, (const uint8_t *)dp, (uint8_t *)(dp + L.o_err), (uint8_t *)(dp + L.o_conv),
+                                llr ? (double *)(dp + L.o_llr) : nullptr, (int32_t *)(dp + L.o_it), stream, &lc);
+        if (st != LDPC_OK) return st;
+        if ((st = ldpc_detail::wait_flag(d->lat.flag(), lc.ticket, stream, d->device, "latency path (flag of the last workgroup)")) != LDPC_OK) return st;
+        results_out(v, hp, L, 0, B, conv, llr, iters);
+        return LDPC_OK;
     }
-    // Large batches: chunks flow through a 3-slot pipeline -- host memcpy into pinned memory (a few
-    // threads), H2D on a copy stream, decode on the compute stream, D2H on a second copy stream, host
-    // memcpy out -- so that PCIe runs at pinned-memory speed in both directions while the GPU decodes.
-    // (A single pageable hipMemcpy each way measured 11 GB/s and made the call 5-7x slower than the
-    // HBM-resident entry for small codes.)
-    {
-        const size_t bps = s + n + 1 + sizeof(int32_t) + (llr ? n * sizeof(double) : 0);   // bytes per syndrome
-        const bool lds_path = d->variant != 1 && d->lds_logS[llr ? 1 : 0] >= 0;
-        size_t chunk_mb = 24;
-        if (const char *e = exp_env("LDPC_PIPE_CHUNK_MB")) chunk_mb = std::max<long>(1, std::atol(e));
-        size_t cb = (chunk_mb << 20) / std::max<size_t>(bps, 1);
-        cb = std::max<size_t>(cb, lds_path ? 32768 : 65536);      // enough syndromes to fill the chip
-        cb = (cb + 4095) & ~(size_t)4095;
-        if (B < cb + cb / 2) cb = B;                               // no tiny trailing chunk
-        const size_t nchunks = (B + cb - 1) / cb;
-        ldpc_detail::Carve image;
-        image.take(cb * s);
-        const size_t o_err = image.take(cb * n), o_conv = image.take(cb), o_it = image.take(cb * sizeof(int32_t)),
-                     o_llr = image.take(llr ? cb * n * sizeof(double) : 0), total = image.at;
-        for (int q = 0; q < 3; ++q)
-            if (!d->pipe_stream[q]) LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
-        for (auto &row : d->pipe_ev)
-            for (hipEvent_t &e : row)
-                if (!e) LDPC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const int R = (int)std::min<size_t>(ldpc_bp_decoder::kPipe, nchunks);
-        if (d->pipe_pin_cap < total) {
-            for (void *&q : d->pipe_pin) {
-                if (q) (void)hipHostFree(q);
-                q = nullptr;
-            }
-            d->pipe_pin_cap = 0;
-        }
-        for (int q = 0; q < R; ++q) {
-            if (!d->pipe_pin[q]) LDPC_HIP_TRY(hipHostMalloc(&d->pipe_pin[q], total, hipHostMallocDefault));
-            if ((st = d->pipe_dev[q].ensure(total)) != LDPC_OK) return st;
-        }
-        d->pipe_pin_cap = std::max(d->pipe_pin_cap, total);
-        hipStream_t s_in = d->pipe_stream[0], s_comp = d->pipe_stream[1], s_out = d->pipe_stream[2];
-        auto drain = [&](size_t j) -> ldpc_status {
-            const int slot = (int)(j % (size_t)R);
-            const size_t b0 = j * cb, nb = std::min(cb, B - b0);
-            {
-                const ldpc_status wst = ldpc_detail::wait_event(d->pipe_ev[slot][2], d->device, "ldpc_bp_decode_batch (host pipeline: results of a chunk)");
-                if (wst != LDPC_OK) return wst;
-            }
-            const char *hp = (const char *)d->pipe_pin[slot];
-            parallel_memcpy(err + b0 * n, hp + o_err, nb * n);
-            std::memcpy(conv + b0, hp + o_conv, nb);
-            if (iters) std::memcpy(iters + b0, hp + o_it, nb * sizeof(int32_t));
-            if (llr) parallel_memcpy(llr + b0 * n, hp + o_llr, nb * n * sizeof(double));
-            return LDPC_OK;
-        };
-        ldpc_status pst = LDPC_OK;
-        for (size_t k = 0; k < nchunks && pst == LDPC_OK; ++k) {
-            const int slot = (int)(k % (size_t)R);
-            const size_t b0 = k * cb, nb = std::min(cb, B - b0);
-            if (k >= (size_t)R && (pst = drain(k - R)) != LDPC_OK) break;
-            char *hp = (char *)d->pipe_pin[slot], *dp = (char *)d->pipe_dev[slot].p;
-            parallel_memcpy(hp, syn + b0 * s, nb * s);
-            hipError_t e = hipSuccess;
-            if (s > 0) e = hipMemcpyAsync(dp, hp, nb * s, hipMemcpyHostToDevice, s_in);
-            if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][0], s_in);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s_comp, d->pipe_ev[slot][0], 0);
-            if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, std::string("host pipeline (H2D): ") + hipGetErrorString(e)); break; }
-            pst = ldpc_bp_decode_batch_device(d, (int64_t)nb, (const uint8_t *)dp, (uint8_t *)(dp + o_err),
-                                              (uint8_t *)(dp + o_conv), llr ? (double *)(dp + o_llr) : nullptr,
-                                              (int32_t *)(dp + o_it), s_comp);
-            if (pst != LDPC_OK) break;
-            e = hipEventRecord(d->pipe_ev[slot][1], s_comp);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s_out, d->pipe_ev[slot][1], 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, s_out);
-            if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][2], s_out);
-            if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, std::string("host pipeline (D2H): ") + hipGetErrorString(e)); break; }
-        }
-        if (pst == LDPC_OK)
-            for (size_t j = nchunks > (size_t)R ? nchunks - R : 0; j < nchunks && pst == LDPC_OK; ++j) pst = drain(j);
-        if (pst != LDPC_OK) {
-            const std::string keep = ldpc_detail::last_error();
-            (void)ldpc_detail::wait_device(d->device, "ldpc_bp_decode_batch (host pipeline: drain after an error)");   // nothing of this call may still be in flight when we return
-            (void)fail(pst, keep);
-        }
-        return pst;
-    }
+    return host_decode(d, v, B, conv, llr, iters);
 }
-
-}  // extern "C"
 
 // ---- bit-packed entries (include/ldpc_mi355x.h: ldpc_bp_decode_batch_bits[_device]) -- conversion at the boundary:
 // bits -> the handle's byte staging, the byte entry's kernels unchanged on it, bytes -> bits (bit_io_kernels.hpp).
@@ -2132,171 +2134,18 @@ extern "C" ldpc_status ldpc_bp_decode_batch_bits_device(ldpc_bp_decoder *d, int6
     return LDPC_OK;
 }
 
-namespace {
-// Bits [off, off + nbits) of src -> the same bits of dst (word 0 of both holds bit 0 of the numbering).  Interior words
-// are copied; a partial first / last word is merged under its mask with atomic and / or on the word, because the shards
-// of the multi-device entry merge from threads of their own and two neighbouring shards can share a word.
-void merge_bit_range(uint64_t *dst, const uint64_t *src, int off, size_t nbits)
-{
-    if (!nbits) return;
-    const size_t nw = ((size_t)off + nbits + 63) >> 6;
-    const int end = (int)(((size_t)off + nbits) & 63);
-    auto masked = [&](size_t q, uint64_t mask) {
-        (void)__atomic_fetch_and(&dst[q], ~mask, __ATOMIC_RELAXED);
-        (void)__atomic_fetch_or(&dst[q], src[q] & mask, __ATOMIC_RELAXED);
-    };
-    const uint64_t mfirst = ~(uint64_t)0 << off, mlast = end ? ((uint64_t)1 << end) - 1 : ~(uint64_t)0;
-    if (nw == 1) { masked(0, mfirst & mlast); return; }
-    size_t lo = 0, hi = nw;
-    if (off) { masked(0, mfirst); lo = 1; }
-    if (end) { masked(nw - 1, mlast); hi = nw - 1; }
-    if (hi > lo) parallel_memcpy(dst + lo, src + lo, (hi - lo) * sizeof(uint64_t));
-}
-}  // namespace
-
-static ldpc_status decode_batch_bits_host_impl(ldpc_bp_decoder *d, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
-                                               uint64_t *err_w, int64_t err_bit0, uint8_t *conv, double *llr, int32_t *iters)
-{
-    LDPC_HIP_TRY(hipSetDevice(d->device));
-    const size_t s = (size_t)d->s, n = (size_t)d->n, B = (size_t)batch;
-    ldpc_status st;
-    auto wbytes = [](size_t nbits) { return (((nbits + 63) >> 6) + 1) * sizeof(uint64_t); };   // words covering nbits at any offset
-    // one chunk of columns [b0, b0 + nb) in a host image hp: where its words lie in the caller's arrays
-    struct Span { size_t w0; int off; size_t nwords; };
-    auto span_of = [](int64_t bit0, size_t b0, size_t nb, size_t r) {
-        const size_t lo = (size_t)bit0 + b0 * r;
-        Span sp;
-        sp.w0 = lo >> 6; sp.off = (int)(lo & 63);
-        sp.nwords = nb * r ? (size_t)ldpc_bitio::words_covering(sp.off, (long long)(nb * r)) : 0;
-        return sp;
-    };
-    {
-        // Small batches (a plain decode! is batch = 1): one pinned image, one copy in, one copy out -- as the byte entry
-        ldpc_detail::Carve image;
-        image.take(wbytes(B * s));
-        const size_t o_err = image.take(wbytes(B * n)), o_conv = image.take(B), o_it = image.take(B * sizeof(int32_t)),
-                     o_llr = image.take(llr ? B * n * sizeof(double) : 0), total = image.at;
-        if (total <= ((size_t)4 << 20)) {
-            hipStream_t stream = nullptr;
-            if ((st = d->st_all.ensure(total)) != LDPC_OK) return st;
-            if (d->pin_cap < total) {
-                if (d->pin) (void)hipHostFree(d->pin);
-                d->pin = nullptr; d->pin_cap = 0;
-                LDPC_HIP_TRY(hipHostMalloc(&d->pin, total, hipHostMallocDefault));
-                d->pin_cap = total;
-            }
-            char *hp = (char *)d->pin, *dp = (char *)d->st_all.p;
-            const Span ss = span_of(syn_bit0, 0, B, s), se = span_of(err_bit0, 0, B, n);
-            if (ss.nwords) {
-                std::memcpy(hp, syn_w + ss.w0, ss.nwords * sizeof(uint64_t));
-                LDPC_HIP_TRY(hipMemcpyAsync(dp, hp, ss.nwords * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            }
-            st = ldpc_bp_decode_batch_bits_device(d, batch, (const uint64_t *)dp, ss.off, (uint64_t *)(dp + o_err), se.off,
-                                                  (uint8_t *)(dp + o_conv), llr ? (double *)(dp + o_llr) : nullptr,
-                                                  (int32_t *)(dp + o_it), stream);
-            if (st != LDPC_OK) return st;
-            LDPC_HIP_TRY(hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, stream));
-            if ((st = ldpc_detail::wait_stream(stream, d->device, "ldpc_bp_decode_batch_bits (small batch: stream synchronise)")) != LDPC_OK) return st;
-            merge_bit_range(err_w + se.w0, (const uint64_t *)(hp + o_err), se.off, B * n);
-            std::memcpy(conv, hp + o_conv, B);
-            if (iters) std::memcpy(iters, hp + o_it, B * sizeof(int32_t));
-            if (llr) std::memcpy(llr, hp + o_llr, B * n * sizeof(double));
-            return LDPC_OK;
-        }
-    }
-    // Large batches: the byte entry's 3-slot pipeline (pinned copy, H2D, decode, D2H, copy out) on word images.  A chunk
-    // of columns starts at any bit: its image holds the words that cover it, the device entry gets the offset into the
-    // first one, and the copy out merges the first / last word under a mask.
-    {
-        const size_t bps = (s + n + 7) / 8 + 1 + sizeof(int32_t) + (llr ? n * sizeof(double) : 0);   // bytes per syndrome, bit layout
-        const bool lds_path = d->variant != 1 && d->lds_logS[llr ? 1 : 0] >= 0;
-        size_t cb = ((size_t)24 << 20) / std::max<size_t>(bps, 1);
-        cb = std::max<size_t>(cb, lds_path ? 32768 : 65536);      // enough syndromes to fill the chip
-        cb = (cb + 4095) & ~(size_t)4095;
-        if (B < cb + cb / 2) cb = B;                               // no tiny trailing chunk
-        if (const char *e = exp_env("LDPC_BITS_CHUNK_SYNDROMES")) cb = (size_t)std::max<long>(1, std::atol(e));   // (tests: chunk borders inside words)
-        const size_t nchunks = (B + cb - 1) / cb;
-        ldpc_detail::Carve image;
-        image.take(wbytes(cb * s));
-        const size_t o_err = image.take(wbytes(cb * n)), o_conv = image.take(cb), o_it = image.take(cb * sizeof(int32_t)),
-                     o_llr = image.take(llr ? cb * n * sizeof(double) : 0), total = image.at;
-        for (int q = 0; q < 3; ++q)
-            if (!d->pipe_stream[q]) LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->pipe_stream[q], hipStreamNonBlocking));
-        for (auto &row : d->pipe_ev)
-            for (hipEvent_t &e : row)
-                if (!e) LDPC_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const int R = (int)std::min<size_t>(ldpc_bp_decoder::kPipe, nchunks);
-        for (int q = 0; q < R; ++q) {
-            if (d->bits_pin_cap[q] < total) {
-                if (d->bits_pin[q]) (void)hipHostFree(d->bits_pin[q]);
-                d->bits_pin[q] = nullptr; d->bits_pin_cap[q] = 0;
-                LDPC_HIP_TRY(hipHostMalloc(&d->bits_pin[q], total, hipHostMallocDefault));
-                d->bits_pin_cap[q] = total;
-            }
-            if ((st = d->pipe_dev[q].ensure(total)) != LDPC_OK) return st;
-        }
-        hipStream_t s_in = d->pipe_stream[0], s_comp = d->pipe_stream[1], s_out = d->pipe_stream[2];
-        auto drain = [&](size_t j) -> ldpc_status {
-            const int slot = (int)(j % (size_t)R);
-            const size_t b0 = j * cb, nb = std::min(cb, B - b0);
-            {
-                const ldpc_status wst = ldpc_detail::wait_event(d->pipe_ev[slot][2], d->device, "ldpc_bp_decode_batch_bits (host pipeline: results of a chunk)");
-                if (wst != LDPC_OK) return wst;
-            }
-            const char *hp = (const char *)d->bits_pin[slot];
-            const Span se = span_of(err_bit0, b0, nb, n);
-            merge_bit_range(err_w + se.w0, (const uint64_t *)(hp + o_err), se.off, nb * n);
-            std::memcpy(conv + b0, hp + o_conv, nb);
-            if (iters) std::memcpy(iters + b0, hp + o_it, nb * sizeof(int32_t));
-            if (llr) parallel_memcpy(llr + b0 * n, hp + o_llr, nb * n * sizeof(double));
-            return LDPC_OK;
-        };
-        ldpc_status pst = LDPC_OK;
-        for (size_t k = 0; k < nchunks && pst == LDPC_OK; ++k) {
-            const int slot = (int)(k % (size_t)R);
-            const size_t b0 = k * cb, nb = std::min(cb, B - b0);
-            if (k >= (size_t)R && (pst = drain(k - R)) != LDPC_OK) break;
-            char *hp = (char *)d->bits_pin[slot], *dp = (char *)d->pipe_dev[slot].p;
-            const Span ss = span_of(syn_bit0, b0, nb, s), se = span_of(err_bit0, b0, nb, n);
-            hipError_t e = hipSuccess;
-            if (ss.nwords) {
-                parallel_memcpy(hp, syn_w + ss.w0, ss.nwords * sizeof(uint64_t));
-                e = hipMemcpyAsync(dp, hp, ss.nwords * sizeof(uint64_t), hipMemcpyHostToDevice, s_in);
-            }
-            if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][0], s_in);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s_comp, d->pipe_ev[slot][0], 0);
-            if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, std::string("host pipeline of the bits entry (H2D): ") + hipGetErrorString(e)); break; }
-            pst = ldpc_bp_decode_batch_bits_device(d, (int64_t)nb, (const uint64_t *)dp, ss.off, (uint64_t *)(dp + o_err), se.off,
-                                                   (uint8_t *)(dp + o_conv), llr ? (double *)(dp + o_llr) : nullptr,
-                                                   (int32_t *)(dp + o_it), s_comp);
-            if (pst != LDPC_OK) break;
-            e = hipEventRecord(d->pipe_ev[slot][1], s_comp);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s_out, d->pipe_ev[slot][1], 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(hp + o_err, dp + o_err, total - o_err, hipMemcpyDeviceToHost, s_out);
-            if (e == hipSuccess) e = hipEventRecord(d->pipe_ev[slot][2], s_out);
-            if (e != hipSuccess) { pst = fail(LDPC_ERR_HIP, std::string("host pipeline of the bits entry (D2H): ") + hipGetErrorString(e)); break; }
-        }
-        if (pst == LDPC_OK)
-            for (size_t j = nchunks > (size_t)R ? nchunks - R : 0; j < nchunks && pst == LDPC_OK; ++j) pst = drain(j);
-        if (pst != LDPC_OK) {
-            const std::string keep = ldpc_detail::last_error();
-            (void)ldpc_detail::wait_device(d->device, "ldpc_bp_decode_batch_bits (host pipeline: drain after an error)");   // nothing of this call may still be in flight when we return
-            (void)fail(pst, keep);
-        }
-        return pst;
-    }
-}
-
 extern "C" ldpc_status ldpc_bp_decode_batch_bits(ldpc_bp_decoder *d, int64_t batch, const uint64_t *syn_w, int64_t syn_bit0,
                                                  uint64_t *err_w, int64_t err_bit0, uint8_t *conv, double *llr, int32_t *iters)
 {
     bool done;
     ldpc_status st = bits_check_args(d, batch, syn_w, syn_bit0, err_w, err_bit0, conv, &done);
     if (st != LDPC_OK || done) return st;
-    st = decode_batch_bits_host_impl(d, batch, syn_w, syn_bit0, err_w, err_bit0, conv, llr, iters);
+    // the byte entry's staging on word images; this entry has no latency path
+    const BitsView v{syn_w, syn_bit0, err_w, err_bit0, (size_t)d->s, (size_t)d->n};
+    LDPC_HIP_TRY(hipSetDevice(d->device));
+    st = host_decode(d, v, (size_t)batch, conv, llr, iters);
     // synchronous, like ldpc_bp_decode_batch: a team that lost a workgroup is known by now -- decode once more without teams
-    if (st == LDPC_OK && report_team_fault(d) != LDPC_OK)
-        st = decode_batch_bits_host_impl(d, batch, syn_w, syn_bit0, err_w, err_bit0, conv, llr, iters);
+    if (st == LDPC_OK && report_team_fault(d) != LDPC_OK) st = host_decode(d, v, (size_t)batch, conv, llr, iters);
     return st;
 }
 

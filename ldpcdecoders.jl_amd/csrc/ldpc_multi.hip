@@ -347,7 +347,7 @@ ldpc_status ldpc_bp_decode_batch_multi_bits(ldpc_bp_multi *m, int64_t batch, con
         shard_bounds(batch, G, g, &lo, &hi);
         if (hi <= lo) return;
         (void)hipSetDevice(m->dev[(size_t)g]);   // (the current device is a per-thread setting)
-        // a word that two shards share is merged atomically by each of them (ldpc_mi355x.hip, merge_bit_range)
+        // a word that two shards share is merged atomically by each of them (host_pipe_plan.hpp, merge_bit_range)
         st[(size_t)g] = ldpc_bp_decode_batch_bits(m->h[(size_t)g], hi - lo, syn_w, syn_bit0 + lo * m->s, err_w, err_bit0 + lo * m->n,
                                                   conv + lo, llr ? llr + (size_t)lo * (size_t)m->n : nullptr, iters ? iters + lo : nullptr);
         if (st[(size_t)g] != LDPC_OK) msg[(size_t)g] = ldpc_last_error();

@@ -202,6 +202,55 @@ def test_host_pipeline_over_several_chunks(ldpc, gpu, monkeypatch):
     dec.close()
 
 
+def _image_bytes(rows, syn_bytes, err_bytes, llr_bytes):
+    """Bytes of a staging image [syndromes][errors][converged][iterations][LLRs] of `rows` syndromes, restated from
+    csrc/host_pipe_plan.hpp stage_layout(): every region starts on a 256-byte boundary."""
+    return sum((b + 255) // 256 * 256 for b in (syn_bytes, err_bytes, rows, 4 * rows, llr_bytes))
+
+
+def test_pinned_ring_grows_slot_by_slot_on_one_handle(ldpc, gpu, monkeypatch):
+    """The pinned ring of the host pipeline, shared by the byte and the bits entry, on ONE handle: a call of one chunk
+    with a large image (only slot 0 is touched), then five chunks with a small image (slots 1 and 2 are allocated small),
+    then three chunks with an image in between (slots 1 and 2 must grow: a single capacity for the whole ring would
+    let the copies run past their end), all through the byte entry without LLRs; then the bits entry with four chunks
+    whose image (LLRs) is larger than all of them.  Every result equals the device-resident entry column for column.
+    (12001 syndromes of the n = 1003, s = 517 code: the bits entry's image without LLRs would be 2.3 MB and take the
+    small-batch round trip, hence LLRs there.)"""
+    import torch
+
+    n, s, B = 1003, 517, 12001
+    H = _irregular(n, s, 7)
+    syn = _syndromes(ldpc, H, B, 0.02, seed=9)
+    dec = ldpc.BeliefPropagationDecoder(H, 0.02, 25, experiments=True)
+    d_err = torch.empty((B, n), dtype=torch.uint8, device="cuda")
+    d_conv = torch.empty(B, dtype=torch.uint8, device="cuda")
+    d_it = torch.empty(B, dtype=torch.int32, device="cuda")
+    d_llr = torch.empty((B, n), dtype=torch.float64, device="cuda")
+    dec.decode_batch_device(torch.from_numpy(syn).cuda(), d_err, d_conv, d_llr, d_it)
+    torch.cuda.synchronize()
+    ref = (d_err.cpu().numpy(), d_conv.cpu().numpy(), d_llr.cpu().numpy(), d_it.cpu().numpy())
+    assert 0 < int(ref[1].sum()) and ref[0].any()
+
+    def byte_image(rows):
+        return _image_bytes(rows, rows * s, rows * n, 0)
+
+    def bits_image(rows):
+        return _image_bytes(rows, ((rows * s + 63) // 64 + 1) * 8, ((rows * n + 63) // 64 + 1) * 8, 8 * rows * n)
+
+    small_batch_limit = 4 << 20                               # whole-batch images up to this take the round trip instead
+    assert byte_image(B) > small_batch_limit and bits_image(B) > small_batch_limit
+    assert byte_image(3000) < byte_image(5000) < byte_image(12001) < bits_image(4000)
+    for chunk, nchunks in ((12001, 1), (3000, 5), (5000, 3)):
+        assert -(-B // chunk) == nchunks
+        monkeypatch.setenv("LDPC_BITS_CHUNK_SYNDROMES", str(chunk))   # (the experiments build: both entries' chunk)
+        err, conv, _, its = dec.decode_batch_host(syn, want_llr=False, want_iters=True)
+        assert np.array_equal(err, ref[0]), f"chunk {chunk}: hard decisions differ in columns {np.unique(np.nonzero(err != ref[0])[0])[:8]}"
+        assert np.array_equal(conv, ref[1]) and np.array_equal(its, ref[3]), f"chunk {chunk}"
+    monkeypatch.setenv("LDPC_BITS_CHUNK_SYNDROMES", "4000")           # 4 chunks, the last one a single syndrome
+    _check_bits_entry(dec, syn, 63, 777, True, True, seed=6, ref=ref)
+    dec.close()
+
+
 def test_device_form_on_a_side_stream(ldpc, gpu):
     """ldpc_bp_decode_batch_bits_device on torch tensors, on a non-default stream, two calls back to back without a
     synchronise in between; last_status() clean, last_timing() returns (total_ms spans the conversions)."""
