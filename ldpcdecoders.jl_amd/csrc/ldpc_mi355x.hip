@@ -1,6 +1,6 @@
-// ldpc_mi355x.hip -- host side of libldpc_mi355x.so: the C ABI declared in
-// include/ldpc_mi355x.h, Tanner-graph preparation, workspace management and
-// kernel dispatch.  Device code lives in bp_kernels.hpp.
+// ldpc_mi355x.hip -- host side of libldpc_mi355x.so: the C ABI declared in include/ldpc_mi355x.h, Tanner-graph
+// preparation, workspace management and kernel dispatch (decode_device_impl(): named steps over a DecodeCall and a
+// TileLaunch record).  Device code lives in bp_kernels.hpp.
 //
 // Reference interfaces replaced (QuantumSavory/LDPCDecoders.jl):
 //   BeliefPropagationDecoder(H, per, max_iters)  src/decoders/belief_propagation.jl:61-67
@@ -443,18 +443,25 @@ struct ldpc_bp_decoder {
     unsigned rollcall_ticks = 2000000u;   // 20 ms of the 100 MHz clock: how long the members of a team wait for each other at launch (team_rollcall)
 
     bool device_idle = false;      // ldpc_bp_destroy has waited for the device: frees need not wait again
+    // THE list of the handle's device buffers: f(b) for every DevBuf of h (a handle or a const handle), arrays included.
+    // The destructor releases through it, ldpc_bp_get_info sums the capacities through it: a new buffer is added here.
+    template <class Handle, class F> static void for_each_buffer(Handle &h, F &&f)
+    {
+        for (auto *b : {&h.row_ptr, &h.edge_bit, &h.col_ptr, &h.csc2csr, &h.msg, &h.ctrl, &h.synmask, &h.nevermask,
+                        &h.errmask, &h.finmask, &h.llr_t, &h.st_all, &h.node_msg, &h.done_ctr, &h.team_ws, &h.cold,
+                        &h.rows_ctab, &h.rows_vtab, &h.rows_lds_edge, &h.rows_reg_edge, &h.rows_posmap,
+                        &h.irr_ctab, &h.irr_ptab, &h.irr_ploc, &h.irr_lds_edge, &h.irr_posmap, &h.bits_syn, &h.bits_err})
+            f(*b);
+        for (int l = 0; l < 2; ++l)
+            for (auto *b : {&h.team_ws_lvl[l], &h.lvl_state[l], &h.lvl_list[l], &h.lvl_it[l], &h.lvl_syn[l], &h.lvl_never[l], &h.lvl_err[l], &h.lvl_fin[l], &h.lvl_llr[l]})
+                f(*b);
+        for (auto &b : h.pipe_dev) f(b);
+    }
     ~ldpc_bp_decoder()
     {
         const bool stalled = ldpc_detail::device_stalled(device);   // (then nothing is freed: host_wait.hpp)
         const bool idle = device_idle && !stalled;
-        DevBuf *all[] = {&row_ptr, &edge_bit, &col_ptr, &csc2csr, &msg, &ctrl, &synmask, &nevermask,
-                         &errmask, &finmask, &llr_t, &st_all, &node_msg, &done_ctr, &team_ws, &team_ws_lvl[0], &team_ws_lvl[1], &cold,
-                         &rows_ctab, &rows_vtab, &rows_lds_edge, &rows_reg_edge, &rows_posmap,
-                         &irr_ctab, &irr_ptab, &irr_ploc, &irr_lds_edge, &irr_posmap, &bits_syn, &bits_err};
-        for (DevBuf *b : all) b->release(idle);
-        for (int l = 0; l < 2; ++l)
-            for (DevBuf *b : {&lvl_state[l], &lvl_list[l], &lvl_it[l], &lvl_syn[l], &lvl_never[l], &lvl_err[l], &lvl_fin[l], &lvl_llr[l]}) b->release(idle);
-        for (DevBuf &b : pipe_dev) b.release(idle);
+        for_each_buffer(*this, [idle](DevBuf &b) { b.release(idle); });
         if (stalled) return;   // pinned memory the device may still write, streams it may still run: left alone
         if (pin) (void)hipHostFree(pin);
         lat.release();
@@ -867,14 +874,7 @@ ldpc_status ldpc_bp_get_info(const ldpc_bp_decoder *d, ldpc_bp_info *info)
     info->max_check_degree = d->max_cdeg; info->max_bit_degree = d->max_bdeg;
     info->device = d->device; info->tile_syndromes = kTile; info->waves_per_tile = d->last_threads / 64;
     info->resident_tiles = d->last_grid;
-    const DevBuf *all[] = {&d->row_ptr, &d->edge_bit, &d->col_ptr, &d->csc2csr, &d->msg, &d->ctrl, &d->synmask,
-                           &d->nevermask, &d->errmask, &d->finmask, &d->llr_t, &d->st_all, &d->node_msg, &d->pipe_dev[0], &d->pipe_dev[1], &d->pipe_dev[2],
-                           &d->lvl_state[0], &d->lvl_state[1], &d->lvl_list[0], &d->lvl_list[1], &d->lvl_it[0], &d->lvl_it[1],
-                           &d->lvl_syn[0], &d->lvl_syn[1], &d->lvl_never[0], &d->lvl_never[1], &d->lvl_err[0], &d->lvl_err[1], &d->lvl_fin[0], &d->lvl_fin[1],
-                           &d->lvl_llr[0], &d->lvl_llr[1], &d->team_ws, &d->team_ws_lvl[0], &d->team_ws_lvl[1],
-                           &d->rows_ctab, &d->rows_vtab, &d->rows_lds_edge, &d->rows_reg_edge, &d->rows_posmap,
-                           &d->irr_ctab, &d->irr_ptab, &d->irr_ploc, &d->irr_lds_edge, &d->irr_posmap, &d->bits_syn, &d->bits_err};
-    for (const DevBuf *b : all) info->workspace_bytes += (int64_t)b->cap;
+    ldpc_bp_decoder::for_each_buffer(*d, [info](const DevBuf &b) { info->workspace_bytes += (int64_t)b.cap; });
     info->last_kernel = d->last_kernel;
     info->last_team_size = d->last_team;
     info->last_lds_rows = d->last_lds_rows;
@@ -1273,19 +1273,57 @@ static ldpc_status report_team_fault(ldpc_bp_decoder *d)
                 ") are invalid; teams are off for this decoder from here on");
 }
 
-static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const uint8_t *d_syn,
-                                      uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters,
-                                      void *stream_v, const LatencyCtl *lat)
+// ---- ldpc_bp_decode_batch_device: decode_device_impl() at the end of this block is the list of steps; each step is a
+// function over two records.  DecodeCall: what one call is about, built once on the stack.  TileLaunch (further down):
+// the state of the tile / team path, which the refused-team-grid fallback changes.  A decode is begin_call(), then ONE
+// of decode_zero_iters(), decode_lds(), decode_node() (both through launch_single(); node_launch_setup()) and
+// decode_tiles(): ensure_call_buffers(), plan_tile_launch(), plan_levels() (the rule: level_plan_pure(), team_plan.cpp),
+// ensure_level_buffers(), pack_fresh_batch(), fill_pass_params(), launch_fresh_pass() (team_params(),
+// choose_team_tables(), dump_team_debug()), launch_level_passes(), unpack_results(), launch_level_node_passes().
+// DESIGN.md section 4 says what each enqueues.
+//
+// The 64-byte control slot of a call (ctrl = d->ctrl.p + 64 * slot; zero when the call starts), in ONE place:
+//   +0  u32  queue of the fresh pass (tiles / groups / syndromes drawn)     +4  u32  level 1: syndromes handed in
+//   +8  u64  sum of the iteration counts                                    +16 u64[3] phase ticks
+//   +40 u32  level 1: tile queue      +44 u32  level 2: tile queue
+//   +48 u32  level 1: node queue      +52 u32  level 2: node queue          +56 u32  level 2: syndromes handed in
+namespace {
+
+struct DecodeCall {
+    ldpc_bp_decoder *d;
+    int64_t batch;
+    const uint8_t *d_syn; uint8_t *d_err, *d_conv; double *d_llr; int32_t *d_iters;   // the caller's device arrays
+    hipStream_t stream;
+    const LatencyCtl *lat;
+    bool want_llr;
+    int slot = 0, nslot = 0;         // of the timing ring: this call's, the next call's
+    hipEvent_t *ev = nullptr;        // d->ev[slot]
+    char *ctrl = nullptr, *next_ctrl = nullptr;   // the control slots of the two
+    const int *a_row = nullptr, *a_eb = nullptr, *a_col = nullptr, *a_c2r = nullptr;   // the device graph
+};
+
+// the words of a packed level in the control slot (layout: above)
+struct LevelWords { unsigned int *count, *tile_queue, *node_queue; };
+static LevelWords level_words(char *ctrl, int l)
 {
+    return l == 1 ? LevelWords{(unsigned int *)(ctrl + 4), (unsigned int *)(ctrl + 40), (unsigned int *)(ctrl + 48)}
+                  : LevelWords{(unsigned int *)(ctrl + 56), (unsigned int *)(ctrl + 44), (unsigned int *)(ctrl + 52)};
+}
+
+}  // namespace
+
+// Argument checks, a stalled device, a pending team fault; then the call's number, its slot of the timing ring and the
+// stream ordering.  *proceed stays false where the call is over already (an empty batch: LDPC_OK).
+static ldpc_status begin_call(DecodeCall &c, bool *proceed)
+{
+    ldpc_bp_decoder *d = c.d;
     if (!d) return fail(LDPC_ERR_INVALID_ARGUMENT, "decoder is NULL");
-    if (batch < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
-    hipStream_t stream = (hipStream_t)stream_v;
-    if (batch == 0) return LDPC_OK;
-    if ((d->s > 0 && !d_syn) || (d->n > 0 && !d_err) || !d_conv)
+    if (c.batch < 0) return fail(LDPC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (c.batch == 0) return LDPC_OK;
+    if ((d->s > 0 && !c.d_syn) || (d->n > 0 && !c.d_err) || !c.d_conv)
         return fail(LDPC_ERR_INVALID_ARGUMENT, "syndromes/errors/converged pointer is NULL");
     LDPC_HIP_TRY(hipSetDevice(d->device));
     if (ldpc_detail::device_stalled(d->device)) return ldpc_detail::stalled_error(d->device);
-    const int64_t s = d->s, n = d->n;
     {
         const ldpc_status fst = report_team_fault(d);   // a refused call is not counted and enqueues nothing
         if (fst != LDPC_OK) return fst;
@@ -1293,158 +1331,206 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
     // From here on the call has a number and a slot of the timing ring.  If a HIP call fails further down the
     // function returns with the launches made so far enqueued (they only touch this call's own buffers and the
     // handle's workspace), the slot consumed and `timed` false: ldpc_bp_call_timing reports zeros for it.
-    const int slot = (int)(d->ncalls++ % ldpc_bp_decoder::kRing);
-    hipEvent_t *ev = d->ev[slot];
-    char *ctrl = (char *)d->ctrl.p + 64 * slot;
-    d->timed[slot] = false;
-    d->two_events[slot] = false;
-    d->bits_timed[slot] = false;
+    c.slot = (int)(d->ncalls++ % ldpc_bp_decoder::kRing);
+    c.ev = d->ev[c.slot];
+    c.ctrl = (char *)d->ctrl.p + 64 * c.slot;
+    d->timed[c.slot] = false;
+    d->two_events[c.slot] = false;
+    d->bits_timed[c.slot] = false;
     // single-kernel paths: the kernel zeroes the control slot of the NEXT call, so a call that finds its
     // slot clean enqueues no memset, and only two events bracket the one kernel (measured on C2, batch
     // 4096: fill kernel 3.5 us + ~10 us of dependency gap on either side of a 94 us decode kernel)
-    const int nslot = (slot + 1) % ldpc_bp_decoder::kRing;
-    char *next_ctrl = (char *)d->ctrl.p + 64 * nslot;
+    c.nslot = (c.slot + 1) % ldpc_bp_decoder::kRing;
+    c.next_ctrl = (char *)d->ctrl.p + 64 * c.nslot;
     // Calls on one handle execute in call order whatever streams they are given (they share its workspace and
     // its control slots -- a kernel of call N zeroes the slot of call N+1): a call that arrives on another
     // stream than its predecessor waits for that one's last event first.
-    if (d->last_ev && d->last_stream != stream) LDPC_HIP_TRY(hipStreamWaitEvent(stream, d->last_ev, 0));
-    d->last_stream = stream;
+    if (d->last_ev && d->last_stream != c.stream) LDPC_HIP_TRY(hipStreamWaitEvent(c.stream, d->last_ev, 0));
+    d->last_stream = c.stream;
+    c.a_row = (const int *)d->row_ptr.p; c.a_eb = (const int *)d->edge_bit.p; c.a_col = (const int *)d->col_ptr.p;
+    c.a_c2r = (const int *)d->csc2csr.p;
+    *proceed = true;
+    return LDPC_OK;
+}
 
-    if (d->max_iters == 0) {
-        // the loop at belief_propagation.jl:134 never runs: err = 0, log_probabs = 0, converged = false
-        if (n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)batch * n, stream));
-        LDPC_HIP_TRY(hipMemsetAsync(d_conv, 0, (size_t)batch, stream));
-        if (d_llr && n > 0) LDPC_HIP_TRY(hipMemsetAsync(d_llr, 0, (size_t)batch * n * sizeof(double), stream));
-        if (d_iters) LDPC_HIP_TRY(hipMemsetAsync(d_iters, 0, (size_t)batch * sizeof(int32_t), stream));
-        return LDPC_OK;
+static ldpc_status decode_zero_iters(const DecodeCall &c)
+{
+    const int64_t n = c.d->n, batch = c.batch;
+    // the loop at belief_propagation.jl:134 never runs: err = 0, log_probabs = 0, converged = false
+    if (n > 0) LDPC_HIP_TRY(hipMemsetAsync(c.d_err, 0, (size_t)batch * n, c.stream));
+    LDPC_HIP_TRY(hipMemsetAsync(c.d_conv, 0, (size_t)batch, c.stream));
+    if (c.d_llr && n > 0) LDPC_HIP_TRY(hipMemsetAsync(c.d_llr, 0, (size_t)batch * n * sizeof(double), c.stream));
+    if (c.d_iters) LDPC_HIP_TRY(hipMemsetAsync(c.d_iters, 0, (size_t)batch * sizeof(int32_t), c.stream));
+    return LDPC_OK;
+}
+
+// The launch of a single-kernel path.  Latency mode: the launch and nothing else -- no memset, no events.  Otherwise
+// between two events, the control slot zeroed first unless the call before left it clean, as this kernel leaves the next.
+template <class Kernel, class Params>
+static ldpc_status launch_single(const DecodeCall &c, Kernel fn, int64_t grid, int threads, size_t lds, const Params &params)
+{
+    ldpc_bp_decoder *d = c.d;
+    if (!c.lat) {
+        if (!d->ctrl_clean[c.slot]) LDPC_HIP_TRY(hipMemsetAsync(c.ctrl, 0, 64, c.stream));
+        d->ctrl_clean[c.slot] = false;
+        LDPC_HIP_TRY(hipEventRecord(c.ev[1], c.stream));
     }
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)threads), lds, c.stream, params, c.a_row, c.a_eb, c.a_col, c.a_c2r);
+    LDPC_HIP_TRY(hipGetLastError());
+    if (c.lat) return LDPC_OK;
+    LDPC_HIP_TRY(hipEventRecord(c.ev[2], c.stream));
+    d->ctrl_clean[c.nslot] = true; d->timed[c.nslot] = false;
+    d->timed[c.slot] = true; d->two_events[c.slot] = true;
+    d->last_ev = c.ev[2];
+    return LDPC_OK;
+}
 
-    const int *a_row = (const int *)d->row_ptr.p, *a_eb = (const int *)d->edge_bit.p, *a_col = (const int *)d->col_ptr.p,
-              *a_c2r = (const int *)d->csc2csr.p;
-    // The launch of a single-kernel path.  Latency mode: the launch and nothing else -- no memset, no events.  Otherwise
-    // between two events, the control slot zeroed first unless the call before left it clean, as this kernel leaves the next.
-    auto single_kernel = [&](auto fn, int64_t grid, int threads, size_t lds, const auto &params) -> ldpc_status {
-        if (!lat) {
-            if (!d->ctrl_clean[slot]) LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
-            d->ctrl_clean[slot] = false;
-            LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
-        }
-        hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, params, a_row, a_eb, a_col, a_c2r);
-        LDPC_HIP_TRY(hipGetLastError());
-        if (lat) return LDPC_OK;
-        LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
-        d->ctrl_clean[nslot] = true; d->timed[nslot] = false;
-        d->timed[slot] = true; d->two_events[slot] = true;
-        d->last_ev = ev[2];
-        return LDPC_OK;
-    };
-    // Set-up of a node-parallel launch (bp_node_kernels.hpp), for a fresh batch and for the stragglers of a packed level:
-    // where the messages live, the instantiation, its LDS and message slots, and the NodeParams fields that do not depend
-    // on who launches.  threads_global: the thread count with the messages in the global slots (in LDS, in part or whole:
-    // one 16-wave workgroup per CU); grid_of(per_cu, msg_mode): the caller's grid.
-    struct NodeLaunch { int msg_mode, threads, grid; size_t lds; node_kernel_t fn; };
-    auto node_launch_setup = [&](int threads_global, auto &&grid_of, NodeLaunch &nl, NodeParams &np) -> ldpc_status {
-        nl.msg_mode = d->node_msg_lds ? 1 : (d->node_split_check > 0 ? 2 : 0);
-        nl.threads = nl.msg_mode ? 1024 : threads_global;
-        nl.lds = node_lds_bytes((int)s, (int)n) +
-                 (nl.msg_mode == 1 ? (size_t)d->nnz : nl.msg_mode == 2 ? (size_t)d->node_split_edge : 0) * sizeof(double);
-        nl.fn = pick_node_kernel(d->max_cdeg, d->max_bdeg, d_llr != nullptr, nl.threads, nl.msg_mode);
-        int per_cu = 0;
-        ldpc_status nst = d->prepare_kernel((const void *)nl.fn, nl.threads, nl.lds, &per_cu);
-        if (nst != LDPC_OK) return nst;
-        nl.grid = grid_of(per_cu, nl.msg_mode);
-        const size_t stride = (std::max<size_t>((size_t)d->nnz, 1) + 63) & ~(size_t)63;   // 512-byte aligned slots
-        if ((nst = d->node_msg.ensure(nl.msg_mode == 1 ? 64 : (size_t)nl.grid * stride * sizeof(double))) != LDPC_OK) return nst;
-        np.s = (int)s; np.n = (int)n; np.nnz = (int)d->nnz; np.max_iters = (int)d->max_iters; np.r = d->per / (1 - d->per);
-        np.syn = d_syn; np.err = d_err; np.conv = d_conv; np.iters = d_iters; np.llr = d_llr; np.llr_exact = d->llr_exact ? 1 : 0;
-        np.msg = (double *)d->node_msg.p; np.slot_stride = (long long)stride;
-        np.sum_iters = (u64 *)(ctrl + 8);
-        np.split_check = d->node_split_check; np.split_edge = d->node_split_edge;
-        return LDPC_OK;   // (queue, index / count / it0 / state and the done counters: the caller's; zero so far)
-    };
+// Set-up of a node-parallel launch (bp_node_kernels.hpp), for a fresh batch and for the stragglers of a packed level:
+// where the messages live, the instantiation, its LDS and message slots, and the NodeParams fields that do not depend
+// on who launches.  threads_global: the thread count with the messages in the global slots (in LDS, in part or whole:
+// one 16-wave workgroup per CU); grid_of(per_cu, msg_mode): the caller's grid.
+namespace { struct NodeLaunch { int msg_mode, threads, grid; size_t lds; node_kernel_t fn; }; }
+template <class GridOf>
+static ldpc_status node_launch_setup(const DecodeCall &c, int threads_global, GridOf &&grid_of, NodeLaunch &nl, NodeParams &np)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t s = d->s, n = d->n;
+    nl.msg_mode = d->node_msg_lds ? 1 : (d->node_split_check > 0 ? 2 : 0);
+    nl.threads = nl.msg_mode ? 1024 : threads_global;
+    nl.lds = node_lds_bytes((int)s, (int)n) +
+             (nl.msg_mode == 1 ? (size_t)d->nnz : nl.msg_mode == 2 ? (size_t)d->node_split_edge : 0) * sizeof(double);
+    nl.fn = pick_node_kernel(d->max_cdeg, d->max_bdeg, c.d_llr != nullptr, nl.threads, nl.msg_mode);
+    int per_cu = 0;
+    ldpc_status nst = d->prepare_kernel((const void *)nl.fn, nl.threads, nl.lds, &per_cu);
+    if (nst != LDPC_OK) return nst;
+    nl.grid = grid_of(per_cu, nl.msg_mode);
+    const size_t stride = (std::max<size_t>((size_t)d->nnz, 1) + 63) & ~(size_t)63;   // 512-byte aligned slots
+    if ((nst = d->node_msg.ensure(nl.msg_mode == 1 ? 64 : (size_t)nl.grid * stride * sizeof(double))) != LDPC_OK) return nst;
+    np.s = (int)s; np.n = (int)n; np.nnz = (int)d->nnz; np.max_iters = (int)d->max_iters; np.r = d->per / (1 - d->per);
+    np.syn = c.d_syn; np.err = c.d_err; np.conv = c.d_conv; np.iters = c.d_iters; np.llr = c.d_llr; np.llr_exact = d->llr_exact ? 1 : 0;
+    np.msg = (double *)d->node_msg.p; np.slot_stride = (long long)stride;
+    np.sum_iters = (u64 *)(c.ctrl + 8);
+    np.split_check = d->node_split_check; np.split_edge = d->node_split_edge;
+    return LDPC_OK;   // (queue, index / count / it0 / state and the done counters: the caller's; zero so far)
+}
 
-    const bool want_llr_early = d_llr != nullptr;
-    if (takes_lds_kernel(d, want_llr_early)) {
-        // ---- on-chip path: messages never leave the LDS (bp_lds_kernels.hpp)
-        const int logS = d->lds_logS[want_llr_early ? 1 : 0];
-        const int64_t ngroups64 = (batch + (1ll << logS) - 1) >> logS;
-        if (ngroups64 > (1ll << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-        d->last_kernel = 2; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0;
-        LdsParams lp{};
-        lp.s = (int)s; lp.n = (int)n; lp.nnz = (int)d->nnz; lp.max_iters = (int)d->max_iters;
-        lp.logS = logS; lp.ngroups = (int)ngroups64; lp.batch = batch;
-        lp.r = d->per / (1 - d->per);
-        lp.syn = d_syn; lp.err = d_err; lp.conv = d_conv; lp.iters = d_iters; lp.llr = d_llr;
-        lp.llr_exact = d->llr_exact ? 1 : 0;
-        lp.queue = (unsigned int *)ctrl;
-        lp.sum_iters = (u64 *)(ctrl + 8);
-        lp.phase_ticks = (u64 *)(ctrl + 16);
-        lp.done_count = (unsigned int *)d->done_ctr.p;
-        const size_t lds = lds_bytes_needed((int)s, (int)n, (int)d->nnz, 1 << logS, want_llr_early);
-        // 512 threads when two or more workgroups share a CU; when the LDS footprint admits only
-        // one, give that one all 16 waves (measured +21 % on the (9,10)-regular n=1000 code)
-        const bool lone = 2 * (lds + 256) > (size_t)160 * 1024;
-        const int lthreads = d->wpt_fixed ? ((d->wpt_fixed == 4) ? 256 : (d->wpt_fixed >= 12 ? 1024 : 512))
-                                          : (lone ? 1024 : 512);
-        lds_kernel_t lk = pick_lds_kernel(d->max_cdeg, d->max_bdeg, want_llr_early, lthreads);
-        int per_cu = 0;
-        ldpc_status pst = d->prepare_kernel((const void *)lk, lthreads, lds, &per_cu);
-        if (pst != LDPC_OK) return pst;
-        const int lgrid = (int)std::min<int64_t>(ngroups64, (int64_t)per_cu * d->num_cus);
-        // dequeue in chunks: ~16 dequeues per workgroup keep the load balanced and the queue word quiet
-        lp.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, ngroups64 / ((int64_t)lgrid * 16)));
-        if (lat) {   // no queue (a workgroup per group), no statistics
-            lp.queue = nullptr; lp.sum_iters = nullptr; lp.chunk = 1;
-            lp.done_flag = lat->flag; lp.done_ticket = lat->ticket;
-        } else lp.next_ctrl = (u64 *)next_ctrl;
-        return single_kernel(lk, lat ? ngroups64 : (int64_t)lgrid, lthreads, lds, lp);
-    }
+// ---- on-chip path: messages never leave the LDS (bp_lds_kernels.hpp)
+static ldpc_status decode_lds(const DecodeCall &c)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t s = d->s, n = d->n, batch = c.batch;
+    const LatencyCtl *lat = c.lat;
+    const int logS = d->lds_logS[c.want_llr ? 1 : 0];
+    const int64_t ngroups64 = (batch + (1ll << logS) - 1) >> logS;
+    if (ngroups64 > (1ll << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
+    d->last_kernel = 2; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0;
+    LdsParams lp{};
+    lp.s = (int)s; lp.n = (int)n; lp.nnz = (int)d->nnz; lp.max_iters = (int)d->max_iters;
+    lp.logS = logS; lp.ngroups = (int)ngroups64; lp.batch = batch;
+    lp.r = d->per / (1 - d->per);
+    lp.syn = c.d_syn; lp.err = c.d_err; lp.conv = c.d_conv; lp.iters = c.d_iters; lp.llr = c.d_llr;
+    lp.llr_exact = d->llr_exact ? 1 : 0;
+    lp.queue = (unsigned int *)c.ctrl;
+    lp.sum_iters = (u64 *)(c.ctrl + 8);
+    lp.phase_ticks = (u64 *)(c.ctrl + 16);
+    lp.done_count = (unsigned int *)d->done_ctr.p;
+    const size_t lds = lds_bytes_needed((int)s, (int)n, (int)d->nnz, 1 << logS, c.want_llr);
+    // 512 threads when two or more workgroups share a CU; when the LDS footprint admits only
+    // one, give that one all 16 waves (measured +21 % on the (9,10)-regular n=1000 code)
+    const bool lone = 2 * (lds + 256) > (size_t)160 * 1024;
+    const int lthreads = d->wpt_fixed ? ((d->wpt_fixed == 4) ? 256 : (d->wpt_fixed >= 12 ? 1024 : 512))
+                                      : (lone ? 1024 : 512);
+    lds_kernel_t lk = pick_lds_kernel(d->max_cdeg, d->max_bdeg, c.want_llr, lthreads);
+    int per_cu = 0;
+    ldpc_status pst = d->prepare_kernel((const void *)lk, lthreads, lds, &per_cu);
+    if (pst != LDPC_OK) return pst;
+    const int lgrid = (int)std::min<int64_t>(ngroups64, (int64_t)per_cu * d->num_cus);
+    // dequeue in chunks: ~16 dequeues per workgroup keep the load balanced and the queue word quiet
+    lp.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(64, ngroups64 / ((int64_t)lgrid * 16)));
+    if (lat) {   // no queue (a workgroup per group), no statistics
+        lp.queue = nullptr; lp.sum_iters = nullptr; lp.chunk = 1;
+        lp.done_flag = lat->flag; lp.done_ticket = lat->ticket;
+    } else lp.next_ctrl = (u64 *)c.next_ctrl;
+    return launch_single(c, lk, lat ? ngroups64 : (int64_t)lgrid, lthreads, lds, lp);
+}
 
-    if (takes_node_kernel(d, batch, want_llr_early)) {
-        // ---- small batch on a large graph: one workgroup per syndrome, one thread per node (bp_node_kernels.hpp)
-        if (batch > (1ll << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-        // all 16 waves of a CU on one syndrome while there are CUs to spare, else two 8-wave workgroups per CU
-        NodeLaunch nl; NodeParams np{};
-        const ldpc_status pst = node_launch_setup(
-            d->wpt_fixed ? (d->wpt_fixed >= 12 ? 1024 : 512) : (batch <= d->num_cus ? 1024 : 512),
-            [&](int per_cu, int) { return lat ? (int)batch : (int)std::min<int64_t>(batch, (int64_t)std::min(per_cu, 2) * d->num_cus); }, nl, np);
-        if (pst != LDPC_OK) return pst;
-        d->last_kernel = 3; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0;
-        np.batch = batch;
-        np.queue = (unsigned int *)ctrl;
-        np.done_count = (unsigned int *)d->done_ctr.p;
-        if (lat) {   // no queue (a workgroup per syndrome), no statistics
-            np.queue = nullptr; np.sum_iters = nullptr;
-            np.done_flag = lat->flag; np.done_ticket = lat->ticket;
-        } else np.next_ctrl = (u64 *)next_ctrl;
-        const ldpc_status lst = single_kernel(nl.fn, nl.grid, nl.threads, nl.lds, np);
-        if (lst == LDPC_OK && !lat) { d->last_threads = nl.threads; d->last_grid = nl.grid; }
-        return lst;
-    }
+// ---- small batch on a large graph: one workgroup per syndrome, one thread per node (bp_node_kernels.hpp)
+static ldpc_status decode_node(const DecodeCall &c)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t batch = c.batch;
+    const LatencyCtl *lat = c.lat;
+    if (batch > (1ll << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
+    // all 16 waves of a CU on one syndrome while there are CUs to spare, else two 8-wave workgroups per CU
+    NodeLaunch nl; NodeParams np{};
+    const ldpc_status pst = node_launch_setup(
+        c, d->wpt_fixed ? (d->wpt_fixed >= 12 ? 1024 : 512) : (batch <= d->num_cus ? 1024 : 512),
+        [&](int per_cu, int) { return lat ? (int)batch : (int)std::min<int64_t>(batch, (int64_t)std::min(per_cu, 2) * d->num_cus); }, nl, np);
+    if (pst != LDPC_OK) return pst;
+    d->last_kernel = 3; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0;
+    np.batch = batch;
+    np.queue = (unsigned int *)c.ctrl;
+    np.done_count = (unsigned int *)d->done_ctr.p;
+    if (lat) {   // no queue (a workgroup per syndrome), no statistics
+        np.queue = nullptr; np.sum_iters = nullptr;
+        np.done_flag = lat->flag; np.done_ticket = lat->ticket;
+    } else np.next_ctrl = (u64 *)c.next_ctrl;
+    const ldpc_status lst = launch_single(c, nl.fn, nl.grid, nl.threads, nl.lds, np);
+    if (lst == LDPC_OK && !lat) { d->last_threads = nl.threads; d->last_grid = nl.grid; }
+    return lst;
+}
 
-    if (lat) return fail(LDPC_ERR_HIP, "internal: latency mode reached the tile kernel");
-    const int64_t ntiles64 = (batch + kTile - 1) / kTile;
-    if (ntiles64 > (1 << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
-    const int ntiles = (int)ntiles64;
-    const bool want_llr = d_llr != nullptr;
+// ---- the tile / team path.  What its steps share; the refused-team-grid fallback (launch_fresh_pass()) changes
+// threads, grid, p.msg, team_ran, llr_raw_out and llr_posmap, which every later step reads.
+namespace {
+struct TileLaunch {
+    int ntiles = 0;
+    int threads = 0, grid = 0;             // of the fresh pass: the tile kernel's, or 512 threads x one slot per team
+    int tile_threads = 0, tile_grid = 0;   // ... the tile kernel's in any case
+    size_t slot_stride_bytes = 0;
+    TeamPlan plan;                         // plan.G > 1: teams take the fresh pass
+    bool team_scatter = false;
+    int team_grid = 0;
+    LevelPlan levels;                      // the packed levels of the straggler hand-off (team_plan.hpp) ...
+    LevelWords words[3] = {};              // ... and their device words in the control slot
+    bool syn_v4 = false, err_v4 = false;   // four checks (bits) per lane in the pack / unpack kernels
+    unsigned ticket = 0;
+    BPCold cold[3] = {};                   // per pass: the hot parameters travel by value (BPParams), the rest in a BPCold block in device memory
+    BPCold *d_cold = nullptr;
+    BPParams p{};                          // the fresh pass's; the passes over the levels start from a copy
+    bool team_ran = false;
+    int llr_raw_out = 0;                   // the fresh pass left posterior odds, not logarithms, in llr_t (TeamParams::llr_raw)
+    const int *llr_posmap = nullptr;       // ... in the dealt bit order of the rows-on-chip tables: position of every bit
+};
+}  // namespace
 
+// the per-batch buffers (grow only)
+static ldpc_status ensure_call_buffers(const DecodeCall &c, const TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t s = d->s, n = d->n;
+    const int ntiles = t.ntiles;
     ldpc_status st;
     if ((st = d->synmask.ensure(std::max<size_t>((size_t)ntiles * s, 1) * sizeof(u64))) != LDPC_OK) return st;
     if ((st = d->nevermask.ensure((size_t)ntiles * sizeof(u64))) != LDPC_OK) return st;
     // (two sets of decision words: a team that runs ahead -- bp_team_kernels.hpp -- writes those of odd iterations into the second)
     if ((st = d->errmask.ensure(2 * std::max<size_t>((size_t)ntiles * n, 1) * sizeof(u64))) != LDPC_OK) return st;
     if ((st = d->finmask.ensure(std::max<size_t>((size_t)ntiles * n, 1) * sizeof(u64))) != LDPC_OK) return st;
-    if (want_llr && (st = d->llr_t.ensure(std::max<size_t>((size_t)ntiles * (((size_t)n + 3) & ~(size_t)3), 1) * kTile * sizeof(double))) != LDPC_OK)
+    if (c.want_llr && (st = d->llr_t.ensure(std::max<size_t>((size_t)ntiles * (((size_t)n + 3) & ~(size_t)3), 1) * kTile * sizeof(double))) != LDPC_OK)
         return st;
-    // Geometry of this launch: 8 waves per tile (three workgroups per CU) is the measured best
-    // whenever there are more tiles than CUs -- also against geometries that make every tile
-    // resident at once (6 waves x 4 per CU: -10 %); with at most one tile per CU, 16 waves per
-    // tile put more of the chip to work.  The caller may fix it.
-    int threads = 0, grid = 0;
+    return LDPC_OK;
+}
+
+// Geometry of the fresh pass (tile_waves() / tile_geometry_pure(), team_plan.cpp: the rule and its measurements), the
+// team plan, the handle's record of the launch, and the message workspace.
+static ldpc_status plan_tile_launch(const DecodeCall &c, TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const bool want_llr = c.want_llr;
+    const int ntiles = t.ntiles;
     {
         const size_t slot_bytes = std::max<size_t>((size_t)d->nnz, 1) * kTile * sizeof(double) + slot_pad_bytes();
-        const int max_slots = (int)std::max<size_t>(std::min<size_t>(d->ws_budget / slot_bytes, 1u << 30), 1);
-        const int wpt = d->wpt_fixed ? d->wpt_fixed : (ntiles <= d->num_cus ? 16 : 8);
+        const int wpt = tile_waves(d->wpt_fixed, ntiles, d->num_cus);
         int &bc = d->blocks_cache[want_llr ? 1 : 0][wpt];
         if (bc < 0) {
             bp_kernel_t kq = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, wpt * 64);
@@ -1455,76 +1541,68 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             }
             bc = nb;
         }
-        int slots = d->resident_fixed ? d->resident_fixed : bc * d->num_cus;
-        slots = std::max(1, std::min(slots, max_slots));
-        threads = wpt * 64;
-        grid = std::min(slots, ntiles);
+        const TileGeometry g = tile_geometry_pure(d->ws_budget, slot_bytes, wpt, bc, d->resident_fixed, d->num_cus, ntiles);
+        t.threads = g.threads;
+        t.grid = g.grid;
     }
     // Teams of workgroups on the tiles (bp_team_kernels.hpp, team_plan()): medium batches, where one workgroup per
     // tile leaves CUs idle, and large ones of graphs whose team slots fit the Infinity Cache.
     // (kernel_variant 4 skips the LDS and node kernels; batches the team kernel cannot take -- an empty graph,
     // slots beyond the cache -- go to the tile kernel)
-    const TeamPlan plan = team_plan(d, batch, want_llr);
+    t.plan = team_plan(d, c.batch, want_llr);
+    const TeamPlan &plan = t.plan;
     const int team = plan.G;
-    const int tile_grid = grid, tile_threads = threads;
-    if (team > 1) { threads = 512; grid = plan.nteams; }
-    d->last_threads = threads;
+    t.tile_grid = t.grid; t.tile_threads = t.threads;
+    if (team > 1) { t.threads = 512; t.grid = plan.nteams; }
+    d->last_threads = t.threads;
     // fewer than 8 tiles: a team inside one XCD would be bound by that XCD's share of the bandwidth (1.1 TB/s);
     // dealt over all XCDs (scatter mode: team = block / G) its sweeps run 1.4x faster and the barriers (now with
     // the L2 write-back) twice as long -- 6.1 -> 5.4 ms for 64 syndromes of the C3 code, all 50 iterations.
     // (The environment switch is read per call: a test turns it on and off.)
-    const bool team_scatter = team > 1 && (exp_env("LDPC_TEAM_SCATTER") || plan.scatter);
+    t.team_scatter = team > 1 && (exp_env("LDPC_TEAM_SCATTER") || plan.scatter);
     // scatter mode launches exactly the members (8 * team blocks for <= 4 tiles would be up to 512 workgroups,
     // more than the wide-degree instantiations can keep resident: one 8-wave workgroup per CU)
-    const int team_grid = team > 1 ? (team_scatter ? plan.nteams * team : plan.grid) : 0;
-    d->last_grid = team > 1 ? plan.nteams * team : grid;   // (teams: the workgroups that take part; on an XCD that hosts no team the blocks leave at once)
+    t.team_grid = team > 1 ? (t.team_scatter ? plan.nteams * team : plan.grid) : 0;
+    d->last_grid = team > 1 ? plan.nteams * team : t.grid;   // (teams: the workgroups that take part; on an XCD that hosts no team the blocks leave at once)
     d->last_kernel = team > 1 ? 4 : 1;
     d->last_team = team;
     d->last_lds_rows = 0; d->last_rows_on_chip = 0;
-    const size_t slot_stride_bytes = std::max<size_t>((size_t)d->nnz, 1) * kTile * sizeof(double) + slot_pad_bytes();
-    if ((st = ensure_workspace(d, (size_t)grid * slot_stride_bytes, grid, slot_stride_bytes, stream)) != LDPC_OK)
-        return st;
+    t.team_ran = team > 1;
+    t.slot_stride_bytes = std::max<size_t>((size_t)d->nnz, 1) * kTile * sizeof(double) + slot_pad_bytes();
+    return ensure_workspace(d, (size_t)t.grid * t.slot_stride_bytes, t.grid, t.slot_stride_bytes, c.stream);
+}
 
-    // Straggler hand-off in LEVELS: a tile whose active lanes have dwindled to <= T0 gives those syndromes up
-    // together with their message columns (bp_kernels.hpp: packed tiles of level 1); a pass over level 1 resumes
-    // them where they stood, densely packed again, and may itself hand its stragglers (<= T1 lanes) on to level 2,
-    // whose pass runs them to the end.  Nothing is decoded twice, results are those of an undisturbed run
-    // (the decoder is deterministic per syndrome).  Everything stays on the stream: every pass reads its syndrome
-    // count from device memory, grids are sized for the level's capacity and blocks past the count return at once.
-    // A level that is full refuses further tiles (they carry on by themselves), so capacities are a memory
-    // budget, not a correctness bound.
-    const int T0 = (d->defer_thresh < 0 || d->max_iters < 4 || ntiles < 2) ? 0
-                   : (d->defer_thresh ? d->defer_thresh : d->defer_t0);
-    struct Level {
-        int thresh_in = 0;        // lanes at which the level below hands off into this one
-        int cap_tiles = 0;        // packed tiles it can hold
-        unsigned int *count = nullptr;   // device word: syndromes handed in
-        unsigned int *tile_queue = nullptr, *node_queue = nullptr;
-        unsigned node_take = 0;   // up to this many syndromes: the node-parallel kernel finishes them
-        unsigned team_cap = 0;    // above node_take up to this many: teams of workgroups on the packed tiles
-        int t_per_xcd = 0, t_gcap = 0, t_G = 0, t_nteams = 0, t_grid = 0, t_xcds = 8;   // teams on the packed tiles: members, teams
-    } lv[3];
-    int nlevels = 0;
-    if (T0 > 0) {
-        lv[1].thresh_in = T0;
-        const int worst1 = (int)(((int64_t)ntiles * T0 + kTile - 1) / kTile) + 1;
-        lv[1].cap_tiles = d->lvl_cap_force > 0 ? d->lvl_cap_force : std::min(worst1, std::max(8, std::max(grid, tile_grid) / 3));
-        nlevels = 1;
-        const int T1 = d->defer_t1;
-        if (T1 > 0 && (lv[1].cap_tiles >= 8 || d->lvl_cap_force > 0)) {
-            lv[2].thresh_in = T1;
-            const int worst2 = (int)(((int64_t)lv[1].cap_tiles * T1 + kTile - 1) / kTile) + 1;
-            lv[2].cap_tiles = d->lvl_cap_force > 0 ? d->lvl_cap_force : std::min(worst2, std::max(4, lv[1].cap_tiles / 4));
-            nlevels = 2;
-        }
-    }
-    lv[1].count = (unsigned int *)(ctrl + 4);   lv[1].tile_queue = (unsigned int *)(ctrl + 40); lv[1].node_queue = (unsigned int *)(ctrl + 48);
-    lv[2].count = (unsigned int *)(ctrl + 56);  lv[2].tile_queue = (unsigned int *)(ctrl + 44); lv[2].node_queue = (unsigned int *)(ctrl + 52);
-    for (int l = 1; l <= nlevels; ++l) {
-        Level &L = lv[l];
-        const size_t ct = (size_t)L.cap_tiles;
-        if ((st = big_alloc(d->lvl_state[l - 1], ct * slot_stride_bytes, d->device)) == LDPC_ERR_UNSUPPORTED)
-            st = d->lvl_state[l - 1].ensure(ct * slot_stride_bytes);
+// The levels of the straggler hand-off: the rule is level_plan_pure() (team_plan.cpp); here its inputs from the handle
+// and the launch, and the levels' device words.
+static void plan_levels(const DecodeCall &c, TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    LevelPlanIn in;
+    in.ntiles = t.ntiles; in.max_iters = d->max_iters;
+    in.defer_thresh = d->defer_thresh; in.defer_t0 = d->defer_t0; in.defer_t1 = d->defer_t1; in.lvl_cap_force = d->lvl_cap_force;
+    in.grid_max = std::max(t.grid, t.tile_grid);
+    in.node_ok = d->node_ok && d->variant == 0;
+    in.node_take_max = d->node_take_max;
+    // The team inputs are asked for only where the rule can use them, as before it moved: a level exists (the hand-off
+    // is on, >= 4 iterations, >= 2 tiles), it has a node pass for teams to sit above, <= 4096 iterations, gcap >= 3.
+    const bool levels_possible = d->defer_thresh >= 0 && d->max_iters >= 4 && d->max_iters <= 4096 && t.ntiles >= 2;
+    in.team_ok = levels_possible && in.node_ok && in.node_take_max > 0 && team_geometry(d, c.want_llr, &in.per_xcd, &in.gcap);
+    if (in.team_ok && in.gcap >= 3) in.team = team_plan_in(d, in.per_xcd, in.gcap);
+    t.levels = level_plan_pure(in);
+    t.words[1] = level_words(c.ctrl, 1);
+    t.words[2] = level_words(c.ctrl, 2);
+}
+
+// the buffers of the packed levels: message tiles, batch positions, iteration counts, images of the per-batch buffers
+static ldpc_status ensure_level_buffers(const DecodeCall &c, const TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t s = d->s, n = d->n;
+    ldpc_status st;
+    for (int l = 1; l <= t.levels.nlevels; ++l) {
+        const size_t ct = (size_t)t.levels.lv[l].cap_tiles;
+        if ((st = big_alloc(d->lvl_state[l - 1], ct * t.slot_stride_bytes, d->device)) == LDPC_ERR_UNSUPPORTED)
+            st = d->lvl_state[l - 1].ensure(ct * t.slot_stride_bytes);
         if (st != LDPC_OK) return st;
         if ((st = d->lvl_list[l - 1].ensure(ct * kTile * sizeof(int))) != LDPC_OK) return st;
         if ((st = d->lvl_it[l - 1].ensure(ct * kTile * sizeof(int))) != LDPC_OK) return st;
@@ -1532,277 +1610,335 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
         if ((st = d->lvl_never[l - 1].ensure(ct * sizeof(u64))) != LDPC_OK) return st;
         if ((st = d->lvl_err[l - 1].ensure(std::max<size_t>(ct * n, 1) * sizeof(u64))) != LDPC_OK) return st;
         if ((st = d->lvl_fin[l - 1].ensure(std::max<size_t>(ct * n, 1) * sizeof(u64))) != LDPC_OK) return st;
-        if (want_llr && (st = d->lvl_llr[l - 1].ensure(std::max<size_t>(ct * n, 1) * kTile * sizeof(double))) != LDPC_OK) return st;
-        LDPC_HIP_TRY(hipMemsetAsync(d->lvl_never[l - 1].p, 0, ct * sizeof(u64), stream));
-        // Few stragglers (the usual case): the node-parallel kernel finishes them, one workgroup per syndrome
-        // straight from / into the caller's arrays, instead of a handful of tiles that each sweep the whole
-        // graph with a few lanes alive.  Decided on the device: the launches of the paths not taken find the
-        // level's count on the wrong side of node_take / team_cap and return at once.
-        L.node_take = (d->node_ok && d->variant == 0 && d->node_take_max > 0)
-                          ? (unsigned)std::min<int64_t>(d->node_take_max, (int64_t)L.cap_tiles * kTile) : 0u;
-        if (L.node_take && d->max_iters <= 4096 && team_geometry(d, want_llr, &L.t_per_xcd, &L.t_gcap) && L.t_gcap >= 3) {
-            // persistent teams inside the packed tiles, as many as keep the tiles in flight inside the cache budget
-            // (team_fit()); they take whatever the level holds.  Nothing fits (LDPC_TEAM_CACHE_MIB=0, large graphs):
-            // one tile per team, up to as many tiles as leave every team 3 members.
-            int tiles_max, x = 8, t = 1, g = 3;
-            if (team_fit(team_plan_in(d, L.t_per_xcd, L.t_gcap), L.cap_tiles, false, &x, &t, &g)) {
-                tiles_max = L.cap_tiles;
-            } else {
-                x = 8; t = L.t_per_xcd / 3; g = 3;           // (the members of surplus teams are idle: round 1's geometry in fixed form)
-                tiles_max = std::min(x * t, L.cap_tiles);
-            }
-            L.t_G = g; L.t_xcds = x; L.t_nteams = x * t; L.t_grid = 8 * g * t;
-            if ((unsigned)tiles_max * kTile > L.node_take) L.team_cap = (unsigned)tiles_max * kTile;
-        }
+        if (c.want_llr && (st = d->lvl_llr[l - 1].ensure(std::max<size_t>(ct * n, 1) * kTile * sizeof(double))) != LDPC_OK) return st;
+        LDPC_HIP_TRY(hipMemsetAsync(d->lvl_never[l - 1].p, 0, ct * sizeof(u64), c.stream));
     }
+    return LDPC_OK;
+}
 
-    LDPC_HIP_TRY(hipMemsetAsync(ctrl, 0, 64, stream));
-    d->ctrl_clean[slot] = false;
-    LDPC_HIP_TRY(hipMemsetAsync(d->nevermask.p, 0, (size_t)ntiles * sizeof(u64), stream));
-    LDPC_HIP_TRY(hipEventRecord(ev[0], stream));
+// Pack / unpack between the caller's arrays and the masks of `tiles` tiles: level 0 over the batch (list and count
+// NULL), a packed level over the positions in its list (batch 0; beyond node_take syndromes only).
+static ldpc_status launch_pack(const DecodeCall &c, const TileLaunch &t, DevBuf &syn_m, DevBuf &never_m, int tiles, long long batch_or_0,
+                               const int *list, const unsigned int *count, unsigned node_take)
+{
+    const int64_t s = c.d->s;
+    if (s <= 0) return LDPC_OK;
+    const dim3 g((unsigned)((s + (t.syn_v4 ? 255 : 63)) / (t.syn_v4 ? 256 : 64)), (unsigned)tiles);
+    hipLaunchKernelGGL(t.syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, c.stream, c.d_syn, batch_or_0, (int)s,
+                       (u64 *)syn_m.p, (u64 *)never_m.p, list, count, node_take);
+    LDPC_HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+static ldpc_status launch_unpack_errors(const DecodeCall &c, const TileLaunch &t, DevBuf &fin_m, int tiles, long long batch_or_0,
+                                        const int *list, const unsigned int *count, unsigned node_take)
+{
+    const int64_t n = c.d->n;
+    const dim3 g((unsigned)((n + (t.err_v4 ? 255 : 63)) / (t.err_v4 ? 256 : 64)), (unsigned)tiles);
+    hipLaunchKernelGGL(t.err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, g, dim3(64), 0, c.stream, (const u64 *)fin_m.p,
+                       batch_or_0, (int)n, c.d_err, list, count, node_take);
+    LDPC_HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+// (raw / exact / posmap: what a team's fresh pass left in llr_t, TeamParams::llr_raw; 0 / 0 / NULL for logarithms in bit order)
+static ldpc_status launch_unpack_llr(const DecodeCall &c, DevBuf &llr_m, int tiles, long long batch_or_0, const int *list,
+                                     const unsigned int *count, unsigned node_take, int raw, int exact, const int *posmap)
+{
+    const int64_t n = c.d->n;
+    const dim3 g((unsigned)((n + 63) / 64), ((unsigned)tiles + 7u) & ~7u);   // (unpack_llr_kernel deals the tiles over the XCDs in eights)
+    hipLaunchKernelGGL(unpack_llr_kernel, g, dim3(256), 0, c.stream, (const double *)llr_m.p, batch_or_0, (int)n, c.d_llr, list, count,
+                       node_take, raw, exact, posmap);
+    LDPC_HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+// The call's control slot and never-mask zeroed, the first event, the batch packed into the masks of level 0.
+static ldpc_status pack_fresh_batch(const DecodeCall &c, TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    LDPC_HIP_TRY(hipMemsetAsync(c.ctrl, 0, 64, c.stream));
+    d->ctrl_clean[c.slot] = false;
+    LDPC_HIP_TRY(hipMemsetAsync(d->nevermask.p, 0, (size_t)t.ntiles * sizeof(u64), c.stream));
+    LDPC_HIP_TRY(hipEventRecord(c.ev[0], c.stream));
     // four checks (bits) per lane in the pack / unpack kernels where the caller's arrays allow 4-byte accesses
-    const bool syn_v4 = s % 4 == 0 && ((uintptr_t)d_syn & 3u) == 0, err_v4 = n % 4 == 0 && ((uintptr_t)d_err & 3u) == 0;
-    // Pack / unpack between the caller's arrays and the masks of `tiles` tiles: level 0 over the batch (list and count
-    // NULL), a packed level over the positions in its list (batch 0; beyond node_take syndromes only).
-    auto launch_pack = [&](DevBuf &syn_m, DevBuf &never_m, int tiles, long long batch_or_0, const int *list, const unsigned int *count,
-                           unsigned node_take) -> ldpc_status {
-        if (s <= 0) return LDPC_OK;
-        const dim3 g((unsigned)((s + (syn_v4 ? 255 : 63)) / (syn_v4 ? 256 : 64)), (unsigned)tiles);
-        hipLaunchKernelGGL(syn_v4 ? pack_syndromes_kernel<4> : pack_syndromes_kernel<1>, g, dim3(64), 0, stream, d_syn, batch_or_0, (int)s,
-                           (u64 *)syn_m.p, (u64 *)never_m.p, list, count, node_take);
-        LDPC_HIP_TRY(hipGetLastError());
-        return LDPC_OK;
-    };
-    auto launch_unpack_errors = [&](DevBuf &fin_m, int tiles, long long batch_or_0, const int *list, const unsigned int *count,
-                                    unsigned node_take) -> ldpc_status {
-        const dim3 g((unsigned)((n + (err_v4 ? 255 : 63)) / (err_v4 ? 256 : 64)), (unsigned)tiles);
-        hipLaunchKernelGGL(err_v4 ? unpack_errors_kernel<4> : unpack_errors_kernel<1>, g, dim3(64), 0, stream, (const u64 *)fin_m.p,
-                           batch_or_0, (int)n, d_err, list, count, node_take);
-        LDPC_HIP_TRY(hipGetLastError());
-        return LDPC_OK;
-    };
-    // (raw / exact / posmap: what a team's fresh pass left in llr_t, TeamParams::llr_raw; 0 / 0 / NULL for logarithms in bit order)
-    auto launch_unpack_llr = [&](DevBuf &llr_m, int tiles, long long batch_or_0, const int *list, const unsigned int *count,
-                                 unsigned node_take, int raw, int exact, const int *posmap) -> ldpc_status {
-        const dim3 g((unsigned)((n + 63) / 64), ((unsigned)tiles + 7u) & ~7u);   // (unpack_llr_kernel deals the tiles over the XCDs in eights)
-        hipLaunchKernelGGL(unpack_llr_kernel, g, dim3(256), 0, stream, (const double *)llr_m.p, batch_or_0, (int)n, d_llr, list, count,
-                           node_take, raw, exact, posmap);
-        LDPC_HIP_TRY(hipGetLastError());
-        return LDPC_OK;
-    };
-    if ((st = launch_pack(d->synmask, d->nevermask, ntiles, (long long)batch, nullptr, nullptr, 0u)) != LDPC_OK) return st;
-    const unsigned ticket = (unsigned)(d->ncalls & 0x7fffffffu) ? (unsigned)(d->ncalls & 0x7fffffffu) : 0x7fffffffu;
-    // per pass: the hot parameters travel by value (BPParams), the rest in a BPCold block in device memory
-    BPCold cold[3] = {};
-    auto hand_off_into = [&](BPParams &q, BPCold &c, int l) {   // the pass (q, c) hands its stragglers to level l (0 = to nobody)
-        if (l < 1 || l > nlevels) { q.defer_thresh = 0; c.defer_list = nullptr; c.defer_it = nullptr; c.defer_count = nullptr;
-                                    c.next_state = nullptr; c.next_stride = 0; c.next_cap = 0; return; }
-        q.defer_thresh = lv[l].thresh_in;
-        c.defer_list = (int *)d->lvl_list[l - 1].p;
-        c.defer_it = (int *)d->lvl_it[l - 1].p;
-        c.defer_count = lv[l].count;
-        c.next_state = (double *)d->lvl_state[l - 1].p;
-        c.next_stride = (long long)(slot_stride_bytes / sizeof(double));
-        c.next_cap = (unsigned)lv[l].cap_tiles * kTile;
-    };
+    t.syn_v4 = d->s % 4 == 0 && ((uintptr_t)c.d_syn & 3u) == 0; t.err_v4 = d->n % 4 == 0 && ((uintptr_t)c.d_err & 3u) == 0;
+    return launch_pack(c, t, d->synmask, d->nevermask, t.ntiles, (long long)c.batch, nullptr, nullptr, 0u);
+}
+
+// the pass (q, cold) hands its stragglers to level l (0 = to nobody)
+static void hand_off_into(const DecodeCall &c, const TileLaunch &t, BPParams &q, BPCold &cold, int l)
+{
+    ldpc_bp_decoder *d = c.d;
+    if (l < 1 || l > t.levels.nlevels) { q.defer_thresh = 0; cold.defer_list = nullptr; cold.defer_it = nullptr; cold.defer_count = nullptr;
+                                         cold.next_state = nullptr; cold.next_stride = 0; cold.next_cap = 0; return; }
+    q.defer_thresh = t.levels.lv[l].thresh_in;
+    cold.defer_list = (int *)d->lvl_list[l - 1].p;
+    cold.defer_it = (int *)d->lvl_it[l - 1].p;
+    cold.defer_count = t.words[l].count;
+    cold.next_state = (double *)d->lvl_state[l - 1].p;
+    cold.next_stride = (long long)(t.slot_stride_bytes / sizeof(double));
+    cold.next_cap = (unsigned)t.levels.lv[l].cap_tiles * kTile;
+}
+
+// The parameters of the passes: the ticket, BPParams of the fresh pass, the BPCold blocks of all passes and their
+// store into device memory.
+static ldpc_status fill_pass_params(const DecodeCall &c, TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t s = d->s, n = d->n;
+    const int nlevels = t.levels.nlevels;
+    char *ctrl = c.ctrl;
+    ldpc_status st;
+    t.ticket = (unsigned)(d->ncalls & 0x7fffffffu) ? (unsigned)(d->ncalls & 0x7fffffffu) : 0x7fffffffu;
     if ((st = d->cold.ensure(3 * sizeof(BPCold))) != LDPC_OK) return st;
-    BPCold *const d_cold = (BPCold *)d->cold.p;
-    BPParams p{};
+    t.d_cold = (BPCold *)d->cold.p;
+    BPParams &p = t.p;
     p.s = (int)s; p.n = (int)n; p.nnz = (int)d->nnz; p.max_iters = (int)d->max_iters;
-    p.ntiles = ntiles; p.batch = batch;
+    p.ntiles = t.ntiles; p.batch = c.batch;
     p.r = d->per / (1 - d->per);  // belief_propagation.jl:129,153 (IEEE double division, same on host)
     p.msg = (double *)d->msg.p;
-    p.slot_stride = (long long)(slot_stride_bytes / sizeof(double));
+    p.slot_stride = (long long)(t.slot_stride_bytes / sizeof(double));
     p.errmask = (u64 *)d->errmask.p;
     p.finmask = (u64 *)d->finmask.p;
-    p.llr = want_llr ? (double *)d->llr_t.p : nullptr;
+    p.llr = c.want_llr ? (double *)d->llr_t.p : nullptr;
     p.queue = (unsigned int *)ctrl;
-    p.cold = d_cold + 0;
+    p.cold = t.d_cold + 0;
     p.defer_min_iter = 2;
     p.count_dev = nullptr;
     p.count_skip = 0;
     p.resumed = 0;
     p.llr_exact = d->llr_exact ? 1 : 0;
-    for (BPCold &c : cold) {
-        c.iters = d_iters;
-        c.conv = d_conv;
-        c.sum_iters = (u64 *)(ctrl + 8);
-        c.phase_ticks = (u64 *)(ctrl + 16);
+    for (BPCold &cold : t.cold) {
+        cold.iters = c.d_iters;
+        cold.conv = c.d_conv;
+        cold.sum_iters = (u64 *)(ctrl + 8);
+        cold.phase_ticks = (u64 *)(ctrl + 16);
     }
-    hand_off_into(p, cold[0], 1);
+    hand_off_into(c, t, p, t.cold[0], 1);
     for (int l = 1; l <= nlevels; ++l) {
         BPParams unused{};
-        cold[l].index = (const int *)d->lvl_list[l - 1].p;
-        cold[l].it0 = (const int *)d->lvl_it[l - 1].p;
-        hand_off_into(unused, cold[l], l + 1);
+        t.cold[l].index = (const int *)d->lvl_list[l - 1].p;
+        t.cold[l].it0 = (const int *)d->lvl_it[l - 1].p;
+        hand_off_into(c, t, unused, t.cold[l], l + 1);
     }
-    hipLaunchKernelGGL(store_cold_kernel, dim3(1), dim3(64), 0, stream, cold[0], cold[1], cold[2], d_cold);
+    hipLaunchKernelGGL(store_cold_kernel, dim3(1), dim3(64), 0, c.stream, t.cold[0], t.cold[1], t.cold[2], t.d_cold);
     LDPC_HIP_TRY(hipGetLastError());
-    bp_kernel_t kfn = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, threads);
-    const int always_release = d->team_always_release ? 1 : 0;
-    auto team_params = [&](DevBuf &wsbuf, int nteams, int tiles, TeamParams &tp) -> ldpc_status {
-        const size_t ctl_bytes = ((size_t)nteams + 1) * kTeamCtlWords * sizeof(unsigned int);   // + the block of the tile queue
-        const size_t mism_stride = ((size_t)d->max_iters + 31) & ~(size_t)31;
-        const size_t ws_bytes = ctl_bytes + (size_t)tiles * mism_stride * sizeof(u64);
-        ldpc_status r = wsbuf.ensure(ws_bytes);
-        if (r != LDPC_OK) return r;
-        LDPC_HIP_TRY(hipMemsetAsync(wsbuf.p, 0, ws_bytes, stream));
-        tp.ctl = (unsigned int *)wsbuf.p;
-        tp.mism = (u64 *)((char *)wsbuf.p + ctl_bytes);
-        tp.mism_stride = (int)mism_stride;
-        tp.fault = d->team_fault_dev;
-        tp.always_release = always_release;
-        tp.nteams = nteams;
-        tp.xcds = 8;
-        tp.dynamic = d->team_dynamic;
-        tp.pairs = d->team_pairs;
-        tp.scatter = 0;
-        tp.count_max = 0;
-        tp.inject_fault = 0;
-        tp.ticket = ticket;
-        tp.rollcall_ticks = d->rollcall_ticks;
-        tp.errmask_alt = nullptr;
-        tp.ahead_min = 0;
-        tp.ahead_from = 2;
-        tp.llr_raw = 0;
-        return LDPC_OK;
-    };
-    bool team_ran = team > 1;
-    int llr_raw_out = 0;   // the fresh pass left posterior odds, not logarithms, in llr_t (TeamParams::llr_raw)
-    const int *llr_posmap = nullptr;   // ... in the dealt bit order of the rows-on-chip tables: position of every bit
-    LDPC_HIP_TRY(hipEventRecord(ev[1], stream));
+    return LDPC_OK;
+}
+
+// The control blocks of a team grid (arrival counters + mismatch words) sized, zeroed on the stream, and the
+// TeamParams fields that do not depend on which pass launches.
+static ldpc_status team_params(const DecodeCall &c, const TileLaunch &t, DevBuf &wsbuf, int nteams, int tiles, TeamParams &tp)
+{
+    ldpc_bp_decoder *d = c.d;
+    const size_t ctl_bytes = ((size_t)nteams + 1) * kTeamCtlWords * sizeof(unsigned int);   // + the block of the tile queue
+    const size_t mism_stride = ((size_t)d->max_iters + 31) & ~(size_t)31;
+    const size_t ws_bytes = ctl_bytes + (size_t)tiles * mism_stride * sizeof(u64);
+    ldpc_status r = wsbuf.ensure(ws_bytes);
+    if (r != LDPC_OK) return r;
+    LDPC_HIP_TRY(hipMemsetAsync(wsbuf.p, 0, ws_bytes, c.stream));
+    tp.ctl = (unsigned int *)wsbuf.p;
+    tp.mism = (u64 *)((char *)wsbuf.p + ctl_bytes);
+    tp.mism_stride = (int)mism_stride;
+    tp.fault = d->team_fault_dev;
+    tp.always_release = d->team_always_release ? 1 : 0;
+    tp.nteams = nteams;
+    tp.xcds = 8;
+    tp.dynamic = d->team_dynamic;
+    tp.pairs = d->team_pairs;
+    tp.scatter = 0;
+    tp.count_max = 0;
+    tp.inject_fault = 0;
+    tp.ticket = t.ticket;
+    tp.rollcall_ticks = d->rollcall_ticks;
+    tp.errmask_alt = nullptr;
+    tp.ahead_min = 0;
+    tp.ahead_from = 2;
+    tp.llr_raw = 0;
+    return LDPC_OK;
+}
+
+// Which team instantiation takes the fresh pass and what it reads: whole checks in LDS (an irregular graph), rows on
+// chip (a regular one), or every row in the slot.  Sets tp.rows / tp.pre and the handle's last_lds_rows / last_rows_on_chip.
+namespace {
+struct TeamTables {
+    team_kernel_t tk; size_t lds;
+    const int *row, *col, *c2r;   // the kernel's three table arguments (the graph, unless the instantiation reads its own tables)
+    const int *posmap;            // position of every bit in the dealt order (NULL: bit order)
+};
+}  // namespace
+static TeamTables choose_team_tables(const DecodeCall &c, const TileLaunch &t, TeamParams &tp)
+{
+    ldpc_bp_decoder *d = c.d;
+    const bool want_llr = c.want_llr;
+    const TeamPlan &plan = t.plan;
+    const int team = plan.G;
+    TeamTables tt{pick_team_kernel(d->max_cdeg, d->max_bdeg, want_llr), team_lds_bytes(), c.a_row, c.a_col, c.a_c2r, nullptr};
+    if (plan.irr && !t.team_scatter && team_irr_build(d, team) == LDPC_OK && d->irr_on_chip > 0) {
+        // an irregular graph: whole checks in the LDS of their owners (bp_team_kernels.hpp, IRR)
+        team_kernel_t tki = pick_team_kernel_irr(d->irr_dcb, d->max_bdeg, want_llr);
+        const size_t need = (size_t)d->irr_R * kTile * sizeof(double);
+        int occ_irr = 0;
+        if (tki && d->prepare_kernel((const void *)tki, LDPC_TEAM_THREADS, need, &occ_irr) == LDPC_OK && occ_irr >= 1) {
+            tt.tk = tki; tt.lds = need;
+            d->last_lds_rows = d->irr_R; d->last_rows_on_chip = d->irr_on_chip;
+            tp.rows.lds_edge = (const int *)d->irr_lds_edge.p;
+            tp.rows.R = d->irr_R;
+            tp.rows.reg_edge = nullptr; tp.rows.regs = 0;
+            tp.rows.static_c = tp.rows.static_v = LDPC_TEAM_THREADS / 64; tp.rows.flip = 0;
+            tt.row = (const int *)d->irr_ctab.p;      // (this instantiation reads its tables through these three arguments)
+            tt.col = (const int *)d->irr_ptab.p;
+            tt.c2r = (const int *)d->irr_ploc.p;
+            tt.posmap = (const int *)d->irr_posmap.p;
+        }
+    }
+    if (plan.rows && team_rows_build(d, team) == LDPC_OK) {   // (also with LDPC_TEAM_SCATTER: members over all XCDs, a test)
+        // rows that only one member touches live in its LDS (TeamRows)
+        team_kernel_t tkr = pick_team_kernel_rows(d->rows_dc, d->rows_dv, want_llr, d->rows_regs > 0);
+        const size_t need = (size_t)(d->rows_R + (d->rows_regs > 0 ? 1 : 0)) * kTile * sizeof(double);   // (+ the dummy row of the register rows)
+        int occ_rows = 0;
+        if (tkr && d->prepare_kernel((const void *)tkr, LDPC_TEAM_THREADS, need, &occ_rows) == LDPC_OK && occ_rows >= 1) {
+            tt.tk = tkr; tt.lds = need;
+            d->last_lds_rows = d->rows_R; d->last_rows_on_chip = d->rows_on_chip;
+            tp.rows.lds_edge = (const int *)d->rows_lds_edge.p;
+            tp.rows.R = d->rows_R;
+            tp.rows.reg_edge = (const int *)d->rows_reg_edge.p;
+            tp.rows.regs = d->rows_regs;
+            tp.rows.static_c = d->rows_static_c; tp.rows.static_v = d->rows_static_v; tp.rows.flip = d->team_flip;
+            tp.rows.first_c = d->rows_first_c;
+            // (wide teams -- members over all XCDs, a barrier of ~20 us: every on-chip chunk fits its shadow.  n = 65536, 16,384
+            //  syndromes x 50 iterations: 905.6 / 892.3 / 880.9 ms with 0 / 2 / 4 chunks a wave; profiles/r04_wide_teams.txt)
+            tp.pre = std::min((plan.wide && !d->team_pre_set) ? 8 : d->team_pre, d->rows_first_c / (LDPC_TEAM_THREADS / 64));
+            tt.col = (const int *)d->rows_ctab.p;     // (this instantiation reads its tables through these two arguments)
+            tt.c2r = (const int *)d->rows_vtab.p;
+            tt.posmap = (const int *)d->rows_posmap.p;
+        }
+    }
+    return tt;
+}
+
+// LDPC_TEAM_DEBUG diagnostics: which XCDs did the teams land on?
+static void dump_team_debug(const DecodeCall &call, const TileLaunch &tl, const TeamParams &tp)
+{
+    ldpc_bp_decoder *d = call.d;
+    hipStream_t stream = call.stream;
+    const TeamPlan &plan = tl.plan;
+    const int ntiles = tl.ntiles, team = plan.G, team_grid = tl.team_grid;
+    const int nt = std::min(plan.nteams, ntiles);
+    std::vector<unsigned> xm((size_t)nt);
+    (void)ldpc_detail::wait_stream(stream, d->device, "LDPC_TEAM_DEBUG (stream synchronise)");
+    for (int t = 0; t < nt; ++t)
+        (void)hipMemcpy(&xm[(size_t)t], tp.ctl + (size_t)t * kTeamCtlWords + 32, sizeof(unsigned), hipMemcpyDeviceToHost);
+    int single = 0;
+    for (unsigned v : xm) single += __builtin_popcount(v) == 1;
+    std::fprintf(stderr, "[ldpc] team kernel: %d tiles, %d teams x %d workgroups, grid %d; %d teams on one XCD (first masks %x %x %x)\n",
+                 ntiles, plan.nteams, team, team_grid, single, xm[0], nt > 1 ? xm[1] : 0u, nt > 2 ? xm[2] : 0u);
+    // per team: its members' own check / variable sweep times (100 MHz ticks over the whole call: mean, fastest,
+    // slowest, and where the slowest ran: XCC_ID is not stored, HW_ID gives CU (bits 8-11), SH (12), SE (13-15))
+    for (int t = 0; t < nt; ++t) {
+        std::vector<unsigned> ml((size_t)team * 32);
+        (void)hipMemcpy(ml.data(), tp.ctl + (size_t)t * kTeamCtlWords + kTeamCtlMember, ml.size() * sizeof(unsigned), hipMemcpyDeviceToHost);
+        double sc = 0, sv = 0; unsigned cmin = ~0u, cmax = 0, vmin = ~0u, vmax = 0; int cm = 0, vm = 0;
+        for (int m = 0; m < team; ++m) {
+            const unsigned c = ml[(size_t)m * 32 + 1], v = ml[(size_t)m * 32 + 2];
+            sc += c; sv += v;
+            if (c < cmin) cmin = c;
+            if (c > cmax) { cmax = c; cm = m; }
+            if (v < vmin) vmin = v;
+            if (v > vmax) { vmax = v; vm = m; }
+        }
+        const unsigned hc = ml[(size_t)cm * 32 + 3], hv = ml[(size_t)vm * 32 + 3];
+        std::fprintf(stderr, "[ldpc]   team %d (xcc mask %x): check mean %.0f min %u max %u (member %d cu %u se %u)  var mean %.0f min %u max %u (member %d cu %u se %u)\n",
+                     t, xm[(size_t)t], sc / team, cmin, cmax, cm, (hc >> 8) & 15u, (hc >> 13) & 7u, sv / team, vmin, vmax, vm, (hv >> 8) & 15u, (hv >> 13) & 7u);
+    }
+}
+
+// The fresh pass over the batch: the team grid, or the tile kernel -- also where the runtime refuses the team grid.
+static ldpc_status launch_fresh_pass(const DecodeCall &c, TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const bool want_llr = c.want_llr;
+    hipStream_t stream = c.stream;
+    const TeamPlan &plan = t.plan;
+    const int team = plan.G, ntiles = t.ntiles;
+    const int64_t n = d->n;
+    BPParams &p = t.p;
+    ldpc_status st;
     if (team > 1) {
         TeamParams tp{};
-        if ((st = team_params(d->team_ws, plan.nteams, ntiles, tp)) != LDPC_OK) return st;
+        if ((st = team_params(c, t, d->team_ws, plan.nteams, ntiles, tp)) != LDPC_OK) return st;
         tp.G = team;
         tp.xcds = plan.xcds;
-        tp.scatter = team_scatter ? 1 : 0;
+        tp.scatter = t.team_scatter ? 1 : 0;
         tp.inject_fault = d->inject_fault;   // (tests; the kernel only looks at it in the experiments build)
         tp.errmask_alt = (u64 *)d->errmask.p + std::max<size_t>((size_t)ntiles * n, 1);
         tp.ahead_min = d->team_ahead;
         tp.ahead_from = d->team_ahead_from;
         tp.llr_raw = want_llr ? d->team_llr_raw : 0;
-        llr_raw_out = tp.llr_raw == 6 ? 4 : tp.llr_raw;
+        t.llr_raw_out = tp.llr_raw == 6 ? 4 : tp.llr_raw;
         // one round of teams over all XCDs (<= 3 tiles: a single decode!): no other tile waits for this team, so a sweep
         // ahead that turns out to be for nothing costs one sweep at the end, and the barrier saved in every iteration
         // is worth it whatever the number of active lanes (one syndrome, 50 iterations: 2.62 -> 2.31 ms)
         if (plan.scatter && !d->team_ahead_set && tp.ahead_min > 0) tp.ahead_min = 1;
-        team_kernel_t tk = pick_team_kernel(d->max_cdeg, d->max_bdeg, want_llr);
-        size_t team_lds = team_lds_bytes();
-        const int *t_col = a_col, *t_c2r = a_c2r, *t_row = a_row;
-        if (plan.irr && !team_scatter && team_irr_build(d, team) == LDPC_OK && d->irr_on_chip > 0) {
-            // an irregular graph: whole checks in the LDS of their owners (bp_team_kernels.hpp, IRR)
-            team_kernel_t tki = pick_team_kernel_irr(d->irr_dcb, d->max_bdeg, want_llr);
-            const size_t need = (size_t)d->irr_R * kTile * sizeof(double);
-            int occ_irr = 0;
-            if (tki && d->prepare_kernel((const void *)tki, LDPC_TEAM_THREADS, need, &occ_irr) == LDPC_OK && occ_irr >= 1) {
-                tk = tki; team_lds = need;
-                d->last_lds_rows = d->irr_R; d->last_rows_on_chip = d->irr_on_chip;
-                tp.rows.lds_edge = (const int *)d->irr_lds_edge.p;
-                tp.rows.R = d->irr_R;
-                tp.rows.reg_edge = nullptr; tp.rows.regs = 0;
-                tp.rows.static_c = tp.rows.static_v = LDPC_TEAM_THREADS / 64; tp.rows.flip = 0;
-                t_row = (const int *)d->irr_ctab.p;      // (this instantiation reads its tables through these three arguments)
-                t_col = (const int *)d->irr_ptab.p;
-                t_c2r = (const int *)d->irr_ploc.p;
-                llr_posmap = (const int *)d->irr_posmap.p;
-            }
-        }
-        if (plan.rows && team_rows_build(d, team) == LDPC_OK) {   // (also with LDPC_TEAM_SCATTER: members over all XCDs, a test)
-            // rows that only one member touches live in its LDS (TeamRows)
-            team_kernel_t tkr = pick_team_kernel_rows(d->rows_dc, d->rows_dv, want_llr, d->rows_regs > 0);
-            const size_t need = (size_t)(d->rows_R + (d->rows_regs > 0 ? 1 : 0)) * kTile * sizeof(double);   // (+ the dummy row of the register rows)
-            int occ_rows = 0;
-            if (tkr && d->prepare_kernel((const void *)tkr, LDPC_TEAM_THREADS, need, &occ_rows) == LDPC_OK && occ_rows >= 1) {
-                tk = tkr; team_lds = need;
-                d->last_lds_rows = d->rows_R; d->last_rows_on_chip = d->rows_on_chip;
-                tp.rows.lds_edge = (const int *)d->rows_lds_edge.p;
-                tp.rows.R = d->rows_R;
-                tp.rows.reg_edge = (const int *)d->rows_reg_edge.p;
-                tp.rows.regs = d->rows_regs;
-                tp.rows.static_c = d->rows_static_c; tp.rows.static_v = d->rows_static_v; tp.rows.flip = d->team_flip;
-                tp.rows.first_c = d->rows_first_c;
-                // (wide teams -- members over all XCDs, a barrier of ~20 us: every on-chip chunk fits its shadow.  n = 65536, 16,384
-                //  syndromes x 50 iterations: 905.6 / 892.3 / 880.9 ms with 0 / 2 / 4 chunks a wave; profiles/r04_wide_teams.txt)
-                tp.pre = std::min((plan.wide && !d->team_pre_set) ? 8 : d->team_pre, d->rows_first_c / (LDPC_TEAM_THREADS / 64));
-                t_col = (const int *)d->rows_ctab.p;     // (this instantiation reads its tables through these two arguments)
-                t_c2r = (const int *)d->rows_vtab.p;
-                llr_posmap = (const int *)d->rows_posmap.p;
-            }
-        }
+        TeamTables tt = choose_team_tables(c, t, tp);
+        t.llr_posmap = tt.posmap;
         const u64 *a_syn = (const u64 *)d->synmask.p, *a_nev = (const u64 *)d->nevermask.p;
-        void *args[] = {&p, &tp, &t_row, &a_eb, &t_col, &t_c2r, &a_syn, &a_nev};
-        const hipError_t te = launch_team_grid(d, tk, team_grid, args, stream, team_lds);
+        const int *a_eb = c.a_eb;
+        void *args[] = {&p, &tp, &tt.row, &a_eb, &tt.col, &tt.c2r, &a_syn, &a_nev};
+        const hipError_t te = launch_team_grid(d, tt.tk, t.team_grid, args, stream, tt.lds);
         if (te != hipSuccess) {
             // a team grid the runtime refuses must not fail the call: the tile kernel decodes the batch (one
             // workgroup per tile, same results), and teams stay off for this decoder
             (void)hipGetLastError();
             d->team_max = 1;
-            threads = tile_threads; grid = tile_grid;
-            d->last_kernel = 1; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0; d->last_grid = grid; d->last_threads = threads;
-            if ((st = ensure_workspace(d, (size_t)grid * slot_stride_bytes, grid, slot_stride_bytes, stream)) != LDPC_OK) return st;
+            t.threads = t.tile_threads; t.grid = t.tile_grid;
+            d->last_kernel = 1; d->last_team = 1; d->last_lds_rows = 0; d->last_rows_on_chip = 0; d->last_grid = t.grid; d->last_threads = t.threads;
+            if ((st = ensure_workspace(d, (size_t)t.grid * t.slot_stride_bytes, t.grid, t.slot_stride_bytes, stream)) != LDPC_OK) return st;
             p.msg = (double *)d->msg.p;
-            kfn = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, threads);
-            team_ran = false;
-            llr_raw_out = 0;
-            llr_posmap = nullptr;
+            t.team_ran = false;
+            t.llr_raw_out = 0;
+            t.llr_posmap = nullptr;
         }
-        if (team_ran && exp_env("LDPC_TEAM_DEBUG")) {   // diagnostics: which XCDs did the teams land on?
-            const int nt = std::min(plan.nteams, ntiles);
-            std::vector<unsigned> xm((size_t)nt);
-            (void)ldpc_detail::wait_stream(stream, d->device, "LDPC_TEAM_DEBUG (stream synchronise)");
-            for (int t = 0; t < nt; ++t)
-                (void)hipMemcpy(&xm[(size_t)t], tp.ctl + (size_t)t * kTeamCtlWords + 32, sizeof(unsigned), hipMemcpyDeviceToHost);
-            int single = 0;
-            for (unsigned v : xm) single += __builtin_popcount(v) == 1;
-            std::fprintf(stderr, "[ldpc] team kernel: %d tiles, %d teams x %d workgroups, grid %d; %d teams on one XCD (first masks %x %x %x)\n",
-                         ntiles, plan.nteams, team, team_grid, single, xm[0], nt > 1 ? xm[1] : 0u, nt > 2 ? xm[2] : 0u);
-            // per team: its members' own check / variable sweep times (100 MHz ticks over the whole call: mean, fastest,
-            // slowest, and where the slowest ran: XCC_ID is not stored, HW_ID gives CU (bits 8-11), SH (12), SE (13-15))
-            for (int t = 0; t < nt; ++t) {
-                std::vector<unsigned> ml((size_t)team * 32);
-                (void)hipMemcpy(ml.data(), tp.ctl + (size_t)t * kTeamCtlWords + kTeamCtlMember, ml.size() * sizeof(unsigned), hipMemcpyDeviceToHost);
-                double sc = 0, sv = 0; unsigned cmin = ~0u, cmax = 0, vmin = ~0u, vmax = 0; int cm = 0, vm = 0;
-                for (int m = 0; m < team; ++m) {
-                    const unsigned c = ml[(size_t)m * 32 + 1], v = ml[(size_t)m * 32 + 2];
-                    sc += c; sv += v;
-                    if (c < cmin) cmin = c;
-                    if (c > cmax) { cmax = c; cm = m; }
-                    if (v < vmin) vmin = v;
-                    if (v > vmax) { vmax = v; vm = m; }
-                }
-                const unsigned hc = ml[(size_t)cm * 32 + 3], hv = ml[(size_t)vm * 32 + 3];
-                std::fprintf(stderr, "[ldpc]   team %d (xcc mask %x): check mean %.0f min %u max %u (member %d cu %u se %u)  var mean %.0f min %u max %u (member %d cu %u se %u)\n",
-                             t, xm[(size_t)t], sc / team, cmin, cmax, cm, (hc >> 8) & 15u, (hc >> 13) & 7u, sv / team, vmin, vmax, vm, (hv >> 8) & 15u, (hv >> 13) & 7u);
-            }
-        }
+        if (t.team_ran && exp_env("LDPC_TEAM_DEBUG")) dump_team_debug(c, t, tp);
     }
-    if (!team_ran) {
-        hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3((unsigned)threads), 0, stream, p, a_row, a_eb, a_col, a_c2r,
+    if (!t.team_ran) {
+        bp_kernel_t kfn = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, t.threads);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)t.grid), dim3((unsigned)t.threads), 0, stream, p, c.a_row, c.a_eb, c.a_col, c.a_c2r,
                            (const u64 *)d->synmask.p, (const u64 *)d->nevermask.p);
         LDPC_HIP_TRY(hipGetLastError());
     }
-    // ---- passes over the packed levels (tile kernel in place / teams on packed tiles; the node kernel comes last)
+    return LDPC_OK;
+}
+
+// ---- passes over the packed levels (tile kernel in place / teams on packed tiles; the node kernel comes last)
+static ldpc_status launch_level_passes(const DecodeCall &c, TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const bool want_llr = c.want_llr;
+    hipStream_t stream = c.stream;
+    const int nlevels = t.levels.nlevels, threads = t.threads;
+    const int *a_row = c.a_row, *a_eb = c.a_eb, *a_col = c.a_col, *a_c2r = c.a_c2r;
+    ldpc_status st;
     bp_kernel_t kfn2 = pick_kernel(d->max_cdeg, d->max_bdeg, want_llr, threads, true);
     int occ2 = 1;
     if (nlevels && (st = d->prepare_kernel((const void *)kfn2, threads, 0, &occ2)) != LDPC_OK) return st;
     for (int l = 1; l <= nlevels; ++l) {
-        Level &L = lv[l];
+        const LevelPlan::Level &L = t.levels.lv[l];
+        const LevelWords &W = t.words[l];
         const u64 *l_syn = (const u64 *)d->lvl_syn[l - 1].p, *l_nev = (const u64 *)d->lvl_never[l - 1].p;
-        if ((st = launch_pack(d->lvl_syn[l - 1], d->lvl_never[l - 1], L.cap_tiles, 0, (const int *)d->lvl_list[l - 1].p, L.count, L.node_take)) != LDPC_OK)
+        if ((st = launch_pack(c, t, d->lvl_syn[l - 1], d->lvl_never[l - 1], L.cap_tiles, 0, (const int *)d->lvl_list[l - 1].p, W.count, L.node_take)) != LDPC_OK)
             return st;
-        BPParams q = p;
+        BPParams q = t.p;
         q.msg = (double *)d->lvl_state[l - 1].p;
         q.errmask = (u64 *)d->lvl_err[l - 1].p;
         q.finmask = (u64 *)d->lvl_fin[l - 1].p;
         q.llr = want_llr ? (double *)d->lvl_llr[l - 1].p : nullptr;
-        q.queue = L.tile_queue;
-        q.cold = d_cold + l;
+        q.queue = W.tile_queue;
+        q.cold = t.d_cold + l;
         q.resumed = 1;
-        q.count_dev = L.count;
+        q.count_dev = W.count;
         q.count_skip = std::max(L.node_take, L.team_cap);
         q.defer_min_iter = 1;
-        hand_off_into(q, cold[l], l + 1);   // (sets q.defer_thresh too)
+        hand_off_into(c, t, q, t.cold[l], l + 1);   // (sets q.defer_thresh too)
         const int g2 = std::max(1, std::min(occ2 * d->num_cus, L.cap_tiles));
         hipLaunchKernelGGL(kfn2, dim3((unsigned)g2), dim3((unsigned)threads), 0, stream, q, a_row, a_eb, a_col, a_c2r, l_syn, l_nev);
         LDPC_HIP_TRY(hipGetLastError());
@@ -1810,7 +1946,7 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             BPParams q3 = q;
             q3.count_skip = L.node_take;
             TeamParams tp{};
-            if ((st = team_params(d->team_ws_lvl[l - 1], L.t_nteams, (int)(L.team_cap / kTile), tp)) != LDPC_OK) return st;
+            if ((st = team_params(c, t, d->team_ws_lvl[l - 1], L.t_nteams, (int)(L.team_cap / kTile), tp)) != LDPC_OK) return st;
             tp.G = L.t_G;
             tp.xcds = L.t_xcds;
             tp.count_max = L.team_cap;
@@ -1819,38 +1955,92 @@ static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const u
             LDPC_HIP_TRY(launch_team_grid(d, tk, L.t_grid, args, stream, team_lds_bytes()));
         }
     }
-    LDPC_HIP_TRY(hipEventRecord(ev[2], stream));
-    // ---- results out: level 0 first, then every level over the rows its lower levels gave up
-    if (n > 0) {
-        if ((st = launch_unpack_errors(d->finmask, ntiles, (long long)batch, nullptr, nullptr, 0u)) != LDPC_OK) return st;
-        if (want_llr && (st = launch_unpack_llr(d->llr_t, ntiles, (long long)batch, nullptr, nullptr, 0u, llr_raw_out, d->llr_exact ? 1 : 0, llr_posmap)) != LDPC_OK)
+    return LDPC_OK;
+}
+
+// ---- results out: level 0 first, then every level over the rows its lower levels gave up
+static ldpc_status unpack_results(const DecodeCall &c, const TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    const bool want_llr = c.want_llr;
+    ldpc_status st;
+    if (d->n > 0) {
+        if ((st = launch_unpack_errors(c, t, d->finmask, t.ntiles, (long long)c.batch, nullptr, nullptr, 0u)) != LDPC_OK) return st;
+        if (want_llr && (st = launch_unpack_llr(c, d->llr_t, t.ntiles, (long long)c.batch, nullptr, nullptr, 0u, t.llr_raw_out, d->llr_exact ? 1 : 0, t.llr_posmap)) != LDPC_OK)
             return st;
-        for (int l = 1; l <= nlevels; ++l) {
+        for (int l = 1; l <= t.levels.nlevels; ++l) {
+            const LevelPlan::Level &L = t.levels.lv[l];
             const int *list = (const int *)d->lvl_list[l - 1].p;
-            if ((st = launch_unpack_errors(d->lvl_fin[l - 1], lv[l].cap_tiles, 0, list, lv[l].count, lv[l].node_take)) != LDPC_OK) return st;
-            if (want_llr && (st = launch_unpack_llr(d->lvl_llr[l - 1], lv[l].cap_tiles, 0, list, lv[l].count, lv[l].node_take, 0, 0, nullptr)) != LDPC_OK)
+            if ((st = launch_unpack_errors(c, t, d->lvl_fin[l - 1], L.cap_tiles, 0, list, t.words[l].count, L.node_take)) != LDPC_OK) return st;
+            if (want_llr && (st = launch_unpack_llr(c, d->lvl_llr[l - 1], L.cap_tiles, 0, list, t.words[l].count, L.node_take, 0, 0, nullptr)) != LDPC_OK)
                 return st;
         }
     }
-    // ---- levels that hold only a few syndromes: the node-parallel kernel resumes each from its packed column
-    for (int l = 1; l <= nlevels; ++l) {
-        Level &L = lv[l];
+    return LDPC_OK;
+}
+
+// ---- levels that hold only a few syndromes: the node-parallel kernel resumes each from its packed column
+static ldpc_status launch_level_node_passes(const DecodeCall &c, const TileLaunch &t)
+{
+    ldpc_bp_decoder *d = c.d;
+    for (int l = 1; l <= t.levels.nlevels; ++l) {
+        const LevelPlan::Level &L = t.levels.lv[l];
         if (!L.node_take) continue;
         NodeLaunch nl; NodeParams np{};
-        st = node_launch_setup(512 /* (global slots: 1024 x 1 per CU measured the same as 512 x 2) */,
+        const ldpc_status st = node_launch_setup(c, 512 /* (global slots: 1024 x 1 per CU measured the same as 512 x 2) */,
                                [&](int, int msg_mode) { return (int)std::min<int64_t>((int64_t)L.node_take, (int64_t)(msg_mode ? 1 : 2) * d->num_cus); }, nl, np);
         if (st != LDPC_OK) return st;
-        np.batch = 0; np.queue = L.node_queue;
-        np.index = (const int *)d->lvl_list[l - 1].p; np.count_dev = L.count; np.count_max = L.node_take;
+        np.batch = 0; np.queue = t.words[l].node_queue;
+        np.index = (const int *)d->lvl_list[l - 1].p; np.count_dev = t.words[l].count; np.count_max = L.node_take;
         np.it0 = (const int *)d->lvl_it[l - 1].p; np.state = (const double *)d->lvl_state[l - 1].p;
-        np.state_stride = (long long)(slot_stride_bytes / sizeof(double));
-        hipLaunchKernelGGL(nl.fn, dim3((unsigned)nl.grid), dim3((unsigned)nl.threads), nl.lds, stream, np, a_row, a_eb, a_col, a_c2r);
+        np.state_stride = (long long)(t.slot_stride_bytes / sizeof(double));
+        hipLaunchKernelGGL(nl.fn, dim3((unsigned)nl.grid), dim3((unsigned)nl.threads), nl.lds, c.stream, np, c.a_row, c.a_eb, c.a_col, c.a_c2r);
         LDPC_HIP_TRY(hipGetLastError());
     }
-    LDPC_HIP_TRY(hipEventRecord(ev[3], stream));
-    d->timed[slot] = true;
-    d->last_ev = ev[3];
     return LDPC_OK;
+}
+
+// The tile / team path in steps.  Four events: ev[0] after the control memsets, ev[1] before the fresh pass, ev[2]
+// after the passes over the levels, ev[3] at the end.
+static ldpc_status decode_tiles(const DecodeCall &c)
+{
+    ldpc_bp_decoder *d = c.d;
+    const int64_t ntiles64 = (c.batch + kTile - 1) / kTile;
+    if (ntiles64 > (1 << 30)) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one call");
+    TileLaunch t;
+    t.ntiles = (int)ntiles64;
+    ldpc_status st;
+    if ((st = ensure_call_buffers(c, t)) != LDPC_OK) return st;
+    if ((st = plan_tile_launch(c, t)) != LDPC_OK) return st;
+    plan_levels(c, t);
+    if ((st = ensure_level_buffers(c, t)) != LDPC_OK) return st;
+    if ((st = pack_fresh_batch(c, t)) != LDPC_OK) return st;
+    if ((st = fill_pass_params(c, t)) != LDPC_OK) return st;
+    LDPC_HIP_TRY(hipEventRecord(c.ev[1], c.stream));
+    if ((st = launch_fresh_pass(c, t)) != LDPC_OK) return st;
+    if ((st = launch_level_passes(c, t)) != LDPC_OK) return st;
+    LDPC_HIP_TRY(hipEventRecord(c.ev[2], c.stream));
+    if ((st = unpack_results(c, t)) != LDPC_OK) return st;
+    if ((st = launch_level_node_passes(c, t)) != LDPC_OK) return st;
+    LDPC_HIP_TRY(hipEventRecord(c.ev[3], c.stream));
+    d->timed[c.slot] = true;
+    d->last_ev = c.ev[3];
+    return LDPC_OK;
+}
+
+static ldpc_status decode_device_impl(ldpc_bp_decoder *d, int64_t batch, const uint8_t *d_syn,
+                                      uint8_t *d_err, uint8_t *d_conv, double *d_llr, int32_t *d_iters,
+                                      void *stream_v, const LatencyCtl *lat)
+{
+    DecodeCall c{d, batch, d_syn, d_err, d_conv, d_llr, d_iters, (hipStream_t)stream_v, lat, d_llr != nullptr};
+    bool proceed = false;
+    const ldpc_status st = begin_call(c, &proceed);
+    if (!proceed) return st;
+    if (d->max_iters == 0) return decode_zero_iters(c);
+    if (takes_lds_kernel(d, c.want_llr)) return decode_lds(c);
+    if (takes_node_kernel(d, batch, c.want_llr)) return decode_node(c);
+    if (lat) return fail(LDPC_ERR_HIP, "internal: latency mode reached the tile kernel");
+    return decode_tiles(c);
 }
 
 extern "C" {

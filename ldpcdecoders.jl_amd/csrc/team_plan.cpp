@@ -136,6 +136,75 @@ TeamPlan team_plan_pure(const TeamPlanIn &in, int64_t batch)
     return pl;
 }
 
+// Straggler hand-off in LEVELS: a tile whose active lanes have dwindled to <= T0 gives those syndromes up
+// together with their message columns (bp_kernels.hpp: packed tiles of level 1); a pass over level 1 resumes
+// them where they stood, densely packed again, and may itself hand its stragglers (<= T1 lanes) on to level 2,
+// whose pass runs them to the end.  Nothing is decoded twice, results are those of an undisturbed run
+// (the decoder is deterministic per syndrome).  Everything stays on the stream: every pass reads its syndrome
+// count from device memory, grids are sized for the level's capacity and blocks past the count return at once.
+// A level that is full refuses further tiles (they carry on by themselves), so capacities are a memory
+// budget, not a correctness bound.
+LevelPlan level_plan_pure(const LevelPlanIn &in)
+{
+    LevelPlan pl;
+    const int T0 = (in.defer_thresh < 0 || in.max_iters < 4 || in.ntiles < 2) ? 0
+                   : (in.defer_thresh ? in.defer_thresh : in.defer_t0);
+    if (T0 > 0) {
+        pl.lv[1].thresh_in = T0;
+        const int worst1 = (int)(((int64_t)in.ntiles * T0 + kTile - 1) / kTile) + 1;
+        pl.lv[1].cap_tiles = in.lvl_cap_force > 0 ? in.lvl_cap_force : std::min(worst1, std::max(8, in.grid_max / 3));
+        pl.nlevels = 1;
+        const int T1 = in.defer_t1;
+        if (T1 > 0 && (pl.lv[1].cap_tiles >= 8 || in.lvl_cap_force > 0)) {
+            pl.lv[2].thresh_in = T1;
+            const int worst2 = (int)(((int64_t)pl.lv[1].cap_tiles * T1 + kTile - 1) / kTile) + 1;
+            pl.lv[2].cap_tiles = in.lvl_cap_force > 0 ? in.lvl_cap_force : std::min(worst2, std::max(4, pl.lv[1].cap_tiles / 4));
+            pl.nlevels = 2;
+        }
+    }
+    for (int l = 1; l <= pl.nlevels; ++l) {
+        LevelPlan::Level &L = pl.lv[l];
+        // Few stragglers (the usual case): the node-parallel kernel finishes them, one workgroup per syndrome
+        // straight from / into the caller's arrays, instead of a handful of tiles that each sweep the whole
+        // graph with a few lanes alive.  Decided on the device: the launches of the paths not taken find the
+        // level's count on the wrong side of node_take / team_cap and return at once.
+        L.node_take = (in.node_ok && in.node_take_max > 0)
+                          ? (unsigned)std::min<int64_t>(in.node_take_max, (int64_t)L.cap_tiles * kTile) : 0u;
+        if (L.node_take && in.max_iters <= 4096 && in.team_ok && in.gcap >= 3) {
+            // persistent teams inside the packed tiles, as many as keep the tiles in flight inside the cache budget
+            // (team_fit()); they take whatever the level holds.  Nothing fits (LDPC_TEAM_CACHE_MIB=0, large graphs):
+            // one tile per team, up to as many tiles as leave every team 3 members.
+            int tiles_max, x = 8, t = 1, g = 3;
+            if (team_fit(in.team, L.cap_tiles, false, &x, &t, &g)) {
+                tiles_max = L.cap_tiles;
+            } else {
+                x = 8; t = in.per_xcd / 3; g = 3;           // (the members of surplus teams are idle: round 1's geometry in fixed form)
+                tiles_max = std::min(x * t, L.cap_tiles);
+            }
+            L.t_G = g; L.t_xcds = x; L.t_nteams = x * t; L.t_grid = 8 * g * t;
+            if ((unsigned)tiles_max * kTile > L.node_take) L.team_cap = (unsigned)tiles_max * kTile;
+        }
+    }
+    return pl;
+}
+
+// Geometry of a tile launch: 8 waves per tile (three workgroups per CU) is the measured best
+// whenever there are more tiles than CUs -- also against geometries that make every tile
+// resident at once (6 waves x 4 per CU: -10 %); with at most one tile per CU, 16 waves per
+// tile put more of the chip to work.  The caller may fix it.
+int tile_waves(int wpt_fixed, int ntiles, int num_cus) { return wpt_fixed ? wpt_fixed : (ntiles <= num_cus ? 16 : 8); }
+
+TileGeometry tile_geometry_pure(size_t ws_budget, size_t slot_bytes, int wpt, int blocks_per_cu, int resident_fixed, int num_cus, int ntiles)
+{
+    const int max_slots = (int)std::max<size_t>(std::min<size_t>(ws_budget / slot_bytes, 1u << 30), 1);
+    int slots = resident_fixed ? resident_fixed : blocks_per_cu * num_cus;
+    slots = std::max(1, std::min(slots, max_slots));
+    TileGeometry g;
+    g.threads = wpt * 64;
+    g.grid = std::min(slots, ntiles);
+    return g;
+}
+
 // the static part of a member's share under a plan: `frac_num / 4` of the smallest member's chunks, whole rounds of W
 TeamRegPlan team_reg_plan(int n, int s, int G, int regs_per_wave, int quarters, int dv, int dc)
 {

@@ -1,10 +1,12 @@
 // team_plan.hpp -- how a batch is dealt to teams of workgroups and the index tables the team kernel
-// (bp_team_kernels.hpp) reads: the plan (TeamPlanIn -> TeamPlan), the rows-on-chip tables of a regular graph
-// (TeamRegPlan, TeamRowTables) and the whole-checks-in-LDS tables of an irregular one (TeamIrrTables).  Pure host code
-// over team_layout.hpp and the standard library -- no HIP, no decoder handle, no environment -- so that it builds with
-// a plain C++ compiler and runs under the sanitizers on the CPU (tests/native/team_plan_sanitize.cpp).  The host unit
-// (ldpc_mi355x.hip: team_plan_in(), team_rows_build(), team_irr_build()) fills the inputs from a decoder and uploads
-// the tables; ldpc_debug_team_plan / _rows / _irr hand them to the CPU tests.
+// (bp_team_kernels.hpp) reads: the plan (TeamPlanIn -> TeamPlan), the levels of the straggler hand-off (LevelPlanIn ->
+// LevelPlan, level_plan_pure()), the slot arithmetic of a tile launch (tile_waves(), tile_geometry_pure()), the
+// rows-on-chip tables of a regular graph (TeamRegPlan, TeamRowTables) and the whole-checks-in-LDS tables of an irregular
+// one (TeamIrrTables).  Pure host code over team_layout.hpp and the standard library -- no HIP, no decoder handle, no
+// environment -- so that it builds with a plain C++ compiler and runs under the sanitizers on the CPU
+// (tests/native/team_plan_sanitize.cpp).  The host unit (ldpc_mi355x.hip: team_plan_in(), plan_tile_launch(),
+// plan_levels(), team_rows_build(), team_irr_build()) fills the inputs from a decoder and uploads the tables;
+// ldpc_debug_team_plan / _rows / _irr hand them to the CPU tests.
 #pragma once
 #include "team_layout.hpp"
 
@@ -75,6 +77,41 @@ int team_rows_expected(const TeamPlanIn &in, int G);
 bool team_fit(const TeamPlanIn &in, int64_t ntiles, bool rows, int *xcds, int *tpx, int *G);
 int team_wide_auto(const TeamPlanIn &in, int64_t ntiles);
 TeamPlan team_plan_pure(const TeamPlanIn &in, int64_t batch);
+
+// The straggler hand-off's LEVELS of packed tiles (ldpc_mi355x.hip, plan_levels()): how many there are, at how many
+// lanes a pass hands off into each, how many packed tiles each holds, and which kernel finishes what it holds (the node
+// kernel up to node_take syndromes, teams on the packed tiles up to team_cap, the tile kernel beyond).  What the rule
+// depends on, as data: the host unit fills it from a decoder, its tile launch and team_geometry().
+struct LevelPlanIn {
+    int ntiles = 0;
+    int64_t max_iters = 0;
+    int defer_thresh = 0;      // 0 auto, -1 off, else the lanes at which a fresh tile gives up (ldpc_bp_decoder::defer_thresh)
+    int defer_t0 = 16, defer_t1 = 16;   // LDPC_DEFER_T0 / _T1 (T1 0 = one level)
+    int lvl_cap_force = 0;     // LDPC_DEFER_CAP_TILES: packed tiles per level (tests)
+    int grid_max = 0;          // workgroups of the fresh pass: max(grid, tile_grid) of the tile launch
+    bool node_ok = false;      // the node-parallel kernel may finish stragglers (node_ok && variant == 0)
+    int64_t node_take_max = 0; // ... up to this many of a level
+    bool team_ok = false;      // team_geometry() succeeded, with ...
+    int per_xcd = 0, gcap = 0; // ... its team workgroups per XCD and members per team at most
+    TeamPlanIn team;           // team_plan_in(d, per_xcd, gcap): what team_fit() is asked with
+};
+struct LevelPlan {
+    int nlevels = 0;
+    struct Level {
+        int thresh_in = 0;        // lanes at which the level below hands off into this one
+        int cap_tiles = 0;        // packed tiles it can hold
+        unsigned node_take = 0;   // up to this many syndromes: the node-parallel kernel finishes them
+        unsigned team_cap = 0;    // above node_take up to this many: teams of workgroups on the packed tiles
+        int t_G = 0, t_xcds = 8, t_nteams = 0, t_grid = 0;   // teams on the packed tiles: members, XCDs, teams, workgroups
+    } lv[3];                      // [1], [2]: the levels; [0] unused (level 0 is the batch)
+};
+LevelPlan level_plan_pure(const LevelPlanIn &in);
+
+// Geometry of a tile-kernel launch: waves per tile (tile_waves(); the occupancy of that instantiation is the host
+// unit's to ask), then threads and grid from the workspace slots the budget and the chip admit.
+struct TileGeometry { int threads = 0, grid = 0; };
+int tile_waves(int wpt_fixed, int ntiles, int num_cus);
+TileGeometry tile_geometry_pure(size_t ws_budget, size_t slot_bytes, int wpt, int blocks_per_cu, int resident_fixed, int num_cus, int ntiles);
 
 // The tables of TeamRows for teams of G members (kept until another G is asked for), for a regular graph whose checks
 // have dc edges each and whose bits dv.  Checks are dealt as the kernel deals them -- chunk c of 2 checks to member

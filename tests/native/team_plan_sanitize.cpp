@@ -4,7 +4,9 @@
 // tests/test_team_rows_cpu.py::test_team_plan_under_sanitizers.  What the tables must SAY about the graph is that
 // file's business; here only what is cheap: every call succeeds, the tables have the sizes the layout promises, the
 // write-back lists name edges of the graph, the bit order is a permutation, a plan never asks for more workgroups than
-// the chip hosts; the tile plans of the min-sum and relay decoders (tile_plan.hpp) stay inside the LDS budgets.  Exit code 0 and "OK ..." = nothing found.
+// the chip hosts; the levels of the straggler hand-off (level_plan_pure()) hold what the rule says, as literals; the
+// tile plans of the min-sum and relay decoders (tile_plan.hpp) stay inside the LDS budgets.  Exit code 0 and "OK ..." =
+// nothing found.
 #include "../../ldpcdecoders.jl_amd/csrc/team_plan.hpp"
 #include "../../ldpcdecoders.jl_amd/csrc/tile_plan.hpp"
 
@@ -104,6 +106,106 @@ static bool plans(int *count)
     return true;
 }
 
+// The levels of the straggler hand-off (level_plan_pure()) and the slot arithmetic of a tile launch.  The expected
+// values are worked out by hand from the rule as ldpc_mi355x.hip stated it before it moved into team_plan.cpp:
+//   T0 = 0 if defer_thresh < 0, max_iters < 4 or ntiles < 2, else defer_thresh or (0: automatic) defer_t0
+//   level 1 holds min((ntiles T0 + 63) / 64 + 1, max(8, grid / 3)) tiles, level 2 (if defer_t1 > 0 and level 1 holds >= 8)
+//   min((cap1 T1 + 63) / 64 + 1, max(4, cap1 / 4)); a forced capacity replaces both and admits level 2 at any size
+//   node_take = min(node_take_max, 64 cap); teams (node_take > 0, max_iters <= 4096, geometry, gcap >= 3) from
+//   team_fit(cap, rows = false), else 8 XCDs x per_xcd / 3 teams of 3; team_cap = 64 min(teams, cap) if that is > node_take
+static LevelPlanIn level_in(int ntiles, size_t cache)
+{
+    LevelPlanIn in;
+    in.ntiles = ntiles; in.max_iters = 50; in.grid_max = 768;
+    in.node_ok = true; in.node_take_max = 512;
+    in.team_ok = true; in.per_xcd = 32; in.gcap = 32;
+    in.team.nnz = 65536; in.team.max_iters = 50; in.team.cache = cache; in.team.num_cus = 256;   // (32 MiB a slot)
+    in.team.per_xcd = 32; in.team.gcap = 32; in.team.gcap_one = 32;
+    return in;
+}
+static bool no_teams(const LevelPlan::Level &L) { return L.team_cap == 0u && L.t_G == 0 && L.t_nteams == 0 && L.t_grid == 0; }
+static bool levels()
+{
+    LevelPlanIn in = level_in(1, 0);
+    CHECK(level_plan_pure(in).nlevels == 0);
+    in = level_in(100, 0); in.max_iters = 3;
+    CHECK(level_plan_pure(in).nlevels == 0);
+    in = level_in(100, 0); in.defer_thresh = -1;
+    CHECK(level_plan_pure(in).nlevels == 0);
+    {   // automatic thresholds, nothing fits the cache: 80 teams of 3
+        const LevelPlan pl = level_plan_pure(level_in(100, 0));
+        CHECK(pl.nlevels == 2 && pl.lv[1].thresh_in == 16 && pl.lv[2].thresh_in == 16);
+        CHECK(pl.lv[1].cap_tiles == 26 && pl.lv[2].cap_tiles == 6);
+        CHECK(pl.lv[1].node_take == 512u && pl.lv[2].node_take == 384u);
+        for (int l = 1; l <= 2; ++l) CHECK(pl.lv[l].t_G == 3 && pl.lv[l].t_xcds == 8 && pl.lv[l].t_nteams == 80 && pl.lv[l].t_grid == 240);
+        CHECK(pl.lv[1].team_cap == 1664u);   // 26 tiles
+        CHECK(pl.lv[2].team_cap == 0u);      // 6 tiles = 384 syndromes: all the node kernel's
+    }
+    {   // the node kernel takes all a level can hold: teams planned, none needed
+        in = level_in(100, 0); in.node_take_max = 100000;
+        const LevelPlan pl = level_plan_pure(in);
+        CHECK(pl.lv[1].node_take == 1664u && pl.lv[2].node_take == 384u && pl.lv[1].team_cap == 0u && pl.lv[2].team_cap == 0u);
+    }
+    {   // fewer teams than the level holds tiles: 8 x (6 / 3) = 16
+        in = level_in(100, 0); in.per_xcd = 6;
+        const LevelPlan pl = level_plan_pure(in);
+        CHECK(pl.lv[1].t_G == 3 && pl.lv[1].t_xcds == 8 && pl.lv[1].t_nteams == 16 && pl.lv[1].t_grid == 48 && pl.lv[1].team_cap == 1024u);
+        CHECK(pl.lv[2].team_cap == 0u);
+    }
+    {
+        in = level_in(2, 0); in.grid_max = 2;
+        const LevelPlan pl = level_plan_pure(in);
+        CHECK(pl.nlevels == 1 && pl.lv[1].cap_tiles == 2 && pl.lv[1].thresh_in == 16 && pl.lv[1].node_take == 128u);
+    }
+    in = level_in(100, 0); in.defer_t1 = 0;
+    CHECK(level_plan_pure(in).nlevels == 1 && level_plan_pure(in).lv[1].cap_tiles == 26);
+    {
+        in = level_in(100, 0); in.defer_thresh = 48;
+        const LevelPlan pl = level_plan_pure(in);
+        CHECK(pl.nlevels == 2 && pl.lv[1].thresh_in == 48 && pl.lv[2].thresh_in == 16 && pl.lv[1].cap_tiles == 76 && pl.lv[2].cap_tiles == 19);
+    }
+    {
+        in = level_in(100, 0); in.lvl_cap_force = 2;
+        const LevelPlan pl = level_plan_pure(in);
+        CHECK(pl.nlevels == 2 && pl.lv[1].cap_tiles == 2 && pl.lv[2].cap_tiles == 2 && pl.lv[1].node_take == 128u && pl.lv[2].node_take == 128u);
+    }
+    for (int which = 0; which < 5; ++which) {   // no teams on a level
+        in = level_in(100, (size_t)240 << 20);
+        if (which == 0) in.max_iters = 4097;
+        if (which == 1) in.gcap = 2;
+        if (which == 2) in.node_take_max = 0;
+        if (which == 3) in.node_ok = false;
+        if (which == 4) in.team_ok = false;
+        const LevelPlan pl = level_plan_pure(in);
+        CHECK(pl.nlevels == 2 && pl.lv[1].cap_tiles == 26 && pl.lv[2].cap_tiles == 6 && no_teams(pl.lv[1]) && no_teams(pl.lv[2]));
+        CHECK((pl.lv[1].node_take == 0u) == (which == 2 || which == 3));
+    }
+    {   // the slots fit the cache: what team_fit() says for the level's capacity, every row in the slot
+        in = level_in(100, (size_t)240 << 20);
+        const LevelPlan pl = level_plan_pure(in);
+        for (int l = 1; l <= 2; ++l) {
+            int x = 0, t = 0, g = 0;
+            CHECK(team_fit(in.team, pl.lv[l].cap_tiles, false, &x, &t, &g));
+            CHECK(pl.lv[l].t_G == g && pl.lv[l].t_xcds == x && pl.lv[l].t_nteams == x * t && pl.lv[l].t_grid == 8 * g * t);
+        }
+        CHECK(pl.lv[1].team_cap == 1664u && pl.lv[2].team_cap == 0u);
+    }
+    // the slot arithmetic of a tile launch: 16 waves a tile up to one tile per CU, else 8; slots by occupancy, budget, request
+    CHECK(tile_waves(0, 256, 256) == 16 && tile_waves(0, 257, 256) == 8 && tile_waves(4, 1000, 256) == 4);
+    const size_t slot = (size_t)6048 * 512;
+    TileGeometry g = tile_geometry_pure(100 * slot, slot, 8, 3, 0, 256, 1000);
+    CHECK(g.threads == 512 && g.grid == 100);
+    g = tile_geometry_pure(1000 * slot, slot, 8, 3, 0, 256, 1000);
+    CHECK(g.threads == 512 && g.grid == 768);
+    g = tile_geometry_pure(0, slot, 16, 1, 0, 256, 1000);
+    CHECK(g.threads == 1024 && g.grid == 1);
+    g = tile_geometry_pure(1000 * slot, slot, 8, 3, 5, 256, 1000);
+    CHECK(g.grid == 5);
+    g = tile_geometry_pure(1000 * slot, slot, 16, 1, 0, 256, 3);
+    CHECK(g.grid == 3);
+    return true;
+}
+
 // The tier and the tile width of the min-sum and relay decoders (tile_plan.hpp) over sizes from nothing to the largest
 // create accepts, every variant: a plan is tier 1 with a power of two S <= 64 inside 159 KiB or tier 2 with S = 64, and
 // variant 1 is refused exactly where one syndrome does not fit.
@@ -137,8 +239,8 @@ int main()
                     irregular(1000, 500, 3, 8, 4) && irregular(1000, 500, 3, 16, 16) && irregular(1000, 500, 32, 8, 4) &&
                     irregular(1000, 500, 32, 16, 16) &&
                     irregular(96, 64, 32, 8, 4) && irregular(96, 64, 32, 16, 16) &&   // 24 position chunks: members without a position
-                    plans(&nplans) && tile_plans(&ntile);
+                    plans(&nplans) && levels() && tile_plans(&ntile);
     if (!ok) return 1;
-    std::printf("OK 6 regular and 6 irregular table sets, %d plans, %d tile plans\n", nplans, ntile);
+    std::printf("OK 6 regular and 6 irregular table sets, %d plans, the level plans, %d tile plans\n", nplans, ntile);
     return 0;
 }
