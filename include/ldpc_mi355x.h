@@ -1206,6 +1206,14 @@ typedef struct ldpc_pauli_relay_options {
 #include "ldpc_mi355x_pauli_relay.h"
 
 /* ------------------------------------------------------------------------
+ * Joint Pauli min-sum decoder of a general (non-CSS) stabilizer code, whose checks may mix Pauli types: the rule of
+ * ldpc_pauli_minsum_* with a Pauli type per edge and three message totals per qubit.  THE RULE, the options struct, every
+ * status and the seven ldpc_stab_minsum_* functions are stated in ldpc_mi355x_stab.h, which this header includes here.
+ * Added WITHOUT a change of LDPC_MI355X_ABI_VERSION (symbols only): detect them by symbol lookup.
+ * ------------------------------------------------------------------------ */
+#include "ldpc_mi355x_stab.h"
+
+/* ------------------------------------------------------------------------
  * Sliding-window decoding: the step between two windows.  A model H (D detectors x N mechanisms, zero-based CSC) too
  * long to decode in one piece is decoded window by window: window k sees the detectors det_k and the mechanisms mech_k,
  * any decoder of this library decodes its syndromes against H[det_k, mech_k], the first mechanisms of its guess --

@@ -98,6 +98,12 @@ ldpc_status ldpc_debug_pauli_tile_plan(int64_t s, int64_t n, int64_t rec_words, 
    counterpart. */
 #include "ldpc_mi355x_pauli_relay_debug.h"   /* (declares ldpc_debug_pauli_relay_tile_plan) */
 
+/* The plan of a stabilizer min-sum handle -- csrc/tile_plan.hpp stab_tile_plan(), the function ldpc_stab_minsum_create
+   calls; r checks, n qubits, rec_words over the checks of the union graph.  A tile of S syndromes has a state of
+   S (4 (3 n + rec_words) + r)  bytes (the three message totals MX, MY, MZ, the check records, the syndromes), rounded up to
+   256, and the policy of ldpc_debug_tile_plan runs over that size.  Out and statuses as there.  No reference counterpart. */
+#include "ldpc_mi355x_stab_debug.h"   /* (declares ldpc_debug_stab_tile_plan) */
+
 /* The layers ldpc_minsum_create gives a handle of the layered schedule (options->schedule = 1; THE LAYERED RULE of
    include/ldpc_mi355x.h) -- csrc/layer_plan.hpp layer_plan_build(), the function create calls, followed by the same
    verification (no two checks of a layer share a bit, every non-empty check in exactly one layer).  H as the zero-based

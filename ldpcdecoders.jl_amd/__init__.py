@@ -33,6 +33,7 @@ from .trials import TrialResult, Trials, run_trials  # noqa: F401,E402
 from .css_trials import CSSTrialResult, CSSTrials, conditional_probs, run_css_joint_trials, run_css_trials  # noqa: F401,E402
 from .pauli import PauliMinSumDecoder  # noqa: F401,E402
 from .pauli_relay import PauliRelayMinSumDecoder  # noqa: F401,E402
+from .stabilizer import StabilizerMinSumDecoder, run_stabilizer_trials  # noqa: F401,E402
 from .dem import DetectorErrorModel, phenomenological, run_dem_trials  # noqa: F401,E402
 from .windows import SlidingWindowDecoder, WindowPlan, WindowStep, phenomenological_layers, window_plan  # noqa: F401,E402
 
@@ -44,7 +45,7 @@ __all__ = [
     "MinSumDecoder", "MinSumScratchSpace", "RelayMinSumDecoder", "DecimatedMinSumDecoder",
     "Trials", "TrialResult", "run_trials",
     "CSSTrials", "CSSTrialResult", "run_css_trials", "run_css_joint_trials", "conditional_probs", "PauliMinSumDecoder",
-    "PauliRelayMinSumDecoder",
+    "PauliRelayMinSumDecoder", "StabilizerMinSumDecoder", "run_stabilizer_trials",
     "DetectorErrorModel", "phenomenological", "run_dem_trials",
     "SlidingWindowDecoder", "WindowPlan", "WindowStep", "phenomenological_layers", "window_plan",
 ]

@@ -118,6 +118,14 @@ class PauliRelayOptions(ctypes.Structure):
     ]
 
 
+class StabMinSumOptions(ctypes.Structure):
+    """ldpc_stab_minsum_options: alpha = 0 / clip = 0 select the defaults (0.75, 1e6)."""
+    _fields_ = [
+        ("device", ctypes.c_int32), ("alpha", ctypes.c_float), ("clip", ctypes.c_float),
+        ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 12),
+    ]
+
+
 class TrialsOptions(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("kernel_variant", ctypes.c_int32), ("reserved", ctypes.c_int32 * 14)]
 
@@ -288,6 +296,20 @@ PAULI_RELAY_API = {
 PAULI_RELAY_DEBUG_API = {
     "ldpc_debug_pauli_relay_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
 }
+# The stabilizer (non-CSS) min-sum decoder: include/ldpc_mi355x_stab.h (a part of ldpc_mi355x.h) and its test hook,
+# include/ldpc_mi355x_stab_debug.h (a part of ldpc_mi355x_debug.h), bound the same way.
+STAB_API = {
+    "ldpc_stab_minsum_create": (i32, [i64, P(CSSPattern), P(CSSPattern), vp, vp, vp, i64, P(StabMinSumOptions), P(vp)]),
+    "ldpc_stab_minsum_destroy": (i32, [vp]),
+    "ldpc_stab_minsum_kernel": (i32, [vp]),
+    "ldpc_stab_minsum_tile_syndromes": (i32, [vp]),
+    "ldpc_stab_minsum_last_grid": (i32, [vp]),
+    "ldpc_stab_minsum_decode_batch": (i32, [vp, i64, vp, vp, vp, vp, vp, vp]),
+    "ldpc_stab_minsum_decode_batch_device": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+}
+STAB_DEBUG_API = {
+    "ldpc_debug_stab_tile_plan": (i32, [i64, i64, i64, i32, P(i32), P(i32), P(i64)]),
+}
 EXPORTED_SYMBOLS = tuple(API)
 DEBUG_SYMBOLS = tuple(DEBUG_API)
 DECIM_SYMBOLS = tuple(DECIM_API)
@@ -295,6 +317,8 @@ DECIM_DEBUG_SYMBOLS = tuple(DECIM_DEBUG_API)
 OSD_SEARCH_SYMBOLS = tuple(OSD_SEARCH_API)
 PAULI_RELAY_SYMBOLS = tuple(PAULI_RELAY_API)
 PAULI_RELAY_DEBUG_SYMBOLS = tuple(PAULI_RELAY_DEBUG_API)
+STAB_SYMBOLS = tuple(STAB_API)
+STAB_DEBUG_SYMBOLS = tuple(STAB_DEBUG_API)
 
 
 def build(force: bool = False) -> str:
@@ -332,7 +356,8 @@ def lib(experiments: bool = False) -> ctypes.CDLL:
                            "or `make -C ldpcdecoders.jl_amd/csrc`. There is no CPU fallback.")
     _one_hip_runtime()
     L = ctypes.CDLL(path)
-    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API, OSD_SEARCH_API, PAULI_RELAY_API, PAULI_RELAY_DEBUG_API):
+    for group in (API, DEBUG_API, DECIM_API, DECIM_DEBUG_API, OSD_SEARCH_API, PAULI_RELAY_API, PAULI_RELAY_DEBUG_API,
+                  STAB_API, STAB_DEBUG_API):
         for name, (restype, argtypes) in group.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -236,3 +236,112 @@ def hypergraph_product(H1, H2=None) -> Tuple[sp.csc_matrix, sp.csc_matrix]:
         M.sort_indices()
         out.append(M)
     return out[0], out[1]
+
+
+# ---- general stabilizer codes: the symplectic pair (Sx, Sz), Clifford deformation, logical operators ----------------
+# A stabilizer with X or Y on qubit j has Sx[i, j] = 1, with Z or Y it has Sz[i, j] = 1.  The symplectic product of two
+# Paulis (x1 | z1), (x2 | z2) is x1 . z2 + z1 . x2 over GF(2): 1 where they anticommute.
+PAULI_PERMUTATIONS = ("XYZ", "XZY", "YXZ", "YZX", "ZXY", "ZYX")   # the images of X, Y, Z under a single-qubit Clifford
+
+
+def paulis_to_symplectic(strings) -> Tuple[np.ndarray, np.ndarray]:
+    """Pauli strings over I, X, Y, Z (one per stabilizer, all of one length) -> (Sx, Sz), each r x n uint8."""
+    rows = [str(s).upper() for s in strings]
+    if not rows or any(len(s) != len(rows[0]) for s in rows):
+        raise ValueError("give at least one Pauli string, all of the same length")
+    bad = set("".join(rows)) - set("IXYZ")
+    if bad:
+        raise ValueError(f"a Pauli string holds only I, X, Y and Z (got {sorted(bad)})")
+    A = np.array([list(s) for s in rows]).reshape(len(rows), len(rows[0]))
+    return ((A == "X") | (A == "Y")).astype(np.uint8), ((A == "Z") | (A == "Y")).astype(np.uint8)
+
+
+def five_qubit_code() -> Tuple[np.ndarray, np.ndarray]:
+    """The [[5,1,3]] code: the four cyclic shifts XZZXI, IXZZX, XIXZZ, ZXIXZ.  -> (Sx, Sz), each 4 x 5."""
+    return paulis_to_symplectic(["XZZXI"[-k:] + "XZZXI"[:-k] if k else "XZZXI" for k in range(4)])
+
+
+def clifford_deform(Hx, Hz, perms) -> Tuple[sp.csc_matrix, sp.csc_matrix]:
+    """A CSS code (Hx, Hz) with a single-qubit Clifford on every qubit: perms[j] in 0 .. 5 indexes PAULI_PERMUTATIONS, the
+    images of X, Y, Z on qubit j.  Rows of Hx first (an X-check takes the image of X), then rows of Hz (a Z-check takes the
+    image of Z).  -> (Sx, Sz), sparse uint8 patterns of rx + rz rows; commutation is preserved."""
+    X, Z = sp.csc_matrix(_dense_bits(Hx)), sp.csc_matrix(_dense_bits(Hz))
+    if X.shape[1] != Z.shape[1]:
+        raise AssertionError("Hx and Hz must have the same number of columns")
+    n = X.shape[1]
+    perms = np.asarray(perms, dtype=np.int64).reshape(-1)
+    if perms.shape != (n,) or ((perms < 0) | (perms > 5)).any():
+        raise ValueError(f"one permutation index in 0 .. 5 per qubit: expected {n} entries")
+    img_x = np.array([PAULI_PERMUTATIONS[k][0] for k in perms])
+    img_z = np.array([PAULI_PERMUTATIONS[k][2] for k in perms])
+    zero_x, zero_z = sp.csc_matrix(X.shape, dtype=np.uint8), sp.csc_matrix(Z.shape, dtype=np.uint8)
+
+    def part(letters):   # the columns of (Hx; Hz) whose image has that part
+        in_x = sp.diags(np.isin(img_x, letters).astype(np.uint8))
+        in_z = sp.diags(np.isin(img_z, letters).astype(np.uint8))
+        M = sp.csc_matrix(sp.vstack([X @ in_x if n else zero_x, Z @ in_z if n else zero_z])).astype(np.uint8)
+        M.eliminate_zeros()
+        M.sort_indices()
+        return M
+
+    return part(["X", "Y"]), part(["Z", "Y"])
+
+
+def xzzx_surface_code(d: int) -> Tuple[sp.csc_matrix, sp.csc_matrix]:
+    """The XZZX surface code of distance d: the hypergraph product of two (d - 1) x d repetition checks with X and Z
+    exchanged (permutation ZYX) on the second block of qubits.  n = d^2 + (d - 1)^2, 2 d (d - 1) stabilizers of weight 3
+    and 4, every one a product of X and Z (no Y).  -> (Sx, Sz)."""
+    d = int(d)
+    if d < 2:
+        raise ValueError("d must be >= 2")
+    rep = np.zeros((d - 1, d), dtype=np.uint8)
+    rep[np.arange(d - 1), np.arange(d - 1)] = 1
+    rep[np.arange(d - 1), np.arange(1, d)] = 1
+    Hx, Hz = hypergraph_product(rep, rep)
+    perms = np.zeros(Hx.shape[1], dtype=np.int64)
+    perms[d * d:] = 5
+    return clifford_deform(Hx, Hz, perms)
+
+
+def symplectic_product(Ax, Az, Bx, Bz) -> np.ndarray:
+    """[a][b] = 1 where Pauli a of (Ax | Az) anticommutes with Pauli b of (Bx | Bz)."""
+    Ax, Az, Bx, Bz = (_dense_bits(M) for M in (Ax, Az, Bx, Bz))
+    return _gf2_matmul(Ax, Bz.T) ^ _gf2_matmul(Az, Bx.T)
+
+
+def stabilizer_logicals(Sx, Sz) -> Tuple[np.ndarray, np.ndarray]:
+    """Logical operators of the stabilizer code (Sx, Sz): -> (LSx, LSz), each 2k x n uint8, k = n - rank[Sx | Sz].  The
+    rows commute with every stabilizer, are independent modulo the stabilizers, and are paired: row a anticommutes with
+    row k + a and with no other row.  Host GF(2) elimination (the centralizer is the kernel of [Sz | Sx]) and symplectic
+    Gram-Schmidt, for create time."""
+    X, Z = _dense_bits(Sx), _dense_bits(Sz)
+    if X.shape != Z.shape:
+        raise AssertionError("Sx and Sz must have the same shape")
+    if symplectic_product(X, Z, X, Z).any():
+        raise AssertionError("Sx * Sz' + Sz * Sx' != 0 over GF(2): the stabilizers do not commute")
+    n = X.shape[1]
+    S = np.concatenate([X, Z], axis=1)
+    S = S[_first_independent_rows(S)]
+    K = _gf2_kernel(np.concatenate([Z, X], axis=1))          # (x | z) with Sz x + Sx z = 0: the centralizer
+    both = np.concatenate([S, K], axis=0)
+    keep = [i - S.shape[0] for i in _first_independent_rows(both) if i >= S.shape[0]]
+    L = [K[i].copy() for i in keep]                           # a basis of the centralizer modulo the stabilizers
+    k2 = len(L)
+    if k2 != 2 * (n - S.shape[0]):
+        raise AssertionError("the centralizer modulo the stabilizers has the wrong dimension")
+
+    def anti(u, v):
+        return int((u[:n] & v[n:]).sum() + (u[n:] & v[:n]).sum()) & 1
+
+    firsts, seconds = [], []
+    while L:
+        v = L.pop(0)
+        hit = next((i for i, w in enumerate(L) if anti(v, w)), None)
+        if hit is None:
+            raise AssertionError("the form on the logical space is degenerate")
+        w = L.pop(hit)
+        L = [u ^ (v if anti(u, w) else 0) ^ (w if anti(u, v) else 0) for u in L]
+        firsts.append(v)
+        seconds.append(w)
+    out = np.array(firsts + seconds, dtype=np.uint8).reshape(k2, 2 * n)
+    return np.ascontiguousarray(out[:, :n]), np.ascontiguousarray(out[:, n:])

@@ -1,6 +1,6 @@
 // tile_plan.hpp -- what the host of every decoder of the min-sum family (ldpc_minsum.hip, ldpc_relay.hip, ldpc_pauli.hip,
-// ldpc_decim.hip, ldpc_pauli_relay.hip; device code: minsum_kernels.hpp, layered_kernels.hpp, relay_kernels.hpp,
-// pauli_kernels.hpp, decim_kernels.hpp, pauli_relay_kernels.hpp) derives from a graph's sizes
+// ldpc_decim.hip, ldpc_pauli_relay.hip, ldpc_stab.hip; device code: minsum_kernels.hpp, layered_kernels.hpp, relay_kernels.hpp,
+// pauli_kernels.hpp, decim_kernels.hpp, pauli_relay_kernels.hpp, stab_kernels.hpp) derives from a graph's sizes
 // alone: the sizes of a tile's state, the tier and the tile width chosen from them (the policy: plan_tiles(), the one
 // place it is stated) and the check records of a Tanner graph (ms_records(), the one place they are laid out).  Pure host
 // code over the standard library -- no HIP, no decoder handle, no environment -- so that it builds with a plain C++
@@ -123,6 +123,20 @@ inline size_t pauli_relay_state_bytes(long long s, long long n, long long rec_wo
 inline bool pauli_relay_tile_plan(int64_t s, int64_t n, int64_t rec_words, int variant, TilePlan *out)
 {
     return plan_tiles([=](int S) { return pauli_relay_state_bytes(s, n, rec_words, S); }, variant, out);
+}
+
+// ---- the stabilizer (non-CSS) min-sum decoder -----------------------------------------------------------------------------------
+// bytes of a stabilizer tile's state: S lanes of (3 n + rec_words) words -- the message totals MX, MY, MZ of the three edge
+// types and the check records -- and r syndrome bytes, rounded up to 256
+inline size_t stab_state_bytes(long long r, long long n, long long rec_words, int S)
+{
+    return (((size_t)(3 * n + rec_words) * 4 + (size_t)r) * (size_t)S + 255) & ~(size_t)255;
+}
+
+// Its plan (r checks, rec_words over the checks of the union graph).
+inline bool stab_tile_plan(int64_t r, int64_t n, int64_t rec_words, int variant, TilePlan *out)
+{
+    return plan_tiles([=](int S) { return stab_state_bytes(r, n, rec_words, S); }, variant, out);
 }
 
 // ---- the check records of a graph ------------------------------------------------------------------------------------------
