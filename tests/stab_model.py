@@ -118,6 +118,7 @@ class StabMinSumModel:
             active &= ~stop
             if not active.any():
                 break
+        self.last_messages = c                      # (a hook for the tests: the messages c[i] [B][degree] at the end)
         GX, GY, GZ = self._beliefs(*M)
         G = np.stack([GX, GY, GZ], axis=1)
         assert G.dtype == F and np.all(np.isfinite(G))

@@ -33,10 +33,14 @@ PAULI_RELAY = re.compile(r"^   pauli_relay Hz \((\d+), (\d+)\) B (\d+) leg_iters
 # the leg of the sixth generator: the OSD step by the standard rule
 OSD_SEARCH = re.compile(r"^   osd_search (combination_sweep|exhaustive) order (\d+) weights (none|floats|zero|clamped) batch (\d+) "
                         r"reproducing_rows (\d+) nan=(True|False) (in place|out of place)$")
+# the leg of the seventh generator: the stabilizer (non-CSS) min-sum; the degrees are those of the union graph
+STAB = re.compile(r"^   stab B (\d+) alpha (\S+) clip (\S+) max_iters (\d+) (device|host) entry llr=(True|False) iters=(True|False) "
+                  r"uniform=(True|False) (sampled|arbitrary) syndromes x_edges (\d+) z_edges (\d+) y_edges (\d+) "
+                  r"checks<=32 (\d+) checks33-64 (\d+) checks>64 (\d+) checks_empty (\d+)$")
 OLD_LEGS = ("bitflip", "minsum", "relay", "osd", "trials", "css")
-NEW_LEGS = ("layered", "priors", "pauli", "bpots", "decim", "pauli_relay", "osd_search")
+NEW_LEGS = ("layered", "priors", "pauli", "bpots", "decim", "pauli_relay", "osd_search", "stab")
 # SHA-256 of a FUZZ_DRY listing of 40 cases without its last line (which carries seconds) and without the lines of the legs
-# `pauli_relay` and `osd_search`, computed from the tool as it stood before those two legs: the eleven older legs draw for a
+# `pauli_relay`, `osd_search` and `stab`, computed from the tool as it stood before those legs: the eleven older legs draw for a
 # committed seed exactly what they drew then
 OLDER_LEGS_SHA256 = {20: "79f335c86efda4e16c389aba6c77ae75d485c8f8923acf8f58472b46312e0478", 21: "d0798cff3517aa9a274a5c4bf55af307230cd8ec1dd12ff22a5c4b1b13e2b099"}
 
@@ -111,6 +115,17 @@ def coverage(listing):
                 (f"osd_search: {method}", True), ("osd_search: order 0", order == 0), ("osd_search: order 64", order == 64),
                 (f"osd_search: weights {kind}", True), ("osd_search: a row that reproduces its syndrome", own > 0),
                 ("osd_search: a NaN LLR", m.group(6) == "True"), ("osd_search: in place", m.group(7) == "in place")) if yes}
+        m = STAB.match(line)
+        if m and int(m.group(4)) > 0:
+            B, clip, entry = int(m.group(1)), float(m.group(3)), m.group(5)
+            x, z, y, c32, c64, cbig, ce = (int(v) for v in m.groups()[9:])
+            assert 1 <= B <= 65
+            have |= {name for name, yes in (
+                ("stab: all three edge types", min(x, z, y) > 0), ("stab: check of degree 33 ... 64", c64 > 0),
+                ("stab: check of degree > 64", cbig > 0), ("stab: empty check", ce > 0), ("stab: batch 1", B == 1),
+                ("stab: batch 65", B == 65), (f"stab: {entry} entry", True), ("stab: llr=False", m.group(6) == "False"),
+                ("stab: iters=False", entry == "device" and m.group(7) == "False"), ("stab: one triple for every qubit", m.group(8) == "True"),
+                ("stab: arbitrary syndromes", m.group(9) == "arbitrary"), (f"stab: clip {clip:g}", True)) if yes}
         m = CASE.match(line)
         if not m:
             continue
@@ -148,7 +163,13 @@ WANTED = {"check of degree <= 32", "check of degree 33 ... 64", "check of degree
           # kind of cost, step 1 (bp_err already reproduces the syndrome), the NaN-last order, in place
           "osd_search: combination_sweep", "osd_search: exhaustive", "osd_search: order 0", "osd_search: order 64",
           "osd_search: weights none", "osd_search: weights floats", "osd_search: weights zero", "osd_search: weights clamped",
-          "osd_search: a row that reproduces its syndrome", "osd_search: a NaN LLR", "osd_search: in place"}
+          "osd_search: a row that reproduces its syndrome", "osd_search: a NaN LLR", "osd_search: in place",
+          # stabilizer min-sum, among the legs that run at least one iteration: X-, Z- and Y-type edges in one graph, five-word
+          # and per-edge records and an empty check in the union graph, a one-column and a ragged batch, both entries, each
+          # optional output left out, the clamp at each of the three clips the leg draws
+          "stab: all three edge types", "stab: check of degree 33 ... 64", "stab: check of degree > 64", "stab: empty check",
+          "stab: batch 1", "stab: batch 65", "stab: device entry", "stab: host entry", "stab: llr=False", "stab: iters=False",
+          "stab: one triple for every qubit", "stab: arbitrary syndromes", "stab: clip 4", "stab: clip 20", "stab: clip 1e+06"}
 # A graph without edges is NOT among them: the graphs are the cases' own, drawn from the first generator, whose stream the
 # older legs own; the smallest graph of the committed seeds has 7 edges.  tests/test_gpu_bpots_paths.py
 # (test_a_graph_without_edges) pins that shape instead.
@@ -166,10 +187,10 @@ def test_the_draws_of_a_seed_are_reproducible_and_the_committed_seeds_contain_th
         for leg in OLD_LEGS + NEW_LEGS:
             assert len([ln for ln in first.splitlines() if ln.startswith(f"   {leg} ")]) == CASES, leg
         # ... and every line of a new leg is one that coverage() can read
-        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS, DECIM, PAULI_RELAY, OSD_SEARCH)):
+        for leg, pattern in zip(NEW_LEGS, (LAYERED, PRIORS, PAULI, BPOTS, DECIM, PAULI_RELAY, OSD_SEARCH, STAB)):
             assert all(pattern.match(ln) for ln in first.splitlines() if ln.startswith(f"   {leg} ")), leg
-        # ... and the eleven older legs draw what they drew before the legs pauli_relay and osd_search existed
-        older = [ln for ln in first.splitlines()[:-1] if not ln.startswith(("   pauli_relay ", "   osd_search "))]
+        # ... and the eleven older legs draw what they drew before the legs pauli_relay, osd_search and stab existed
+        older = [ln for ln in first.splitlines()[:-1] if not ln.startswith(("   pauli_relay ", "   osd_search ", "   stab "))]
         assert hashlib.sha256(("\n".join(older) + "\n").encode()).hexdigest() == OLDER_LEGS_SHA256[seed], f"seed {seed}: an older leg draws otherwise"
         have |= coverage(first)
     widths = {name for name in have if name.startswith("bpots: S = ")}

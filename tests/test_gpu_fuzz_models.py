@@ -2,8 +2,8 @@
 boundaries, small Gallager codes), ragged batches, every kernel_variant that create accepts, the bit-flip, min-sum, relay,
 device OSD, trials and CSS trials kernels compared in every element with their numpy models, the three BP-OTS kernels
 (tiers 2, 3, 5: LDS-resident, node-parallel, unlimited) with the C oracle, the guided-decimation min-sum kernels (tiers 1
-and 2), the Pauli relay min-sum kernels (tiers 1 and 2) and the OSD step by the standard rule (tiers 1, 2, 3) with their
-numpy models.  (`relay tiers` is a substring of `pauli_relay tiers`: the patterns are anchored on the separator.)"""
+and 2), the Pauli relay min-sum kernels (tiers 1 and 2), the OSD step by the standard rule (tiers 1, 2, 3) and the
+stabilizer (non-CSS) min-sum kernels (tiers 1 and 2) with their numpy models.  (`relay tiers` is a substring of `pauli_relay tiers`: the patterns are anchored on the separator.)"""
 import os
 import re
 import subprocess
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TIERS = {"bitflip": {1, 2, 3}, "minsum": {1, 2}, "relay": {1, 2}, "osd": {1, 2, 3}, "trials": {1, 2}, "css": {1, 2},
          "layered": {1, 2}, "priors": {1, 2}, "pauli": {1, 2}, "bpots": {2, 3, 5}, "decim": {1, 2}, "pauli_relay": {1, 2},
-         "osd_search": {1, 2, 3}}
+         "osd_search": {1, 2, 3}, "stab": {1, 2}}
 _REPORTS = {}
 
 

@@ -2,7 +2,12 @@
 every element -- gx, gz, flags, iteration counts, and the three LLR planes as bit patterns.  The arithmetic has no
 division and no transcendental function, so there is no tolerance.  What ran is read back and asserted (`.kernel`,
 `.tile_syndromes`, `.last_grid`), so a case that misses its tier or width fails instead of passing on another path.
-Every batch holds converged and unconverged columns.  Every model result is computed once, shared, and never written to."""
+Every batch holds converged and unconverged columns.  Every model result is computed once, shared, and never written to.
+
+Tested elsewhere: every tile width (S = 64 ... 1, both LDS budgets, the largest on-chip state, the unlimited tier by size) in
+tests/test_gpu_stab_widths.py; the record forms at degrees 31, 32, 33, 63, 64 and 65 and the zeros and ties of the decision
+in tests/test_gpu_stab_boundaries.py (CPU twin: tests/test_stab_boundaries_cpu.py); random graphs in the leg `stab` of
+tools/fuzz_models.py (tests/test_gpu_fuzz_models.py)."""
 import functools
 
 import numpy as np

@@ -438,3 +438,79 @@ def test_model_five_qubit_code_all_16_syndromes(alpha):
     else:
         assert ok == [0, 1, 2, 4, 7, 8, 11, 13, 14] and (its[conv != 0] == 1).all() and (its[conv == 0] == 10).all()
         assert weight.tolist() == [0, 1, 1, 3, 1, 3, 3, 5, 1, 3, 3, 5, 3, 5, 5, 0]     # (converged ones of weight 5 among them)
+
+
+# ---- the table of tests/test_gpu_stab_widths.py -------------------------------------------------------------------------------
+# The core is the hypergraph product of two 3-bit repetition checks (n = 13, 6 + 6 checks) under the single-qubit Cliffords of
+# default_rng(0).integers(0, 6, 13): 12 checks of union degree 3 or 4, so 48 record words.  Padded with isolated qubits up to n
+# and with `empty` empty checks a lane takes 4 (3 n + 48) + 12 + empty = 12 n + 204 + empty bytes.
+# n -> (empty, lane bytes, tier, S, the budget S was found under)
+KIB79, KIB159 = 79 * 1024, 159 * 1024
+STAB_WIDTH_TABLE = {
+    80: (4, 1168, 1, 64, KIB79),
+    160: (4, 2128, 1, 32, KIB79),
+    320: (4, 4048, 1, 16, KIB79),
+    640: (4, 7888, 1, 8, KIB79),
+    1280: (4, 15568, 1, 4, KIB79),
+    2560: (4, 30928, 1, 2, KIB79),
+    5120: (4, 61648, 1, 1, KIB79),
+    6725: (4, 80908, 1, 2, KIB159),      # one lane misses 79 KiB by 12 bytes; two lanes, 161816 -> 162048, fit 159 KiB: S = 2, not 1
+    13550: (12, 162816, 1, 1, KIB159),   # 159 KiB exactly: the largest state that launches on chip
+    13600: (4, 163408, 2, 64, 0),        # the unlimited tier by size
+}
+STAB_WIDTH_REC_WORDS = 48
+
+
+@functools.lru_cache(maxsize=None)
+def stab_width_core():
+    """-> (Sx, Sz) 12 x 13 csc: 19 X-, 9 Z- and 12 Y-type edges, union degrees [3, 4, 3, 3, 4, 3, 3, 3, 4, 4, 3, 3]."""
+    rep = np.array([[1, 1, 0], [0, 1, 1]], dtype=np.uint8)
+    Hx, Hz = codes.hypergraph_product(rep, rep)
+    assert Hx.shape == Hz.shape == (6, 13)
+    Sx, Sz = codes.clifford_deform(Hx, Hz, np.random.default_rng(0).integers(0, 6, 13))
+    assert Sx.shape == Sz.shape == (12, 13) and _edge_types(Sx, Sz) == (19, 9, 12)
+    union = np.asarray(((Sx + Sz) != 0).sum(axis=1)).ravel().tolist()
+    assert union == [3, 4, 3, 3, 4, 3, 3, 3, 4, 4, 3, 3]
+    assert 4 * len(union) == STAB_WIDTH_REC_WORDS                  # every record has the four-word form (degree <= 32)
+    return Sx, Sz
+
+
+def stab_lib_plan(r, n, rec_words, variant=0, experiments=False):
+    """(tier, S, state bytes) of the library's plan, or its status where it refuses."""
+    L = ldpc._capi.lib(experiments)
+    tier, S, state = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int64(-1)
+    st = L.ldpc_debug_stab_tile_plan(r, n, rec_words, variant, ctypes.byref(tier), ctypes.byref(S), ctypes.byref(state))
+    return (tier.value, S.value, state.value) if st == 0 else st
+
+
+def stab_lane_bytes(r, n, rec_words):
+    """One syndrome: MX, MY, MZ (3 n words), the records, the syndrome (bytes)."""
+    return 4 * (3 * n + rec_words) + r
+
+
+def stab_state_bytes(r, n, rec_words, S):
+    return (S * stab_lane_bytes(r, n, rec_words) + 255) // 256 * 256
+
+
+@pytest.mark.parametrize("experiments", [False, True])
+@pytest.mark.parametrize("n", sorted(STAB_WIDTH_TABLE))
+def test_the_table_of_the_width_tests(n, experiments):
+    empty, lane, tier, S, budget = STAB_WIDTH_TABLE[n]
+    stab_width_core()
+    r, rec = 12 + empty, STAB_WIDTH_REC_WORDS
+    bytes_of = lambda w: stab_state_bytes(r, n, rec, w)   # noqa: E731
+    assert stab_lane_bytes(r, n, rec) == lane == 12 * n + 204 + empty
+    assert stab_lib_plan(r, n, rec, 0, experiments) == (tier, S, bytes_of(S))
+    if tier == 1:
+        assert stab_lib_plan(r, n, rec, 1, experiments) == (tier, S, bytes_of(S))
+        assert bytes_of(S) <= budget and (S == 64 or bytes_of(2 * S) > budget)      # the next wider S misses the budget
+        assert (budget == KIB79) == (bytes_of(1) <= KIB79)                          # 159 KiB is tried only where 79 KiB holds nothing
+    else:
+        assert bytes_of(1) > KIB159 and stab_lib_plan(r, n, rec, 1, experiments) == UNSUPPORTED
+    assert stab_lib_plan(r, n, rec, 2, experiments) == (2, 64, bytes_of(64))
+    if n == 6725:      # the window: one lane lies in (79 KiB, 159 KiB / 2]
+        assert KIB79 + 12 == 80908 <= KIB159 // 2 and 2 * 80908 == 161816 and bytes_of(2) == 162048 <= KIB159
+    if n == 13550:     # one more empty check and nothing fits
+        assert bytes_of(1) == KIB159 == 162816
+        assert stab_lane_bytes(r + 1, n, rec) == 162817 and stab_lib_plan(r + 1, n, rec, 0, experiments)[:2] == (2, 64)
+        assert stab_lib_plan(r + 1, n, rec, 1, experiments) == UNSUPPORTED

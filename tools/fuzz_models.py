@@ -2,7 +2,7 @@
 """Randomised model-parity fuzz (GPU box) of the kernels that tools/fuzz_parity.py does not reach: the bit-flip decoder,
 min-sum (flooding and layered schedule, shared and per-syndrome priors), relay min-sum, the joint X/Z (Pauli) min-sum, the
 device OSD step, the one-matrix and CSS trial steps, the three BP-OTS kernels at parameters fuzz_parity.py leaves out, the Pauli relay min-sum, the OSD step by the
-standard rule, and the guided-decimation min-sum (leg `decim`: 2 ... 4 model seconds for the 40 cases of seeds 20 and 21).  Random Tanner graphs (irregular with empty and heavy nodes and
+standard rule, the stabilizer (non-CSS) min-sum, and the guided-decimation min-sum (leg `decim`: 2 ... 4 model seconds for the 40 cases of seeds 20 and 21).  Random Tanner graphs (irregular with empty and heavy nodes and
 sizes around the word boundaries, or small Gallager codes), ragged batches, every `kernel_variant` that create accepts,
 every result compared in every element with the numpy models of tests/ (the min-sum family and relay: the LLR bit patterns
 too).  Usage: fuzz_models.py [cases] [seed] -- count-based: a seed names a fixed set of cases.
@@ -34,7 +34,15 @@ batch of `osd_search` is capped at 65, so that its model costs no more than the 
 seconds of these two legs for 40 cases, all thirteen legs in one run on one core of a faster machine than the figures
 above come from, with the relay leg of the same run beside them:
   seed 20: pauli_relay 3.59, osd_search 0.92 (relay 2.67)
-  seed 21: pauli_relay 3.04, osd_search 1.01 (relay 2.26)"""
+  seed 21: pauli_relay 3.04, osd_search 1.01 (relay 2.26)
+
+The leg `stab` (the joint Pauli min-sum of a general stabilizer code: Sx the case's graph, Sz a second drawn pattern of the
+same shape, an edge both store is Y-type; the rows need not commute) draws from a seventh generator (seeded [seed, 6]): the
+thirteen older legs draw what they drew.  Its batch is capped at 65 and its second pattern is sparser than the case's, so
+that the model, which walks the union graph, costs less than the relay leg's.  Model seconds for 40 cases, all fourteen
+legs in one run on one core, with the relay leg of the same run beside them:
+  seed 20: stab 1.91 (relay 3.03)
+  seed 21: stab 1.76 (relay 2.49)"""
 import os
 import sys
 import time
@@ -59,6 +67,7 @@ from osd_search_model import METHODS as OSD_SEARCH_METHODS, osd_search_model, we
 from pauli_model import PauliMinSumModel, pauli_priors  # noqa: E402
 from pauli_relay_model import PauliRelayModel  # noqa: E402
 from relay_model import RelayModel  # noqa: E402
+from stab_model import StabMinSumModel  # noqa: E402
 from oracle import BPOTSOracle  # noqa: E402
 
 DRY = os.environ.get("FUZZ_DRY") == "1"
@@ -72,7 +81,7 @@ UNSUPPORTED = 5
 # max_iters * max bit degree >= 2^31 and is held by test_unlimited_tier_with_64_bit_votes.)
 TIERS = {"bitflip": (1, 2, 3), "minsum": (1, 2), "relay": (1, 2), "osd": (1, 2, 3), "trials": (1, 2), "css": (1, 2),
          "layered": (1, 2), "priors": (1, 2), "pauli": (1, 2), "bpots": (2, 3, 5), "decim": (1, 2), "pauli_relay": (1, 2),
-         "osd_search": (1, 2, 3)}
+         "osd_search": (1, 2, 3), "stab": (1, 2)}
 BOUNDARY = (31, 32, 33, 63, 64, 65, 127, 128, 129)
 
 if GPU:
@@ -92,6 +101,7 @@ rng3 = np.random.default_rng([seed, 2])      # the bpots leg
 rng4 = np.random.default_rng([seed, 3])      # the decim leg
 rng5 = np.random.default_rng([seed, 4])      # the pauli_relay leg
 rng6 = np.random.default_rng([seed, 5])      # the osd_search leg
+rng7 = np.random.default_rng([seed, 6])      # the stab leg
 t0 = time.time()
 ran = {c: set() for c in TIERS}          # tiers that decoded
 legs_run = {c: 0 for c in TIERS}
@@ -1055,6 +1065,79 @@ def leg_osd_search(H, B, run):
     on_every_tier("osd_search", (1, 2, 3), Post, go, text)
 
 
+# ---- the leg of the seventh generator ----------------------------------------------------------------------------------
+STAB_BATCH_CAP = 65      # (the model walks the union graph, which has more edges than the case's)
+
+
+def draw_sz(s, n, g):
+    """(A dense, Sz csc): a second pattern of the case's shape, sparser than the first, with an empty row and a row of
+    33 ... 80 ones now and then; where it meets the case's pattern the edge is Y-type."""
+    A = (g.random((s, n)) < g.uniform(0.01, 0.12)).astype(np.uint8)
+    if g.random() < 0.35:
+        A[g.integers(0, s), :] = 0
+    if g.random() < 0.4 and n >= 33:          # a row of 33 ... 80 ones
+        A[g.integers(0, s), g.choice(n, size=min(n, int(g.integers(33, 81))), replace=False)] = 1
+    Sz = sp.csc_matrix(A)
+    Sz.sort_indices()
+    return A, Sz
+
+
+def leg_stab(H, B, run):
+    """The stabilizer min-sum on Sx = the case's H and a second drawn Sz of the same shape: an edge only H stores is X-type,
+    one only Sz stores Z-type, one both store Y-type.  The rows need not commute (check=False)."""
+    g = rng7
+    r, n = H.shape
+    A, Sz = draw_sz(r, n, g)
+    alpha, clip, max_iters = draw_rule(g)
+    probs, uniform = draw_pauli_probs(n, g)
+    device_entry, want_llr, want_iters = (bool(g.random() < 0.5) for _ in range(3))
+    Bs = min(B, STAB_BATCH_CAP)
+    sampled = bool(g.random() < 0.6)
+    if sampled:                               # the syndromes of sampled Pauli errors: s = Sx ez ^ Sz ex
+        rate = g.uniform(0.01, 0.15)
+        ex, ez = ((g.random((Bs, n)) < rate).astype(np.uint8) for _ in range(2))
+        syn = ldpc.codes.syndromes_of(H, ez) ^ ldpc.codes.syndromes_of(Sz, ex)
+    else:
+        syn = g.integers(0, 2, (Bs, r)).astype(np.uint8)
+    Hd = np.asarray(H.todense()) != 0
+    union = sp.csc_matrix((Hd | (A != 0)).astype(np.uint8))
+    text = (f"B {Bs} alpha {alpha} clip {clip} max_iters {max_iters} {'device' if device_entry else 'host'} entry llr={want_llr} "
+            f"iters={want_iters} uniform={uniform} {'sampled' if sampled else 'arbitrary'} syndromes x_edges {int((Hd & (A == 0)).sum())} "
+            f"z_edges {int((~Hd & (A != 0)).sum())} y_edges {int((Hd & (A != 0)).sum())}")
+    if DRY or VERBOSE:
+        print(f"   stab {text} {degrees_text(union, 'checks')}", flush=True)
+    if not run:
+        return
+    tables = pauli_priors(probs)
+    mgx, mgz, mconv, mits, mG = timed_model(
+        "stab", lambda: StabMinSumModel(H, Sz, tables, max_iters, alpha=alpha, clip=clip).decode(syn))
+    if not GPU:
+        return
+
+    def go(dec, variant):
+        for name, got, want in zip("xyz", (dec.prior_x, dec.prior_y, dec.prior_z), tables):
+            if not (got.dtype == np.float32 and np.array_equal(got.view(np.int32), want.view(np.int32))):
+                fail("stab", f"prior_{name} differs from the model's table {text}", probs=probs, got=got, want=want)
+        if device_entry:
+            gx, conv, llr, its = device_outputs(Bs, n, 3, want_llr, want_iters)
+            gz = torch.full((Bs, n), 7, dtype=torch.uint8, device="cuda")
+            dec.decode_batch_device(dev(syn), gx, gz, conv, llr, its)
+            torch.cuda.synchronize()
+            gx, gz, conv, llr, its = (host_of(x) for x in (gx, gz, conv, llr, its))
+        else:
+            gx, gz, conv, llr, its = dec.decode_batch_host(syn, want_llr=want_llr)
+            if (llr is None) != (not want_llr):
+                fail("stab", f"the host entry returns LLRs it was not asked for, or none, kernel_variant {variant} {text}")
+        ok = (same(gx, mgx) and same(gz, mgz) and same(conv, mconv) and (its is None or same(its, mits))
+              and (llr is None or same_bits(llr, mG)))
+        if not ok:
+            fail("stab", f"kernel_variant {variant} {text}", sx_colptr=H.indptr, sx_rowval=H.indices, shape=H.shape, sz=A, probs=probs,
+                 syn=syn, gx=gx, gz=gz, conv=conv, its=its, llr=llr, mgx=mgx, mgz=mgz, mconv=mconv, mits=mits, mG=mG)
+
+    on_every_tier("stab", (1, 2), lambda v: ldpc.StabilizerMinSumDecoder(H, Sz, None, max_iters, pauli_probs=probs, alpha=alpha, clip=clip,
+                                                                         kernel_variant=v, check=False), go, text)
+
+
 # ---- the cases ---------------------------------------------------------------------------------------------------------
 last_note = t0
 for case in range(ncases):
@@ -1079,6 +1162,7 @@ for case in range(ncases):
     leg_decim(H, B, run)
     leg_pauli_relay(H, B, run)
     leg_osd_search(H, B, run)
+    leg_stab(H, B, run)
     if time.time() - last_note > 60:   # a silent GPU job looks hung to the runner
         last_note = time.time()
         print(f"... {case + 1} cases, {time.time() - t0:.0f} s", flush=True)
